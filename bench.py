@@ -18,7 +18,16 @@ the 8-GPU config), `--config cfg5` (100 k triangles 1920x1080x256); `--scene/--w
 The scene is resident in HBM before the timed region (it is ~1 KB; the boundary hands over host tables, and
 uploading them costs microseconds — see DESIGN.md).
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the steps and prints the headline line (metric, value, unit, ms_per_step, ...).
+`--dump-outputs DIR` also writes what the last timed step computed, the frame rank 0 receives, as DIR/frame.npy (float32
+[H][W][3]; a frame above 64 MB is written as a fixed, seeded sample of its pixels: DIR/frame_sample.npy [n][3] and the pixels'
+linear ids y * W + x in DIR/frame_sample_index.npy, float64).  The inputs are the same in every run with the same arguments.
+
+`--full` adds what the headline does not need (off by default):
+  scene_build_s, scene_build_first_in_process_s, scene_device_bytes   what the scene costs to build and what it occupies
+  <other>_scaling  N > 1: the other scaling mode, measured with the same steps / warmup
+
+Extra objects on the JSON line with `--full`:
   roofline      bound = VALU issue (not HBM, not MFMA).  achieved = algorithmic lane-ops/sample
                 (oracle exit-point counters x the per-exit op costs of SURVEY.md §8d) x samples/s of the render
                 kernel, measured with HIP events on the launch stream; `executed_over_algorithmic` = the PMC's
@@ -251,6 +260,26 @@ def weak_frame(width: int, height: int, n_gpus: int):
     return int(round(width * n_gpus ** 0.5)), int(round(height * n_gpus ** 0.5))
 
 
+DUMP_MAX_BYTES = 64 * 10**6  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out_dir: Path, frame, seed: int = 0) -> None:
+    """--dump-outputs: the frame a caller of render() receives, float32 [H][W][3] -> out_dir/frame.npy.  A frame above
+    DUMP_MAX_BYTES is written as a fixed, seeded sample of its pixels (frame_sample.npy [n][3], float32) with the pixels'
+    linear ids y * W + x (frame_sample_index.npy, float64: exact below 2^53), in ascending order."""
+    import numpy as np
+    out_dir.mkdir(parents=True, exist_ok=True)
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if frame.nbytes <= DUMP_MAX_BYTES:
+        np.save(out_dir / "frame.npy", frame)
+        return
+    h, w, c = frame.shape
+    n = DUMP_MAX_BYTES // (c * 4 + 8)
+    idx = np.sort(np.random.default_rng(seed).choice(h * w, size=n, replace=False))
+    np.save(out_dir / "frame_sample.npy", frame.reshape(h * w, c)[idx])
+    np.save(out_dir / "frame_sample_index.npy", idx.astype(np.float64))
+
+
 CONFIGS = {  # BASELINE.json `configs`
     "cfg1": dict(scene="smoke", width=400, height=225, spp=64),          # the reference's own CPU-runnable case (main.cpp defaults)
     "cfg2": dict(scene="cornell", width=1920, height=1080, spp=1024),    # the headline: what `metric` is quoted on
@@ -308,7 +337,14 @@ def main() -> None:
                          "weak = a frame with N x the pixels (same aspect)")
     ap.add_argument("--dist-single", action="store_true",
                     help="testing aid: run the N>1 code path (RCCL process group, sharded render, gather) with world size 1")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: scene-build timing, roofline, cpu_baseline + "
+                         "parity (N = 1), the other scaling mode (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame of the last timed step to DIR/*.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     cfg = dict(CONFIGS[args.config])
     for k in ("scene", "width", "height", "spp"):
         if getattr(args, k) is not None:
@@ -357,14 +393,15 @@ def main() -> None:
     ds = R.DeviceScene(packed)
     torch.cuda.synchronize()
     scene_build_first_s = time.perf_counter() - t_build  # the first one of the process also pays the HIP runtime's one-off costs (its fill / copy kernels are loaded on first use: ~0.1 s)
-    ds.close()
-    t_build = time.perf_counter()
-    ds = R.DeviceScene(packed)
-    torch.cuda.synchronize()
-    scene_build_s = time.perf_counter() - t_build
-    from path_tracer_amd import abi as _abi
-    scene_device_bytes = int(_abi.load_library().pt_scene_device_bytes(ds.handle))
-    library_build_id = _abi.load_library().pt_build_id().decode()
+    if args.full:  # a second build, timed without the one-off costs
+        ds.close()
+        t_build = time.perf_counter()
+        ds = R.DeviceScene(packed)
+        torch.cuda.synchronize()
+        scene_build_s = time.perf_counter() - t_build
+        from path_tracer_amd import abi as _abi
+        scene_device_bytes = int(_abi.load_library().pt_scene_device_bytes(ds.handle))
+        library_build_id = _abi.load_library().pt_build_id().decode()
 
     def barrier():
         if dist_path:
@@ -422,8 +459,10 @@ def main() -> None:
     Ww, Hw = weak_frame(W1, H1, world)
     W, H = (Ww, Hw) if (world > 1 and args.scaling == "weak") else (W1, H1)
     elapsed, kern_ms, fb, cam, dist_detail = measure(W, H, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), fb.cpu().numpy())
     other = None
-    if world > 1:  # the other scaling mode, reported beside the headline (same steps / warmup)
+    if world > 1 and args.full:  # the other scaling mode, reported beside the headline (same steps / warmup)
         Wo, Ho = (W1, H1) if args.scaling == "weak" else (Ww, Hw)
         eo, ko, _, _, _ = measure(Wo, Ho, args.steps, args.warmup)
         other = {"scaling": "strong" if args.scaling == "weak" else "weak", "frame": f"{Wo}x{Ho}",
@@ -433,130 +472,6 @@ def main() -> None:
     if rank == 0:
         samples_per_step = W * H * SPP
         value = samples_per_step * args.steps / elapsed / 1e6
-        ops = ALGORITHMIC_OPS_PER_SAMPLE[scene_name]
-        ops_culled = ALGORITHMIC_OPS_PER_SAMPLE_CULLED.get(scene_name)
-        # which algorithm the kernel runs is read off the scene as pt_scene_create(desc) flattens it — the library's defaults with the PT_*
-        # variables applied, which is how THIS program creates its scene (pt_debug_tri_pool: spheres in a culling grid, triangles in a pool);
-        # a caller that creates scenes with an explicit PtTuning would have to ask pt_debug_flatten_tuned instead
-        import ctypes as C_
-        from path_tracer_amd import abi as abi_
-        st_scene = (C_.c_int32 * 8)()
-        abi_.check(abi_.load_library().pt_debug_tri_pool(C_.byref(packed.desc), st_scene), "pt_debug_tri_pool")
-        grid_culled, tri_culled = st_scene[7] > 0, st_scene[0] > 0
-        if (scene_name == "smoke" and not grid_culled) or (scene_name == "triangles" and not tri_culled):
-            ops_culled = None  # the A/B knobs select the reference's algorithm as written
-        cpu_line = None
-        if world == 1 and not args.no_cpu_baseline:
-            # --- cpu_baseline leg: the only place bench.py touches oracle/ (test infrastructure) ---------------
-            from oracle import binding as orc
-            orc.set_math(True)
-            cw, ch, cs = (480, 270, 4) if scene_name != "triangles" else (64, 36, 1)
-            _, ctr = orc.render(packed, scenes.make_camera(cam_args, cw, ch).c, cw, ch, cs, DEPTH, counters=True)
-            ops = ops_per_sample(ctr.as_dict())  # exit-point counters -> algorithmic ops per sample, live
-            if GRID_WALK.get(scene_name) and grid_culled:
-                st = st_scene
-                ops_culled = ops_per_sample_culled(ctr.as_dict(), sum(1 for k in packed.kinds() if k == abi_.PT_HIT_SPHERE), st[7], GRID_WALK[scene_name])
-            if TRI_POOL.get(scene_name) and tri_culled:
-                ops_culled = ops_per_sample_culled_tri(ctr.as_dict(), TRI_POOL[scene_name])
-            # bounded sample of the same workload.  Round 6: ~3 s of OpenMP work, ~1 s each for the glibc-math and the
-            # one-thread legs — the whole CPU leg now costs about what the GPU region does (it was 22 s against 3: the driver's gpu_busy
-            # sampler saw an idle device on all of its samples).  The rate does not depend on the sample's size (Msamples/s is resolution-
-            # independent: SURVEY.md §8d), only its noise does.
-            bw, bh = (W // 2, H // 2) if scene_name != "triangles" else (160, 90)
-            bcam = scenes.make_camera(cam_args, bw, bh)
-            # threads: what the container may actually run.  A box that shows 256 CPUs under a 16-CPU cgroup quota ran 128 OpenMP threads in
-            # bursts (a one-sample probe at 65 Msamples/s, the sample it sized at 10: 19.6 s instead of 3); the quota, rounded up, is the
-            # thread count now, and the sample is sized from a second, longer probe.
-            quota = cgroup_cpu_max()
-            if quota:
-                orc.load().orc_set_threads(int(max(1, min(orc.load().orc_max_threads(), math.ceil(quota)))))
-            t1 = time.perf_counter()
-            orc.render(packed, bcam.c, bw, bh, 1, DEPTH)
-            probe = time.perf_counter() - t1
-            ps = int(max(1, min(SPP, round(0.4 / max(probe, 1e-3)))))
-            if ps > 1:
-                t1 = time.perf_counter()
-                orc.render(packed, bcam.c, bw, bh, ps, DEPTH)
-                probe = (time.perf_counter() - t1) / ps
-            bs = int(max(1, min(SPP, round(2.6 / max(probe, 1e-3)))))
-            t1 = time.perf_counter()
-            orc.render(packed, bcam.c, bw, bh, bs, DEPTH)
-            dt = time.perf_counter() - t1
-            # the same sample with glibc's float libm (the reference's own libm semantics; transcendental-free scenes such as
-            # the Cornell-style one give the same image either way), half the sample: it rides beside, it is not `value`
-            orc.set_math(False)
-            gs = max(1, bs // 3)
-            t1 = time.perf_counter()
-            orc.render(packed, bcam.c, bw, bh, gs, DEPTH)
-            dtg = time.perf_counter() - t1
-            orc.set_math(True)
-            # one thread on its own, on a slice of the same workload sized for ~1 s (a smaller frame of the same camera where even one
-            # sample per pixel of the sample's frame would take longer: the 100 k-triangle mesh does ~40 samples/s per thread): what a
-            # "core" of this host is worth, and how the OpenMP run scales over the threads it used (row-dynamic schedule)
-            nthreads = orc.load().orc_max_threads()
-            per_thread_guess = bw * bh * bs / dt / max(nthreads, 1)              # samples / s / thread if the scaling were perfect
-            want = max(64.0, 1.0 * per_thread_guess)                             # samples for ~1 s (a thread alone is at least that fast)
-            s1 = int(max(1, min(bs, want // (bw * bh))))
-            w1, h1 = bw, bh
-            if want < bw * bh:                                                   # fewer samples than pixels: shrink the frame
-                k = (want / (bw * bh)) ** 0.5
-                w1, h1 = max(8, int(bw * k)), max(8, int(bh * k))
-            cam1 = scenes.make_camera(cam_args, w1, h1)
-            orc.load().orc_set_threads(1)
-            t1 = time.perf_counter()
-            orc.render(packed, cam1.c, w1, h1, s1, DEPTH)
-            dt1 = time.perf_counter() - t1
-            orc.load().orc_set_threads(nthreads)
-            one_thread = w1 * h1 * s1 / dt1 / 1e6
-            cpu_line = {"value": round(bw * bh * bs / dt / 1e6, 3), "unit": "Msamples/s",
-                        "cores": nthreads, "kind": "port",
-                        "affinity_cpus": len(os.sched_getaffinity(0)), "os_cpu_count": os.cpu_count(), "cgroup_cpu_max": cgroup_cpu_max(),
-                        "one_thread_value": round(one_thread, 4), "one_thread_sample": f"{w1}x{h1}, {s1} spp ({dt1:.1f} s), 1 OpenMP thread",
-                        "thread_scaling_efficiency": round(bw * bh * bs / dt / 1e6 / (one_thread * max(nthreads, 1)), 3),
-                        "sample": f"same scene, {bw}x{bh}, {bs} spp, depth {DEPTH} ({bw * bh * bs / 1e6:.1f} Msamples, {dt:.1f} s), OpenMP CPU oracle, portable math",
-                        "value_glibc_math": round(bw * bh * gs / dtg / 1e6, 3),
-                        "sample_glibc_math": f"{bw}x{bh}, {gs} spp ({dtg:.1f} s), same oracle with glibc's float libm"}
-            # the "PSNR vs CPU ref" half of the metric: sampled pixels of the LAST timed GPU frame re-rendered by the
-            # oracle at full spp (a pixel depends only on its own RNG stream)
-            import numpy as np
-            rng_ = np.random.default_rng(1)
-            npx = 256 if scene_name == "cornell" else 24 if scene_name == "smoke" else 4
-            xy = np.stack([rng_.integers(0, W, npx), rng_.integers(0, H, npx)], axis=1).astype(np.int32)
-            ref = orc.render_pixels(packed, cam.c, W, H, SPP, xy, DEPTH)
-            got = fb.cpu().numpy()[xy[:, 1], xy[:, 0]]
-            same = (got.view(np.uint32) == ref.view(np.uint32)) | (np.isnan(got) & np.isnan(ref))
-            g8, r8 = orc.tonemap_rgb8(got[None]), orc.tonemap_rgb8(ref[None])
-            mse = float(np.mean((g8.astype(np.float64) - r8.astype(np.float64)) ** 2))
-            parity = {"pixels_checked": int(npx), "bit_identical_pixels": int(same.all(axis=1).sum()),
-                      "psnr_db_8bit": None if mse == 0 else round(10 * np.log10(255.0 ** 2 / mse), 2),
-                      "note": "GPU frame vs CPU oracle (portable math) at sampled pixels, full spp; null PSNR = identical"
-                              + ("; fast mode is NOT expected to be bit-identical" if args.mode == "fast" else "")}
-        # the committed counters are those of the parity kernels with default flags: any other mode / flag set gets nulls
-        pmc = pmc_traffic(scene_name, W, H, SPP) if (world == 1 and args.flags == 0) else None
-        # ... and they are RECORDINGS: they describe the build they were recorded on.  A recording of another build (its kernel-source hash
-        # differs from this tree's) is not reported as if it were this run's: every PMC-derived field is nulled, the line says which
-        # recording was refused.  (tools/pmc_summary.py stamps kernels_sha16 / recorded_at_head; older summaries carry neither = stale.)
-        # "this build" is the LIBRARY that ran (pt_build_id: the hash of the kernel sources it was compiled from, csrc/Makefile), not the
-        # tree beside it (a stale .so or a PT_RENDER_LIB override would otherwise pass for the tree's build)
-        kernels_now = library_build_id
-        pmc_record = {"file": pmc[1], "kernels_sha16": pmc[3], "recorded_at_head": pmc[4], "matches_this_build": pmc[3] == kernels_now} if pmc else None
-        if pmc and pmc[3] != kernels_now:
-            pmc = None
-        kernel_samples_per_s = samples_per_step / (kern_ms * 1e-3)  # whole job; each rank renders 1/world of it
-        ops_reference = ops
-        if ops_culled:  # a kernel that provably skips tests is priced for the algorithm it runs; the reference's figure rides beside
-            ops = ops_culled
-        achieved = ops * kernel_samples_per_s / 1e12 / world  # per GPU
-        # algorithmic HBM bytes of one launch: the frame written once (12 B per pixel of this rank's share) + the scene read once
-        # (the flattened blob with its culling tables, the material table, the texture atlas)
-        # (the triangle pools' tables are a buffer of their own since round 5: pt_debug_flatten_pool)
-        # (round 6: what the scene occupies on the device, from the scene itself — pt_scene_device_bytes — instead of a second flatten of it)
-        scene_bytes = scene_device_bytes
-        algorithmic_bytes = W * H * 12 // world + scene_bytes
-        valu_frac = achieved / PEAK_TLANEOPS
-        # memory leg: bytes that went past L2 (FETCH_SIZE + WRITE_SIZE of the committed PMC passes of this workload) / kernel time / 8 TB/s
-        mem_frac = (pmc[0] / (kern_ms * 1e-3) / 8e12) if pmc else None
-        bound = "hbm" if (mem_frac is not None and mem_frac > valu_frac) else "valu"
         headline = (scene_name, W1, H1, SPP) == ("cornell", 1920, 1080, 1024)
         at = "1080p 1024spp" if (W, H, SPP) == (1920, 1080, 1024) else f"{W}x{H} {SPP}spp"
         scaling = args.scaling  # (at N = 1 both modes coincide; the label stays the one the N > 1 lines of the same sweep carry)
@@ -567,48 +482,178 @@ def main() -> None:
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": scaling,
             "vs_baseline": None, "dtype": "f32", "data": "synthetic", "frame": f"{W}x{H}",
-            # outside the timed region, and therefore said: seconds of pt_scene_create (flatten + culling structures + upload) and the
-            # device bytes of the scene's data (records, materials, triangle-pool tables, atlas)
-            "scene_build_s": round(scene_build_s, 4), "scene_build_first_in_process_s": round(scene_build_first_s, 4), "scene_device_bytes": scene_device_bytes,
             "config": {"workload": f"{scene_name}: {SCENE_TEXT[scene_name]}, {W}x{H}, {SPP} spp, depth {DEPTH}, "
                                    + ("seed = pixel linear id" if args.mode == "parity" else "FAST MODE: one RNG stream per (pixel, sample)"),
                        "baseline_config": args.config, "hittables": packed.n_hittables, "mode": args.mode,
                        "frame_at_1_gpu": f"{W1}x{H1}",
                        "sharding": "whole frame" if world == 1 else f"8x8 tiles round-robin over {world} ranks + RCCL gather"},
-            # `bound`: the larger of the VALU fraction (algorithmic lane-ops / s over the issue peak) and the memory fraction (bytes past
-            # L2 per second over 8 TB/s).  achieved / peak / unit / frac describe THAT leg; the other one rides in "valu" / "hbm".
-            "roofline": {"bound": bound,
-                         "achieved": round(achieved, 3) if bound == "valu" else round(pmc[0] / (kern_ms * 1e-3) / 1e9, 1),
-                         "peak": round(PEAK_TLANEOPS, 1) if bound == "valu" else 8000.0,
-                         "unit": "Tlaneop/s" if bound == "valu" else "GB/s",
-                         "frac": round(valu_frac if bound == "valu" else mem_frac, 4),
-                         "valu": {"achieved_tlaneops": round(achieved, 3), "peak_tlaneops": round(PEAK_TLANEOPS, 1), "frac": round(valu_frac, 4)},
-                         # `achieved` prices the algorithm the kernel RUNS: the reference's as written, except where an exact
-                         # culling structure provably skips tests (sphere grid: ops_per_sample_culled); the reference's own
-                         # figure rides beside as algorithmic_ops_per_sample_reference
-                         "frac_note": ("exceeds 1: the kernel skips tests the pricing still counts" if achieved / PEAK_TLANEOPS > 1 else None),
-                         "priced_algorithm": (("culled: " + ("sphere grid" if GRID_WALK.get(scene_name) else "triangle pool") + " (counted in-kernel: "
-                                               + (GRID_WALK.get(scene_name) or TRI_POOL.get(scene_name) or {"source": "recorded figure"})["source"] + ")")
-                                              if ops_culled else "the reference's algorithm as written"),
-                         "algorithmic_ops_per_sample_reference": round(ops_reference, 1),
-                         "traffic": pmc[0] if pmc else None, "traffic_source": pmc[1] if pmc else None,
-                         # which recording the PMC-derived fields (traffic, hbm, *_pmc, executed_over_algorithmic) come from; nulled when stale
-                         "pmc_recording": pmc_record, "kernels_sha16": kernels_now, "tree_kernels_sha16": kernels_sha16(), "recorded_at_head": pmc_record["recorded_at_head"] if pmc_record else None,
-                         # north-star evidence: HBM is not the limiter, VALU issue is busy (PMC of the committed profile)
-                         "hbm": {"achieved_gbs": round(pmc[0] / (kern_ms * 1e-3) / 1e9, 3), "peak_gbs": 8000.0,
-                                 "frac": round(mem_frac, 6), "traffic_over_algorithmic": round(pmc[0] / algorithmic_bytes, 2)} if pmc else None,
-                         "valu_issue_occupancy_pmc": round(pmc[2].get("valu_issue_occupancy", 0.0), 3) if pmc else None,
-                         "valu_lane_utilisation_pmc": round(pmc[2].get("valu_lane_utilisation", 0.0), 3) if pmc else None,
-                         "issue_slot_occupancy_pmc": round(pmc[2]["issue_slot_occupancy"], 3) if pmc and "issue_slot_occupancy" in pmc[2] else None,
-                         "valu_lane_instr_per_sample_pmc": round(pmc[2].get("valu_lane_instr_per_sample", 0.0), 1) if pmc else None,
-                         # how much more the kernel executes than the reference's arithmetic as written
-                         "executed_over_algorithmic": round(pmc[2]["valu_lane_instr_per_sample"] / ops, 3)
-                         if pmc and pmc[2].get("valu_lane_instr_per_sample") else None,
-                         "kernel": "render_kernel", "kernel_ms": round(kern_ms, 3),
-                         "algorithmic_ops_per_sample": round(ops, 1),
-                         "kernel_msamples_per_s_per_gpu": round(kernel_samples_per_s / world / 1e6, 2),
-                         "hbm_algorithmic_bytes": algorithmic_bytes, "hbm_algorithmic_bytes_scene": scene_bytes},
         }
+        if args.full:
+            ops = ALGORITHMIC_OPS_PER_SAMPLE[scene_name]
+            ops_culled = ALGORITHMIC_OPS_PER_SAMPLE_CULLED.get(scene_name)
+            # which algorithm the kernel runs is read off the scene as pt_scene_create(desc) flattens it — the library's defaults with the PT_*
+            # variables applied, which is how THIS program creates its scene (pt_debug_tri_pool: spheres in a culling grid, triangles in a pool);
+            # a caller that creates scenes with an explicit PtTuning would have to ask pt_debug_flatten_tuned instead
+            import ctypes as C_
+            from path_tracer_amd import abi as abi_
+            st_scene = (C_.c_int32 * 8)()
+            abi_.check(abi_.load_library().pt_debug_tri_pool(C_.byref(packed.desc), st_scene), "pt_debug_tri_pool")
+            grid_culled, tri_culled = st_scene[7] > 0, st_scene[0] > 0
+            if (scene_name == "smoke" and not grid_culled) or (scene_name == "triangles" and not tri_culled):
+                ops_culled = None  # the A/B knobs select the reference's algorithm as written
+            cpu_line = None
+            if world == 1 and not args.no_cpu_baseline:
+                # --- cpu_baseline leg: the only place bench.py touches oracle/ (test infrastructure) ---------------
+                from oracle import binding as orc
+                orc.set_math(True)
+                cw, ch, cs = (480, 270, 4) if scene_name != "triangles" else (64, 36, 1)
+                _, ctr = orc.render(packed, scenes.make_camera(cam_args, cw, ch).c, cw, ch, cs, DEPTH, counters=True)
+                ops = ops_per_sample(ctr.as_dict())  # exit-point counters -> algorithmic ops per sample, live
+                if GRID_WALK.get(scene_name) and grid_culled:
+                    st = st_scene
+                    ops_culled = ops_per_sample_culled(ctr.as_dict(), sum(1 for k in packed.kinds() if k == abi_.PT_HIT_SPHERE), st[7], GRID_WALK[scene_name])
+                if TRI_POOL.get(scene_name) and tri_culled:
+                    ops_culled = ops_per_sample_culled_tri(ctr.as_dict(), TRI_POOL[scene_name])
+                # bounded sample of the same workload.  Round 6: ~3 s of OpenMP work, ~1 s each for the glibc-math and the
+                # one-thread legs — the whole CPU leg now costs about what the GPU region does (it was 22 s against 3: the driver's gpu_busy
+                # sampler saw an idle device on all of its samples).  The rate does not depend on the sample's size (Msamples/s is resolution-
+                # independent: SURVEY.md §8d), only its noise does.
+                bw, bh = (W // 2, H // 2) if scene_name != "triangles" else (160, 90)
+                bcam = scenes.make_camera(cam_args, bw, bh)
+                # threads: what the container may actually run.  A box that shows 256 CPUs under a 16-CPU cgroup quota ran 128 OpenMP threads in
+                # bursts (a one-sample probe at 65 Msamples/s, the sample it sized at 10: 19.6 s instead of 3); the quota, rounded up, is the
+                # thread count now, and the sample is sized from a second, longer probe.
+                quota = cgroup_cpu_max()
+                if quota:
+                    orc.load().orc_set_threads(int(max(1, min(orc.load().orc_max_threads(), math.ceil(quota)))))
+                t1 = time.perf_counter()
+                orc.render(packed, bcam.c, bw, bh, 1, DEPTH)
+                probe = time.perf_counter() - t1
+                ps = int(max(1, min(SPP, round(0.4 / max(probe, 1e-3)))))
+                if ps > 1:
+                    t1 = time.perf_counter()
+                    orc.render(packed, bcam.c, bw, bh, ps, DEPTH)
+                    probe = (time.perf_counter() - t1) / ps
+                bs = int(max(1, min(SPP, round(2.6 / max(probe, 1e-3)))))
+                t1 = time.perf_counter()
+                orc.render(packed, bcam.c, bw, bh, bs, DEPTH)
+                dt = time.perf_counter() - t1
+                # the same sample with glibc's float libm (the reference's own libm semantics; transcendental-free scenes such as
+                # the Cornell-style one give the same image either way), half the sample: it rides beside, it is not `value`
+                orc.set_math(False)
+                gs = max(1, bs // 3)
+                t1 = time.perf_counter()
+                orc.render(packed, bcam.c, bw, bh, gs, DEPTH)
+                dtg = time.perf_counter() - t1
+                orc.set_math(True)
+                # one thread on its own, on a slice of the same workload sized for ~1 s (a smaller frame of the same camera where even one
+                # sample per pixel of the sample's frame would take longer: the 100 k-triangle mesh does ~40 samples/s per thread): what a
+                # "core" of this host is worth, and how the OpenMP run scales over the threads it used (row-dynamic schedule)
+                nthreads = orc.load().orc_max_threads()
+                per_thread_guess = bw * bh * bs / dt / max(nthreads, 1)              # samples / s / thread if the scaling were perfect
+                want = max(64.0, 1.0 * per_thread_guess)                             # samples for ~1 s (a thread alone is at least that fast)
+                s1 = int(max(1, min(bs, want // (bw * bh))))
+                w1, h1 = bw, bh
+                if want < bw * bh:                                                   # fewer samples than pixels: shrink the frame
+                    k = (want / (bw * bh)) ** 0.5
+                    w1, h1 = max(8, int(bw * k)), max(8, int(bh * k))
+                cam1 = scenes.make_camera(cam_args, w1, h1)
+                orc.load().orc_set_threads(1)
+                t1 = time.perf_counter()
+                orc.render(packed, cam1.c, w1, h1, s1, DEPTH)
+                dt1 = time.perf_counter() - t1
+                orc.load().orc_set_threads(nthreads)
+                one_thread = w1 * h1 * s1 / dt1 / 1e6
+                cpu_line = {"value": round(bw * bh * bs / dt / 1e6, 3), "unit": "Msamples/s",
+                            "cores": nthreads, "kind": "port",
+                            "affinity_cpus": len(os.sched_getaffinity(0)), "os_cpu_count": os.cpu_count(), "cgroup_cpu_max": cgroup_cpu_max(),
+                            "one_thread_value": round(one_thread, 4), "one_thread_sample": f"{w1}x{h1}, {s1} spp ({dt1:.1f} s), 1 OpenMP thread",
+                            "thread_scaling_efficiency": round(bw * bh * bs / dt / 1e6 / (one_thread * max(nthreads, 1)), 3),
+                            "sample": f"same scene, {bw}x{bh}, {bs} spp, depth {DEPTH} ({bw * bh * bs / 1e6:.1f} Msamples, {dt:.1f} s), OpenMP CPU oracle, portable math",
+                            "value_glibc_math": round(bw * bh * gs / dtg / 1e6, 3),
+                            "sample_glibc_math": f"{bw}x{bh}, {gs} spp ({dtg:.1f} s), same oracle with glibc's float libm"}
+                # the "PSNR vs CPU ref" half of the metric: sampled pixels of the LAST timed GPU frame re-rendered by the
+                # oracle at full spp (a pixel depends only on its own RNG stream)
+                import numpy as np
+                rng_ = np.random.default_rng(1)
+                npx = 256 if scene_name == "cornell" else 24 if scene_name == "smoke" else 4
+                xy = np.stack([rng_.integers(0, W, npx), rng_.integers(0, H, npx)], axis=1).astype(np.int32)
+                ref = orc.render_pixels(packed, cam.c, W, H, SPP, xy, DEPTH)
+                got = fb.cpu().numpy()[xy[:, 1], xy[:, 0]]
+                same = (got.view(np.uint32) == ref.view(np.uint32)) | (np.isnan(got) & np.isnan(ref))
+                g8, r8 = orc.tonemap_rgb8(got[None]), orc.tonemap_rgb8(ref[None])
+                mse = float(np.mean((g8.astype(np.float64) - r8.astype(np.float64)) ** 2))
+                parity = {"pixels_checked": int(npx), "bit_identical_pixels": int(same.all(axis=1).sum()),
+                          "psnr_db_8bit": None if mse == 0 else round(10 * np.log10(255.0 ** 2 / mse), 2),
+                          "note": "GPU frame vs CPU oracle (portable math) at sampled pixels, full spp; null PSNR = identical"
+                                  + ("; fast mode is NOT expected to be bit-identical" if args.mode == "fast" else "")}
+            # the committed counters are those of the parity kernels with default flags: any other mode / flag set gets nulls
+            pmc = pmc_traffic(scene_name, W, H, SPP) if (world == 1 and args.flags == 0) else None
+            # ... and they are RECORDINGS: they describe the build they were recorded on.  A recording of another build (its kernel-source hash
+            # differs from this tree's) is not reported as if it were this run's: every PMC-derived field is nulled, the line says which
+            # recording was refused.  (tools/pmc_summary.py stamps kernels_sha16 / recorded_at_head; older summaries carry neither = stale.)
+            # "this build" is the LIBRARY that ran (pt_build_id: the hash of the kernel sources it was compiled from, csrc/Makefile), not the
+            # tree beside it (a stale .so or a PT_RENDER_LIB override would otherwise pass for the tree's build)
+            kernels_now = library_build_id
+            pmc_record = {"file": pmc[1], "kernels_sha16": pmc[3], "recorded_at_head": pmc[4], "matches_this_build": pmc[3] == kernels_now} if pmc else None
+            if pmc and pmc[3] != kernels_now:
+                pmc = None
+            kernel_samples_per_s = samples_per_step / (kern_ms * 1e-3)  # whole job; each rank renders 1/world of it
+            ops_reference = ops
+            if ops_culled:  # a kernel that provably skips tests is priced for the algorithm it runs; the reference's figure rides beside
+                ops = ops_culled
+            achieved = ops * kernel_samples_per_s / 1e12 / world  # per GPU
+            # algorithmic HBM bytes of one launch: the frame written once (12 B per pixel of this rank's share) + the scene read once
+            # (the flattened blob with its culling tables, the material table, the texture atlas)
+            # (the triangle pools' tables are a buffer of their own since round 5: pt_debug_flatten_pool)
+            # (round 6: what the scene occupies on the device, from the scene itself — pt_scene_device_bytes — instead of a second flatten of it)
+            scene_bytes = scene_device_bytes
+            algorithmic_bytes = W * H * 12 // world + scene_bytes
+            valu_frac = achieved / PEAK_TLANEOPS
+            # memory leg: bytes that went past L2 (FETCH_SIZE + WRITE_SIZE of the committed PMC passes of this workload) / kernel time / 8 TB/s
+            mem_frac = (pmc[0] / (kern_ms * 1e-3) / 8e12) if pmc else None
+            bound = "hbm" if (mem_frac is not None and mem_frac > valu_frac) else "valu"
+            line.update({
+                # outside the timed region, and therefore said: seconds of pt_scene_create (flatten + culling structures + upload) and the
+                # device bytes of the scene's data (records, materials, triangle-pool tables, atlas)
+                "scene_build_s": round(scene_build_s, 4), "scene_build_first_in_process_s": round(scene_build_first_s, 4), "scene_device_bytes": scene_device_bytes,
+                # `bound`: the larger of the VALU fraction (algorithmic lane-ops / s over the issue peak) and the memory fraction (bytes past
+                # L2 per second over 8 TB/s).  achieved / peak / unit / frac describe THAT leg; the other one rides in "valu" / "hbm".
+                "roofline": {"bound": bound,
+                             "achieved": round(achieved, 3) if bound == "valu" else round(pmc[0] / (kern_ms * 1e-3) / 1e9, 1),
+                             "peak": round(PEAK_TLANEOPS, 1) if bound == "valu" else 8000.0,
+                             "unit": "Tlaneop/s" if bound == "valu" else "GB/s",
+                             "frac": round(valu_frac if bound == "valu" else mem_frac, 4),
+                             "valu": {"achieved_tlaneops": round(achieved, 3), "peak_tlaneops": round(PEAK_TLANEOPS, 1), "frac": round(valu_frac, 4)},
+                             # `achieved` prices the algorithm the kernel RUNS: the reference's as written, except where an exact
+                             # culling structure provably skips tests (sphere grid: ops_per_sample_culled); the reference's own
+                             # figure rides beside as algorithmic_ops_per_sample_reference
+                             "frac_note": ("exceeds 1: the kernel skips tests the pricing still counts" if achieved / PEAK_TLANEOPS > 1 else None),
+                             "priced_algorithm": (("culled: " + ("sphere grid" if GRID_WALK.get(scene_name) else "triangle pool") + " (counted in-kernel: "
+                                                   + (GRID_WALK.get(scene_name) or TRI_POOL.get(scene_name) or {"source": "recorded figure"})["source"] + ")")
+                                                  if ops_culled else "the reference's algorithm as written"),
+                             "algorithmic_ops_per_sample_reference": round(ops_reference, 1),
+                             "traffic": pmc[0] if pmc else None, "traffic_source": pmc[1] if pmc else None,
+                             # which recording the PMC-derived fields (traffic, hbm, *_pmc, executed_over_algorithmic) come from; nulled when stale
+                             "pmc_recording": pmc_record, "kernels_sha16": kernels_now, "tree_kernels_sha16": kernels_sha16(), "recorded_at_head": pmc_record["recorded_at_head"] if pmc_record else None,
+                             # north-star evidence: HBM is not the limiter, VALU issue is busy (PMC of the committed profile)
+                             "hbm": {"achieved_gbs": round(pmc[0] / (kern_ms * 1e-3) / 1e9, 3), "peak_gbs": 8000.0,
+                                     "frac": round(mem_frac, 6), "traffic_over_algorithmic": round(pmc[0] / algorithmic_bytes, 2)} if pmc else None,
+                             "valu_issue_occupancy_pmc": round(pmc[2].get("valu_issue_occupancy", 0.0), 3) if pmc else None,
+                             "valu_lane_utilisation_pmc": round(pmc[2].get("valu_lane_utilisation", 0.0), 3) if pmc else None,
+                             "issue_slot_occupancy_pmc": round(pmc[2]["issue_slot_occupancy"], 3) if pmc and "issue_slot_occupancy" in pmc[2] else None,
+                             "valu_lane_instr_per_sample_pmc": round(pmc[2].get("valu_lane_instr_per_sample", 0.0), 1) if pmc else None,
+                             # how much more the kernel executes than the reference's arithmetic as written
+                             "executed_over_algorithmic": round(pmc[2]["valu_lane_instr_per_sample"] / ops, 3)
+                             if pmc and pmc[2].get("valu_lane_instr_per_sample") else None,
+                             "kernel": "render_kernel", "kernel_ms": round(kern_ms, 3),
+                             "algorithmic_ops_per_sample": round(ops, 1),
+                             "kernel_msamples_per_s_per_gpu": round(kernel_samples_per_s / world / 1e6, 2),
+                             "hbm_algorithmic_bytes": algorithmic_bytes, "hbm_algorithmic_bytes_scene": scene_bytes},
+            })
+            if cpu_line:
+                line["cpu_baseline"] = cpu_line
+                line["parity"] = parity
         if dist_path:
             # the N > 1 line explains itself: every rank's kernel time, the exchange step on its own, what the collective layer reports,
             # and (parity mode) the shard's own chain floor as measured on ONE GPU — where strong scaling must flatten
@@ -625,9 +670,6 @@ def main() -> None:
                 line["predicted_chain_floor_source"] = floor[1] if floor else None
         if other:
             line[other["scaling"] + "_scaling"] = other
-        if cpu_line:
-            line["cpu_baseline"] = cpu_line
-            line["parity"] = parity
         print(json.dumps(line), flush=True)
     if dist_path:
         dist.destroy_process_group()

@@ -243,3 +243,37 @@ def test_pmc_recordings_carry_the_build_they_belong_to(tmp_path):
     (tmp_path / "x_pmc_summary.json").write_text(json.dumps(rec))
     got = bench.pmc_traffic("cornell", 8, 8, 1, tmp_path)
     assert got[3] == "0" * 16 and got[4] == "abc" and got[3] != bench.kernels_sha16()   # main() nulls the PMC fields for such a record
+
+
+def test_dump_outputs_writes_the_frame_or_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: the frame as float32 .npy when it fits in DUMP_MAX_BYTES, else the same seeded sample of its pixels in every
+    run (values float32, linear pixel ids float64), within the limit."""
+    import numpy as np
+    bench = load_bench()
+    frame = np.random.default_rng(5).random((18, 32, 3), dtype=np.float32)
+    bench.dump_outputs(tmp_path / "a", frame)
+    got = np.load(tmp_path / "a" / "frame.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, frame)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 2000)
+    for d in ("b", "c"):
+        bench.dump_outputs(tmp_path / d, frame)
+    vals, idx = np.load(tmp_path / "b" / "frame_sample.npy"), np.load(tmp_path / "b" / "frame_sample_index.npy")
+    assert not (tmp_path / "b" / "frame.npy").exists()
+    assert vals.dtype == np.float32 and idx.dtype == np.float64 and vals.nbytes + idx.nbytes <= 2000
+    assert np.all(np.diff(idx) > 0) and idx[-1] < 18 * 32
+    assert np.array_equal(vals, frame.reshape(-1, 3)[idx.astype(np.int64)])
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "frame_sample_index.npy"))
+
+
+def test_full_and_dump_outputs_options_reach_the_ranks():
+    """--full and --dump-outputs are options of the command line, and a self-launched N-GPU run hands them to its ranks."""
+    import subprocess
+    import sys
+    import os
+    env = dict(os.environ, PT_BENCH_DRY_LAUNCH="1")
+    env.pop("WORLD_SIZE", None)
+    args = ["--gpus", "2", "--steps", "2", "--warmup", "0", "--full", "--dump-outputs", "out"]
+    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), *args], env=env, capture_output=True, text=True, check=True).stdout
+    assert json.loads(out)["launch"][-len(args):] == args
+    bad = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "0"], env=env, capture_output=True, text=True)
+    assert bad.returncode != 0 and "--steps" in bad.stderr

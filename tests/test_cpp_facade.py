@@ -158,12 +158,12 @@ def test_example_main_missing_image_gets_the_fallback_texel(example_bin, tmp_pat
     assert img[:, 40:44].copy().view(np.float32)[:, 0].tolist() == [1.0, 5.0]
 
 
-@pytest.mark.skipif(not Path("/root/reference/images/Xilinx.jpg").exists(), reason="the reference tree is only present in the build container")
 def test_example_main_opens_the_references_own_image_files(example_bin, tmp_path):
     """run with the reference's own ../images directory, the C++ host decodes Xilinx.jpg and SYCL.png itself
     (pt/image_io.hpp) and builds byte for byte the tables and the atlas layout the Python host builds from the same files (PIL)."""
     out = tmp_path / "smoke.bin"
-    r = subprocess.run([str(example_bin), "400", "225", "1", str(tmp_path / "x.png"), str(out), "/root/reference/images"], check=True,
+    ref_images = ROOT / "tests" / "golden" / "reference_images"  # the reference's images/ directory, byte for byte
+    r = subprocess.run([str(example_bin), "400", "225", "1", str(tmp_path / "x.png"), str(out), str(ref_images)], check=True,
                        capture_output=True, text=True)
     assert "ERROR" not in r.stderr
     n, (hb, mb, tb, cb) = read_dump(out)

@@ -41,7 +41,7 @@ def test_bench_distributed_line_schema():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_PORT=str(29700 + os.getpid() % 200))
     env.pop("WORLD_SIZE", None); env.pop("RANK", None)
     out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--dist-single", "--config", "cfg2", "--steps", "1", "--warmup", "0",
-                          "--spp", "16", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=900)
+                          "--spp", "16", "--no-cpu-baseline", "--full"], capture_output=True, text=True, env=env, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.lstrip().startswith('{"metric"')][-1])
     d = line["distributed"]

@@ -1,7 +1,7 @@
 """pt/image_io.hpp — the C++ host's own PNG / baseline-JPEG / PPM decoders and its PNG writer (a main.cpp-style
 C++ caller opens the reference's own images/Xilinx.jpg and images/SYCL.png and writes out.png, without stb).  Every decoded pixel is
 compared with PIL's — the loader of the Python host, so both hosts put the same texels into the atlas — on the reference's two images
-(when /root/reference is present: the build container) and on generated files: chroma sub-sampling 4:4:4 / 4:2:2 / 4:2:0 / 4:4:0, restart
+(copies of its images/ directory under tests/golden/reference_images) and on generated files: chroma sub-sampling 4:4:4 / 4:2:2 / 4:2:0 / 4:4:0, restart
 intervals, sizes that are not multiples of the MCU, grey JPEG; PNG colour types grey / RGB / palette / with alpha, 8 and 16 bits, all five
 filter types, multi-chunk IDAT.  Unsupported files fail with a reason (the caller then falls back like texture.hpp:106-111)."""
 import io
@@ -15,7 +15,7 @@ import pytest
 
 PIL = pytest.importorskip("PIL.Image")
 ROOT = Path(__file__).resolve().parent.parent
-REF_IMAGES = Path("/root/reference/images")
+REF_IMAGES = ROOT / "tests" / "golden" / "reference_images"  # the reference's images/Xilinx.jpg and images/SYCL.png, byte for byte
 
 
 @pytest.fixture(scope="module")
@@ -52,7 +52,6 @@ def picture(w, h, seed):
     return np.clip(img, 0, 255).astype(np.uint8)
 
 
-@pytest.mark.skipif(not REF_IMAGES.exists(), reason="the reference tree is only present in the build container")
 def test_the_references_own_images_decode_like_the_python_host(tool, tmp_path):
     for name, shape in (("Xilinx.jpg", (512, 1024, 3)), ("SYCL.png", (559, 1280, 3))):
         got = decode(tool, REF_IMAGES / name, tmp_path)

@@ -22,13 +22,24 @@ def test_xorshift_matches_reference_golden(orc):
         assert orc.xorshift_stream(int(seed), len(values)) == values, f"seed {seed}"
 
 
+def ref_kat_stdout(binary: Path, name: str) -> str:
+    """stdout of a known-answer binary built from the reference's own headers (oracle/_ref: oracle/Makefile target `ref`, only where
+    the reference tree is present): run live where it was built — and then it must equal the record — else the record of its
+    output, tests/golden/ref_kat_outputs.json."""
+    rec = json.loads((GOLDEN / "ref_kat_outputs.json").read_text())[name]
+    if not binary.exists():
+        return rec["stdout"]
+    out = subprocess.run([str(binary)] + rec["args"], capture_output=True, text=True, check=True).stdout
+    assert out == rec["stdout"], f"{binary.name}: output differs from tests/golden/ref_kat_outputs.json"
+    return out
+
+
 def test_xorshift_matches_reference_binary_live(orc):
     """oracle/_ref/xorshift_kat is the reference's own xorshift.hpp compiled from /root/reference."""
-    if not orc.REF_KAT.exists():
-        pytest.skip("oracle/_ref not built (reference tree absent)")
     seeds = [1, 2, 12345, 2463534242, 0xFFFFFFFF, 0x80000000, 77777]
-    out = subprocess.run([str(orc.REF_KAT), "64"] + [str(s) for s in seeds], capture_output=True, text=True, check=True)
-    for line, seed in zip(out.stdout.strip().splitlines(), seeds):
+    out = ref_kat_stdout(orc.REF_KAT, "xorshift_kat")
+    assert len(out.strip().splitlines()) == len(seeds)
+    for line, seed in zip(out.strip().splitlines(), seeds):
         head, vals = line.split(":")
         assert int(head) == seed
         assert orc.xorshift_stream(seed, 64) == [int(v) for v in vals.split()]
@@ -39,10 +50,8 @@ def test_dev_visit_dispatches_by_variant_index_live(orc):
     whose position in the variant equals index(), and hands the callable THAT alternative — so the ABI's integer tags
     (include/pt_render.h: PT_HIT_* / PT_MAT_* / PT_TEX_*, the rect axis, the medium's boundary kind), which are the reference's
     variant positions, name the code path the reference would take."""
-    if not orc.REF_VISIT_KAT.exists():
-        pytest.skip("oracle/_ref not built (reference tree absent)")
     from path_tracer_amd import abi
-    out = subprocess.run([str(orc.REF_VISIT_KAT)], capture_output=True, text=True, check=True).stdout.strip().splitlines()
+    out = ref_kat_stdout(orc.REF_VISIT_KAT, "visit_kat").strip().splitlines()
     rows = [l.split() for l in out]
     fam = {}
     for name, index, tag, payload in rows:

@@ -17,10 +17,10 @@ tools/profile_round.sh r06_cornell 3 1 > $O/profile_cornell.log 2>&1            
 tools/profile_round.sh r06_smoke 3 1 --config cfg3 > $O/profile_smoke.log 2>&1                                      # cfg3
 tools/profile_round.sh r06_cfg1 20 3 --config cfg1 > $O/profile_cfg1.log 2>&1                                       # cfg1: the reference's own workload
 PT_PROFILE_MEM=1 tools/profile_round.sh r06_triangles 1 0 --config cfg5 > $O/profile_triangles.log 2>&1            # cfg5 (+ the memory-system passes)
-python bench.py --steps 20 --warmup 2 > $O/bench_cfg2_steps20.json 2> $O/bench_cfg2_steps20.err
+python bench.py --full --steps 20 --warmup 2 > $O/bench_cfg2_steps20.json 2> $O/bench_cfg2_steps20.err
 if [ "$1" != "profiles-only" ]; then
-  python bench.py --steps 5 --warmup 1 --mode fast > $O/bench_cfg2_fast_mode.json 2>/dev/null
-  python bench.py --gpus 1 --dist-single --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_cfg2_dist_single.json 2>/dev/null
+  python bench.py --full --steps 5 --warmup 1 --mode fast > $O/bench_cfg2_fast_mode.json 2>/dev/null
+  python bench.py --full --gpus 1 --dist-single --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_cfg2_dist_single.json 2>/dev/null
   PT_ROUND=6 PT_SHARD_JSON=$O/shard_table_cornell_1080p_1024spp.json python tools/shard_table.py cornell 2>&1 | grep -v amdgpu.ids > $O/shard_table_cornell_1080p_1024spp.txt
   PT_ROUND=6 PT_SHARD_JSON=$O/shard_table_smoke_4k_512spp.json python tools/shard_table.py smoke 3840 2160 512 2>&1 | grep -v amdgpu.ids > $O/shard_table_smoke_4k_512spp.txt
   PT_ROUND=6 PT_SHARD_JSON=$O/shard_table_smoke_4k_4096spp.json python tools/shard_table.py smoke 3840 2160 4096 2>&1 | grep -v amdgpu.ids > $O/shard_table_smoke_4k_4096spp.txt
