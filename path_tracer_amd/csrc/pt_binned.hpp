@@ -287,12 +287,12 @@ __global__ __launch_bounds__(kBlock, PT_MIN_WAVES_TRIPOOL) void bin_finish_kerne
 // ---- the counting sort of a generation's requests -----------------------------------------------------------------------------------
 // keys: [0, n_keys); hist[k] = requests under key k.  bin_count_kernel: per block of 1024 keys the number of requests and of packets
 // (ceil(count / 64) each); bin_prefix_kernel: the exclusive prefix of the blocks' totals; bin_offsets_kernel: per key the offset of its
-// rays in `sorted`, per packet its (key, chunk); zeroes the histogram for the next generation.
+// rays in `sorted`, per packet its (key, ordinal within the key); zeroes the histogram for the next generation.
 struct SortArgs {
   unsigned int* hist;    // [n_keys]
   unsigned int* offs;    // [n_keys + 1]
   uint2* block_tot;      // [n_blocks]: (requests, packets) of a block, then their exclusive prefix
-  int2* packets;         // (key, chunk)
+  int2* packets;         // (key, the packet's ordinal within the key)
   unsigned int* ctl;     // [0] -, [1] n_packets, [2] band_kernel's packet counter, [3] live pixels of the generation (read by the host), [4] the accumulator bin_step_kernel adds to, [5] bin_finish_kernel's pixel queue
   int n_keys, n_blocks;
   int full_slices;       // a packet of the last key ("every triangle, exactly") is cut into this many slices of the run, one wave each
@@ -352,7 +352,9 @@ __global__ __launch_bounds__(1024) void bin_offsets_kernel(SortArgs sa) {
     const unsigned int off = bt.x + bs + is - c;
     unsigned int pk = bt.y + bq + iq - q;
     sa.offs[k] = off;
-    for (unsigned int ch = 0; ch < q; ch++) sa.packets[pk + ch] = int2{k, (int)((ch / slices) | ((ch % slices) << 16))}; // (chunk | slice << 16)
+    // a packet is (key, its ordinal within the key): band_kernel derives chunk = ordinal / slices and slice = ordinal % slices.  No bit
+    // fields — a key may hold the whole frame (every pixel irregular, or beyond the last rho class), far more than 2^16 chunks of 64 rays
+    for (unsigned int ch = 0; ch < q; ch++) sa.packets[pk + ch] = int2{k, (int)ch};
     if (c) sa.hist[k] = 0u;
   }
 }
@@ -414,7 +416,9 @@ __global__ __launch_bounds__(64 * kBandWaves, 4) void band_kernel(BandArgs b) {
     pid = (unsigned int)__builtin_amdgcn_readfirstlane((int)pid);
     if (pid >= n_packets) break;
     const int2 pk = b.packets[pid];
-    const int key = __builtin_amdgcn_readfirstlane(pk.x), chunk = __builtin_amdgcn_readfirstlane(pk.y) & 0xffff, slice = __builtin_amdgcn_readfirstlane(pk.y) >> 16;
+    const int key = __builtin_amdgcn_readfirstlane(pk.x);
+    const unsigned int ord = (unsigned int)__builtin_amdgcn_readfirstlane(pk.y), slices = key > base_all ? (unsigned int)b.full_slices : 1u; // (bin_offsets_kernel)
+    const int chunk = (int)(ord / slices), slice = (int)(ord % slices);
     const unsigned int o0 = b.offs[key], o1 = b.offs[key + 1];
     const int n = min(64, (int)(o1 - o0) - chunk * 64);
     // the list of this key: a bin of one of the maps, or every record

@@ -1610,7 +1610,7 @@ struct TriPrimCtx {
   bool prim;  // per lane: this ray is a camera ray (the first of its sample) of a pinhole camera
   int xy;     // per lane: pixel x | y << 16
   int pix;    // per lane: the pixel's id in this render (the cache tag)
-  const __attribute__((address_space(4))) float* foot; // uniform: (llc - origin) xyz, hor / W xyz, ver / H xyz, dd  (the kernel arguments' KArgs::foot)
+  const __attribute__((address_space(4))) float* foot; // uniform: (llc - origin) xyz, hor / W xyz, ver / H xyz, dd, the camera's absolute rounding (the kernel arguments' KArgs::foot)
   unsigned int* cache; // all lanes' cache lines; NULL: no cache
 };
 
@@ -1860,18 +1860,37 @@ __device__ __forceinline__ bool tri_pool_scan(glb_f4p pool, cst_f4p cblob, int h
         else {
           const f4 D = cblob[hdr + 8 + listed_k];
           const int R = as_i(D.x);
-          int k0 = 0, i0 = R, i1 = -1, j0 = R, j1 = -1;
-          bool one_face = true;
-#pragma unroll
-          for (int q = 0; q < 4; q++) {
-            const V3 dq4 = cr.d + ((q & 1) ? 0.5f : -0.5f) * fh + ((q & 2) ? 0.5f : -0.5f) * fv;
-            int k, ci, cj;
-            tri_dir_cell(dq4, R, k, ci, cj);
-            if (q == 0) k0 = k;
-            one_face = one_face && k == k0;
-            i0 = min(i0, ci); i1 = max(i1, ci); j0 = min(j0, cj); j1 = max(j1, cj);
+          // THE BINS, CONSERVATIVELY: every camera ray's own bin (tri_dir_bin of the ray as rounded) must be among them.  A camera ray of the
+          // pixel is llc + s hor + t ver - origin rounded in binary32, s and t within half a pixel of the centre's, so per component
+          //   |d_i - cr.d_i| <= 0.5 (|fh_i| + |fv_i|) x 1.001 (the rounding of fh, fv, s, t, relative)  +  foot[10] (the absolute rounding of
+          //   the camera arithmetic and of cr.d: it scales with |origin| and |llc|, not with |d|, and far from the origin exceeds a pixel).
+          // The pixel's four corner directions are no bound: they are rounded at the magnitude of |d|, the rays at that of |origin|.  Over the
+          // box [lo, hi] the face is k for every ray only if |d_k| exceeds both other components everywhere in it (else: no cache); with
+          // d_k of one sign, d_a / d_k and d_b / d_k are monotone in each argument, so the box's corners span their ranges; widened by 1e-5
+          // (tri_dir_cell's rcp, product and sum, and these quotients, err by a few ulp of |p| <= 1, i.e. < 1e-6), the cells of the two
+          // ends bound the cell of every ray.  Up to 2 x 2 bins of one face are listed; a wider box (a far camera, a wide pixel) gets no cache.
+          const float rr = pc->foot[10];
+          const V3 ext = mk(0.5f * (__builtin_fabsf(fh.x) + __builtin_fabsf(fv.x)) * 1.001f + rr, 0.5f * (__builtin_fabsf(fh.y) + __builtin_fabsf(fv.y)) * 1.001f + rr,
+                            0.5f * (__builtin_fabsf(fh.z) + __builtin_fabsf(fv.z)) * 1.001f + rr);
+          const V3 lo = cr.d - ext, hi = cr.d + ext;
+          auto amin = [](float l, float u) { return l > 0.0f ? l : u < 0.0f ? -u : 0.0f; };
+          auto amax = [](float l, float u) { return __builtin_fmaxf(__builtin_fabsf(l), __builtin_fabsf(u)); };
+          const float n0 = amin(lo.x, hi.x), n1 = amin(lo.y, hi.y), n2 = amin(lo.z, hi.z), m0 = amax(lo.x, hi.x), m1 = amax(lo.y, hi.y), m2 = amax(lo.z, hi.z);
+          const int k0 = (n0 > m1 && n0 > m2) ? 0 : (n1 > m0 && n1 > m2) ? 1 : (n2 > m0 && n2 > m1) ? 2 : -1;
+          int i0 = R, i1 = -1, j0 = R, j1 = -1;
+          if (k0 >= 0) {
+            const float kl = k0 == 0 ? lo.x : k0 == 1 ? lo.y : lo.z, kh = k0 == 0 ? hi.x : k0 == 1 ? hi.y : hi.z;
+            const float al = k0 == 0 ? lo.y : k0 == 1 ? lo.z : lo.x, ah = k0 == 0 ? hi.y : k0 == 1 ? hi.z : hi.x;
+            const float bl = k0 == 0 ? lo.z : k0 == 1 ? lo.x : lo.y, bh = k0 == 0 ? hi.z : k0 == 1 ? hi.x : hi.y;
+            const float halfR = 0.5f * (float)R;
+            auto cell = [&](float p) { return min(max((int)__builtin_floorf((p + 1.0f) * halfR), 0), R - 1); };
+            const float a0 = al / kl, a1 = al / kh, a2 = ah / kl, a3 = ah / kh, b0 = bl / kl, b1 = bl / kh, b2 = bh / kl, b3 = bh / kh;
+            i0 = cell(__builtin_fminf(__builtin_fminf(a0, a1), __builtin_fminf(a2, a3)) - 1e-5f);
+            i1 = cell(__builtin_fmaxf(__builtin_fmaxf(a0, a1), __builtin_fmaxf(a2, a3)) + 1e-5f);
+            j0 = cell(__builtin_fminf(__builtin_fminf(b0, b1), __builtin_fminf(b2, b3)) - 1e-5f);
+            j1 = cell(__builtin_fmaxf(__builtin_fmaxf(b0, b1), __builtin_fmaxf(b2, b3)) + 1e-5f);
           }
-          if (!one_face || (i1 - i0 + 1) * (j1 - j0 + 1) > 4) n = -1;
+          if (k0 < 0 || (i1 - i0 + 1) * (j1 - j0 + 1) > 4) n = -1;
           const unsigned int foff = (unsigned int)as_i(D.z);
           for (int cj = j0; cj <= j1 && n >= 0; cj++)
             for (int ci = i0; ci <= i1 && n >= 0; ci++) {

@@ -133,7 +133,7 @@ struct KArgs {
   long long fast_stride; // floats per chunk plane of the workspace
   // the camera rays' candidate cache of the triangle-pool kernels (pt_device.hpp: TriPrimCtx): one line per resident lane; NULL: none
   unsigned int* tri_cache;
-  float foot[10];        // (llc - origin) xyz, hor / W xyz, ver / H xyz, the bound dd on |d - d_centre| over a pixel's camera rays
+  float foot[11];        // (llc - origin) xyz, hor / W xyz, ver / H xyz, the bound dd on |d - d_centre| over a pixel's camera rays, dd's rounding term
 };
 
 // Per-lane state of the persistent loop.  A lane owns ONE pixel at a time, for all of its samples (the
@@ -1882,6 +1882,8 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
       lh = std::sqrt(lh); lv = std::sqrt(lv);
       // half a pixel each way (the jitter may round to the pixel's far edge), + the binary32 rounding of the camera's own arithmetic and of the centre ray
       a.foot[9] = (float)((0.5 * (lh + lv)) * 1.001 + 1e-5 * dmax);
+      // ... and that rounding term alone, per component (the cache's choice of bins: pt_device.hpp, tri_pool_scan)
+      a.foot[10] = (float)(1e-5 * dmax);
     }
     hipLaunchKernelGGL(kernel, grid, block, shmem, st, a);
     PT_HIP(hipGetLastError());

@@ -147,11 +147,14 @@ def test_random_scene_sharded(orc, seed):
     assert_bit_identical(unshard_reference(np.stack(parts), w, h, 3), ref, f"seed {seed} 3 shards")
 
 
-def random_sphere_field(seed: int):
+def random_sphere_field(seed: int, offset=None, cam_dist=None, vfov=None):
     """Runs of small spheres big enough for the culling grid (>= 48), with everything the grid has to get right varied at
     random: radii spread (so the "small" threshold and the margin differ), flat or tall fields, moving fractions, touching and
     duplicated spheres, negative radii, big spheres inside the field, large coordinates, a second sphere run, other kinds
-    before / between / after, and cameras inside, near, far and very far (beyond the grid's rlimit: full-list fallback)."""
+    before / between / after, and cameras inside, near, far and very far (beyond the grid's rlimit: full-list fallback).
+    offset: a world offset, in units of the field's scale, added to the field's centre (scene and camera move together); cam_dist
+    (also in units of the scale) and vfov replace the drawn camera distance and field of view.  None: the scene of the seed as it always was (every
+    random draw is made either way, so the rest of the scene does not change)."""
     rng = np.random.default_rng(seed)
 
     def color():
@@ -164,6 +167,8 @@ def random_sphere_field(seed: int):
 
     scale = float(10.0 ** rng.integers(-1, 3))          # field size 0.1 .. 100
     centre = np.array([(rng.random() - 0.5) * 50 * (seed % 3 == 0) for _ in range(3)])
+    if offset is not None:
+        centre = centre + np.asarray(offset, dtype=np.float64) * scale
     r_med = 0.02 * scale * (0.5 + rng.random())
     tall = rng.random() < 0.4
     n = int(rng.integers(60, 400))
@@ -196,9 +201,11 @@ def random_sphere_field(seed: int):
         hs.append(constant_medium(sphere(tuple(centre + [0, 0.2 * scale, 0]), float(0.2 * scale), lambertian_material((1, 1, 1))),
                                   float(2.0 / scale), color()))
     dist = float(rng.choice([0.3, 1.5, 40.0, 4000.0])) * scale
+    if cam_dist is not None:
+        dist = float(cam_dist) * scale
     frm = centre + np.array([dist * 0.7, dist * 0.35 + 0.05 * scale, dist * 0.6])
     cam = dict(look_from=tuple(float(x) for x in frm), look_at=tuple(float(x) for x in centre + [0, 0.05 * scale, 0]), vup=(0, 1, 0),
-               vfov=float(min(70.0, 2 * np.degrees(np.arctan(0.7 * scale / max(dist, 1e-6))) + 5.0)),
+               vfov=float(min(70.0, 2 * np.degrees(np.arctan(0.7 * scale / max(dist, 1e-6))) + 5.0)) if vfov is None else float(vfov),
                aperture=float(0.02 * scale * (rng.random() < 0.3)), focus_dist=float(max(dist, 0.1 * scale)),
                time0=float(-0.3 * (seed % 7 == 5)), time1=1.0)
     return pack(hs), cam
@@ -298,7 +305,7 @@ def test_random_box_fields_through_the_slab_culling(orc, lib, seed):
     assert_bit_identical(R.render_host(w, h, 70, ps, c, flags=F), orc.render(ps, c.c, w, h, 70, flags=F), f"box field seed {seed} fast mode")
 
 
-def random_triangle_field(seed: int, images: int = 0):
+def random_triangle_field(seed: int, images: int = 0, offset=None, cam_dist=None, vfov=None):
     """Long runs of Moller-Trumbore triangles for the exact triangle pool (csrc/pt_tripool.hpp; pt_device.hpp: tri_pool_scan),
     with what it has to get right varied at random: small random triangles, SLIVERS (edges nearly parallel: wide grazing
     bands, the always list), degenerate triangles (repeated vertices, collinear vertices), exact duplicates and coplanar
@@ -306,7 +313,8 @@ def random_triangle_field(seed: int, images: int = 0):
     the coordinate planes seen by cameras that look along those planes (every primary ray grazes them), huge and tiny
     scales, off-origin centres, a second triangle run behind another kind, and cameras inside, near, far and beyond the
     pool's rlimit (fallback to the full scan).  images = 1: an image-textured sphere beside the field (the pool kernels that carry
-    the winner's u, v); images = 2: image-textured triangles as well (u, v of every accepted triangle)."""
+    the winner's u, v); images = 2: image-textured triangles as well (u, v of every accepted triangle).  offset, cam_dist, vfov: as
+    random_sphere_field (None: the seed's scene as it always was)."""
     rng = np.random.default_rng(seed)
     atlas = TextureAtlas() if images else None
     img = image_texture.from_array(rng.integers(0, 256, (11, 19, 3), dtype=np.uint8), 1.5, atlas) if images else None
@@ -321,6 +329,8 @@ def random_triangle_field(seed: int, images: int = 0):
 
     scale = float(10.0 ** rng.integers(-2, 3))          # field size 0.01 .. 100
     centre = np.array([(rng.random() - 0.5) * 300 * scale * (seed % 4 == 1) for _ in range(3)])
+    if offset is not None:
+        centre = centre + np.asarray(offset, dtype=np.float64) * scale
     size = scale * float(rng.choice([0.03, 0.1, 0.3]))   # typical edge
     n = int(rng.integers(300, 2500))
     mats = [material() for _ in range(12)]
@@ -382,13 +392,15 @@ def random_triangle_field(seed: int, images: int = 0):
                           float(centre[2] - 0.7 * scale), lightsource_material((4, 4, 4))))
     mode = int(rng.integers(0, 5))
     dist = float([0.05, 0.6, 2.0, 40.0, 30000.0][mode]) * scale
+    if cam_dist is not None:
+        dist = float(cam_dist) * scale
     frm = centre + np.array([dist * 0.55, dist * 0.3, dist * 0.75])
     at = centre.copy()
     if seed % 3 == 0:                                       # look ALONG a coordinate plane through the centre
         frm = centre + np.array([dist + 0.3 * scale, 0.0, 0.0])
         at = centre + np.array([0.0, 0.0, 0.0])
     cam = dict(look_from=tuple(float(x) for x in frm), look_at=tuple(float(x) for x in at), vup=(0, 1, 0),
-               vfov=float(70.0 if dist < scale else min(70.0, 2 * np.degrees(np.arctan(0.7 * scale / dist)) + 5.0)),
+               vfov=float(70.0 if dist < scale else min(70.0, 2 * np.degrees(np.arctan(0.7 * scale / dist)) + 5.0)) if vfov is None else float(vfov),
                aperture=0.0, focus_dist=float(max(dist, 0.1 * scale)), time0=0.0, time1=1.0)
     return (pack(hs, atlas) if images else pack(hs)), cam
 
