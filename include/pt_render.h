@@ -365,6 +365,66 @@ int pt_unshard_tiles(const float* gathered_device, const PtRenderParams* p,
 int pt_tonemap_rgb8(const float* fb_device, int32_t width, int32_t height,
                     uint8_t* rgb8_device, void* stream);
 
+/* ---- progressive rendering: one frame rendered in sample windows -------------------------------------------------------------------
+ * Added without an ABI version change (PT_ABI_VERSION stays 2): a caller detects the feature by the presence of these symbols.
+ *
+ * A PtAccum holds the device-resident per-pixel state of one frame: the plain radiance sum (float3, laid out like pt_render's frame
+ * buffer: [y][x][3], or [local tile][64][3] for shards) and the xorshift32 generator state (u32 per local pixel, indexed like the
+ * scheduler's per-pixel states: local tile * 64 + ly * 8 + lx).  pt_render_accumulate renders the samples [done, done + samples) of
+ * every pixel into it: a window that starts at 0 seeds the generator with the pixel's linear id (render.hpp:130-132), a later one
+ * resumes from the saved state — the reference's single stream per pixel, summed in order (render.hpp:95-102).
+ *
+ * CONTRACT: after any sequence of windows totalling N samples, pt_accum_resolve writes the same bits that pt_render writes with
+ * samples = N and the same scene, camera, depth, shard and flags — for every split, N windows of 1 sample included.  (PT_FLAG_FAST_RNG:
+ * the same holds against pt_render's fast mode, under the window rule below.)
+ *
+ * Binding.  The accumulator is bound at create to the scene and to the frame parameters (width, height, depth, shard, flags; `samples`
+ * is ignored), and by its first window to that window's camera: a later window whose PtCamera differs (byte compare of the 96 bytes)
+ * returns PT_ERR_INVALID_ARG.  The scene must outlive the accumulator and stay the same scene: the state means nothing against other
+ * tables.  Windows are stream-ordered like renders of one PtScene (same stream, or synchronised by the caller; one host thread at a
+ * time); they share the scene's launch workspaces with its other renders, never its tile order: the accumulator keeps its own.
+ *
+ * Rejected (PT_ERR_INVALID_ARG): samples <= 0 or a total past INT32_MAX; PT_FLAG_SINGLE_STREAM (one global stream, no per-pixel state);
+ * pt_accum_resolve / pt_accum_tonemap_rgb8 at 0 samples; pt_accum_tonemap_rgb8 with shard_count > 1 (pt_tonemap_rgb8's frame layout).
+ * PT_FLAG_FAST_RNG: a window may only START on a multiple of PT_FAST_CHUNK_SPP samples (once one ends off a multiple, the next is
+ * refused) and holds at most 8 128 samples (PT_ERR_TOO_LARGE, as pt_render); the total is not capped.
+ *
+ * Scheduling.  A window long enough for pt_render's cost probe (16 samples and more) probes with its own length, starting from the
+ * state; a shorter one dequeues tiles in the heaviest-first order the accumulator kept from its last probed window (raster order
+ * before the first).  Scenes with PtTuning.tri_binned render their windows with the persistent kernels (the same image).
+ *
+ * Device memory: pt_accum_create allocates the state (pt_accum_state_bytes, less the header) and sizes the scene's launch workspaces
+ * for the frame; pt_render_accumulate allocates nothing, except in fast mode, whose chunk workspace pt_scene_reserve sizes (called
+ * with samples = the largest window).
+ *
+ * Export format (pt_accum_export / pt_accum_import; host byte order): a PT_ACCUM_HEADER_BYTES header — u32 magic PT_ACCUM_MAGIC, u32 format
+ * PT_ACCUM_FORMAT, i32 width, height, depth, shard_index, shard_count, u32 flags, i32 samples done, i32 camera bound (0 / 1), 6 reserved
+ * words (0), the bound PtCamera (96 bytes) — then pt_framebuffer_floats() floats of sums, then pt_shard_tiles() * 64 u32 generator
+ * states.  Import refuses a state whose header does not match the accumulator's frame parameters.                                   */
+#define PT_ACCUM_MAGIC 0x43415450u /* "PTAC" */
+#define PT_ACCUM_FORMAT 1
+#define PT_ACCUM_HEADER_BYTES 160
+typedef struct PtAccum PtAccum; /* device-resident per-pixel state of a frame rendered in sample windows */
+/* Validates the parameters (before any device call), allocates and zeroes the state on the current device (the scene's). */
+int pt_accum_create(const PtScene* scene, const PtRenderParams* p, PtAccum** out);
+void pt_accum_destroy(PtAccum* acc);
+/* Back to 0 samples: same scene and frame parameters; the camera binding and the kept tile order are released (a camera that moved
+ * starts a new image: the next window binds its camera). */
+int pt_accum_reset(PtAccum* acc, void* stream);
+int32_t pt_accum_samples(const PtAccum* acc); /* samples rendered so far (host-side count; -1 for NULL) */
+/* Render samples [done, done + samples) of every pixel; asynchronous on `stream` like pt_render. */
+int pt_render_accumulate(PtAccum* acc, const PtCamera* cam, int32_t samples, void* stream);
+/* fb = sum / done (correctly rounded, as render.hpp:102), pt_render's layout and bits; fb_device: pt_framebuffer_floats() floats. */
+int pt_accum_resolve(const PtAccum* acc, float* fb_device, void* stream);
+/* resolve + the output stage of pt_tonemap_rgb8 in one pass (whole frames): rgb8_device is [height][width][3], row 0 = top. */
+int pt_accum_tonemap_rgb8(const PtAccum* acc, uint8_t* rgb8_device, void* stream);
+/* Host function, no GPU: bytes of an exported state for these frame parameters (samples ignored); < 0 for invalid ones. */
+int64_t pt_accum_state_bytes(const PtRenderParams* p);
+/* Checkpoint into host memory of exactly pt_accum_state_bytes() bytes (synchronises `stream`). */
+int pt_accum_export(const PtAccum* acc, void* host, int64_t bytes, void* stream);
+/* Restore a checkpoint (validates the header; synchronises `stream`).  The next window resumes from it. */
+int pt_accum_import(PtAccum* acc, const void* host, int64_t bytes, void* stream);
+
 /* ---- function-level probes (parity tests call these; not used by render) ---- */
 
 /* One iteration of the bounce loop render.hpp:58-89 per record: hit_world,

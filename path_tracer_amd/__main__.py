@@ -1,8 +1,13 @@
 """Command-line caller of the hot path — the role of the reference's src/main.cpp:61-197 (scene → render → PNG).
 
     python -m path_tracer_amd --scene cornell --width 800 --height 480 --spp 100 --out out.png
+    python -m path_tracer_amd --scene cornell --spp 1024 --preview-every 64 --preview-dir previews --out out.png
+
+With --preview-every N the frame is rendered progressively (render.Accumulator): windows of N samples, DIR/preview_<spp>.png after
+each; the final --out PNG is byte-identical to the one written without these options.
 """
 import argparse
+import os
 import time
 
 from . import render as R
@@ -23,7 +28,12 @@ def main() -> None:
     ap.add_argument("--textures", default="reference", choices=["reference", "procedural"],
                     help="smoke scene: the decoded reference images (tests/golden/cfg1_textures.npz) or generated stand-ins")
     ap.add_argument("--export-textures", metavar="DIR", help="write Xilinx.ppm / SYCL.ppm for the C++ host and exit (no GPU)")
+    ap.add_argument("--preview-every", type=int, default=0, metavar="N",
+                    help="render in windows of N samples and write a preview PNG after each (progressive rendering)")
+    ap.add_argument("--preview-dir", default="previews", metavar="DIR", help="where --preview-every writes preview_<spp>.png")
     a = ap.parse_args()
+    if a.preview_every < 0:
+        ap.error("--preview-every must be >= 0")
     if a.export_textures:
         print(*scenes.export_reference_textures(a.export_textures), sep="\n")
         return
@@ -33,8 +43,23 @@ def main() -> None:
     packed, cam_args = scenes.build(a.scene, **kw)
     cam = scenes.make_camera(cam_args, a.width, a.height)
     t0 = time.perf_counter()
-    fb, ms = R.render(a.width, a.height, a.spp, packed, cam, a.depth, timed=True)
-    rgb8 = R.tonemap_rgb8(fb)
+    if a.preview_every > 0:
+        os.makedirs(a.preview_dir, exist_ok=True)
+        acc = R.Accumulator(a.width, a.height, packed, cam, a.depth)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ms = 0.0
+        while acc.samples < a.spp:
+            e0.record()
+            acc.add(min(a.preview_every, a.spp - acc.samples))
+            e1.record()
+            rgb8 = acc.tonemap_rgb8()
+            torch.cuda.synchronize()
+            ms += e0.elapsed_time(e1)
+            write_png(os.path.join(a.preview_dir, f"preview_{acc.samples}.png"), rgb8.cpu().numpy())
+        acc.close()
+    else:
+        fb, ms = R.render(a.width, a.height, a.spp, packed, cam, a.depth, timed=True)
+        rgb8 = R.tonemap_rgb8(fb)
     torch.cuda.synchronize()
     write_png(a.out, rgb8.cpu().numpy())
     n = a.width * a.height * a.spp

@@ -167,7 +167,25 @@ SIGNATURES = {
                                         C.POINTER(C.c_uint8), _FP]),
     "pt_debug_tri_pool": (C.c_int, [C.POINTER(PtSceneDesc), C.POINTER(C.c_int32)]),
     "pt_debug_flatten_pool": (C.c_int, [C.POINTER(PtSceneDesc), C.POINTER(PtTuning), C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_int64)]),
+    # progressive rendering (PtAccum): added without an ABI version change, so loaded optionally (ACCUM_SYMBOLS)
+    "pt_accum_create": (C.c_int, [_SCENE_P, C.POINTER(PtRenderParams), C.POINTER(C.c_void_p)]),
+    "pt_accum_destroy": (None, [C.c_void_p]),
+    "pt_accum_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pt_accum_samples": (C.c_int32, [C.c_void_p]),
+    "pt_render_accumulate": (C.c_int, [C.c_void_p, C.POINTER(PtCamera), C.c_int32, C.c_void_p]),
+    "pt_accum_resolve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pt_accum_tonemap_rgb8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pt_accum_state_bytes": (C.c_int64, [C.POINTER(PtRenderParams)]),
+    "pt_accum_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "pt_accum_import": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
 }
+
+# Entry points a library may lack and still load for everything else (include/pt_render.h: the feature is detected by their presence);
+# has_accumulator() tells whether the loaded one has them.
+ACCUM_SYMBOLS = frozenset(n for n in SIGNATURES if n.startswith("pt_accum_") or n == "pt_render_accumulate")
+PT_ACCUM_MAGIC = 0x43415450
+PT_ACCUM_FORMAT = 1
+PT_ACCUM_HEADER_BYTES = 160
 
 LIB_NAME = "libpt_render.so"
 _lib = None
@@ -212,7 +230,7 @@ def load_library() -> C.CDLL:
         pass  # torch-free hosts bind to /opt/rocm/lib through the library's RUNPATH
     lib = C.CDLL(str(path))
     for name, (res, args) in SIGNATURES.items():
-        if override_is_older_build(path, lib, name):
+        if override_is_older_build(path, lib, name) or (name in ACCUM_SYMBOLS and not hasattr(lib, name)):
             continue
         fn = getattr(lib, name)  # AttributeError if the library does not export what the header declares
         fn.restype = res
@@ -222,6 +240,12 @@ def load_library() -> C.CDLL:
         raise ImportError(f"{path}: ABI version {lib.pt_abi_version()} != {PT_ABI_VERSION}")
     _lib = lib
     return lib
+
+
+def has_accumulator(lib=None) -> bool:
+    """Does the loaded library offer progressive rendering (the PtAccum entry points)?"""
+    lib = lib or load_library()
+    return all(hasattr(lib, n) for n in ACCUM_SYMBOLS)
 
 
 def check(code: int, where: str) -> None:

@@ -109,6 +109,9 @@ struct KArgs {
   // sample resume_spp — the same stream, the same order of additions (render.hpp:95-101), and no sample is rendered twice.
   unsigned int* resume_rng;
   int resume_spp;
+  // Sample windows of a PtAccum (pt_render_accumulate): `samples` is the window's END, resume_spp its start, and a finished pixel leaves
+  // its plain radiance sum in fb and its generator's state in resume_rng — the probe's branch of lane_store — instead of the mean.
+  int keep_state;
   // Headline-family launches (launch_render): once prio_onset queue positions are taken, a wave sets its issue priority — every 64
   // iterations — by the samples its slowest pixel still has to render: >= prio_t3 -> 3, >= prio_t2 -> 2, >= prio_t1 -> 1, else 0 (render_kernel).
   // prio_t1 = 0: never.
@@ -130,6 +133,7 @@ struct KArgs {
   // then the chunk length, fast_chunks the chunks per pixel, samples_total the caller's spp, fb the partial-sum workspace
   // [chunk][framebuffer layout] (fast_reduce_kernel adds the chunks in order and divides).  0 = the reference's single stream.
   int fast_chunks, samples_total;
+  int fast_chunk0;       // global index of the launch's first chunk (sample windows start at 64 x fast_chunk0; pt_render: 0)
   long long fast_stride; // floats per chunk plane of the workspace
   // the camera rays' candidate cache of the triangle-pool kernels (pt_device.hpp: TriPrimCtx): one line per resident lane; NULL: none
   unsigned int* tri_cache;
@@ -347,7 +351,7 @@ __device__ __forceinline__ void lane_acquire(Lane& L, const KArgs& a) {
     // the last chunk of a pixel may be shorter: its sample counter starts ahead so that every chunk ends at k.samples
     const int n_here = min(k.samples, k.samples_total - chunk * k.samples);
     L.cold.begin((l * PT_TILE_PIXELS + in_tile) | (chunk << 24), x, y, k.samples - n_here);
-    L.rng = fast_seed(id, (uint32_t)chunk);
+    L.rng = fast_seed(id, (uint32_t)(chunk + k.fast_chunk0));
   } else {
     L.cold.begin(l * PT_TILE_PIXELS + in_tile, x, y);
     L.rng = id;
@@ -376,12 +380,16 @@ __device__ __forceinline__ void lane_store(Lane& L, const KArgs& a) {
   L.live = false;
   PT_COLD_ARGS(k, a);
   if (L.wide && ((threadIdx.x & 63) & ((1 << L.wide) - 1))) return; // wide phase: one lane of the group writes
-  if (k.cost) { // cost-probe pass: only the tile's ray count is kept
-    // a wave holds a tile until its last pixel is done, so a tile's duration follows its heaviest pixel; the cooperative
-    // kernels' model also needs the lane time, i.e. the sum
-    if (k.cost_max) atomicMax(&k.cost[L.cold.get_pix() >> 6], L.cold.get_iters() * PT_TILE_PIXELS);
-    else atomicAdd(&k.cost[L.cold.get_pix() >> 6], L.cold.get_iters());
-    if (k.resume_rng) { // ... and, where the frame launch resumes from it, the pixel's state after these samples (KArgs.resume_rng)
+  if (k.cost || k.keep_state) {
+    if (k.cost) { // cost-probe pass: only the tile's ray count is kept
+      // a wave holds a tile until its last pixel is done, so a tile's duration follows its heaviest pixel; the cooperative
+      // kernels' model also needs the lane time, i.e. the sum
+      if (k.cost_max) atomicMax(&k.cost[L.cold.get_pix() >> 6], L.cold.get_iters() * PT_TILE_PIXELS);
+      else atomicAdd(&k.cost[L.cold.get_pix() >> 6], L.cold.get_iters());
+    }
+    // ... and, where a later launch resumes from it (the frame launch after the probe, the next sample window of a PtAccum), the
+    // pixel's state after these samples (KArgs.resume_rng)
+    if (k.resume_rng) {
       const long long at = k.shard_count == 1 ? ((long long)L.cold.get_y() * k.width + L.cold.get_x()) * 3 : (long long)L.cold.get_pix() * 3;
       store_rgb(k.fb + at, L.cold.get_acc());
       k.resume_rng[L.cold.get_pix()] = L.rng;
@@ -1010,6 +1018,38 @@ __global__ void tonemap_kernel(const float* __restrict__ fb, uint8_t* __restrict
   }
 }
 
+// ---- sample windows (PtAccum) ---------------------------------------------------------------------------------------------------
+// fast mode: the window's chunk planes added to the running sum in chunk order, NOT divided — fast_reduce_kernel's order of additions
+// continued across windows (its first addition is 0 + plane 0, as the accumulator's sum starts at 0)
+__global__ void fast_accum_kernel(const float* __restrict__ partial, float* __restrict__ sum, long long n, long long stride, int chunks) {
+  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float s = sum[i];
+  for (int c = 0; c < chunks; c++) s = s + partial[(long long)c * stride + i];
+  sum[i] = s;
+}
+
+// fb = sum / done: lane_store's correctly rounded IEEE division (render.hpp:102; -fhip-fp32-correctly-rounded-divide-sqrt, no reciprocal)
+__global__ void accum_resolve_kernel(const float* __restrict__ sum, float* __restrict__ fb, long long n, float samples) {
+  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  fb[i] = sum[i] / samples;
+}
+
+// resolve + tonemap_kernel in one pass (whole frames): the same mean, then main.cpp:33-59 exactly as tonemap_kernel does it
+__global__ void accum_tonemap_kernel(const float* __restrict__ sum, uint8_t* __restrict__ rgb8, int width, int height, float samples) {
+  int x = blockIdx.x * blockDim.x + threadIdx.x, row = blockIdx.y; // row 0 = top
+  if (x >= width) return;
+  int j = height - 1 - row;
+  for (int ch = 0; ch < 3; ch++) {
+    float s = sqrt_rn(sum[((long long)j * width + x) * 3 + ch] / samples);
+    float cl = (s < 0.0f) ? 0.0f : (0.999f < s) ? 0.999f : s;
+    float sc = 256.0f * cl;
+    int v = (sc == sc) ? (int)sc : 0;
+    rgb8[((long long)row * width + x) * 3 + ch] = (uint8_t)v;
+  }
+}
+
 thread_local std::string g_last_error;
 
 // ---- tuning: include/pt_render.h PtTuning.  Resolved ONCE per scene (pt_scene_create / pt_debug_flatten), never on the launch path.
@@ -1525,6 +1565,15 @@ static int reserve_tiles(const PtScene* s, int local_tiles) {
   s->ws_tiles = local_tiles;
   return PT_OK;
 }
+// the camera rays' candidate cache of the triangle-pool kernels: one PT_TRI_CACHE_WORDS line per lane of the launch (grow-only)
+static int grow_tricache(const PtScene* s, size_t lanes) {
+  if (s->ws_tricache_lanes >= lanes) return PT_OK;
+  if (s->ws_tricache) (void)hipFree(s->ws_tricache);
+  s->ws_tricache = nullptr; s->ws_tricache_lanes = 0;
+  PT_HIP(hipMalloc((void**)&s->ws_tricache, lanes * PT_TRI_CACHE_WORDS * 4));
+  s->ws_tricache_lanes = lanes;
+  return PT_OK;
+}
 static int reserve_partial(const PtScene* s, size_t floats) {
   if (s->ws_partial_floats >= floats) return PT_OK;
   if (s->ws_partial) (void)hipFree(s->ws_partial);
@@ -1657,7 +1706,16 @@ static int reserve_binned(const PtScene* s, size_t N, size_t K, size_t& bytes) {
   return PT_OK;
 }
 
-static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderParams* p, float* fb, hipStream_t st) {
+// One sample window of a PtAccum (pt_render_accumulate): p->samples is the window's length, fb the accumulator's radiance sums.
+struct Window {
+  int done;          // samples the state already holds: the window renders [done, done + p->samples)
+  unsigned int* rng; // per local pixel: the generator's state after `done` samples
+  int* order;        // the accumulator's own heaviest-first tile order (and the cooperative kernels' split) ...
+  int* nsplit;
+  bool* has_order;   // ... valid once a window has probed
+};
+
+static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderParams* p, float* fb, hipStream_t st, const Window* w = nullptr) {
   int cur = -1;
   PT_HIP(hipGetDevice(&cur));
   if (cur != s->device)
@@ -1674,8 +1732,9 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
   a.shard_index = p->shard_index; a.shard_count = p->shard_count;
   a.n_tiles = n_tiles_of(p, &a.tiles_x);
   const int local_tiles = (a.n_tiles - p->shard_index + p->shard_count - 1) / p->shard_count; // tiles this shard owns
-  // pixels no lane owns (edge tiles, padded last tile, depth 0) read as 0
-  PT_HIP(hipMemsetAsync(fb, 0, (size_t)pt_framebuffer_floats(p) * sizeof(float), st));
+  a.keep_state = 0; a.fast_chunk0 = 0;
+  // pixels no lane owns (edge tiles, padded last tile, depth 0) read as 0 (a window's sums: zeroed by pt_accum_create / _reset)
+  if (!w) PT_HIP(hipMemsetAsync(fb, 0, (size_t)pt_framebuffer_floats(p) * sizeof(float), st));
   if (local_tiles <= 0) return PT_OK;
   a.fast_ok = (s->fast_ok && !(p->flags & PT_FLAG_NO_FASTDIV)) ? 1 : 0;
   if (p->flags & PT_FLAG_SINGLE_STREAM) { // the reference's single-task executor: one sequential chain, one lane
@@ -1688,7 +1747,8 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
     return PT_OK;
   }
   a.coop_prefix = (s->coop_ok && a.fast_ok && !(p->flags & PT_FLAG_NO_COOP)) ? s->coop_prefix : -1;
-  if (s->binned && !(p->flags & (PT_FLAG_FORCE_STREAM | PT_FLAG_FAST_RNG))) return launch_binned(s, a, p, local_tiles, st);
+  // (sample windows run the persistent kernels: both renderers give the reference's image, and only these resume a pixel)
+  if (s->binned && !w && !(p->flags & (PT_FLAG_FORCE_STREAM | PT_FLAG_FAST_RNG))) return launch_binned(s, a, p, local_tiles, st);
   const size_t blob_bytes = (size_t)s->blob_f4 * 16;
   // a scene with a triangle pool is queried through per-lane loads from the global blob: the scalar-cache resident kernels,
   // whatever its size (PT_FLAG_FORCE_STREAM: the streaming kernel, which scans every triangle, as the A/B)
@@ -1722,6 +1782,8 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
   a.tri_cache = nullptr;
   for (float& f : a.foot) f = 0.0f;
   a.resume_rng = nullptr; a.resume_spp = 0;
+  const bool window = w && !(p->flags & PT_FLAG_FAST_RNG); // a parity-mode sample window: resumes from / keeps the per-pixel state
+  if (window) { a.samples = w->done + p->samples; a.resume_rng = w->rng; a.resume_spp = w->done; a.keep_state = 1; }
   a.prio_onset = 0; a.prio_t1 = a.prio_t2 = a.prio_t3 = 0;
   a.order = nullptr;
   const bool mlds = lds && blob_bytes + (size_t)s->mats_f4 * 16 <= kMaxLdsWithMaterials;
@@ -1802,12 +1864,6 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
     // duplicate pixels): the NEW launch's stream waits for that launch's event on the device — the host does not block, so
     // pt_render stays asynchronous however many renders are queued (round 3 synchronised the host here, with the scene's
     // scheduling mutex held).
-    const unsigned int slot = s->next_queue % kQueueRing;
-    if (s->ring_done[slot]) PT_HIP(hipStreamWaitEvent(st, s->ring_done[slot], 0));
-    else PT_HIP(hipEventCreateWithFlags(&s->ring_done[slot], hipEventDisableTiming));
-    s->next_queue++; // (only once nothing above can fail any more)
-    a.queue = s->queues + 2 * slot; // [0] ordinary queue, [1] wide-phase queue
-    PT_HIP(hipMemsetAsync(a.queue, 0, 2 * sizeof(unsigned int), st));
     // one wave per tile is enough, except in the wide phase, where a split tile keeps G waves busy (how many tiles are
     // split is decided on the device, so such a launch simply fills the chip; surplus waves find the queues empty and exit)
     long long wanted = a.n_split ? (long long)resident_blocks : (launch_units + waves_per_block - 1) / waves_per_block;
@@ -1859,14 +1915,12 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
     // The camera rays' candidate cache (pt_device.hpp: TriPrimCtx): triangle-pool kernels, a pinhole camera (the rays of a pixel share
     // their origin), pixel coordinates that fit 16 bits.  One 1 KB line per lane of the launch; every line starts out belonging to no pixel.
     a.tri_cache = nullptr;
-    if (tri_pool && a.cam.lens_radius == 0.0f && !s->knobs.no_tri_cache && p->width <= 65535 && p->height <= 65535) {
-      const size_t lanes = (size_t)grid.x * block.x;
-      if (s->ws_tricache_lanes < lanes) {
-        if (s->ws_tricache) (void)hipFree(s->ws_tricache);
-        s->ws_tricache = nullptr; s->ws_tricache_lanes = 0;
-        PT_HIP(hipMalloc((void**)&s->ws_tricache, lanes * PT_TRI_CACHE_WORDS * 4));
-        s->ws_tricache_lanes = lanes;
-      }
+    // (sized ahead by pt_accum_create — reserve_tricache; grown here otherwise, BEFORE the queue slot below is taken, and a failed
+    // allocation only costs the cache: the image does not depend on it)
+    const size_t cache_lanes = (size_t)grid.x * block.x;
+    if (tri_pool && a.cam.lens_radius == 0.0f && !s->knobs.no_tri_cache && p->width <= 65535 && p->height <= 65535 &&
+        grow_tricache(s, cache_lanes) == PT_OK) {
+      const size_t lanes = cache_lanes;
       PT_HIP(hipMemsetAsync(s->ws_tricache, 0xff, lanes * PT_TRI_CACHE_WORDS * 4, st));
       a.tri_cache = s->ws_tricache;
       // the footprint of a pixel in direction space (camera.hpp:93-100 with lens_radius 0: d = llc + s hor + t ver - origin, s in [x / W, (x + 1) / W])
@@ -1885,6 +1939,12 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
       // ... and that rounding term alone, per component (the cache's choice of bins: pt_device.hpp, tri_pool_scan)
       a.foot[10] = (float)(1e-5 * dmax);
     }
+    const unsigned int slot = s->next_queue % kQueueRing;
+    if (s->ring_done[slot]) PT_HIP(hipStreamWaitEvent(st, s->ring_done[slot], 0));
+    else PT_HIP(hipEventCreateWithFlags(&s->ring_done[slot], hipEventDisableTiming));
+    s->next_queue++; // (only once nothing above can fail any more)
+    a.queue = s->queues + 2 * slot; // [0] ordinary queue, [1] wide-phase queue
+    PT_HIP(hipMemsetAsync(a.queue, 0, 2 * sizeof(unsigned int), st));
     hipLaunchKernelGGL(kernel, grid, block, shmem, st, a);
     PT_HIP(hipGetLastError());
     PT_HIP(hipEventRecord(s->ring_done[slot], st));
@@ -1974,9 +2034,16 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
     a.cost = s->ws_cost;
     a.cost_max = (cost_by_max && !coop) ? 1 : 0;
     a.samples = probe_spp;
+    a.keep_state = 0;
     // the probe's samples are kept (KArgs.resume_rng) — not in the opt-in fast mode, whose chunks are streams of their own
     const bool resume = !(p->flags & PT_FLAG_FAST_RNG) && !s->knobs.no_resume;
     a.resume_rng = resume ? s->ws_rng : nullptr;
+    a.resume_spp = 0;
+    // a sample window's probe renders the window's first samples from the accumulator's state, in place; with probe_resume = -1 it
+    // only costs (from the pixels' seeds: it writes nothing) and the frame launch renders the whole window
+    if (window && resume) { a.samples = w->done + probe_spp; a.resume_rng = w->rng; a.resume_spp = w->done; }
+    int* const order_out = w ? w->order : s->ws_order;
+    int* const nsplit_out = w ? w->nsplit : s->ws_nsplit;
     int rc = launch_variant();
     if (rc) return rc;
     // rough per-iteration instruction counts: traversal (splittable) vs shading + camera + cooperative overhead (not)
@@ -1988,22 +2055,29 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
       ranked = s->ws_rank;
     }
     // rough per-iteration instruction counts: traversal (splittable) vs shading + camera (not)
-    hipLaunchKernelGGL(lpt_order_kernel, dim3(1), dim3(1024), 0, st, ranked, local_tiles, s->ws_order, n_waves_resident,
-                       std::max(1.0f, s->traversal_cost), s->knobs.model_fixed, s->knobs.model_chain, forced_logG, coop ? s->ws_nsplit : nullptr);
+    hipLaunchKernelGGL(lpt_order_kernel, dim3(1), dim3(1024), 0, st, ranked, local_tiles, order_out, n_waves_resident,
+                       std::max(1.0f, s->traversal_cost), s->knobs.model_fixed, s->knobs.model_chain, forced_logG, coop ? nsplit_out : nullptr);
     PT_HIP(hipGetLastError());
     if (s->knobs.has_split_tiles) { // tuning knob: fixed number of split tiles (< 0: all)
       if (coop) {
         const int k = s->knobs.split_tiles;
         s->nsplit_override = k < 0 ? local_tiles : std::min(k, local_tiles);
-        PT_HIP(hipMemcpyAsync(s->ws_nsplit, &s->nsplit_override, sizeof(int), hipMemcpyHostToDevice, st));
+        PT_HIP(hipMemcpyAsync(nsplit_out, &s->nsplit_override, sizeof(int), hipMemcpyHostToDevice, st));
       }
     }
     // (A second, ORDERED probe stage of samples / 8 that keeps counting also removes the slow launches tile_dilate_kernel is there for — 1080p x
     // 1024 spp 375 / 407 -> 380.8 +- 1.5 — at the price of the fast ones and of 4 % on chain-bound shards: not kept.)
     a = main_args;
-    if (resume) { a.resume_rng = s->ws_rng; a.resume_spp = probe_spp; }
-    a.order = s->ws_order;
-    a.n_split = (coop && !(p->flags & PT_FLAG_NO_SPLIT)) ? s->ws_nsplit : nullptr;
+    if (window) { if (resume) a.resume_spp = w->done + probe_spp; }
+    else if (resume) { a.resume_rng = s->ws_rng; a.resume_spp = probe_spp; }
+    a.order = order_out;
+    a.n_split = (coop && !(p->flags & PT_FLAG_NO_SPLIT)) ? nsplit_out : nullptr;
+    if (w) *w->has_order = true;
+  } else if (w && *w->has_order) {
+    // a window too short to probe: the order its accumulator kept from its last probed window (same scene, camera and frame: the tiles'
+    // costs do not change between windows).  Never the scene's ws_order, which another render on the scene may have rewritten.
+    a.order = w->order;
+    a.n_split = (coop && !(p->flags & PT_FLAG_NO_SPLIT)) ? w->nsplit : nullptr;
   }
   if (p->flags & PT_FLAG_FAST_RNG) {
     // OPT-IN decorrelated mode (include/pt_render.h): (tile, chunk) work units, per-chunk sums into a workspace, then
@@ -2015,6 +2089,7 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
     if (int rc = reserve_partial(s, need)) return rc; // first render at a new size only (or never: pt_scene_reserve)
     PT_HIP(hipMemsetAsync(s->ws_partial, 0, need * sizeof(float), st)); // pixels no lane owns add 0
     a.fast_chunks = chunks;
+    a.fast_chunk0 = w ? w->done / PT_FAST_CHUNK_SPP : 0; // (a window starts on a chunk boundary: pt_render_accumulate)
     a.samples = std::min(p->samples, (int)PT_FAST_CHUNK_SPP);
     a.samples_total = p->samples;
     a.fast_stride = (long long)plane;
@@ -2026,6 +2101,12 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
     s->last_had_wide_phase = false;
     int rc = launch_variant();
     if (rc) return rc;
+    if (w) { // a window: its chunks onto the accumulator's running sums, in chunk order, undivided
+      hipLaunchKernelGGL(fast_accum_kernel, dim3((unsigned int)((plane + 255) / 256)), dim3(256), 0, st, s->ws_partial, fb, (long long)plane,
+                         (long long)plane, chunks);
+      PT_HIP(hipGetLastError());
+      return PT_OK;
+    }
     hipLaunchKernelGGL(fast_reduce_kernel, dim3((unsigned int)((plane + 255) / 256)), dim3(256), 0, st, s->ws_partial, fb,
                        (long long)plane, (long long)plane, chunks, (float)p->samples);
     PT_HIP(hipGetLastError());
@@ -2117,6 +2198,206 @@ int pt_tonemap_rgb8(const float* fb_device, int32_t width, int32_t height, uint8
   dim3 block(256), grid((width + 255) / 256, height);
   hipLaunchKernelGGL(tonemap_kernel, grid, block, 0, (hipStream_t)stream, fb_device, rgb8_device, width, height);
   PT_HIP(hipGetLastError());
+  return PT_OK;
+}
+
+// ---- progressive rendering: sample windows into a PtAccum (include/pt_render.h) ------------------------------------------------
+} // extern "C"
+
+struct PtAccum {
+  const PtScene* scene = nullptr;
+  PtRenderParams p{};           // the frame (samples: unused)
+  int local_tiles = 0;
+  size_t fb_floats = 0, rng_words = 0;
+  float* sum = nullptr;         // plain radiance sums, pt_render's framebuffer layout
+  unsigned int* rng = nullptr;  // generator state per local pixel (ws_rng's indexing)
+  int* order = nullptr;         // heaviest-first tile order of the last probed window (never the scene's ws_order)
+  int* nsplit = nullptr;        // ... and the cooperative kernels' split decided with it
+  bool has_order = false;
+  int32_t done = 0;             // samples the state holds (host-side count)
+  bool cam_bound = false;
+  PtCamera cam{};
+};
+
+namespace {
+struct AccumHeader { // pt_accum_export's header: 160 bytes, then the sums (float) and the generator states (u32)
+  uint32_t magic, version;
+  int32_t width, height, depth, shard_index, shard_count;
+  uint32_t flags;
+  int32_t samples_done, camera_bound;
+  int32_t reserved[6];
+  PtCamera cam;
+};
+static_assert(sizeof(AccumHeader) == PT_ACCUM_HEADER_BYTES, "pt_render.h: PT_ACCUM_HEADER_BYTES");
+
+// the frame of a PtAccum: pt_render's parameter checks with `samples` ignored, and no single-stream executor (no per-pixel state)
+int accum_params(const PtRenderParams* p, PtRenderParams& q) {
+  if (!p) return fail(PT_ERR_INVALID_ARG, "pt_accum: render params are NULL");
+  q = *p;
+  q.samples = 1;
+  if (int rc = check_params(&q)) return rc;
+  if (q.flags & PT_FLAG_SINGLE_STREAM) return fail(PT_ERR_INVALID_ARG, "pt_accum: PT_FLAG_SINGLE_STREAM has one global stream and no per-pixel state to resume");
+  return PT_OK;
+}
+
+// the triangle-pool kernels' candidate cache for every lane they can launch (launch_render would otherwise grow it on a window)
+int reserve_tricache(const PtScene* s, uint32_t flags) {
+  if (s->tri_pooled <= 0 || s->knobs.no_tri_cache || (flags & PT_FLAG_FORCE_STREAM)) return PT_OK;
+  const bool fast = (flags & PT_FLAG_FAST_RNG) != 0;
+  const void* k;
+  if (s->track_uv) k = fast ? (const void*)render_kernel<UV_TRACKED, false, false, false, false, true, false, true, true>
+                            : (const void*)render_kernel<UV_TRACKED, false, false, false, false, false, false, true, true>;
+  else if (s->has_image) k = fast ? (const void*)render_kernel<UV_WINNER, false, false, false, false, true, false, true, true>
+                                  : (const void*)render_kernel<UV_WINNER, false, false, false, false, false, false, true, true>;
+  else k = fast ? (const void*)render_kernel<UV_NONE, false, false, false, false, true, false, true, true>
+                : (const void*)render_kernel<UV_NONE, false, false, false, false, false, false, true, true>;
+  int per_cu = 0;
+  auto cached = s->occupancy.find(k);
+  if (cached != s->occupancy.end()) per_cu = cached->second;
+  else { PT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, kBlock, 0)); s->occupancy[k] = per_cu; }
+  if (s->knobs.blocks_per_cu) per_cu = std::min(per_cu, s->knobs.blocks_per_cu);
+  return grow_tricache(s, (size_t)std::max(1, per_cu) * (size_t)std::max(1, s->num_cus) * kBlock);
+}
+} // namespace
+
+extern "C" {
+
+int64_t pt_accum_state_bytes(const PtRenderParams* p) {
+  PtRenderParams q;
+  if (accum_params(p, q)) return -1;
+  return (int64_t)PT_ACCUM_HEADER_BYTES + 4 * pt_framebuffer_floats(&q) + 4 * (int64_t)pt_shard_tiles(&q) * PT_TILE_PIXELS;
+}
+
+void pt_accum_destroy(PtAccum* acc) {
+  if (!acc) return;
+  if (acc->sum) (void)hipFree(acc->sum);
+  if (acc->rng) (void)hipFree(acc->rng);
+  if (acc->order) (void)hipFree(acc->order);
+  if (acc->nsplit) (void)hipFree(acc->nsplit);
+  delete acc;
+}
+
+int pt_accum_create(const PtScene* scene, const PtRenderParams* p, PtAccum** out) {
+  if (!out) return fail(PT_ERR_INVALID_ARG, "pt_accum_create: out is NULL");
+  *out = nullptr;
+  if (!scene) return fail(PT_ERR_INVALID_ARG, "pt_accum_create: NULL scene");
+  PtRenderParams q;
+  if (int rc = accum_params(p, q)) return rc;
+  int cur = -1;
+  PT_HIP(hipGetDevice(&cur));
+  if (cur != scene->device) return fail(PT_ERR_INVALID_ARG, "pt_accum_create: the scene lives on another device");
+  PtAccum* acc = new PtAccum();
+  acc->scene = scene;
+  acc->p = q;
+  const int n_tiles = n_tiles_of(&q, nullptr);
+  acc->local_tiles = std::max(0, (n_tiles - q.shard_index + q.shard_count - 1) / q.shard_count);
+  acc->fb_floats = (size_t)pt_framebuffer_floats(&q);
+  acc->rng_words = (size_t)pt_shard_tiles(&q) * PT_TILE_PIXELS;
+  auto bail = [&](hipError_t e, const char* what) { pt_accum_destroy(acc); return fail(PT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); };
+  hipError_t e;
+  if ((e = hipMalloc((void**)&acc->sum, acc->fb_floats * sizeof(float))) != hipSuccess) return bail(e, "pt_accum_create: hipMalloc");
+  if ((e = hipMalloc((void**)&acc->rng, std::max<size_t>(acc->rng_words, 1) * sizeof(unsigned int))) != hipSuccess) return bail(e, "pt_accum_create: hipMalloc");
+  if ((e = hipMalloc((void**)&acc->order, (size_t)std::max(acc->local_tiles, 1) * sizeof(int))) != hipSuccess) return bail(e, "pt_accum_create: hipMalloc");
+  if ((e = hipMalloc((void**)&acc->nsplit, 2 * sizeof(int))) != hipSuccess) return bail(e, "pt_accum_create: hipMalloc");
+  if ((e = hipMemset(acc->sum, 0, acc->fb_floats * sizeof(float))) != hipSuccess) return bail(e, "pt_accum_create: hipMemset");
+  if ((e = hipMemset(acc->rng, 0, std::max<size_t>(acc->rng_words, 1) * sizeof(unsigned int))) != hipSuccess) return bail(e, "pt_accum_create: hipMemset");
+  {
+    // the scene's launch workspaces a window uses (probe costs, tile ranks; the candidate cache): sized now, not by a window
+    std::lock_guard<std::mutex> lock(scene->sched);
+    int rc = acc->local_tiles > 0 ? reserve_tiles(scene, acc->local_tiles) : PT_OK;
+    if (!rc) rc = reserve_tricache(scene, q.flags);
+    if (rc) { pt_accum_destroy(acc); return rc; }
+  }
+  *out = acc;
+  return PT_OK;
+}
+
+int pt_accum_reset(PtAccum* acc, void* stream) {
+  if (!acc) return fail(PT_ERR_INVALID_ARG, "pt_accum_reset: NULL accumulator");
+  PT_HIP(hipMemsetAsync(acc->sum, 0, acc->fb_floats * sizeof(float), (hipStream_t)stream));
+  acc->done = 0;
+  acc->cam_bound = false;
+  acc->has_order = false;
+  return PT_OK;
+}
+
+int32_t pt_accum_samples(const PtAccum* acc) { return acc ? acc->done : -1; }
+
+int pt_render_accumulate(PtAccum* acc, const PtCamera* cam, int32_t samples, void* stream) {
+  if (!acc || !cam) return fail(PT_ERR_INVALID_ARG, "pt_render_accumulate: NULL argument");
+  if (samples <= 0) return fail(PT_ERR_INVALID_ARG, "pt_render_accumulate: samples must be > 0");
+  if ((int64_t)acc->done + samples > (int64_t)INT32_MAX) return fail(PT_ERR_INVALID_ARG, "pt_render_accumulate: the total would pass INT32_MAX samples");
+  if (acc->cam_bound && std::memcmp(&acc->cam, cam, sizeof(PtCamera)) != 0)
+    return fail(PT_ERR_INVALID_ARG, "pt_render_accumulate: the camera differs from the one the accumulator's first window was rendered with");
+  if ((acc->p.flags & PT_FLAG_FAST_RNG) && acc->done % PT_FAST_CHUNK_SPP != 0)
+    return fail(PT_ERR_INVALID_ARG, "pt_render_accumulate: PT_FLAG_FAST_RNG windows start on a multiple of PT_FAST_CHUNK_SPP samples (the last window ended off one)");
+  PtRenderParams q = acc->p;
+  q.samples = samples;
+  Window w{acc->done, acc->rng, acc->order, acc->nsplit, &acc->has_order};
+  if (int rc = launch_render(acc->scene, cam, &q, acc->sum, (hipStream_t)stream, &w)) return rc;
+  acc->done += samples;
+  if (!acc->cam_bound) { acc->cam = *cam; acc->cam_bound = true; }
+  return PT_OK;
+}
+
+int pt_accum_resolve(const PtAccum* acc, float* fb_device, void* stream) {
+  if (!acc || !fb_device) return fail(PT_ERR_INVALID_ARG, "pt_accum_resolve: NULL argument");
+  if (acc->done <= 0) return fail(PT_ERR_INVALID_ARG, "pt_accum_resolve: no samples rendered yet");
+  const long long n = (long long)acc->fb_floats;
+  hipLaunchKernelGGL(accum_resolve_kernel, dim3((unsigned int)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, acc->sum, fb_device, n,
+                     (float)acc->done);
+  PT_HIP(hipGetLastError());
+  return PT_OK;
+}
+
+int pt_accum_tonemap_rgb8(const PtAccum* acc, uint8_t* rgb8_device, void* stream) {
+  if (!acc || !rgb8_device) return fail(PT_ERR_INVALID_ARG, "pt_accum_tonemap_rgb8: NULL argument");
+  if (acc->done <= 0) return fail(PT_ERR_INVALID_ARG, "pt_accum_tonemap_rgb8: no samples rendered yet");
+  if (acc->p.shard_count != 1) return fail(PT_ERR_INVALID_ARG, "pt_accum_tonemap_rgb8: whole frames only (shard_count == 1)");
+  dim3 block(256), grid((acc->p.width + 255) / 256, acc->p.height);
+  hipLaunchKernelGGL(accum_tonemap_kernel, grid, block, 0, (hipStream_t)stream, acc->sum, rgb8_device, acc->p.width, acc->p.height, (float)acc->done);
+  PT_HIP(hipGetLastError());
+  return PT_OK;
+}
+
+int pt_accum_export(const PtAccum* acc, void* host, int64_t bytes, void* stream) {
+  if (!acc || !host) return fail(PT_ERR_INVALID_ARG, "pt_accum_export: NULL argument");
+  if (bytes != pt_accum_state_bytes(&acc->p)) return fail(PT_ERR_INVALID_ARG, "pt_accum_export: the buffer is not pt_accum_state_bytes() long");
+  AccumHeader h;
+  std::memset(&h, 0, sizeof h);
+  h.magic = PT_ACCUM_MAGIC; h.version = PT_ACCUM_FORMAT;
+  h.width = acc->p.width; h.height = acc->p.height; h.depth = acc->p.depth;
+  h.shard_index = acc->p.shard_index; h.shard_count = acc->p.shard_count; h.flags = acc->p.flags;
+  h.samples_done = acc->done; h.camera_bound = acc->cam_bound ? 1 : 0;
+  h.cam = acc->cam;
+  char* out = (char*)host;
+  std::memcpy(out, &h, sizeof h);
+  const hipStream_t st = (hipStream_t)stream;
+  PT_HIP(hipMemcpyAsync(out + sizeof h, acc->sum, acc->fb_floats * sizeof(float), hipMemcpyDeviceToHost, st));
+  PT_HIP(hipMemcpyAsync(out + sizeof h + acc->fb_floats * sizeof(float), acc->rng, acc->rng_words * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+  PT_HIP(hipStreamSynchronize(st));
+  return PT_OK;
+}
+
+int pt_accum_import(PtAccum* acc, const void* host, int64_t bytes, void* stream) {
+  if (!acc || !host) return fail(PT_ERR_INVALID_ARG, "pt_accum_import: NULL argument");
+  if (bytes != pt_accum_state_bytes(&acc->p)) return fail(PT_ERR_INVALID_ARG, "pt_accum_import: the state is not pt_accum_state_bytes() long for this accumulator");
+  AccumHeader h;
+  std::memcpy(&h, host, sizeof h);
+  if (h.magic != PT_ACCUM_MAGIC || h.version != PT_ACCUM_FORMAT) return fail(PT_ERR_INVALID_ARG, "pt_accum_import: not an exported accumulator state (magic / format version)");
+  if (h.width != acc->p.width || h.height != acc->p.height || h.depth != acc->p.depth || h.shard_index != acc->p.shard_index ||
+      h.shard_count != acc->p.shard_count || h.flags != acc->p.flags)
+    return fail(PT_ERR_INVALID_ARG, "pt_accum_import: the state was exported from an accumulator with other frame parameters");
+  if (h.samples_done < 0 || (h.camera_bound != 0) != (h.samples_done > 0)) return fail(PT_ERR_INVALID_ARG, "pt_accum_import: inconsistent header");
+  const char* in = (const char*)host;
+  const hipStream_t st = (hipStream_t)stream;
+  PT_HIP(hipMemcpyAsync(acc->sum, in + sizeof h, acc->fb_floats * sizeof(float), hipMemcpyHostToDevice, st));
+  PT_HIP(hipMemcpyAsync(acc->rng, in + sizeof h + acc->fb_floats * sizeof(float), acc->rng_words * sizeof(unsigned int), hipMemcpyHostToDevice, st));
+  PT_HIP(hipStreamSynchronize(st)); // (the caller's buffer may go as soon as this returns)
+  acc->done = h.samples_done;
+  acc->cam_bound = h.camera_bound != 0;
+  acc->cam = h.cam;
+  acc->has_order = false; // (the next window long enough to probe orders the tiles again)
   return PT_OK;
 }
 

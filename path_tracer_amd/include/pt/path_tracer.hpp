@@ -361,4 +361,69 @@ void render(frame_buffer& frame_buf, std::vector<hittable_t>& hittables, camera&
   render(width, height, samples, frame_buf, hittables, cam);
 }
 
+// Progressive rendering: one frame in sample windows; RAII over pt_accum_create / pt_accum_destroy (include/pt_render.h, PtAccum).
+// After windows totalling N samples, resolve() holds the bits render() gives at samples = N.  The scene must outlive the accumulator;
+// windows run on the default stream (or `stream`) and are ordered like renders of the scene.
+class accumulator {
+ public:
+  accumulator(const device_scene& scene, const camera& cam, int width, int height, int depth = 50, uint32_t flags = 0, int shard_index = 0,
+              int shard_count = 1)
+      : cam_(cam.c), p_{width, height, 1, depth, shard_index, shard_count, flags, 0} {
+    check(pt_accum_create(scene.s, &p_, &a_), "pt_accum_create");
+  }
+  ~accumulator() { pt_accum_destroy(a_); }
+  accumulator(const accumulator&) = delete;
+  accumulator& operator=(const accumulator&) = delete;
+
+  // the next `samples` samples of every pixel
+  void add(int samples, void* stream = nullptr) { check(pt_render_accumulate(a_, &cam_, samples, stream), "pt_render_accumulate"); }
+  int samples() const { return pt_accum_samples(a_); }
+  void reset(void* stream = nullptr) { check(pt_accum_reset(a_, stream), "pt_accum_reset"); }
+
+  // the mean so far, in render()'s layout (host memory: from the exported sums, divided here with the same correctly rounded IEEE
+  // division as the device's resolve — the host build has no fast-math, no contraction)
+  void resolve(frame_buffer& frame_buf) const {
+    if (samples() <= 0) throw pt_error(PT_ERR_INVALID_ARG, "accumulator::resolve: no samples rendered yet");
+    const std::vector<uint8_t> st = state();
+    const std::size_t floats = (std::size_t)pt_framebuffer_floats(&p_);
+    frame_buf.resize(floats / 3);
+    static_assert(sizeof(color) == 12);
+    float* out = reinterpret_cast<float*>(frame_buf.data());
+    std::memcpy(out, st.data() + PT_ACCUM_HEADER_BYTES, floats * sizeof(float));
+    const float n = (float)samples();
+    for (std::size_t i = 0; i < floats; i++) out[i] = out[i] / n;
+  }
+
+  // checkpoint (pt_accum_export's format) / restore into this accumulator (same frame parameters; the camera comes with the state)
+  std::vector<uint8_t> state() const {
+    std::vector<uint8_t> st((std::size_t)pt_accum_state_bytes(&p_));
+    check(pt_accum_export(a_, st.data(), (int64_t)st.size(), nullptr), "pt_accum_export");
+    return st;
+  }
+  void restore(const std::vector<uint8_t>& st) {
+    check(pt_accum_import(a_, st.data(), (int64_t)st.size(), nullptr), "pt_accum_import");
+    if (samples() > 0) std::memcpy(&cam_, st.data() + PT_ACCUM_HEADER_BYTES - sizeof(PtCamera), sizeof(PtCamera));
+  }
+  void save(const std::string& path) const {
+    const std::vector<uint8_t> st = state();
+    std::FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f || std::fwrite(st.data(), 1, st.size(), f) != st.size()) { if (f) std::fclose(f); throw std::runtime_error("accumulator::save: cannot write " + path); }
+    std::fclose(f);
+  }
+  void load(const std::string& path) {
+    std::vector<uint8_t> st((std::size_t)pt_accum_state_bytes(&p_));
+    std::FILE* f = std::fopen(path.c_str(), "rb");
+    const bool ok = f && std::fread(st.data(), 1, st.size(), f) == st.size() && std::fgetc(f) == EOF;
+    if (f) std::fclose(f);
+    if (!ok) throw std::runtime_error("accumulator::load: " + path + " is not a state of this accumulator's size");
+    restore(st);
+  }
+  PtAccum* handle() const { return a_; }
+
+ private:
+  PtCamera cam_;
+  PtRenderParams p_;
+  PtAccum* a_ = nullptr;
+};
+
 } // namespace pt

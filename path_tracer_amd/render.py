@@ -201,3 +201,146 @@ def tonemap_rgb8(fb):
     abi.check(lib.pt_tonemap_rgb8(C.c_void_p(fb.data_ptr()), w, h, C.c_void_p(out.data_ptr()), _stream_ptr(torch)),
               "pt_tonemap_rgb8")
     return out
+
+
+class Accumulator:
+    """Progressive rendering (include/pt_render.h PtAccum): one frame rendered in sample windows.
+
+    After windows totalling N samples, resolve() gives the same bits as render(..., samples=N, ...) with the same scene, camera,
+    depth, flags and shard — for every split of N.  `add` is asynchronous on torch's current stream; the accumulator and the scene
+    it renders must be used from one stream (as render() requires of a scene).  `scene`: as for render().
+    """
+
+    def __init__(self, width: int, height: int, scene, cam: camera, depth: int = 50, *, flags: int = 0, shard_index: int = 0,
+                 shard_count: int = 1):
+        import torch
+
+        if not torch.cuda.is_available():
+            raise RuntimeError("path_tracer_amd.render.Accumulator needs a HIP device: there is no CPU path in the product")
+        self.lib = abi.load_library()
+        if not abi.has_accumulator(self.lib):
+            raise ImportError(f"{abi.library_path()} predates progressive rendering (no pt_accum_* entry points)")
+        self.width, self.height, self.depth, self.flags = int(width), int(height), int(depth), int(flags)
+        self.shard_index, self.shard_count = int(shard_index), int(shard_count)
+        self.cam = cam
+        self.handle = C.c_void_p()
+        self._ds = _as_device_scene(scene, cache_key=("cuda", torch.cuda.current_device(), torch.cuda.current_stream().cuda_stream))
+        self._p = _params(width, height, 1, depth, shard_index, shard_count, flags)
+        abi.check(self.lib.pt_accum_create(self._ds.handle, C.byref(self._p), C.byref(self.handle)), "pt_accum_create")
+
+    @property
+    def samples(self) -> int:
+        """Samples of every pixel rendered so far."""
+        return int(self.lib.pt_accum_samples(self.handle))
+
+    def add(self, samples: int) -> "Accumulator":
+        """Render the next `samples` samples of every pixel (asynchronous on torch's current stream)."""
+        import torch
+
+        abi.check(self.lib.pt_render_accumulate(self.handle, C.byref(self.cam.c), int(samples), _stream_ptr(torch)), "pt_render_accumulate")
+        return self
+
+    def _shape(self, n: int):
+        return (self.height, self.width, 3) if self.shard_count == 1 else (n // (abi.PT_TILE_PIXELS * 3), abi.PT_TILE_PIXELS, 3)
+
+    def resolve(self, out=None):
+        """The mean of the samples so far, as render() returns it ([H][W][3], or this shard's tiles [tiles][64][3])."""
+        import torch
+
+        n = self.lib.pt_framebuffer_floats(C.byref(self._p))
+        if out is None:
+            out = torch.empty(self._shape(n), dtype=torch.float32, device="cuda")
+        elif out.numel() != n or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float32 CUDA tensor of pt_framebuffer_floats() elements")
+        abi.check(self.lib.pt_accum_resolve(self.handle, C.c_void_p(out.data_ptr()), _stream_ptr(torch)), "pt_accum_resolve")
+        return out
+
+    def tonemap_rgb8(self):
+        """resolve() + tonemap_rgb8() in one pass (whole frames): uint8 [H][W][3], row 0 = top."""
+        import torch
+
+        out = torch.empty((self.height, self.width, 3), dtype=torch.uint8, device="cuda")
+        abi.check(self.lib.pt_accum_tonemap_rgb8(self.handle, C.c_void_p(out.data_ptr()), _stream_ptr(torch)), "pt_accum_tonemap_rgb8")
+        return out
+
+    def reset(self) -> None:
+        """Back to 0 samples (the next window binds its camera: set .cam first to render another view)."""
+        import torch
+
+        abi.check(self.lib.pt_accum_reset(self.handle, _stream_ptr(torch)), "pt_accum_reset")
+
+    def state(self) -> np.ndarray:
+        """The exported state (pt_accum_export: header, sums, generator states) as bytes in a uint8 array."""
+        import torch
+
+        buf = np.empty(self.lib.pt_accum_state_bytes(C.byref(self._p)), dtype=np.uint8)
+        abi.check(self.lib.pt_accum_export(self.handle, buf.ctypes.data_as(C.c_void_p), buf.size, _stream_ptr(torch)), "pt_accum_export")
+        return buf
+
+    def save(self, path) -> None:
+        """Checkpoint to a raw file (the pt_accum_export format, include/pt_render.h)."""
+        with open(path, "wb") as f:
+            f.write(self.state().tobytes())
+
+    @classmethod
+    def load(cls, path, scene, cam: "camera | None" = None) -> "Accumulator":
+        """A new accumulator over `scene` (the same tables as the saved one's) resumed from a checkpoint; the frame parameters and
+        the camera come from the file (`cam` is needed only for a state saved at 0 samples)."""
+        buf = np.fromfile(path, dtype=np.uint8)
+        if buf.size < abi.PT_ACCUM_HEADER_BYTES:
+            raise ValueError(f"{path}: not an accumulator state")
+        magic, _fmt, w, h, depth, si, sc, flags, _done, bound = np.frombuffer(buf[:40].tobytes(), dtype="<u4").astype(np.int64)
+        if magic != abi.PT_ACCUM_MAGIC:
+            raise ValueError(f"{path}: not an accumulator state")
+        if bound:
+            cam = _BoundCamera(abi.PtCamera.from_buffer_copy(buf[64:abi.PT_ACCUM_HEADER_BYTES].tobytes()))
+        elif cam is None:
+            raise ValueError(f"{path}: the state has no samples (no bound camera): pass cam")
+        acc = cls(int(w), int(h), scene, cam, int(depth), flags=int(flags), shard_index=int(si), shard_count=int(sc))
+        acc.restore(buf)
+        return acc
+
+    def restore(self, state: np.ndarray) -> None:
+        """pt_accum_import of an exported state (the header must match this accumulator's frame parameters)."""
+        import torch
+
+        state = np.ascontiguousarray(state, dtype=np.uint8)
+        abi.check(self.lib.pt_accum_import(self.handle, state.ctypes.data_as(C.c_void_p), state.size, _stream_ptr(torch)), "pt_accum_import")
+        if self.lib.pt_accum_samples(self.handle) > 0:
+            self.cam = _BoundCamera(abi.PtCamera.from_buffer_copy(state[64:abi.PT_ACCUM_HEADER_BYTES].tobytes()))
+
+    def close(self) -> None:
+        if self.handle:
+            self.lib.pt_accum_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+
+class _BoundCamera:
+    """A camera given as its PtCamera (the one an exported state is bound to)."""
+
+    def __init__(self, c: "abi.PtCamera"):
+        self.c = c
+
+
+def render_progressive(width: int, height: int, samples: int, scene, cam: camera, depth: int = 50, *, step: int, flags: int = 0,
+                       shard_index: int = 0, shard_count: int = 1):
+    """Render `samples` spp in windows of `step` (the last one shorter): yields (samples_done, framebuffer) after each window; the
+    last framebuffer has the bits render() gives at `samples`."""
+    if step <= 0 or samples <= 0:
+        raise ValueError("samples and step must be > 0")
+    acc = Accumulator(width, height, scene, cam, depth, flags=flags, shard_index=shard_index, shard_count=shard_count)
+    try:
+        done = 0
+        while done < samples:
+            n = min(step, samples - done)
+            acc.add(n)
+            done += n
+            yield done, acc.resolve()
+    finally:
+        acc.close()
