@@ -425,6 +425,68 @@ int pt_accum_export(const PtAccum* acc, void* host, int64_t bytes, void* stream)
 /* Restore a checkpoint (validates the header; synchronises `stream`).  The next window resumes from it. */
 int pt_accum_import(PtAccum* acc, const void* host, int64_t bytes, void* stream);
 
+/* ---- adaptive sampling: progressive rendering with a sample count per pixel -----------------------------------------------------------
+ * Added without an ABI version change, like PtAccum: a caller detects the feature by the presence of these symbols.
+ *
+ * An ADAPTIVE accumulator (pt_adaptive_create) is a PtAccum that also keeps, per pixel, its sample count n, how many of those samples
+ * are in "half A" (a) and the radiance sum of half A (H).  A pixel's work in a window depends only on its sum and its generator state,
+ * never on the sample index, so a pixel that reaches n samples through any pattern of windows is the reference's render at n samples.
+ *
+ * CONTRACT: after any sequence of windows, masked or not, pixel p resolves to the same bits that pt_render writes at p with
+ * samples = n_p (same scene, camera, depth, flags and shard) — for every kernel family, with or without the cost probe, for shards and
+ * across a checkpoint.  A pixel with n_p = 0 resolves to 0.  Plain accumulators keep every behaviour and every exported byte.
+ *
+ * Per-pixel arrays (masks: u8, counts: i32, errors: f32) hold one element per pixel in the frame buffer's layout without the channel:
+ * [height][width] for whole frames, [local tile][64] (ly * 8 + lx) for shards.  Padding pixels of a shard are ignored (mask 0, count 0).
+ *
+ * Window.  pt_adaptive_window renders `samples` more samples of every pixel whose mask byte is nonzero (mask_device = NULL: every pixel);
+ * the other pixels keep their sum, generator state and counts bit for bit.  pt_render_accumulate on an adaptive accumulator is the same
+ * call with a NULL mask.  A masked window renders the local tiles that hold an active pixel, in the accumulator's kept heaviest-first
+ * order (raster order before its first probed window), without the cost probe or the cooperative wide phase; it SYNCHRONISES `stream`
+ * once, to read the active-tile count that sizes its launch.  A window with an empty mask is a no-op.  After each window a bookkeeping
+ * pass puts it into half A or half B of each pixel it rendered: with D = the window's contribution to the sum (S after - S before,
+ * binary32), if a < n - a then H += D and a += samples (ties go to half B); then n += samples.
+ * Rejected (PT_ERR_INVALID_ARG): a plain accumulator; samples <= 0; a per-pixel total that could pass INT32_MAX; a camera other than the
+ * bound one.
+ *
+ * Error (Dammertz et al. 2010, the two-half-buffer estimate), per pixel: +inf where a == 0 or a == n; otherwise, with the correctly
+ * rounded binary32 means I = S / (float)n and A = H / (float)a per channel,
+ *   err = ((|I.x - A.x| + |I.y - A.y|) + |I.z - A.z|) / (1e-4f + sqrt((I.x + I.y) + I.z)).
+ * Select: noisy(q) = n_q < max_spp && !(err_q <= threshold) (NaN and inf stay noisy); pixel p is active when n_p < max_spp and
+ * n_p < min_spp, or noisy(p), or (PT_ADAPTIVE_DILATE) a pixel of p's 8-neighbourhood inside the frame is noisy.  A negative threshold
+ * keeps every pixel active up to max_spp.  PT_ADAPTIVE_DILATE with shard_count > 1 is refused.
+ *
+ * pt_adaptive_create refuses PT_FLAG_FAST_RNG and PT_FLAG_SINGLE_STREAM before any device call and seeds every pixel's generator state
+ * with its linear id (the state of a pixel at 0 samples), so that every window resumes from the state.  pt_accum_reset restores that and
+ * zeroes n, a and H.  pt_accum_samples returns the samples of the windows rendered without a mask (every pixel has at least these).
+ * pt_accum_resolve and pt_accum_tonemap_rgb8 divide each pixel by its own n_p (the same correctly rounded division; 0 where n_p = 0);
+ * they are refused only before the first window.  pt_accum_export / pt_accum_import refuse adaptive accumulators.
+ *
+ * Export format PT_ADAPTIVE_FORMAT (pt_adaptive_export / pt_adaptive_import; host byte order): the PT_ACCUM_HEADER_BYTES header of
+ * pt_accum_export with format = PT_ADAPTIVE_FORMAT (samples done = the unmasked windows' samples), then F floats of sums, R u32 generator
+ * states, F floats of H, P i32 counts n and P i32 counts a (F = pt_framebuffer_floats, R = pt_shard_tiles * 64, P = F / 3).
+ * pt_adaptive_import also takes a PT_ACCUM_FORMAT state of a plain accumulator with the same frame parameters: every pixel gets
+ * n = samples done, a = 0, H = 0 (start uniform, continue adaptively).  It validates the header and 0 <= a <= n on the host.         */
+#define PT_ADAPTIVE_FORMAT 2
+#define PT_ADAPTIVE_DILATE 1u
+/* Validates the parameters (before any device call) and allocates the state on the current device; destroyed with pt_accum_destroy. */
+int pt_adaptive_create(const PtScene* scene, const PtRenderParams* p, PtAccum** out);
+/* `samples` more samples of each pixel whose mask byte is nonzero (NULL: every pixel); a mask synchronises `stream` once. */
+int pt_adaptive_window(PtAccum* acc, const PtCamera* cam, int32_t samples, const uint8_t* mask_device, void* stream);
+/* Per-pixel sample counts n (P i32). */
+int pt_adaptive_counts(const PtAccum* acc, int32_t* counts_device, void* stream);
+/* Per-pixel error estimate (P f32; the formula above). */
+int pt_adaptive_error(const PtAccum* acc, float* err_device, void* stream);
+/* The next window's mask (P u8: 1 active, 0 not) by the rule above; synchronises `stream`: n_active is a host value. */
+int pt_adaptive_select(const PtAccum* acc, float threshold, int32_t min_spp, int32_t max_spp, uint32_t flags,
+                       uint8_t* mask_device, int64_t* n_active, void* stream);
+/* Host function, no GPU: bytes of an exported adaptive state for these frame parameters; < 0 for invalid ones. */
+int64_t pt_adaptive_state_bytes(const PtRenderParams* p);
+/* Checkpoint into host memory of exactly pt_adaptive_state_bytes() bytes (synchronises `stream`). */
+int pt_adaptive_export(const PtAccum* acc, void* host, int64_t bytes, void* stream);
+/* Restore a PT_ADAPTIVE_FORMAT checkpoint, or upgrade a plain PT_ACCUM_FORMAT one (synchronises `stream`). */
+int pt_adaptive_import(PtAccum* acc, const void* host, int64_t bytes, void* stream);
+
 /* ---- function-level probes (parity tests call these; not used by render) ---- */
 
 /* One iteration of the bounce loop render.hpp:58-89 per record: hit_world,

@@ -3,8 +3,13 @@
     python -m path_tracer_amd --scene cornell --width 800 --height 480 --spp 100 --out out.png
     python -m path_tracer_amd --scene cornell --spp 1024 --preview-every 64 --preview-dir previews --out out.png
 
+    python -m path_tracer_amd --scene cornell --spp 1024 --noise-threshold 0.02 --min-spp 16 --counts-out counts.png --out out.png
+
 With --preview-every N the frame is rendered progressively (render.Accumulator): windows of N samples, DIR/preview_<spp>.png after
 each; the final --out PNG is byte-identical to the one written without these options.
+With --noise-threshold T the frame is rendered adaptively (render.render_adaptive): --min-spp samples of every pixel, then windows of
+--adaptive-step samples of the pixels whose noise estimate is above T, up to --spp; --counts-out writes the per-pixel counts as a grey
+PNG (row 0 at the top, --spp = white).  A negative T renders every pixel to --spp: the same out.png as without the options.
 """
 import argparse
 import os
@@ -31,19 +36,52 @@ def main() -> None:
     ap.add_argument("--preview-every", type=int, default=0, metavar="N",
                     help="render in windows of N samples and write a preview PNG after each (progressive rendering)")
     ap.add_argument("--preview-dir", default="previews", metavar="DIR", help="where --preview-every writes preview_<spp>.png")
+    ap.add_argument("--noise-threshold", type=float, default=None, metavar="T",
+                    help="adaptive sampling: render each pixel until its noise estimate is <= T (--spp is the maximum)")
+    ap.add_argument("--min-spp", type=int, default=None, metavar="N", help="adaptive sampling: samples of every pixel (default 16)")
+    ap.add_argument("--adaptive-step", type=int, default=None, metavar="N", help="adaptive sampling: samples per window (default --min-spp)")
+    ap.add_argument("--counts-out", default=None, metavar="PATH", help="adaptive sampling: grey PNG of the per-pixel sample counts")
     a = ap.parse_args()
     if a.preview_every < 0:
         ap.error("--preview-every must be >= 0")
+    adaptive = a.noise_threshold is not None
+    if not adaptive and (a.min_spp is not None or a.adaptive_step is not None or a.counts_out is not None):
+        ap.error("--min-spp, --adaptive-step and --counts-out need --noise-threshold")
+    if adaptive:
+        if a.preview_every > 0:
+            ap.error("--noise-threshold cannot be combined with --preview-every")
+        a.min_spp = 16 if a.min_spp is None else a.min_spp
+        a.adaptive_step = a.min_spp if a.adaptive_step is None else a.adaptive_step
+        if a.min_spp <= 0 or a.adaptive_step <= 0:
+            ap.error("--min-spp and --adaptive-step must be > 0")
+        if a.spp < a.min_spp or (a.spp - a.min_spp) % a.adaptive_step != 0:
+            ap.error(f"--spp ({a.spp}) must be --min-spp ({a.min_spp}) plus a multiple of --adaptive-step ({a.adaptive_step})")
     if a.export_textures:
         print(*scenes.export_reference_textures(a.export_textures), sep="\n")
         return
+    import numpy as np
     import torch
 
     kw = {"n_triangles": a.triangles} if a.scene == "triangles" else {"textures": a.textures} if a.scene == "smoke" else {}
     packed, cam_args = scenes.build(a.scene, **kw)
     cam = scenes.make_camera(cam_args, a.width, a.height)
     t0 = time.perf_counter()
-    if a.preview_every > 0:
+    mean_spp = None
+    if adaptive:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fb, counts = R.render_adaptive(a.width, a.height, packed, cam, a.depth, threshold=a.noise_threshold, min_spp=a.min_spp,
+                                       max_spp=a.spp, step=a.adaptive_step)
+        e1.record()
+        rgb8 = R.tonemap_rgb8(fb)
+        torch.cuda.synchronize()
+        ms = e0.elapsed_time(e1)
+        counts = counts.cpu().numpy()
+        mean_spp = float(counts.mean())
+        if a.counts_out:
+            grey = np.round(counts[::-1].astype(np.float64) * (255.0 / a.spp)).astype(np.uint8)  # row 0 = top, like out.png
+            write_png(a.counts_out, np.repeat(grey[:, :, None], 3, axis=2))
+    elif a.preview_every > 0:
         os.makedirs(a.preview_dir, exist_ok=True)
         acc = R.Accumulator(a.width, a.height, packed, cam, a.depth)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -62,6 +100,12 @@ def main() -> None:
         rgb8 = R.tonemap_rgb8(fb)
     torch.cuda.synchronize()
     write_png(a.out, rgb8.cpu().numpy())
+    if mean_spp is not None:
+        n = int(counts.sum())
+        print(f"{a.scene}: {packed.n_hittables} hittables, {a.width}x{a.height}, adaptive {a.min_spp}..{a.spp} spp (threshold "
+              f"{a.noise_threshold:g}), mean {mean_spp:.1f} spp -> {a.out}; {ms:.1f} ms = {n / ms / 1e3:.1f} Msamples/s "
+              f"(wall {time.perf_counter() - t0:.2f} s)")
+        return
     n = a.width * a.height * a.spp
     print(f"{a.scene}: {packed.n_hittables} hittables, {a.width}x{a.height}x{a.spp} spp -> {a.out}; "
           f"kernel {ms:.1f} ms = {n / ms / 1e3:.1f} Msamples/s (wall {time.perf_counter() - t0:.2f} s)")

@@ -178,6 +178,16 @@ SIGNATURES = {
     "pt_accum_state_bytes": (C.c_int64, [C.POINTER(PtRenderParams)]),
     "pt_accum_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "pt_accum_import": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    # adaptive sampling (a PtAccum with per-pixel counts): likewise optional (ADAPTIVE_SYMBOLS)
+    "pt_adaptive_create": (C.c_int, [_SCENE_P, C.POINTER(PtRenderParams), C.POINTER(C.c_void_p)]),
+    "pt_adaptive_window": (C.c_int, [C.c_void_p, C.POINTER(PtCamera), C.c_int32, C.c_void_p, C.c_void_p]),
+    "pt_adaptive_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pt_adaptive_error": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pt_adaptive_select": (C.c_int, [C.c_void_p, C.c_float, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.POINTER(C.c_int64),
+                                     C.c_void_p]),
+    "pt_adaptive_state_bytes": (C.c_int64, [C.POINTER(PtRenderParams)]),
+    "pt_adaptive_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "pt_adaptive_import": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
 }
 
 # Entry points a library may lack and still load for everything else (include/pt_render.h: the feature is detected by their presence);
@@ -186,6 +196,10 @@ ACCUM_SYMBOLS = frozenset(n for n in SIGNATURES if n.startswith("pt_accum_") or 
 PT_ACCUM_MAGIC = 0x43415450
 PT_ACCUM_FORMAT = 1
 PT_ACCUM_HEADER_BYTES = 160
+# adaptive sampling (include/pt_render.h: pt_adaptive_*); has_adaptive() tells whether the loaded library has them
+ADAPTIVE_SYMBOLS = frozenset(n for n in SIGNATURES if n.startswith("pt_adaptive_"))
+PT_ADAPTIVE_FORMAT = 2
+PT_ADAPTIVE_DILATE = 1
 
 LIB_NAME = "libpt_render.so"
 _lib = None
@@ -230,7 +244,7 @@ def load_library() -> C.CDLL:
         pass  # torch-free hosts bind to /opt/rocm/lib through the library's RUNPATH
     lib = C.CDLL(str(path))
     for name, (res, args) in SIGNATURES.items():
-        if override_is_older_build(path, lib, name) or (name in ACCUM_SYMBOLS and not hasattr(lib, name)):
+        if override_is_older_build(path, lib, name) or (name in ACCUM_SYMBOLS | ADAPTIVE_SYMBOLS and not hasattr(lib, name)):
             continue
         fn = getattr(lib, name)  # AttributeError if the library does not export what the header declares
         fn.restype = res
@@ -246,6 +260,12 @@ def has_accumulator(lib=None) -> bool:
     """Does the loaded library offer progressive rendering (the PtAccum entry points)?"""
     lib = lib or load_library()
     return all(hasattr(lib, n) for n in ACCUM_SYMBOLS)
+
+
+def has_adaptive(lib=None) -> bool:
+    """Does the loaded library offer adaptive sampling (the pt_adaptive_* entry points)?"""
+    lib = lib or load_library()
+    return has_accumulator(lib) and all(hasattr(lib, n) for n in ADAPTIVE_SYMBOLS)
 
 
 def check(code: int, where: str) -> None:

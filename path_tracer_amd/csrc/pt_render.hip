@@ -112,6 +112,9 @@ struct KArgs {
   // Sample windows of a PtAccum (pt_render_accumulate): `samples` is the window's END, resume_spp its start, and a finished pixel leaves
   // its plain radiance sum in fb and its generator's state in resume_rng — the probe's branch of lane_store — instead of the mean.
   int keep_state;
+  // Masked windows of an adaptive PtAccum (pt_adaptive_window): one byte per pixel in the frame buffer's layout without the channel
+  // ([y][x], or [local tile][64] for shards); lane_acquire skips a pixel whose byte is 0 like a padding pixel.  NULL: every pixel.
+  const uint8_t* mask;
   // Headline-family launches (launch_render): once prio_onset queue positions are taken, a wave sets its issue priority — every 64
   // iterations — by the samples its slowest pixel still has to render: >= prio_t3 -> 3, >= prio_t2 -> 2, >= prio_t1 -> 1, else 0 (render_kernel).
   // prio_t1 = 0: never.
@@ -344,7 +347,9 @@ __device__ __forceinline__ void lane_acquire(Lane& L, const KArgs& a) {
   const long long g = (long long)l * k.shard_count + k.shard_index; // global tile (pt_render.h: round-robin shards)
   const int tx = (int)(g % k.tiles_x), ty = (int)(g / k.tiles_x);
   const int x = tx * PT_TILE + (in_tile & 7), y = ty * PT_TILE + (in_tile >> 3);
-  if (g >= k.n_tiles || x >= k.width || y >= k.height) return; // padding pixel: stays 0, ask again next iteration
+  // padding pixel, or a pixel outside a masked window's mask: stays as it is, ask again next iteration
+  if (g >= k.n_tiles || x >= k.width || y >= k.height ||
+      (k.mask && !k.mask[k.shard_count == 1 ? (long long)y * k.width + x : (long long)l * PT_TILE_PIXELS + in_tile])) return;
   // render.hpp:130-132: seed = linear id of the pixel in the WHOLE frame, truncated to 32 bits
   const uint32_t id = (uint32_t)((unsigned long long)y * (unsigned long long)k.width + (unsigned long long)x);
   if constexpr (FAST) {
@@ -1050,6 +1055,163 @@ __global__ void accum_tonemap_kernel(const float* __restrict__ sum, uint8_t* __r
   }
 }
 
+// ---- adaptive sampling (pt_adaptive_*): per-pixel counts, the two-half-buffer error estimate and masked windows ---------------------
+// The frame of an adaptive PtAccum as its small kernels see it.  Per-pixel arrays use the frame buffer's layout without the channel:
+// pixel i is (i % width, i / width) for whole frames and (local tile i / 64, ly * 8 + lx = i % 64) for shards, whose padding pixels
+// (edge tiles, the padded last tile) are no pixels of the frame.
+struct AFrame {
+  int width, height, shard_index, shard_count, tiles_x, n_tiles;
+  long long pixels; // P = pt_framebuffer_floats / 3
+};
+
+__host__ __device__ __forceinline__ bool aframe_xy(const AFrame& f, long long i, int& x, int& y) {
+  if (f.shard_count == 1) { x = (int)(i % f.width); y = (int)(i / f.width); return true; }
+  const long long g = (i >> 6) * f.shard_count + f.shard_index;
+  const int in = (int)(i & 63);
+  x = (int)(g % f.tiles_x) * PT_TILE + (in & 7); y = (int)(g / f.tiles_x) * PT_TILE + (in >> 3);
+  return g < f.n_tiles && x < f.width && y < f.height;
+}
+
+// every pixel's generator state at 0 samples: its linear id in the whole frame (render.hpp:130-132), indexed like KArgs.resume_rng
+__global__ void adaptive_seed_kernel(AFrame f, unsigned int* __restrict__ rng, long long words) {
+  const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= words) return;
+  const long long g = (j >> 6) * f.shard_count + f.shard_index;
+  const int in = (int)(j & 63);
+  const int x = (int)(g % f.tiles_x) * PT_TILE + (in & 7), y = (int)(g / f.tiles_x) * PT_TILE + (in >> 3);
+  rng[j] = (g < f.n_tiles && x < f.width && y < f.height) ? (uint32_t)((unsigned long long)y * (unsigned long long)f.width + (unsigned long long)x) : 0u;
+}
+
+// masked window, step 1: which local tiles hold at least one pixel of the mask
+__global__ void adaptive_tiles_kernel(AFrame f, const uint8_t* __restrict__ mask, int local_tiles, uint8_t* __restrict__ active) {
+  const int l = blockIdx.x * blockDim.x + threadIdx.x;
+  if (l >= local_tiles) return;
+  uint8_t any = 0;
+  for (int in = 0; in < PT_TILE_PIXELS && !any; in++) {
+    const long long pix = (long long)l * PT_TILE_PIXELS + in;
+    int x, y;
+    const long long g = (long long)l * f.shard_count + f.shard_index;
+    x = (int)(g % f.tiles_x) * PT_TILE + (in & 7); y = (int)(g / f.tiles_x) * PT_TILE + (in >> 3);
+    if (g >= f.n_tiles || x >= f.width || y >= f.height) continue;
+    any = mask[f.shard_count == 1 ? (long long)y * f.width + x : pix];
+  }
+  active[l] = any ? 1 : 0;
+}
+
+// masked window, step 2 (one workgroup): the active tiles in dequeue order — the kept heaviest-first order, or raster order — by a
+// stable scan; count[0] = how many
+__global__ __launch_bounds__(1024) void adaptive_compact_kernel(const uint8_t* __restrict__ active, const int* __restrict__ order, int n,
+                                                                int* __restrict__ list, int* __restrict__ count) {
+  __shared__ int wave_sum[16];
+  __shared__ int base;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (tid == 0) base = 0;
+  __syncthreads();
+  for (int start = 0; start < n; start += 1024) {
+    const int i = start + tid;
+    const int t = i < n ? (order ? order[i] : i) : 0;
+    const bool on = i < n && active[t];
+    const unsigned long long b = __builtin_amdgcn_ballot_w64(on);
+    if (lane == 0) wave_sum[wave] = __builtin_popcountll(b);
+    __syncthreads();
+    int at = base;
+    for (int v = 0; v < wave; v++) at += wave_sum[v];
+    if (on) list[at + __builtin_popcountll(b & ((1ull << lane) - 1ull))] = t;
+    __syncthreads();
+    if (tid == 0) for (int v = 0; v < 16; v++) base += wave_sum[v];
+    __syncthreads();
+  }
+  if (tid == 0) *count = base;
+}
+
+// after a window of w samples, over the pixels it rendered: its contribution D = S after - S before goes to half A while A has fewer
+// samples than B (ties to B), then n += w; and S before := S after, for the next window (PtAccum.prev)
+__global__ void adaptive_book_kernel(AFrame f, const uint8_t* __restrict__ mask, const float* __restrict__ sum, float* __restrict__ prev,
+                                     float* __restrict__ half, int* __restrict__ cnt, int* __restrict__ cnt_a, int w) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= f.pixels) return;
+  int x, y;
+  if (!aframe_xy(f, i, x, y) || (mask && !mask[i])) return;
+  const int n = cnt[i], a = cnt_a[i];
+  const float s0 = sum[3 * i], s1 = sum[3 * i + 1], s2 = sum[3 * i + 2];
+  if (a < n - a) {
+    half[3 * i] = half[3 * i] + (s0 - prev[3 * i]);
+    half[3 * i + 1] = half[3 * i + 1] + (s1 - prev[3 * i + 1]);
+    half[3 * i + 2] = half[3 * i + 2] + (s2 - prev[3 * i + 2]);
+    cnt_a[i] = a + w;
+  }
+  cnt[i] = n + w;
+  prev[3 * i] = s0; prev[3 * i + 1] = s1; prev[3 * i + 2] = s2;
+}
+
+// the two-half-buffer error (include/pt_render.h): correctly rounded binary32 throughout, no contraction (-ffp-contract=off)
+__device__ __forceinline__ float adaptive_err(const float* __restrict__ sum, const float* __restrict__ half, int n, int a, long long i) {
+  if (a == 0 || a == n) return __builtin_inff();
+  const float fn = (float)n, fa = (float)a;
+  const float ix = sum[3 * i] / fn, iy = sum[3 * i + 1] / fn, iz = sum[3 * i + 2] / fn;
+  const float ax = half[3 * i] / fa, ay = half[3 * i + 1] / fa, az = half[3 * i + 2] / fa;
+  const float num = (fabsf(ix - ax) + fabsf(iy - ay)) + fabsf(iz - az);
+  return num / (1e-4f + sqrt_rn((ix + iy) + iz));
+}
+
+__global__ void adaptive_error_kernel(AFrame f, const float* __restrict__ sum, const float* __restrict__ half, const int* __restrict__ cnt,
+                                      const int* __restrict__ cnt_a, float* __restrict__ err) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= f.pixels) return;
+  err[i] = adaptive_err(sum, half, cnt[i], cnt_a[i], i);
+}
+
+// the next window's mask: active = n < max_spp && (n < min_spp || noisy(p) || (dilate && a neighbour in the frame is noisy)),
+// noisy(q) = n_q < max_spp && !(err_q <= threshold); n_active += the active pixels (one atomic per wave)
+__global__ void adaptive_select_kernel(AFrame f, const float* __restrict__ sum, const float* __restrict__ half, const int* __restrict__ cnt,
+                                       const int* __restrict__ cnt_a, float threshold, int min_spp, int max_spp, int dilate,
+                                       uint8_t* __restrict__ mask, unsigned long long* __restrict__ n_active) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  bool on = false;
+  if (i < f.pixels) {
+    int x, y;
+    if (aframe_xy(f, i, x, y)) {
+      auto noisy = [&](long long q) { const int n = cnt[q]; return n < max_spp && !(adaptive_err(sum, half, n, cnt_a[q], q) <= threshold); };
+      const int n = cnt[i];
+      if (n < max_spp) {
+        on = n < min_spp || noisy(i);
+        if (!on && dilate) // (whole frames only: pt_adaptive_select)
+          for (int dy = -1; dy <= 1 && !on; dy++)
+            for (int dx = -1; dx <= 1 && !on; dx++) {
+              const int qx = x + dx, qy = y + dy;
+              if ((dx || dy) && qx >= 0 && qx < f.width && qy >= 0 && qy < f.height) on = noisy((long long)qy * f.width + qx);
+            }
+      }
+    }
+    mask[i] = on ? 1 : 0;
+  }
+  const unsigned long long b = __builtin_amdgcn_ballot_w64(on);
+  if ((threadIdx.x & 63) == 0 && b) atomicAdd(n_active, (unsigned long long)__builtin_popcountll(b));
+}
+
+// fb = sum / n per pixel (accum_resolve_kernel's correctly rounded division), 0 where n = 0
+__global__ void adaptive_resolve_kernel(const float* __restrict__ sum, const int* __restrict__ cnt, float* __restrict__ fb, long long floats) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= floats) return;
+  const int n = cnt[i / 3];
+  fb[i] = n > 0 ? sum[i] / (float)n : 0.0f;
+}
+
+// adaptive_resolve_kernel + tonemap_kernel in one pass (whole frames), as accum_tonemap_kernel
+__global__ void adaptive_tonemap_kernel(const float* __restrict__ sum, const int* __restrict__ cnt, uint8_t* __restrict__ rgb8, int width, int height) {
+  int x = blockIdx.x * blockDim.x + threadIdx.x, row = blockIdx.y; // row 0 = top
+  if (x >= width) return;
+  int j = height - 1 - row;
+  const int n = cnt[(long long)j * width + x];
+  for (int ch = 0; ch < 3; ch++) {
+    float s = sqrt_rn(n > 0 ? sum[((long long)j * width + x) * 3 + ch] / (float)n : 0.0f);
+    float cl = (s < 0.0f) ? 0.0f : (0.999f < s) ? 0.999f : s;
+    float sc = 256.0f * cl;
+    int v = (sc == sc) ? (int)sc : 0;
+    rgb8[((long long)row * width + x) * 3 + ch] = (uint8_t)v;
+  }
+}
+
 thread_local std::string g_last_error;
 
 // ---- tuning: include/pt_render.h PtTuning.  Resolved ONCE per scene (pt_scene_create / pt_debug_flatten), never on the launch path.
@@ -1713,6 +1875,11 @@ struct Window {
   int* order;        // the accumulator's own heaviest-first tile order (and the cooperative kernels' split) ...
   int* nsplit;
   bool* has_order;   // ... valid once a window has probed
+  // a masked window of an adaptive PtAccum (pt_adaptive_window): the per-pixel mask, and the n_active local tiles that hold one of its
+  // pixels in dequeue order — the launch sees a frame of that many tiles; no probe, no wide phase, no scene scheduling workspace
+  const uint8_t* mask = nullptr;
+  const int* active = nullptr;
+  int n_active = 0;
 };
 
 static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderParams* p, float* fb, hipStream_t st, const Window* w = nullptr) {
@@ -1731,8 +1898,11 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
   a.pinhole = cam_is_pinhole(a.cam) ? 1 : 0;
   a.shard_index = p->shard_index; a.shard_count = p->shard_count;
   a.n_tiles = n_tiles_of(p, &a.tiles_x);
-  const int local_tiles = (a.n_tiles - p->shard_index + p->shard_count - 1) / p->shard_count; // tiles this shard owns
+  const bool masked = w && w->mask;
+  // tiles this shard owns (a masked window: the tiles it renders)
+  const int local_tiles = masked ? w->n_active : (a.n_tiles - p->shard_index + p->shard_count - 1) / p->shard_count;
   a.keep_state = 0; a.fast_chunk0 = 0;
+  a.mask = masked ? w->mask : nullptr;
   // pixels no lane owns (edge tiles, padded last tile, depth 0) read as 0 (a window's sums: zeroed by pt_accum_create / _reset)
   if (!w) PT_HIP(hipMemsetAsync(fb, 0, (size_t)pt_framebuffer_floats(p) * sizeof(float), st));
   if (local_tiles <= 0) return PT_OK;
@@ -2027,7 +2197,9 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
   // (the triangle-pool kernels deal every wave a stratified sample of the frame's tiles — lane_acquire, scatter_p — which balances the
   // waves without knowing the costs: the probe only costs there, 1080p x 32 spp 3.12 -> 2.95 s without it; PT_LPT_SCATTER=1 keeps it)
   const bool probe_pays = !(a.scatter_p > 0) || s->knobs.lpt_with_scatter;
-  if (probe_spp >= 1 && local_tiles >= 64 && !(p->flags & PT_FLAG_NO_LPT) && probe_pays) {
+  if (masked) {
+    a.order = w->active; // (n_split stays NULL: no wide phase)
+  } else if (probe_spp >= 1 && local_tiles >= 64 && !(p->flags & PT_FLAG_NO_LPT) && probe_pays) {
     if (int rc = reserve_tiles(s, local_tiles)) return rc; // first render at a new size only (or never: pt_scene_reserve)
     PT_HIP(hipMemsetAsync(s->ws_cost, 0, (size_t)local_tiles * sizeof(unsigned int), st));
     KArgs main_args = a;
@@ -2214,9 +2386,22 @@ struct PtAccum {
   int* order = nullptr;         // heaviest-first tile order of the last probed window (never the scene's ws_order)
   int* nsplit = nullptr;        // ... and the cooperative kernels' split decided with it
   bool has_order = false;
-  int32_t done = 0;             // samples the state holds (host-side count)
+  int32_t done = 0;             // samples the state holds (host-side count; adaptive: the unmasked windows' samples)
   bool cam_bound = false;
   PtCamera cam{};
+  // adaptive accumulators (pt_adaptive_create): per-pixel counts and half A, in the frame buffer's layout without the channel
+  bool adaptive = false;
+  size_t pixels = 0;            // P = fb_floats / 3
+  float* half = nullptr;        // H: radiance sum of half A (fb_floats)
+  float* prev = nullptr;        // the sums before the next window (fb_floats): its contribution for the bookkeeping ...
+  bool prev_synced = false;     // ... equal to `sum` (the bookkeeping pass keeps it so; otherwise a window copies it first)
+  int* cnt = nullptr;           // n per pixel
+  int* cnt_a = nullptr;         // a per pixel: samples in half A
+  uint8_t* tile_on = nullptr;   // masked windows: per local tile, holds an active pixel ...
+  int* active = nullptr;        // ... the active tiles in dequeue order ...
+  int* n_active = nullptr;      // ... and how many (device)
+  unsigned long long* n_sel = nullptr; // pt_adaptive_select's count (device)
+  int64_t max_n = 0;            // bound on every pixel's n (host-side; 0: nothing rendered)
 };
 
 namespace {
@@ -2274,21 +2459,54 @@ void pt_accum_destroy(PtAccum* acc) {
   if (acc->rng) (void)hipFree(acc->rng);
   if (acc->order) (void)hipFree(acc->order);
   if (acc->nsplit) (void)hipFree(acc->nsplit);
+  for (void* b : {(void*)acc->half, (void*)acc->prev, (void*)acc->cnt, (void*)acc->cnt_a, (void*)acc->tile_on, (void*)acc->active,
+                  (void*)acc->n_active, (void*)acc->n_sel})
+    if (b) (void)hipFree(b);
   delete acc;
 }
 
-int pt_accum_create(const PtScene* scene, const PtRenderParams* p, PtAccum** out) {
-  if (!out) return fail(PT_ERR_INVALID_ARG, "pt_accum_create: out is NULL");
+} // extern "C"
+namespace {
+AFrame frame_of(const PtAccum* acc) {
+  AFrame f;
+  f.width = acc->p.width; f.height = acc->p.height; f.shard_index = acc->p.shard_index; f.shard_count = acc->p.shard_count;
+  f.n_tiles = n_tiles_of(&acc->p, &f.tiles_x);
+  f.pixels = (long long)acc->pixels;
+  return f;
+}
+unsigned int blocks_of(long long n) { return (unsigned int)std::max<long long>(1, (n + 255) / 256); }
+
+// an adaptive accumulator at 0 samples: sums, H, n, a zeroed; every generator state the pixel's seed
+int adaptive_clear(PtAccum* acc, hipStream_t st) {
+  PT_HIP(hipMemsetAsync(acc->sum, 0, acc->fb_floats * sizeof(float), st));
+  PT_HIP(hipMemsetAsync(acc->half, 0, acc->fb_floats * sizeof(float), st));
+  PT_HIP(hipMemsetAsync(acc->prev, 0, acc->fb_floats * sizeof(float), st));
+  acc->prev_synced = true;
+  PT_HIP(hipMemsetAsync(acc->cnt, 0, std::max<size_t>(acc->pixels, 1) * sizeof(int), st));
+  PT_HIP(hipMemsetAsync(acc->cnt_a, 0, std::max<size_t>(acc->pixels, 1) * sizeof(int), st));
+  if (acc->rng_words) {
+    hipLaunchKernelGGL(adaptive_seed_kernel, dim3(blocks_of((long long)acc->rng_words)), dim3(256), 0, st, frame_of(acc), acc->rng, (long long)acc->rng_words);
+    PT_HIP(hipGetLastError());
+  }
+  acc->max_n = 0;
+  return PT_OK;
+}
+
+int accum_create(const PtScene* scene, const PtRenderParams* p, PtAccum** out, bool adaptive) {
+  const char* who = adaptive ? "pt_adaptive_create" : "pt_accum_create";
+  if (!out) return fail(PT_ERR_INVALID_ARG, std::string(who) + ": out is NULL");
   *out = nullptr;
-  if (!scene) return fail(PT_ERR_INVALID_ARG, "pt_accum_create: NULL scene");
+  if (!scene) return fail(PT_ERR_INVALID_ARG, std::string(who) + ": NULL scene");
   PtRenderParams q;
   if (int rc = accum_params(p, q)) return rc;
+  if (adaptive && (q.flags & PT_FLAG_FAST_RNG)) return fail(PT_ERR_INVALID_ARG, "pt_adaptive_create: PT_FLAG_FAST_RNG is not offered for adaptive sampling");
   int cur = -1;
   PT_HIP(hipGetDevice(&cur));
-  if (cur != scene->device) return fail(PT_ERR_INVALID_ARG, "pt_accum_create: the scene lives on another device");
+  if (cur != scene->device) return fail(PT_ERR_INVALID_ARG, std::string(who) + ": the scene lives on another device");
   PtAccum* acc = new PtAccum();
   acc->scene = scene;
   acc->p = q;
+  acc->adaptive = adaptive;
   const int n_tiles = n_tiles_of(&q, nullptr);
   acc->local_tiles = std::max(0, (n_tiles - q.shard_index + q.shard_count - 1) / q.shard_count);
   acc->fb_floats = (size_t)pt_framebuffer_floats(&q);
@@ -2301,6 +2519,21 @@ int pt_accum_create(const PtScene* scene, const PtRenderParams* p, PtAccum** out
   if ((e = hipMalloc((void**)&acc->nsplit, 2 * sizeof(int))) != hipSuccess) return bail(e, "pt_accum_create: hipMalloc");
   if ((e = hipMemset(acc->sum, 0, acc->fb_floats * sizeof(float))) != hipSuccess) return bail(e, "pt_accum_create: hipMemset");
   if ((e = hipMemset(acc->rng, 0, std::max<size_t>(acc->rng_words, 1) * sizeof(unsigned int))) != hipSuccess) return bail(e, "pt_accum_create: hipMemset");
+  if (adaptive) {
+    acc->pixels = acc->fb_floats / 3;
+    const size_t P = std::max<size_t>(acc->pixels, 1), T = (size_t)std::max(acc->local_tiles, 1);
+    if ((e = hipMalloc((void**)&acc->half, acc->fb_floats * sizeof(float))) != hipSuccess ||
+        (e = hipMalloc((void**)&acc->prev, acc->fb_floats * sizeof(float))) != hipSuccess ||
+        (e = hipMalloc((void**)&acc->cnt, P * sizeof(int))) != hipSuccess ||
+        (e = hipMalloc((void**)&acc->cnt_a, P * sizeof(int))) != hipSuccess ||
+        (e = hipMalloc((void**)&acc->tile_on, T)) != hipSuccess ||
+        (e = hipMalloc((void**)&acc->active, T * sizeof(int))) != hipSuccess ||
+        (e = hipMalloc((void**)&acc->n_active, sizeof(int))) != hipSuccess ||
+        (e = hipMalloc((void**)&acc->n_sel, sizeof(unsigned long long))) != hipSuccess)
+      return bail(e, "pt_adaptive_create: hipMalloc");
+    if (int rc = adaptive_clear(acc, nullptr)) { pt_accum_destroy(acc); return rc; }
+    if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) return bail(e, "pt_adaptive_create: hipStreamSynchronize");
+  }
   {
     // the scene's launch workspaces a window uses (probe costs, tile ranks; the candidate cache): sized now, not by a window
     std::lock_guard<std::mutex> lock(scene->sched);
@@ -2311,10 +2544,15 @@ int pt_accum_create(const PtScene* scene, const PtRenderParams* p, PtAccum** out
   *out = acc;
   return PT_OK;
 }
+} // namespace
+extern "C" {
+
+int pt_accum_create(const PtScene* scene, const PtRenderParams* p, PtAccum** out) { return accum_create(scene, p, out, false); }
 
 int pt_accum_reset(PtAccum* acc, void* stream) {
   if (!acc) return fail(PT_ERR_INVALID_ARG, "pt_accum_reset: NULL accumulator");
-  PT_HIP(hipMemsetAsync(acc->sum, 0, acc->fb_floats * sizeof(float), (hipStream_t)stream));
+  if (acc->adaptive) { if (int rc = adaptive_clear(acc, (hipStream_t)stream)) return rc; }
+  else PT_HIP(hipMemsetAsync(acc->sum, 0, acc->fb_floats * sizeof(float), (hipStream_t)stream));
   acc->done = 0;
   acc->cam_bound = false;
   acc->has_order = false;
@@ -2325,6 +2563,7 @@ int32_t pt_accum_samples(const PtAccum* acc) { return acc ? acc->done : -1; }
 
 int pt_render_accumulate(PtAccum* acc, const PtCamera* cam, int32_t samples, void* stream) {
   if (!acc || !cam) return fail(PT_ERR_INVALID_ARG, "pt_render_accumulate: NULL argument");
+  if (acc->adaptive) return pt_adaptive_window(acc, cam, samples, nullptr, stream);
   if (samples <= 0) return fail(PT_ERR_INVALID_ARG, "pt_render_accumulate: samples must be > 0");
   if ((int64_t)acc->done + samples > (int64_t)INT32_MAX) return fail(PT_ERR_INVALID_ARG, "pt_render_accumulate: the total would pass INT32_MAX samples");
   if (acc->cam_bound && std::memcmp(&acc->cam, cam, sizeof(PtCamera)) != 0)
@@ -2342,8 +2581,13 @@ int pt_render_accumulate(PtAccum* acc, const PtCamera* cam, int32_t samples, voi
 
 int pt_accum_resolve(const PtAccum* acc, float* fb_device, void* stream) {
   if (!acc || !fb_device) return fail(PT_ERR_INVALID_ARG, "pt_accum_resolve: NULL argument");
-  if (acc->done <= 0) return fail(PT_ERR_INVALID_ARG, "pt_accum_resolve: no samples rendered yet");
+  if (acc->adaptive ? acc->max_n <= 0 : acc->done <= 0) return fail(PT_ERR_INVALID_ARG, "pt_accum_resolve: no samples rendered yet");
   const long long n = (long long)acc->fb_floats;
+  if (acc->adaptive) { // each pixel by its own count
+    hipLaunchKernelGGL(adaptive_resolve_kernel, dim3(blocks_of(n)), dim3(256), 0, (hipStream_t)stream, acc->sum, acc->cnt, fb_device, n);
+    PT_HIP(hipGetLastError());
+    return PT_OK;
+  }
   hipLaunchKernelGGL(accum_resolve_kernel, dim3((unsigned int)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, acc->sum, fb_device, n,
                      (float)acc->done);
   PT_HIP(hipGetLastError());
@@ -2352,9 +2596,14 @@ int pt_accum_resolve(const PtAccum* acc, float* fb_device, void* stream) {
 
 int pt_accum_tonemap_rgb8(const PtAccum* acc, uint8_t* rgb8_device, void* stream) {
   if (!acc || !rgb8_device) return fail(PT_ERR_INVALID_ARG, "pt_accum_tonemap_rgb8: NULL argument");
-  if (acc->done <= 0) return fail(PT_ERR_INVALID_ARG, "pt_accum_tonemap_rgb8: no samples rendered yet");
+  if (acc->adaptive ? acc->max_n <= 0 : acc->done <= 0) return fail(PT_ERR_INVALID_ARG, "pt_accum_tonemap_rgb8: no samples rendered yet");
   if (acc->p.shard_count != 1) return fail(PT_ERR_INVALID_ARG, "pt_accum_tonemap_rgb8: whole frames only (shard_count == 1)");
   dim3 block(256), grid((acc->p.width + 255) / 256, acc->p.height);
+  if (acc->adaptive) {
+    hipLaunchKernelGGL(adaptive_tonemap_kernel, grid, block, 0, (hipStream_t)stream, acc->sum, acc->cnt, rgb8_device, acc->p.width, acc->p.height);
+    PT_HIP(hipGetLastError());
+    return PT_OK;
+  }
   hipLaunchKernelGGL(accum_tonemap_kernel, grid, block, 0, (hipStream_t)stream, acc->sum, rgb8_device, acc->p.width, acc->p.height, (float)acc->done);
   PT_HIP(hipGetLastError());
   return PT_OK;
@@ -2362,6 +2611,7 @@ int pt_accum_tonemap_rgb8(const PtAccum* acc, uint8_t* rgb8_device, void* stream
 
 int pt_accum_export(const PtAccum* acc, void* host, int64_t bytes, void* stream) {
   if (!acc || !host) return fail(PT_ERR_INVALID_ARG, "pt_accum_export: NULL argument");
+  if (acc->adaptive) return fail(PT_ERR_INVALID_ARG, "pt_accum_export: an adaptive accumulator exports with pt_adaptive_export");
   if (bytes != pt_accum_state_bytes(&acc->p)) return fail(PT_ERR_INVALID_ARG, "pt_accum_export: the buffer is not pt_accum_state_bytes() long");
   AccumHeader h;
   std::memset(&h, 0, sizeof h);
@@ -2381,6 +2631,7 @@ int pt_accum_export(const PtAccum* acc, void* host, int64_t bytes, void* stream)
 
 int pt_accum_import(PtAccum* acc, const void* host, int64_t bytes, void* stream) {
   if (!acc || !host) return fail(PT_ERR_INVALID_ARG, "pt_accum_import: NULL argument");
+  if (acc->adaptive) return fail(PT_ERR_INVALID_ARG, "pt_accum_import: an adaptive accumulator imports with pt_adaptive_import");
   if (bytes != pt_accum_state_bytes(&acc->p)) return fail(PT_ERR_INVALID_ARG, "pt_accum_import: the state is not pt_accum_state_bytes() long for this accumulator");
   AccumHeader h;
   std::memcpy(&h, host, sizeof h);
@@ -2398,6 +2649,189 @@ int pt_accum_import(PtAccum* acc, const void* host, int64_t bytes, void* stream)
   acc->cam_bound = h.camera_bound != 0;
   acc->cam = h.cam;
   acc->has_order = false; // (the next window long enough to probe orders the tiles again)
+  return PT_OK;
+}
+
+// ---- adaptive sampling: per-pixel sample counts (include/pt_render.h) ----------------------------------------------------------
+int pt_adaptive_create(const PtScene* scene, const PtRenderParams* p, PtAccum** out) { return accum_create(scene, p, out, true); }
+
+int64_t pt_adaptive_state_bytes(const PtRenderParams* p) {
+  PtRenderParams q;
+  if (accum_params(p, q) || (q.flags & PT_FLAG_FAST_RNG)) return -1;
+  const int64_t F = pt_framebuffer_floats(&q), R = (int64_t)pt_shard_tiles(&q) * PT_TILE_PIXELS, P = F / 3;
+  return (int64_t)PT_ACCUM_HEADER_BYTES + 4 * F + 4 * R + 4 * F + 4 * P + 4 * P;
+}
+
+static int adaptive_only(const PtAccum* acc, const char* who) {
+  if (!acc) return fail(PT_ERR_INVALID_ARG, std::string(who) + ": NULL accumulator");
+  if (!acc->adaptive) return fail(PT_ERR_INVALID_ARG, std::string(who) + ": not an adaptive accumulator (pt_adaptive_create)");
+  return PT_OK;
+}
+
+int pt_adaptive_window(PtAccum* acc, const PtCamera* cam, int32_t samples, const uint8_t* mask_device, void* stream) {
+  if (int rc = adaptive_only(acc, "pt_adaptive_window")) return rc;
+  if (!cam) return fail(PT_ERR_INVALID_ARG, "pt_adaptive_window: NULL camera");
+  if (samples <= 0) return fail(PT_ERR_INVALID_ARG, "pt_adaptive_window: samples must be > 0");
+  // (the kernels count a window from a nominal start of 1: see below)
+  if (acc->max_n + samples > (int64_t)INT32_MAX || samples >= INT32_MAX)
+    return fail(PT_ERR_INVALID_ARG, "pt_adaptive_window: a pixel's total could pass INT32_MAX samples");
+  if (acc->cam_bound && std::memcmp(&acc->cam, cam, sizeof(PtCamera)) != 0)
+    return fail(PT_ERR_INVALID_ARG, "pt_adaptive_window: the camera differs from the one the accumulator's first window was rendered with");
+  const hipStream_t st = (hipStream_t)stream;
+  const AFrame f = frame_of(acc);
+  // Every window resumes from the state (pt_adaptive_create seeded it), whatever its pixels' counts: the kernels read the sample index
+  // only to stop and for the chain-priority poll, so a window runs from a nominal start of 1 to 1 + samples (with done = 0 it would seed).
+  Window w{1, acc->rng, acc->order, acc->nsplit, &acc->has_order};
+  if (mask_device) {
+    if (acc->local_tiles <= 0) return PT_OK;
+    hipLaunchKernelGGL(adaptive_tiles_kernel, dim3(blocks_of(acc->local_tiles)), dim3(256), 0, st, f, mask_device, acc->local_tiles, acc->tile_on);
+    PT_HIP(hipGetLastError());
+    hipLaunchKernelGGL(adaptive_compact_kernel, dim3(1), dim3(1024), 0, st, acc->tile_on, acc->has_order ? acc->order : nullptr, acc->local_tiles,
+                       acc->active, acc->n_active);
+    PT_HIP(hipGetLastError());
+    int n_active = 0;
+    PT_HIP(hipMemcpyAsync(&n_active, acc->n_active, sizeof(int), hipMemcpyDeviceToHost, st));
+    PT_HIP(hipStreamSynchronize(st)); // (the launch is sized by the active tiles)
+    if (n_active <= 0) return PT_OK;  // an empty mask: nothing to render
+    w.mask = mask_device; w.active = acc->active; w.n_active = n_active;
+  }
+  PtRenderParams q = acc->p;
+  q.samples = samples;
+  // S before the window is `prev`, which the last bookkeeping pass left equal to the sums (copied here only where none ran since)
+  if (!acc->prev_synced) PT_HIP(hipMemcpyAsync(acc->prev, acc->sum, acc->fb_floats * sizeof(float), hipMemcpyDeviceToDevice, st));
+  acc->prev_synced = false;
+  if (int rc = launch_render(acc->scene, cam, &q, acc->sum, st, &w)) return rc;
+  hipLaunchKernelGGL(adaptive_book_kernel, dim3(blocks_of(f.pixels)), dim3(256), 0, st, f, mask_device, acc->sum, acc->prev, acc->half,
+                     acc->cnt, acc->cnt_a, (int)samples);
+  PT_HIP(hipGetLastError());
+  acc->prev_synced = true;
+  if (!mask_device) acc->done += samples;
+  acc->max_n += samples;
+  if (!acc->cam_bound) { acc->cam = *cam; acc->cam_bound = true; }
+  return PT_OK;
+}
+
+int pt_adaptive_counts(const PtAccum* acc, int32_t* counts_device, void* stream) {
+  if (int rc = adaptive_only(acc, "pt_adaptive_counts")) return rc;
+  if (!counts_device) return fail(PT_ERR_INVALID_ARG, "pt_adaptive_counts: NULL argument");
+  PT_HIP(hipMemcpyAsync(counts_device, acc->cnt, acc->pixels * sizeof(int), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return PT_OK;
+}
+
+int pt_adaptive_error(const PtAccum* acc, float* err_device, void* stream) {
+  if (int rc = adaptive_only(acc, "pt_adaptive_error")) return rc;
+  if (!err_device) return fail(PT_ERR_INVALID_ARG, "pt_adaptive_error: NULL argument");
+  const AFrame f = frame_of(acc);
+  hipLaunchKernelGGL(adaptive_error_kernel, dim3(blocks_of(f.pixels)), dim3(256), 0, (hipStream_t)stream, f, acc->sum, acc->half, acc->cnt, acc->cnt_a, err_device);
+  PT_HIP(hipGetLastError());
+  return PT_OK;
+}
+
+int pt_adaptive_select(const PtAccum* acc, float threshold, int32_t min_spp, int32_t max_spp, uint32_t flags, uint8_t* mask_device,
+                       int64_t* n_active, void* stream) {
+  if (int rc = adaptive_only(acc, "pt_adaptive_select")) return rc;
+  if (!mask_device || !n_active) return fail(PT_ERR_INVALID_ARG, "pt_adaptive_select: NULL argument");
+  if (flags & ~PT_ADAPTIVE_DILATE) return fail(PT_ERR_INVALID_ARG, "pt_adaptive_select: unknown flags");
+  if ((flags & PT_ADAPTIVE_DILATE) && acc->p.shard_count != 1)
+    return fail(PT_ERR_INVALID_ARG, "pt_adaptive_select: PT_ADAPTIVE_DILATE needs whole frames (a shard's neighbours are other shards' pixels)");
+  const hipStream_t st = (hipStream_t)stream;
+  const AFrame f = frame_of(acc);
+  PT_HIP(hipMemsetAsync(acc->n_sel, 0, sizeof(unsigned long long), st));
+  hipLaunchKernelGGL(adaptive_select_kernel, dim3(blocks_of(f.pixels)), dim3(256), 0, st, f, acc->sum, acc->half, acc->cnt, acc->cnt_a, threshold,
+                     (int)min_spp, (int)max_spp, (flags & PT_ADAPTIVE_DILATE) ? 1 : 0, mask_device, acc->n_sel);
+  PT_HIP(hipGetLastError());
+  unsigned long long n = 0;
+  PT_HIP(hipMemcpyAsync(&n, acc->n_sel, sizeof n, hipMemcpyDeviceToHost, st));
+  PT_HIP(hipStreamSynchronize(st));
+  *n_active = (int64_t)n;
+  return PT_OK;
+}
+
+int pt_adaptive_export(const PtAccum* acc, void* host, int64_t bytes, void* stream) {
+  if (int rc = adaptive_only(acc, "pt_adaptive_export")) return rc;
+  if (!host) return fail(PT_ERR_INVALID_ARG, "pt_adaptive_export: NULL argument");
+  if (bytes != pt_adaptive_state_bytes(&acc->p)) return fail(PT_ERR_INVALID_ARG, "pt_adaptive_export: the buffer is not pt_adaptive_state_bytes() long");
+  AccumHeader h;
+  std::memset(&h, 0, sizeof h);
+  h.magic = PT_ACCUM_MAGIC; h.version = PT_ADAPTIVE_FORMAT;
+  h.width = acc->p.width; h.height = acc->p.height; h.depth = acc->p.depth;
+  h.shard_index = acc->p.shard_index; h.shard_count = acc->p.shard_count; h.flags = acc->p.flags;
+  h.samples_done = acc->done; h.camera_bound = acc->cam_bound ? 1 : 0;
+  h.cam = acc->cam;
+  char* out = (char*)host;
+  std::memcpy(out, &h, sizeof h);
+  const hipStream_t st = (hipStream_t)stream;
+  const size_t F = acc->fb_floats * sizeof(float), R = acc->rng_words * sizeof(unsigned int), P = acc->pixels * sizeof(int);
+  out += sizeof h;
+  PT_HIP(hipMemcpyAsync(out, acc->sum, F, hipMemcpyDeviceToHost, st));
+  PT_HIP(hipMemcpyAsync(out + F, acc->rng, R, hipMemcpyDeviceToHost, st));
+  PT_HIP(hipMemcpyAsync(out + F + R, acc->half, F, hipMemcpyDeviceToHost, st));
+  PT_HIP(hipMemcpyAsync(out + 2 * F + R, acc->cnt, P, hipMemcpyDeviceToHost, st));
+  PT_HIP(hipMemcpyAsync(out + 2 * F + R + P, acc->cnt_a, P, hipMemcpyDeviceToHost, st));
+  PT_HIP(hipStreamSynchronize(st));
+  return PT_OK;
+}
+
+int pt_adaptive_import(PtAccum* acc, const void* host, int64_t bytes, void* stream) {
+  if (int rc = adaptive_only(acc, "pt_adaptive_import")) return rc;
+  if (!host) return fail(PT_ERR_INVALID_ARG, "pt_adaptive_import: NULL argument");
+  if (bytes < (int64_t)sizeof(AccumHeader)) return fail(PT_ERR_INVALID_ARG, "pt_adaptive_import: shorter than a state header");
+  AccumHeader h;
+  std::memcpy(&h, host, sizeof h);
+  if (h.magic != PT_ACCUM_MAGIC || (h.version != PT_ADAPTIVE_FORMAT && h.version != PT_ACCUM_FORMAT))
+    return fail(PT_ERR_INVALID_ARG, "pt_adaptive_import: not an exported accumulator state (magic / format version)");
+  const bool plain = h.version == PT_ACCUM_FORMAT;
+  if (bytes != (plain ? pt_accum_state_bytes(&acc->p) : pt_adaptive_state_bytes(&acc->p)))
+    return fail(PT_ERR_INVALID_ARG, "pt_adaptive_import: the state's size does not fit its format and this accumulator's frame");
+  if (h.width != acc->p.width || h.height != acc->p.height || h.depth != acc->p.depth || h.shard_index != acc->p.shard_index ||
+      h.shard_count != acc->p.shard_count || h.flags != acc->p.flags)
+    return fail(PT_ERR_INVALID_ARG, "pt_adaptive_import: the state was exported from an accumulator with other frame parameters");
+  const char* in = (const char*)host + sizeof h;
+  const size_t F = acc->fb_floats * sizeof(float), R = acc->rng_words * sizeof(unsigned int);
+  const AFrame f = frame_of(acc);
+  std::vector<int> n, na;
+  int64_t max_n = 0;
+  if (plain) { // upgrade: every pixel of the frame at samples_done, nothing in half A
+    if (h.samples_done < 0 || (h.camera_bound != 0) != (h.samples_done > 0)) return fail(PT_ERR_INVALID_ARG, "pt_adaptive_import: inconsistent header");
+    n.assign(acc->pixels, 0);
+    for (size_t i = 0; i < acc->pixels; i++) { int x, y; if (aframe_xy(f, (long long)i, x, y)) n[i] = h.samples_done; }
+    na.assign(acc->pixels, 0);
+    max_n = h.samples_done;
+  } else {
+    n.resize(acc->pixels); na.resize(acc->pixels);
+    std::memcpy(n.data(), in + 2 * F + R, acc->pixels * sizeof(int));
+    std::memcpy(na.data(), in + 2 * F + R + acc->pixels * sizeof(int), acc->pixels * sizeof(int));
+    int64_t min_n = INT32_MAX;
+    for (size_t i = 0; i < acc->pixels; i++) {
+      if (na[i] < 0 || na[i] > n[i]) return fail(PT_ERR_INVALID_ARG, "pt_adaptive_import: a pixel's counts are not 0 <= a <= n");
+      int x, y;
+      if (aframe_xy(f, (long long)i, x, y)) min_n = std::min<int64_t>(min_n, n[i]);
+      max_n = std::max<int64_t>(max_n, n[i]);
+    }
+    if (h.samples_done < 0 || (acc->pixels && h.samples_done > min_n) || (h.camera_bound != 0) != (max_n > 0))
+      return fail(PT_ERR_INVALID_ARG, "pt_adaptive_import: inconsistent header");
+  }
+  const hipStream_t st = (hipStream_t)stream;
+  PT_HIP(hipMemcpyAsync(acc->sum, in, F, hipMemcpyHostToDevice, st));
+  if (plain && h.samples_done == 0) { // (a plain state at 0 samples holds no generator states: the seeds)
+    if (acc->rng_words) {
+      hipLaunchKernelGGL(adaptive_seed_kernel, dim3(blocks_of((long long)acc->rng_words)), dim3(256), 0, st, f, acc->rng, (long long)acc->rng_words);
+      PT_HIP(hipGetLastError());
+    }
+  } else {
+    PT_HIP(hipMemcpyAsync(acc->rng, in + F, R, hipMemcpyHostToDevice, st));
+  }
+  if (plain) PT_HIP(hipMemsetAsync(acc->half, 0, F, st));
+  else PT_HIP(hipMemcpyAsync(acc->half, in + F + R, F, hipMemcpyHostToDevice, st));
+  PT_HIP(hipMemcpyAsync(acc->cnt, n.data(), acc->pixels * sizeof(int), hipMemcpyHostToDevice, st));
+  PT_HIP(hipMemcpyAsync(acc->cnt_a, na.data(), acc->pixels * sizeof(int), hipMemcpyHostToDevice, st));
+  PT_HIP(hipStreamSynchronize(st)); // (the caller's buffer and the host counts may go as soon as this returns)
+  acc->done = h.samples_done;
+  acc->max_n = max_n;
+  acc->cam_bound = h.camera_bound != 0;
+  acc->cam = h.cam;
+  acc->has_order = false;
+  acc->prev_synced = false; // (the next window copies the imported sums)
   return PT_OK;
 }
 

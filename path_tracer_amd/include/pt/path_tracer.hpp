@@ -364,6 +364,13 @@ void render(frame_buffer& frame_buf, std::vector<hittable_t>& hittables, camera&
 // Progressive rendering: one frame in sample windows; RAII over pt_accum_create / pt_accum_destroy (include/pt_render.h, PtAccum).
 // After windows totalling N samples, resolve() holds the bits render() gives at samples = N.  The scene must outlive the accumulator;
 // windows run on the default stream (or `stream`) and are ordered like renders of the scene.
+//
+// Adaptive sampling (pt_adaptive_*): constructed with pt::adaptive, the accumulator keeps a sample count per pixel; add() takes a mask
+// and each pixel resolves to the bits render() gives at its own count.  Masks, counts and errors are DEVICE buffers of one element per
+// pixel ([height][width]; [local tile][64] for shards) that the caller owns, as in the C ABI: this header does no device allocation.
+struct adaptive_t {};
+inline constexpr adaptive_t adaptive{};
+
 class accumulator {
  public:
   accumulator(const device_scene& scene, const camera& cam, int width, int height, int depth = 50, uint32_t flags = 0, int shard_index = 0,
@@ -371,38 +378,83 @@ class accumulator {
       : cam_(cam.c), p_{width, height, 1, depth, shard_index, shard_count, flags, 0} {
     check(pt_accum_create(scene.s, &p_, &a_), "pt_accum_create");
   }
+  accumulator(adaptive_t, const device_scene& scene, const camera& cam, int width, int height, int depth = 50, uint32_t flags = 0,
+              int shard_index = 0, int shard_count = 1)
+      : cam_(cam.c), p_{width, height, 1, depth, shard_index, shard_count, flags, 0}, adaptive_(true) {
+    check(pt_adaptive_create(scene.s, &p_, &a_), "pt_adaptive_create");
+  }
   ~accumulator() { pt_accum_destroy(a_); }
   accumulator(const accumulator&) = delete;
   accumulator& operator=(const accumulator&) = delete;
 
   // the next `samples` samples of every pixel
   void add(int samples, void* stream = nullptr) { check(pt_render_accumulate(a_, &cam_, samples, stream), "pt_render_accumulate"); }
+  // adaptive: the next `samples` samples of the pixels whose mask byte is nonzero (nullptr: every pixel; a mask synchronises `stream`)
+  void add_masked(int samples, const uint8_t* mask_device, void* stream = nullptr) {
+    check(pt_adaptive_window(a_, &cam_, samples, mask_device, stream), "pt_adaptive_window");
+  }
+  void counts(int32_t* counts_device, void* stream = nullptr) const { check(pt_adaptive_counts(a_, counts_device, stream), "pt_adaptive_counts"); }
+  void error(float* err_device, void* stream = nullptr) const { check(pt_adaptive_error(a_, err_device, stream), "pt_adaptive_error"); }
+  // the next window's mask; returns how many pixels are active (synchronises `stream`)
+  int64_t select(float threshold, int min_spp, int max_spp, bool dilate, uint8_t* mask_device, void* stream = nullptr) const {
+    int64_t n = 0;
+    check(pt_adaptive_select(a_, threshold, min_spp, max_spp, dilate ? PT_ADAPTIVE_DILATE : 0u, mask_device, &n, stream), "pt_adaptive_select");
+    return n;
+  }
+  bool is_adaptive() const { return adaptive_; }
+  // adaptive: each pixel's count, from an exported state (host memory)
+  std::vector<int32_t> counts() const {
+    const std::vector<uint8_t> st = state();
+    const std::size_t F = (std::size_t)pt_framebuffer_floats(&p_), R = (std::size_t)pt_shard_tiles(&p_) * PT_TILE_PIXELS;
+    std::vector<int32_t> n(F / 3);
+    std::memcpy(n.data(), st.data() + PT_ACCUM_HEADER_BYTES + 8 * F + 4 * R, n.size() * sizeof(int32_t));
+    return n;
+  }
   int samples() const { return pt_accum_samples(a_); }
   void reset(void* stream = nullptr) { check(pt_accum_reset(a_, stream), "pt_accum_reset"); }
 
   // the mean so far, in render()'s layout (host memory: from the exported sums, divided here with the same correctly rounded IEEE
   // division as the device's resolve — the host build has no fast-math, no contraction)
   void resolve(frame_buffer& frame_buf) const {
-    if (samples() <= 0) throw pt_error(PT_ERR_INVALID_ARG, "accumulator::resolve: no samples rendered yet");
+    if (!adaptive_ && samples() <= 0) throw pt_error(PT_ERR_INVALID_ARG, "accumulator::resolve: no samples rendered yet");
     const std::vector<uint8_t> st = state();
     const std::size_t floats = (std::size_t)pt_framebuffer_floats(&p_);
+    std::vector<int32_t> n;
+    if (adaptive_) { // (refused before the first window, as pt_accum_resolve: no pixel has a sample yet)
+      n = counts();
+      if (std::all_of(n.begin(), n.end(), [](int32_t v) { return v == 0; }))
+        throw pt_error(PT_ERR_INVALID_ARG, "accumulator::resolve: no samples rendered yet");
+    }
     frame_buf.resize(floats / 3);
     static_assert(sizeof(color) == 12);
     float* out = reinterpret_cast<float*>(frame_buf.data());
     std::memcpy(out, st.data() + PT_ACCUM_HEADER_BYTES, floats * sizeof(float));
-    const float n = (float)samples();
-    for (std::size_t i = 0; i < floats; i++) out[i] = out[i] / n;
+    if (adaptive_) { // each pixel by its own count (0 where it has none)
+      for (std::size_t i = 0; i < floats; i++) out[i] = n[i / 3] > 0 ? out[i] / (float)n[i / 3] : 0.0f;
+      return;
+    }
+    const float done = (float)samples();
+    for (std::size_t i = 0; i < floats; i++) out[i] = out[i] / done;
   }
 
   // checkpoint (pt_accum_export's format) / restore into this accumulator (same frame parameters; the camera comes with the state)
+  // (adaptive: pt_adaptive_export's format; restore() also takes a plain accumulator's state and continues it adaptively)
   std::vector<uint8_t> state() const {
+    if (adaptive_) {
+      std::vector<uint8_t> st((std::size_t)pt_adaptive_state_bytes(&p_));
+      check(pt_adaptive_export(a_, st.data(), (int64_t)st.size(), nullptr), "pt_adaptive_export");
+      return st;
+    }
     std::vector<uint8_t> st((std::size_t)pt_accum_state_bytes(&p_));
     check(pt_accum_export(a_, st.data(), (int64_t)st.size(), nullptr), "pt_accum_export");
     return st;
   }
   void restore(const std::vector<uint8_t>& st) {
-    check(pt_accum_import(a_, st.data(), (int64_t)st.size(), nullptr), "pt_accum_import");
-    if (samples() > 0) std::memcpy(&cam_, st.data() + PT_ACCUM_HEADER_BYTES - sizeof(PtCamera), sizeof(PtCamera));
+    if (adaptive_) check(pt_adaptive_import(a_, st.data(), (int64_t)st.size(), nullptr), "pt_adaptive_import");
+    else check(pt_accum_import(a_, st.data(), (int64_t)st.size(), nullptr), "pt_accum_import");
+    int32_t bound = 0;
+    std::memcpy(&bound, st.data() + 36, sizeof bound); // the header's "camera bound" word
+    if (bound) std::memcpy(&cam_, st.data() + PT_ACCUM_HEADER_BYTES - sizeof(PtCamera), sizeof(PtCamera));
   }
   void save(const std::string& path) const {
     const std::vector<uint8_t> st = state();
@@ -410,12 +462,15 @@ class accumulator {
     if (!f || std::fwrite(st.data(), 1, st.size(), f) != st.size()) { if (f) std::fclose(f); throw std::runtime_error("accumulator::save: cannot write " + path); }
     std::fclose(f);
   }
+  // (adaptive: a plain accumulator's checkpoint too, continued adaptively)
   void load(const std::string& path) {
-    std::vector<uint8_t> st((std::size_t)pt_accum_state_bytes(&p_));
+    const std::size_t plain = (std::size_t)pt_accum_state_bytes(&p_), full = adaptive_ ? (std::size_t)pt_adaptive_state_bytes(&p_) : plain;
+    std::vector<uint8_t> st(full + 1);
     std::FILE* f = std::fopen(path.c_str(), "rb");
-    const bool ok = f && std::fread(st.data(), 1, st.size(), f) == st.size() && std::fgetc(f) == EOF;
+    const std::size_t got = f ? std::fread(st.data(), 1, st.size(), f) : 0;
     if (f) std::fclose(f);
-    if (!ok) throw std::runtime_error("accumulator::load: " + path + " is not a state of this accumulator's size");
+    if (got != full && got != plain) throw std::runtime_error("accumulator::load: " + path + " is not a state of this accumulator's size");
+    st.resize(got);
     restore(st);
   }
   PtAccum* handle() const { return a_; }
@@ -424,6 +479,7 @@ class accumulator {
   PtCamera cam_;
   PtRenderParams p_;
   PtAccum* a_ = nullptr;
+  bool adaptive_ = false;
 };
 
 } // namespace pt

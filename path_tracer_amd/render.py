@@ -212,7 +212,9 @@ class Accumulator:
     """
 
     def __init__(self, width: int, height: int, scene, cam: camera, depth: int = 50, *, flags: int = 0, shard_index: int = 0,
-                 shard_count: int = 1):
+                 shard_count: int = 1, adaptive: bool = False):
+        """adaptive: per-pixel sample counts (pt_adaptive_create) — add() takes a mask, and counts() / error() / select() drive it;
+        each pixel resolves to the bits render() gives at its own count."""
         import torch
 
         if not torch.cuda.is_available():
@@ -220,28 +222,73 @@ class Accumulator:
         self.lib = abi.load_library()
         if not abi.has_accumulator(self.lib):
             raise ImportError(f"{abi.library_path()} predates progressive rendering (no pt_accum_* entry points)")
+        if adaptive and not abi.has_adaptive(self.lib):
+            raise ImportError(f"{abi.library_path()} predates adaptive sampling (no pt_adaptive_* entry points)")
         self.width, self.height, self.depth, self.flags = int(width), int(height), int(depth), int(flags)
         self.shard_index, self.shard_count = int(shard_index), int(shard_count)
+        self.adaptive = bool(adaptive)
         self.cam = cam
         self.handle = C.c_void_p()
         self._ds = _as_device_scene(scene, cache_key=("cuda", torch.cuda.current_device(), torch.cuda.current_stream().cuda_stream))
         self._p = _params(width, height, 1, depth, shard_index, shard_count, flags)
-        abi.check(self.lib.pt_accum_create(self._ds.handle, C.byref(self._p), C.byref(self.handle)), "pt_accum_create")
+        create = self.lib.pt_adaptive_create if self.adaptive else self.lib.pt_accum_create
+        abi.check(create(self._ds.handle, C.byref(self._p), C.byref(self.handle)), "pt_adaptive_create" if self.adaptive else "pt_accum_create")
 
     @property
     def samples(self) -> int:
-        """Samples of every pixel rendered so far."""
+        """Samples of every pixel rendered so far (adaptive: the samples of the windows rendered without a mask)."""
         return int(self.lib.pt_accum_samples(self.handle))
 
-    def add(self, samples: int) -> "Accumulator":
-        """Render the next `samples` samples of every pixel (asynchronous on torch's current stream)."""
+    def add(self, samples: int, mask=None) -> "Accumulator":
+        """Render the next `samples` samples of every pixel (asynchronous on torch's current stream) — on an adaptive accumulator, of
+        every pixel whose `mask` element is nonzero (a CUDA uint8 / bool tensor shaped like one channel of resolve(); a mask
+        synchronises the stream once)."""
         import torch
 
-        abi.check(self.lib.pt_render_accumulate(self.handle, C.byref(self.cam.c), int(samples), _stream_ptr(torch)), "pt_render_accumulate")
+        if mask is None:
+            abi.check(self.lib.pt_render_accumulate(self.handle, C.byref(self.cam.c), int(samples), _stream_ptr(torch)), "pt_render_accumulate")
+            return self
+        mask = self._pixel_array(mask, (torch.uint8, torch.bool), "mask")
+        abi.check(self.lib.pt_adaptive_window(self.handle, C.byref(self.cam.c), int(samples), C.c_void_p(mask.data_ptr()), _stream_ptr(torch)),
+                  "pt_adaptive_window")
         return self
 
     def _shape(self, n: int):
         return (self.height, self.width, 3) if self.shard_count == 1 else (n // (abi.PT_TILE_PIXELS * 3), abi.PT_TILE_PIXELS, 3)
+
+    def _pixel_shape(self):
+        return self._shape(self.lib.pt_framebuffer_floats(C.byref(self._p)))[:2]
+
+    def _pixel_array(self, t, dtypes, what):
+        if tuple(t.shape) != self._pixel_shape() or t.dtype not in dtypes or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous CUDA tensor of {self._pixel_shape()} ({', '.join(map(str, dtypes))})")
+        return t
+
+    def counts(self):
+        """Each pixel's sample count (adaptive): int32, shaped like one channel of resolve()."""
+        import torch
+
+        out = torch.empty(self._pixel_shape(), dtype=torch.int32, device="cuda")
+        abi.check(self.lib.pt_adaptive_counts(self.handle, C.c_void_p(out.data_ptr()), _stream_ptr(torch)), "pt_adaptive_counts")
+        return out
+
+    def error(self):
+        """Each pixel's two-half-buffer error estimate (adaptive; include/pt_render.h): float32, shaped like counts()."""
+        import torch
+
+        out = torch.empty(self._pixel_shape(), dtype=torch.float32, device="cuda")
+        abi.check(self.lib.pt_adaptive_error(self.handle, C.c_void_p(out.data_ptr()), _stream_ptr(torch)), "pt_adaptive_error")
+        return out
+
+    def select(self, threshold: float, min_spp: int, max_spp: int, dilate: bool = True):
+        """(mask, n_active): the pixels the next window should render (pt_adaptive_select; synchronises the stream)."""
+        import torch
+
+        mask = torch.empty(self._pixel_shape(), dtype=torch.uint8, device="cuda")
+        n = C.c_int64()
+        abi.check(self.lib.pt_adaptive_select(self.handle, float(threshold), int(min_spp), int(max_spp), abi.PT_ADAPTIVE_DILATE if dilate else 0,
+                                              C.c_void_p(mask.data_ptr()), C.byref(n), _stream_ptr(torch)), "pt_adaptive_select")
+        return mask, int(n.value)
 
     def resolve(self, out=None):
         """The mean of the samples so far, as render() returns it ([H][W][3], or this shard's tiles [tiles][64][3])."""
@@ -270,43 +317,55 @@ class Accumulator:
         abi.check(self.lib.pt_accum_reset(self.handle, _stream_ptr(torch)), "pt_accum_reset")
 
     def state(self) -> np.ndarray:
-        """The exported state (pt_accum_export: header, sums, generator states) as bytes in a uint8 array."""
+        """The exported state (pt_accum_export: header, sums, generator states; adaptive: pt_adaptive_export's format 2, which adds
+        H and the counts n and a) as bytes in a uint8 array."""
         import torch
 
+        if self.adaptive:
+            buf = np.empty(self.lib.pt_adaptive_state_bytes(C.byref(self._p)), dtype=np.uint8)
+            abi.check(self.lib.pt_adaptive_export(self.handle, buf.ctypes.data_as(C.c_void_p), buf.size, _stream_ptr(torch)), "pt_adaptive_export")
+            return buf
         buf = np.empty(self.lib.pt_accum_state_bytes(C.byref(self._p)), dtype=np.uint8)
         abi.check(self.lib.pt_accum_export(self.handle, buf.ctypes.data_as(C.c_void_p), buf.size, _stream_ptr(torch)), "pt_accum_export")
         return buf
 
     def save(self, path) -> None:
-        """Checkpoint to a raw file (the pt_accum_export format, include/pt_render.h)."""
+        """Checkpoint to a raw file (the pt_accum_export / pt_adaptive_export format, include/pt_render.h)."""
         with open(path, "wb") as f:
             f.write(self.state().tobytes())
 
     @classmethod
-    def load(cls, path, scene, cam: "camera | None" = None) -> "Accumulator":
+    def load(cls, path, scene, cam: "camera | None" = None, adaptive: bool = False) -> "Accumulator":
         """A new accumulator over `scene` (the same tables as the saved one's) resumed from a checkpoint; the frame parameters and
-        the camera come from the file (`cam` is needed only for a state saved at 0 samples)."""
+        the camera come from the file (`cam` is needed only for a state saved at 0 samples).  A format-2 state makes an adaptive
+        accumulator; `adaptive=True` also continues a plain (format-1) state adaptively."""
         buf = np.fromfile(path, dtype=np.uint8)
         if buf.size < abi.PT_ACCUM_HEADER_BYTES:
             raise ValueError(f"{path}: not an accumulator state")
-        magic, _fmt, w, h, depth, si, sc, flags, _done, bound = np.frombuffer(buf[:40].tobytes(), dtype="<u4").astype(np.int64)
-        if magic != abi.PT_ACCUM_MAGIC:
+        magic, fmt, w, h, depth, si, sc, flags, _done, bound = np.frombuffer(buf[:40].tobytes(), dtype="<u4").astype(np.int64)
+        if magic != abi.PT_ACCUM_MAGIC or fmt not in (abi.PT_ACCUM_FORMAT, abi.PT_ADAPTIVE_FORMAT):
             raise ValueError(f"{path}: not an accumulator state")
         if bound:
             cam = _BoundCamera(abi.PtCamera.from_buffer_copy(buf[64:abi.PT_ACCUM_HEADER_BYTES].tobytes()))
         elif cam is None:
             raise ValueError(f"{path}: the state has no samples (no bound camera): pass cam")
-        acc = cls(int(w), int(h), scene, cam, int(depth), flags=int(flags), shard_index=int(si), shard_count=int(sc))
+        acc = cls(int(w), int(h), scene, cam, int(depth), flags=int(flags), shard_index=int(si), shard_count=int(sc),
+                  adaptive=adaptive or fmt == abi.PT_ADAPTIVE_FORMAT)
         acc.restore(buf)
         return acc
 
     def restore(self, state: np.ndarray) -> None:
-        """pt_accum_import of an exported state (the header must match this accumulator's frame parameters)."""
+        """pt_accum_import of an exported state (the header must match this accumulator's frame parameters); adaptive:
+        pt_adaptive_import, which also takes a plain (format-1) state."""
         import torch
 
         state = np.ascontiguousarray(state, dtype=np.uint8)
-        abi.check(self.lib.pt_accum_import(self.handle, state.ctypes.data_as(C.c_void_p), state.size, _stream_ptr(torch)), "pt_accum_import")
-        if self.lib.pt_accum_samples(self.handle) > 0:
+        if self.adaptive:
+            abi.check(self.lib.pt_adaptive_import(self.handle, state.ctypes.data_as(C.c_void_p), state.size, _stream_ptr(torch)),
+                      "pt_adaptive_import")
+        else:
+            abi.check(self.lib.pt_accum_import(self.handle, state.ctypes.data_as(C.c_void_p), state.size, _stream_ptr(torch)), "pt_accum_import")
+        if int(np.frombuffer(state[36:40].tobytes(), dtype="<i4")[0]):  # the state's camera is bound: windows continue with it
             self.cam = _BoundCamera(abi.PtCamera.from_buffer_copy(state[64:abi.PT_ACCUM_HEADER_BYTES].tobytes()))
 
     def close(self) -> None:
@@ -342,5 +401,38 @@ def render_progressive(width: int, height: int, samples: int, scene, cam: camera
             acc.add(n)
             done += n
             yield done, acc.resolve()
+    finally:
+        acc.close()
+
+
+def render_adaptive(width: int, height: int, scene, cam: camera, depth: int = 50, *, threshold: float, min_spp: int = 16,
+                    max_spp: int = 1024, step: int = 16, dilate: bool = True, flags: int = 0):
+    """Adaptive sampling (include/pt_render.h: pt_adaptive_*): a window of min_spp samples of every pixel, then windows of `step`
+    samples of the pixels pt_adaptive_select keeps active (noise estimate above `threshold`, or below min_spp; with `dilate`, next to
+    such a pixel) until none is.  Returns (framebuffer, counts): each pixel holds the bits render() gives at its own count, which lies
+    in [min_spp, max_spp] and is min_spp + a multiple of `step`.  A window whose mask is every pixel runs unmasked (cost probe, tile
+    order).  A negative threshold renders every pixel to max_spp: render(..., samples=max_spp, ...).
+
+    Each select synchronises the stream (its count decides the next window).  With a negative threshold every pixel below max_spp is
+    noisy, so the selection follows from the counts alone: while every window has been unmasked, every pixel is active until the
+    counts reach max_spp, and the loop skips the select (and its synchronisation) — the same windows, asynchronous like
+    render_progressive."""
+    if min_spp <= 0 or step <= 0 or max_spp < min_spp or (max_spp - min_spp) % step != 0:
+        raise ValueError("need 0 < min_spp <= max_spp, step > 0 and (max_spp - min_spp) % step == 0")
+    acc = Accumulator(width, height, scene, cam, depth, flags=flags, adaptive=True)
+    try:
+        acc.add(min_spp)
+        pixels = width * height
+        uniform = True  # only unmasked windows so far: every pixel has acc.samples samples
+        while True:
+            if threshold < 0 and uniform:
+                n_active, mask = (pixels if acc.samples < max_spp else 0), None
+            else:
+                mask, n_active = acc.select(threshold, min_spp, max_spp, dilate)
+            if n_active == 0:
+                break
+            uniform = uniform and n_active == pixels
+            acc.add(step, None if n_active == pixels else mask)
+        return acc.resolve(), acc.counts()
     finally:
         acc.close()
