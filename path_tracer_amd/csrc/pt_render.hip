@@ -19,6 +19,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <type_traits>
 #include <string>
@@ -1009,17 +1010,34 @@ __global__ void unshard_kernel(const float* __restrict__ gathered, float* __rest
   fb[dst] = gathered[src]; fb[dst + 1] = gathered[src + 1]; fb[dst + 2] = gathered[src + 2];
 }
 
-// main.cpp:33-59 — sqrt gamma, clamp [0,0.999], *256, truncate, vertical flip.
-__global__ void tonemap_kernel(const float* __restrict__ fb, uint8_t* __restrict__ rgb8, int width, int height) {
+// main.cpp:33-59 for one channel — sqrt gamma, clamp [0,0.999], *256, truncate: THE output stage, every 8-bit image goes through it
+__device__ __forceinline__ uint8_t quantise(float radiance) {
+  float s = sqrt_rn(radiance);
+  float cl = (s < 0.0f) ? 0.0f : (0.999f < s) ? 0.999f : s; // std::clamp
+  float sc = 256.0f * cl;
+  int v = (sc == sc) ? (int)sc : 0; // int(NaN) is UB in the reference; defined as 0
+  return (uint8_t)v;
+}
+
+// THE mean of n samples: lane_store's correctly rounded IEEE division (render.hpp:102; -fhip-fp32-correctly-rounded-divide-sqrt, no
+// reciprocal), 0 where nothing was sampled
+__device__ __forceinline__ float mean_of(float sum, int n) { return n > 0 ? sum / (float)n : 0.0f; }
+
+// the sample count of pixel `pix` of an accumulator: its own (adaptive: cnt) or the one every pixel has (plain: cnt NULL, `done` > 0)
+__device__ __forceinline__ int count_of(const int* __restrict__ cnt, int done, long long pix) { return cnt ? cnt[pix] : done; }
+
+// The output stage with the vertical flip (row 0 = top).  MEAN = false: `src` is a finished frame buffer (pt_tonemap_rgb8: nothing is
+// divided); MEAN = true: resolve + output stage in one pass over an accumulator's sums (whole frames), the same mean as accum_resolve_kernel
+template <bool MEAN>
+__global__ void tonemap_kernel(const float* __restrict__ src, const int* __restrict__ cnt, int done, uint8_t* __restrict__ rgb8, int width, int height) {
   int x = blockIdx.x * blockDim.x + threadIdx.x, row = blockIdx.y; // row 0 = top
   if (x >= width) return;
   int j = height - 1 - row;
+  const long long pix = (long long)j * width + x;
+  const int n = MEAN ? count_of(cnt, done, pix) : 0;
   for (int ch = 0; ch < 3; ch++) {
-    float s = sqrt_rn(fb[((long long)j * width + x) * 3 + ch]);
-    float cl = (s < 0.0f) ? 0.0f : (0.999f < s) ? 0.999f : s; // std::clamp
-    float sc = 256.0f * cl;
-    int v = (sc == sc) ? (int)sc : 0; // int(NaN) is UB in the reference; defined as 0
-    rgb8[((long long)row * width + x) * 3 + ch] = (uint8_t)v;
+    const float v = src[pix * 3 + ch];
+    rgb8[((long long)row * width + x) * 3 + ch] = quantise(MEAN ? mean_of(v, n) : v);
   }
 }
 
@@ -1034,25 +1052,11 @@ __global__ void fast_accum_kernel(const float* __restrict__ partial, float* __re
   sum[i] = s;
 }
 
-// fb = sum / done: lane_store's correctly rounded IEEE division (render.hpp:102; -fhip-fp32-correctly-rounded-divide-sqrt, no reciprocal)
-__global__ void accum_resolve_kernel(const float* __restrict__ sum, float* __restrict__ fb, long long n, float samples) {
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  fb[i] = sum[i] / samples;
-}
-
-// resolve + tonemap_kernel in one pass (whole frames): the same mean, then main.cpp:33-59 exactly as tonemap_kernel does it
-__global__ void accum_tonemap_kernel(const float* __restrict__ sum, uint8_t* __restrict__ rgb8, int width, int height, float samples) {
-  int x = blockIdx.x * blockDim.x + threadIdx.x, row = blockIdx.y; // row 0 = top
-  if (x >= width) return;
-  int j = height - 1 - row;
-  for (int ch = 0; ch < 3; ch++) {
-    float s = sqrt_rn(sum[((long long)j * width + x) * 3 + ch] / samples);
-    float cl = (s < 0.0f) ? 0.0f : (0.999f < s) ? 0.999f : s;
-    float sc = 256.0f * cl;
-    int v = (sc == sc) ? (int)sc : 0;
-    rgb8[((long long)row * width + x) * 3 + ch] = (uint8_t)v;
-  }
+// fb = sum / n, per pixel for an adaptive accumulator (cnt) and by `done` for a plain one (cnt NULL)
+__global__ void accum_resolve_kernel(const float* __restrict__ sum, const int* __restrict__ cnt, int done, float* __restrict__ fb, long long floats) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= floats) return;
+  fb[i] = mean_of(sum[i], count_of(cnt, done, i / 3));
 }
 
 // ---- adaptive sampling (pt_adaptive_*): per-pixel counts, the two-half-buffer error estimate and masked windows ---------------------
@@ -1064,22 +1068,25 @@ struct AFrame {
   long long pixels; // P = pt_framebuffer_floats / 3
 };
 
-__host__ __device__ __forceinline__ bool aframe_xy(const AFrame& f, long long i, int& x, int& y) {
-  if (f.shard_count == 1) { x = (int)(i % f.width); y = (int)(i / f.width); return true; }
-  const long long g = (i >> 6) * f.shard_count + f.shard_index;
-  const int in = (int)(i & 63);
+// pixel `in` (ly * 8 + lx) of local tile l: its place in the frame; false for padding (edge tiles, the padded last tile)
+__host__ __device__ __forceinline__ bool atile_xy(const AFrame& f, long long l, int in, int& x, int& y) {
+  const long long g = l * f.shard_count + f.shard_index;
   x = (int)(g % f.tiles_x) * PT_TILE + (in & 7); y = (int)(g / f.tiles_x) * PT_TILE + (in >> 3);
   return g < f.n_tiles && x < f.width && y < f.height;
 }
+// pixel i of a per-pixel array: row-major for whole frames, (local tile, index in tile) for shards
+__host__ __device__ __forceinline__ bool aframe_xy(const AFrame& f, long long i, int& x, int& y) {
+  if (f.shard_count == 1) { x = (int)(i % f.width); y = (int)(i / f.width); return true; }
+  return atile_xy(f, i >> 6, (int)(i & 63), x, y);
+}
 
-// every pixel's generator state at 0 samples: its linear id in the whole frame (render.hpp:130-132), indexed like KArgs.resume_rng
+// every pixel's generator state at 0 samples: its linear id in the whole frame (render.hpp:130-132), indexed like KArgs.resume_rng —
+// by padded tile for whole frames too (atile_xy), NOT by the row-major pixel of the per-pixel arrays (aframe_xy)
 __global__ void adaptive_seed_kernel(AFrame f, unsigned int* __restrict__ rng, long long words) {
   const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= words) return;
-  const long long g = (j >> 6) * f.shard_count + f.shard_index;
-  const int in = (int)(j & 63);
-  const int x = (int)(g % f.tiles_x) * PT_TILE + (in & 7), y = (int)(g / f.tiles_x) * PT_TILE + (in >> 3);
-  rng[j] = (g < f.n_tiles && x < f.width && y < f.height) ? (uint32_t)((unsigned long long)y * (unsigned long long)f.width + (unsigned long long)x) : 0u;
+  int x, y;
+  rng[j] = atile_xy(f, j >> 6, (int)(j & 63), x, y) ? (uint32_t)((unsigned long long)y * (unsigned long long)f.width + (unsigned long long)x) : 0u;
 }
 
 // masked window, step 1: which local tiles hold at least one pixel of the mask
@@ -1090,9 +1097,7 @@ __global__ void adaptive_tiles_kernel(AFrame f, const uint8_t* __restrict__ mask
   for (int in = 0; in < PT_TILE_PIXELS && !any; in++) {
     const long long pix = (long long)l * PT_TILE_PIXELS + in;
     int x, y;
-    const long long g = (long long)l * f.shard_count + f.shard_index;
-    x = (int)(g % f.tiles_x) * PT_TILE + (in & 7); y = (int)(g / f.tiles_x) * PT_TILE + (in >> 3);
-    if (g >= f.n_tiles || x >= f.width || y >= f.height) continue;
+    if (!atile_xy(f, l, in, x, y)) continue;
     any = mask[f.shard_count == 1 ? (long long)y * f.width + x : pix];
   }
   active[l] = any ? 1 : 0;
@@ -1147,9 +1152,8 @@ __global__ void adaptive_book_kernel(AFrame f, const uint8_t* __restrict__ mask,
 // the two-half-buffer error (include/pt_render.h): correctly rounded binary32 throughout, no contraction (-ffp-contract=off)
 __device__ __forceinline__ float adaptive_err(const float* __restrict__ sum, const float* __restrict__ half, int n, int a, long long i) {
   if (a == 0 || a == n) return __builtin_inff();
-  const float fn = (float)n, fa = (float)a;
-  const float ix = sum[3 * i] / fn, iy = sum[3 * i + 1] / fn, iz = sum[3 * i + 2] / fn;
-  const float ax = half[3 * i] / fa, ay = half[3 * i + 1] / fa, az = half[3 * i + 2] / fa;
+  const float ix = mean_of(sum[3 * i], n), iy = mean_of(sum[3 * i + 1], n), iz = mean_of(sum[3 * i + 2], n); // (0 < a < n here)
+  const float ax = mean_of(half[3 * i], a), ay = mean_of(half[3 * i + 1], a), az = mean_of(half[3 * i + 2], a);
   const float num = (fabsf(ix - ax) + fabsf(iy - ay)) + fabsf(iz - az);
   return num / (1e-4f + sqrt_rn((ix + iy) + iz));
 }
@@ -1187,29 +1191,6 @@ __global__ void adaptive_select_kernel(AFrame f, const float* __restrict__ sum, 
   }
   const unsigned long long b = __builtin_amdgcn_ballot_w64(on);
   if ((threadIdx.x & 63) == 0 && b) atomicAdd(n_active, (unsigned long long)__builtin_popcountll(b));
-}
-
-// fb = sum / n per pixel (accum_resolve_kernel's correctly rounded division), 0 where n = 0
-__global__ void adaptive_resolve_kernel(const float* __restrict__ sum, const int* __restrict__ cnt, float* __restrict__ fb, long long floats) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= floats) return;
-  const int n = cnt[i / 3];
-  fb[i] = n > 0 ? sum[i] / (float)n : 0.0f;
-}
-
-// adaptive_resolve_kernel + tonemap_kernel in one pass (whole frames), as accum_tonemap_kernel
-__global__ void adaptive_tonemap_kernel(const float* __restrict__ sum, const int* __restrict__ cnt, uint8_t* __restrict__ rgb8, int width, int height) {
-  int x = blockIdx.x * blockDim.x + threadIdx.x, row = blockIdx.y; // row 0 = top
-  if (x >= width) return;
-  int j = height - 1 - row;
-  const int n = cnt[(long long)j * width + x];
-  for (int ch = 0; ch < 3; ch++) {
-    float s = sqrt_rn(n > 0 ? sum[((long long)j * width + x) * 3 + ch] / (float)n : 0.0f);
-    float cl = (s < 0.0f) ? 0.0f : (0.999f < s) ? 0.999f : s;
-    float sc = 256.0f * cl;
-    int v = (sc == sc) ? (int)sc : 0;
-    rgb8[((long long)row * width + x) * 3 + ch] = (uint8_t)v;
-  }
 }
 
 thread_local std::string g_last_error;
@@ -1364,20 +1345,33 @@ struct EventPair { // RAII: no leak on an early return
 };
 
 template <typename T>
-struct DevBuf {
+struct DevBuf { // owned device memory (move-only): freed with the local, the PtScene or the PtAccum that holds it
   T* p = nullptr;
+  size_t cap = 0; // elements asked for
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
   ~DevBuf() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t n) { return hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T)); }
+  // n elements (at least one is allocated), in place of what it held
+  hipError_t alloc(size_t n) {
+    if (p) (void)hipFree(p);
+    p = nullptr; cap = 0;
+    const hipError_t e = hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T));
+    if (e == hipSuccess) cap = n; else p = nullptr;
+    return e;
+  }
+  // grow-only workspaces: nothing happens while n elements fit (hipMalloc / hipFree synchronise the device)
+  hipError_t grow(size_t n) { return p && cap >= n ? hipSuccess : alloc(n); }
 };
 
 } // namespace
 
 struct PtScene {
-  f4* blob = nullptr;
-  f4* mats = nullptr;
-  f4* pool = nullptr;   // tables of the triangle pools (a buffer of their own: up to gigabytes)
+  DevBuf<f4> blob;      // [blob records][material table]
+  f4* mats = nullptr;   // ... the material table in it (not owned)
+  DevBuf<f4> pool;      // tables of the triangle pools (a buffer of their own: up to gigabytes)
   size_t pool_bytes = 0;
-  uint8_t* atlas = nullptr;
+  DevBuf<uint8_t> atlas;
   int n_runs = 0, blob_f4 = 0, mats_f4 = 0;
   bool has_image = false;
   bool track_uv = false; // an image texture sits on a triangle or a medium: the stale u,v such hits inherit must be tracked
@@ -1397,23 +1391,19 @@ struct PtScene {
   size_t blob_bytes = 0, atlas_bytes = 0;
   int num_cus = 256;
   size_t lds_per_block = 64 * 1024; // hipDeviceProp_t::sharedMemPerBlock (gfx950: 160 KB; the Makefile's ARCH=gfx942: 64 KB)
-  mutable unsigned int* ws_cost = nullptr; // LPT workspace: per-tile ray counts of the probe pass
-  mutable unsigned int* ws_rank = nullptr; // per local tile: the cost a tile is ranked by (tile_dilate_kernel)
-  mutable unsigned int* ws_rng = nullptr;  // per local pixel: the generator's state after the probe's samples (KArgs.resume_rng)
-  mutable int* ws_order = nullptr;         //                cost-sorted tile order
-  mutable int ws_tiles = 0;
-  int* ws_nsplit = nullptr;                //                number of leading tiles to split (device scalar)
-  mutable float* ws_partial = nullptr;     // PT_FLAG_FAST_RNG: per-chunk partial sums (grow-only)
-  mutable size_t ws_partial_floats = 0;
+  mutable DevBuf<unsigned int> ws_cost; // LPT workspace: per-tile ray counts of the probe pass
+  mutable DevBuf<unsigned int> ws_rank; // per local tile: the cost a tile is ranked by (tile_dilate_kernel)
+  mutable DevBuf<unsigned int> ws_rng;  // per local pixel: the generator's state after the probe's samples (KArgs.resume_rng)
+  mutable DevBuf<int> ws_order;         //                cost-sorted tile order
+  DevBuf<int> ws_nsplit;                //                number of leading tiles to split (device scalar)
+  mutable DevBuf<float> ws_partial;     // PT_FLAG_FAST_RNG: per-chunk partial sums (grow-only)
   // the binned triangle-pool renderer (pt_binned.hpp): the pooled run, the key space of its direction maps, and a grow-only workspace
   int bin_run = -1, bin_hdr = 0, bin_goff = 0, bin_keys = 0, bin_full_slices = 1, bin_base1 = 0;
   bool binned = false;          // this scene's parity-mode renders go through it
-  mutable unsigned int* ws_tricache = nullptr; // the camera rays' candidate cache: one line per resident lane of the triangle-pool kernels
-  mutable size_t ws_tricache_lanes = 0;
-  mutable void* ws_bin = nullptr; // per-pixel state, requests and slots for ws_bin_pixels local pixels; the sort's tables
-  mutable size_t ws_bin_pixels = 0;
+  mutable DevBuf<unsigned int> ws_tricache; // the camera rays' candidate cache: one line per resident lane of the triangle-pool kernels
+  mutable DevBuf<char> ws_bin; // per-pixel state, requests and slots for the local pixels of the largest binned render so far; the sort's tables
   mutable int last_generations = 0; // generations of the last binned render (pt_debug_last_launch)
-  unsigned int* queues = nullptr; // ring of per-launch pixel-queue counters
+  DevBuf<unsigned int> queues; // ring of per-launch pixel-queue counters
   mutable unsigned int next_queue = 0;
   mutable hipEvent_t ring_done[kQueueRing] = {}; // recorded behind the launch that uses a slot: a wrapped ring waits for it
   int device = 0;
@@ -1563,15 +1553,13 @@ int pt_scene_create_tuned(const PtSceneDesc* desc, const PtTuning* tuning, PtSce
   lap("flatten (+ culling tables)");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(PT_ERR_NO_DEVICE, "no HIP device visible");
-  PtScene* s = new PtScene();
+  std::unique_ptr<PtScene> owner(new PtScene()); // (an early return frees what was allocated so far: every buffer is a DevBuf)
+  PtScene* const s = owner.get();
   s->knobs = Knobs(tun);
-  auto cleanup = [&]() { pt_scene_destroy(s); };
-  hipError_t e;
-#define PT_TRY(expr) if ((e = (expr)) != hipSuccess) { cleanup(); return fail(PT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e)); }
-  PT_TRY(hipGetDevice(&s->device));
+  PT_HIP(hipGetDevice(&s->device));
   {
     hipDeviceProp_t prop;
-    PT_TRY(hipGetDeviceProperties(&prop, s->device));
+    PT_HIP(hipGetDeviceProperties(&prop, s->device));
     s->num_cus = prop.multiProcessorCount;
     s->lds_per_block = prop.sharedMemPerBlock;
   }
@@ -1622,14 +1610,14 @@ int pt_scene_create_tuned(const PtSceneDesc* desc, const PtTuning* tuning, PtSce
   s->mats_f4 = (int)flat.mats.size();
   // one buffer: [blob records][material table] so a kernel can stage both with one contiguous copy
   const size_t blob_bytes = flat.blob.size() * 16, mats_bytes = flat.mats.size() * 16;
-  PT_TRY(hipMalloc((void**)&s->blob, std::max<size_t>(blob_bytes + mats_bytes, 16)));
-  s->mats = s->blob + flat.blob.size();
-  if (blob_bytes) PT_TRY(hipMemcpy(s->blob, flat.blob.data(), blob_bytes, hipMemcpyHostToDevice));
-  if (mats_bytes) PT_TRY(hipMemcpy(s->mats, flat.mats.data(), mats_bytes, hipMemcpyHostToDevice));
+  PT_HIP(s->blob.alloc(flat.blob.size() + flat.mats.size()));
+  s->mats = s->blob.p + flat.blob.size();
+  if (blob_bytes) PT_HIP(hipMemcpy(s->blob.p, flat.blob.data(), blob_bytes, hipMemcpyHostToDevice));
+  if (mats_bytes) PT_HIP(hipMemcpy(s->mats, flat.mats.data(), mats_bytes, hipMemcpyHostToDevice));
   if (flat.pool.size_f4) { // the triangle pools' tables: zeroed (spare records between the tables), then table by table from where the builder left them
     s->pool_bytes = (size_t)flat.pool.size_f4 * 16;
-    PT_TRY(hipMalloc((void**)&s->pool, s->pool_bytes));
-    PT_TRY(hipMemset(s->pool, 0, s->pool_bytes));
+    PT_HIP(s->pool.alloc((size_t)flat.pool.size_f4));
+    PT_HIP(hipMemset(s->pool.p, 0, s->pool_bytes));
     if (timing) { (void)hipDeviceSynchronize(); lap("blob upload, pool malloc + memset"); }
     // (the big tables — hundreds of megabytes of direction-map lists — are pinned in place for their copy: a pageable hipMemcpy
     // staged them at ~3 GB/s, a third of the scene's build time in round 6)
@@ -1637,20 +1625,19 @@ int pt_scene_create_tuned(const PtSceneDesc* desc, const PtTuning* tuning, PtSce
       if (sg.dwords.empty()) continue;
       const size_t bytes = sg.dwords.size() * 4;
       const bool pin = bytes >= (8u << 20) && hipHostRegister((void*)sg.dwords.data(), bytes, hipHostRegisterDefault) == hipSuccess;
-      e = hipMemcpy(s->pool + sg.at_f4, sg.dwords.data(), bytes, hipMemcpyHostToDevice);
+      const hipError_t e = hipMemcpy(s->pool.p + sg.at_f4, sg.dwords.data(), bytes, hipMemcpyHostToDevice);
       if (pin) (void)hipHostUnregister((void*)sg.dwords.data());
-      if (e != hipSuccess) { cleanup(); return fail(PT_ERR_HIP, std::string("hipMemcpy of a pool table: ") + hipGetErrorString(e)); }
+      if (e != hipSuccess) return fail(PT_ERR_HIP, std::string("hipMemcpy of a pool table: ") + hipGetErrorString(e));
     }
   }
   lap("upload blob + pool");
   size_t atlas_bytes = flat.has_image ? (size_t)desc->atlas_bytes : 0;
   s->atlas_bytes = atlas_bytes;
-  PT_TRY(hipMalloc((void**)&s->atlas, std::max<size_t>(atlas_bytes, 16)));
-  if (atlas_bytes) PT_TRY(hipMemcpy(s->atlas, desc->atlas, atlas_bytes, hipMemcpyHostToDevice));
-  PT_TRY(hipMalloc((void**)&s->queues, 2 * kQueueRing * sizeof(unsigned int)));
-  PT_TRY(hipMalloc((void**)&s->ws_nsplit, 2 * sizeof(int))); // [0] tiles through the wide phase, [1] log2 of its group size
-#undef PT_TRY
-  *out_scene = s;
+  PT_HIP(s->atlas.alloc(std::max<size_t>(atlas_bytes, 16)));
+  if (atlas_bytes) PT_HIP(hipMemcpy(s->atlas.p, desc->atlas, atlas_bytes, hipMemcpyHostToDevice));
+  PT_HIP(s->queues.alloc(2 * kQueueRing));
+  PT_HIP(s->ws_nsplit.alloc(2)); // [0] tiles through the wide phase, [1] log2 of its group size
+  *out_scene = owner.release();
   return PT_OK;
 }
 
@@ -1666,20 +1653,8 @@ const char* pt_build_id(void) { return PT_BUILD_ID; }
 
 void pt_scene_destroy(PtScene* s) {
   if (!s) return;
-  if (s->blob) (void)hipFree(s->blob);
-  if (s->pool) (void)hipFree(s->pool);
-  if (s->atlas) (void)hipFree(s->atlas);
-  if (s->queues) (void)hipFree(s->queues);
   for (hipEvent_t e : s->ring_done) if (e) (void)hipEventDestroy(e);
-  if (s->ws_cost) (void)hipFree(s->ws_cost);
-  if (s->ws_order) (void)hipFree(s->ws_order);
-  if (s->ws_rng) (void)hipFree(s->ws_rng);
-  if (s->ws_rank) (void)hipFree(s->ws_rank);
-  if (s->ws_nsplit) (void)hipFree(s->ws_nsplit);
-  if (s->ws_partial) (void)hipFree(s->ws_partial);
-  if (s->ws_bin) (void)hipFree(s->ws_bin);
-  if (s->ws_tricache) (void)hipFree(s->ws_tricache);
-  delete s;
+  delete s; // (its buffers: DevBuf members)
 }
 
 static int check_params(const PtRenderParams* p) {
@@ -1714,35 +1689,41 @@ int64_t pt_framebuffer_floats(const PtRenderParams* p) {
 // grow-only per-scene workspaces (LPT cost / order arrays; fast mode's partial sums).  pt_scene_reserve() sizes them ahead of
 // time so that pt_render() neither allocates nor frees (hipMalloc / hipFree synchronise the device).
 static int reserve_tiles(const PtScene* s, int local_tiles) {
-  if (s->ws_tiles >= local_tiles) return PT_OK;
-  if (s->ws_cost) (void)hipFree(s->ws_cost);
-  if (s->ws_order) (void)hipFree(s->ws_order);
-  if (s->ws_rng) (void)hipFree(s->ws_rng);
-  if (s->ws_rank) (void)hipFree(s->ws_rank);
-  s->ws_cost = nullptr; s->ws_order = nullptr; s->ws_rng = nullptr; s->ws_rank = nullptr; s->ws_tiles = 0;
-  PT_HIP(hipMalloc((void**)&s->ws_cost, (size_t)local_tiles * sizeof(unsigned int)));
-  PT_HIP(hipMalloc((void**)&s->ws_order, (size_t)local_tiles * sizeof(int)));
-  PT_HIP(hipMalloc((void**)&s->ws_rng, (size_t)local_tiles * PT_TILE_PIXELS * sizeof(unsigned int)));
-  PT_HIP(hipMalloc((void**)&s->ws_rank, (size_t)local_tiles * sizeof(unsigned int)));
-  s->ws_tiles = local_tiles;
+  const size_t t = (size_t)local_tiles;
+  PT_HIP(s->ws_cost.grow(t));
+  PT_HIP(s->ws_order.grow(t));
+  PT_HIP(s->ws_rng.grow(t * PT_TILE_PIXELS));
+  PT_HIP(s->ws_rank.grow(t));
   return PT_OK;
 }
 // the camera rays' candidate cache of the triangle-pool kernels: one PT_TRI_CACHE_WORDS line per lane of the launch (grow-only)
 static int grow_tricache(const PtScene* s, size_t lanes) {
-  if (s->ws_tricache_lanes >= lanes) return PT_OK;
-  if (s->ws_tricache) (void)hipFree(s->ws_tricache);
-  s->ws_tricache = nullptr; s->ws_tricache_lanes = 0;
-  PT_HIP(hipMalloc((void**)&s->ws_tricache, lanes * PT_TRI_CACHE_WORDS * 4));
-  s->ws_tricache_lanes = lanes;
+  PT_HIP(s->ws_tricache.grow(lanes * PT_TRI_CACHE_WORDS));
   return PT_OK;
 }
 static int reserve_partial(const PtScene* s, size_t floats) {
-  if (s->ws_partial_floats >= floats) return PT_OK;
-  if (s->ws_partial) (void)hipFree(s->ws_partial);
-  s->ws_partial = nullptr; s->ws_partial_floats = 0;
-  PT_HIP(hipMalloc((void**)&s->ws_partial, floats * sizeof(float)));
-  s->ws_partial_floats = floats;
+  PT_HIP(s->ws_partial.grow(floats));
   return PT_OK;
+}
+
+// Resident workgroups per CU of a kernel variant: queried once per scene, then from PtScene.occupancy.  < 0: the query failed (pt_last_error).
+static int occupancy_of(const PtScene* s, const void* kernel, int block_threads, size_t shmem) {
+  auto cached = s->occupancy.find(kernel);
+  if (cached != s->occupancy.end()) return cached->second;
+  int per_cu = 0;
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block_threads, shmem);
+  if (e != hipSuccess) { fail(PT_ERR_HIP, std::string("occupancy query of a kernel variant: ") + hipGetErrorString(e)); return -1; }
+  s->occupancy[kernel] = per_cu;
+  return per_cu;
+}
+
+// The triangle-pool kernel of a scene's UV mode: what launch_uv launches for such a scene, and what reserve_tricache sizes the cache for.
+static auto tripool_kernel(int uv, bool fast) -> void (*)(KArgs) {
+  switch (uv) {
+    case UV_TRACKED: return fast ? render_kernel<UV_TRACKED, false, false, false, false, true, false, true, true> : render_kernel<UV_TRACKED, false, false, false, false, false, false, true, true>;
+    case UV_WINNER: return fast ? render_kernel<UV_WINNER, false, false, false, false, true, false, true, true> : render_kernel<UV_WINNER, false, false, false, false, false, false, true, true>;
+    default: return fast ? render_kernel<UV_NONE, false, false, false, false, true, false, true, true> : render_kernel<UV_NONE, false, false, false, false, false, false, true, true>;
+  }
 }
 
 // The binned triangle-pool renderer (pt_binned.hpp): generations of { step, sort the requests by direction bin, band stage }, until no pixel
@@ -1760,7 +1741,7 @@ static int launch_binned(const PtScene* s, KArgs a, const PtRenderParams* p, int
   size_t bytes = 0;
   if (int rc = reserve_binned(s, N, K, bytes)) return rc;
   // carve the workspace (every array 256-byte aligned)
-  char* base = (char*)s->ws_bin;
+  char* base = s->ws_bin.p;
   size_t at = 0;
   auto take = [&](size_t n) { char* q = base + at; at += (n + 255) & ~(size_t)255; return q; };
   const size_t n_blocks = (K + 1023) / 1024, max_packets = (N / 64 + 1) * (size_t)s->bin_full_slices + std::min(K, N) + 1;
@@ -1788,7 +1769,7 @@ static int launch_binned(const PtScene* s, KArgs a, const PtRenderParams* p, int
     ba.scatter_p = (int)P;
   }
   BandArgs bd;
-  bd.pool = s->pool; bd.blob = s->blob; bd.hdr = s->bin_hdr; bd.goff = s->bin_goff;
+  bd.pool = s->pool.p; bd.blob = s->blob.p; bd.hdr = s->bin_hdr; bd.goff = s->bin_goff;
   bd.A0 = ba.A0; bd.A1 = ba.A1; bd.A5 = ba.A5; bd.slot = ba.slot; bd.offs = sa.offs; bd.packets = sa.packets; bd.ctl = sa.ctl; bd.sorted = sorted;
   bd.dense_min = 16; bd.full_slices = s->bin_full_slices;
   if (const char* e = std::getenv("PT_BAND_DENSE_MIN")) bd.dense_min = std::max(1, std::atoi(e)); // (experiments only)
@@ -1832,12 +1813,10 @@ static int launch_binned(const PtScene* s, KArgs a, const PtRenderParams* p, int
   if (live != 0 && gen <= max_gen) { // the tail: persistent waves finish what is left (ctl[3] live pixels in the list the last step wrote)
     ba.gen = gen; ba.live_in = live_list[gen & 1]; ba.live_out = live_list[(gen + 1) & 1];
     PT_HIP(hipMemsetAsync(sa.ctl + 5, 0, 4, st));
-    int per_cu = 0;
     const void* fk = s->has_image ? (s->mats_simple ? (const void*)bin_finish_kernel<UV_WINNER, MATS_LAMB_LIGHT_SOLID> : (const void*)bin_finish_kernel<UV_WINNER, MATS_ALL>)
                                   : (s->mats_simple ? (const void*)bin_finish_kernel<UV_NONE, MATS_LAMB_LIGHT_SOLID> : (const void*)bin_finish_kernel<UV_NONE, MATS_ALL>);
-    auto cached = s->occupancy.find(fk);
-    if (cached != s->occupancy.end()) per_cu = cached->second;
-    else { PT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fk, kBlock, 0)); s->occupancy[fk] = per_cu; }
+    const int per_cu = occupancy_of(s, fk, kBlock, 0);
+    if (per_cu < 0) return PT_ERR_HIP;
     const unsigned int blocks = (unsigned int)std::min<long long>((long long)std::max(1, per_cu) * std::max(1, s->num_cus), ((long long)live + kBlock - 1) / kBlock * 64);
     const dim3 fgrid(std::max(1u, blocks)), fblock(kBlock);
     if (s->has_image) {
@@ -1860,11 +1839,7 @@ static int reserve_binned(const PtScene* s, size_t N, size_t K, size_t& bytes) {
   const size_t n_blocks = (K + 1023) / 1024, max_packets = (N / 64 + 1) * (size_t)s->bin_full_slices + std::min(K, N) + 1;
   auto r = [](size_t n) { return (n + 255) & ~(size_t)255; };
   bytes = 6 * r(N * 16) + r(N * 8) + r(K * 4) + r((K + 1) * 4) + r(n_blocks * 8) + r(max_packets * 8) + r(64) + 3 * r(N * 4);
-  if (s->ws_bin && s->ws_bin_pixels >= N) return PT_OK;
-  if (s->ws_bin) (void)hipFree(s->ws_bin);
-  s->ws_bin = nullptr; s->ws_bin_pixels = 0;
-  PT_HIP(hipMalloc(&s->ws_bin, bytes));
-  s->ws_bin_pixels = N;
+  PT_HIP(s->ws_bin.grow(bytes)); // (grow-only: the bytes grow with N, the rest is the scene's)
   return PT_OK;
 }
 
@@ -1891,7 +1866,7 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
   std::lock_guard<std::mutex> lock(s->sched);
   KArgs a;
   std::memcpy(&a.cam, cam, sizeof(Cam));
-  a.blob = s->blob; a.mats = s->mats; a.pool = s->pool; a.atlas = s->atlas; a.fb = fb;
+  a.blob = s->blob.p; a.mats = s->mats; a.pool = s->pool.p; a.atlas = s->atlas.p; a.fb = fb;
   a.n_runs = s->n_runs; a.blob_f4 = s->blob_f4; a.mats_f4 = s->mats_f4; a.n_hittables = s->n_hittables;
   a.width = p->width; a.height = p->height; a.samples = p->samples; a.depth = p->depth;
   a.inv_w = 1.0f / (float)p->width; a.inv_h = 1.0f / (float)p->height; // host IEEE division: correctly rounded
@@ -2001,13 +1976,8 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
   // Persistent grid: no more workgroups than the chip holds at once; lanes pull pixels from the queue.
   auto launch = [&](auto kernel, int block_threads = kBlock) -> int {
     const int waves_per_block = block_threads / 64;
-    int per_cu = 0;
-    auto cached = s->occupancy.find((const void*)kernel);
-    if (cached != s->occupancy.end()) per_cu = cached->second;
-    else {
-      PT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block_threads, shmem));
-      s->occupancy[(const void*)kernel] = per_cu;
-    }
+    int per_cu = occupancy_of(s, (const void*)kernel, block_threads, shmem);
+    if (per_cu < 0) return PT_ERR_HIP;
     // (a kernel variant that does not fit a CU at all — its static + dynamic LDS beyond the device's limit — must not be launched and hoped for)
     if (per_cu < 1) return fail(PT_ERR_TOO_LARGE, "pt_render: this scene's kernel variant does not fit a compute unit (LDS " + std::to_string(shmem) + " B dynamic + static)");
     // A headline-family launch with fewer than ~1.15 tiles per wave slot (shard 0 of 4 ... 6 of the 1080p frame) is bound by its heaviest
@@ -2091,8 +2061,8 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
     if (tri_pool && a.cam.lens_radius == 0.0f && !s->knobs.no_tri_cache && p->width <= 65535 && p->height <= 65535 &&
         grow_tricache(s, cache_lanes) == PT_OK) {
       const size_t lanes = cache_lanes;
-      PT_HIP(hipMemsetAsync(s->ws_tricache, 0xff, lanes * PT_TRI_CACHE_WORDS * 4, st));
-      a.tri_cache = s->ws_tricache;
+      PT_HIP(hipMemsetAsync(s->ws_tricache.p, 0xff, lanes * PT_TRI_CACHE_WORDS * 4, st));
+      a.tri_cache = s->ws_tricache.p;
       // the footprint of a pixel in direction space (camera.hpp:93-100 with lens_radius 0: d = llc + s hor + t ver - origin, s in [x / W, (x + 1) / W])
       const Cam& cm = a.cam;
       float base[3], hw[3], vh[3];
@@ -2113,7 +2083,7 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
     if (s->ring_done[slot]) PT_HIP(hipStreamWaitEvent(st, s->ring_done[slot], 0));
     else PT_HIP(hipEventCreateWithFlags(&s->ring_done[slot], hipEventDisableTiming));
     s->next_queue++; // (only once nothing above can fail any more)
-    a.queue = s->queues + 2 * slot; // [0] ordinary queue, [1] wide-phase queue
+    a.queue = s->queues.p + 2 * slot; // [0] ordinary queue, [1] wide-phase queue
     PT_HIP(hipMemsetAsync(a.queue, 0, 2 * sizeof(unsigned int), st));
     hipLaunchKernelGGL(kernel, grid, block, shmem, st, a);
     PT_HIP(hipGetLastError());
@@ -2128,12 +2098,12 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
       return launch(render_kernel<UV, false, false, false, false, false, true>);
     }
     if (a.fast_chunks) { // opt-in decorrelated mode: its own instantiations (no cooperative kernels: a chunk is short)
-      if (tri_pool) return launch(render_kernel<UV, false, false, false, false, true, false, true, true>);
+      if (tri_pool) return launch(tripool_kernel(UV, true));
       if (!resident) return launch(render_kernel_stream<UV, true>);
       if (!lds) return launch(render_kernel<UV, false, false, false, false, true>);
       return mlds ? launch(render_kernel<UV, true, true, false, false, true>) : launch(render_kernel<UV, true, false, false, false, true>);
     }
-    if (tri_pool) return launch(render_kernel<UV, false, false, false, false, false, false, true, true>);
+    if (tri_pool) return launch(tripool_kernel(UV, false));
     if (!resident) return launch(render_kernel_stream<UV>);
     if constexpr (UV == UV_NONE) { // no image texture and no sphere grid (the headline scene): kernels without the grid walk
       if (s->grid_spheres == 0 && !coop) {
@@ -2164,13 +2134,11 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
       if (mlds && shmem <= kMaxLdsColdScene && !s->knobs.no_cold_lds) return launch(render_kernel<UV, true, true, false, true>);
     }
     if (use_grid) { // which walk: decided with the queued-walk kernel's own occupancy
-      int per_cu2 = 0;
+      int per_cu2 = 0; // (stays 0 where the queued walk's LDS does not fit: never asked)
       const void* k2 = mlds ? (const void*)render_kernel<UV, true, true, false, false, false, false, 2> : (const void*)render_kernel<UV, true, false, false, false, false, false, 2>;
-      auto cached = s->occupancy.find(k2);
-      if (cached != s->occupancy.end()) per_cu2 = cached->second;
-      else if (shmem + kQueuedWalkStaticLds <= s->lds_per_block) {
-        PT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu2, k2, kBlock, shmem));
-        s->occupancy[k2] = per_cu2;
+      if (shmem + kQueuedWalkStaticLds <= s->lds_per_block) {
+        per_cu2 = occupancy_of(s, k2, kBlock, shmem);
+        if (per_cu2 < 0) return PT_ERR_HIP;
       }
       decide_walk(s->knobs.blocks_per_cu ? std::min(per_cu2, s->knobs.blocks_per_cu) : per_cu2, kWavesPerBlock);
     }
@@ -2201,30 +2169,30 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
     a.order = w->active; // (n_split stays NULL: no wide phase)
   } else if (probe_spp >= 1 && local_tiles >= 64 && !(p->flags & PT_FLAG_NO_LPT) && probe_pays) {
     if (int rc = reserve_tiles(s, local_tiles)) return rc; // first render at a new size only (or never: pt_scene_reserve)
-    PT_HIP(hipMemsetAsync(s->ws_cost, 0, (size_t)local_tiles * sizeof(unsigned int), st));
+    PT_HIP(hipMemsetAsync(s->ws_cost.p, 0, (size_t)local_tiles * sizeof(unsigned int), st));
     KArgs main_args = a;
-    a.cost = s->ws_cost;
+    a.cost = s->ws_cost.p;
     a.cost_max = (cost_by_max && !coop) ? 1 : 0;
     a.samples = probe_spp;
     a.keep_state = 0;
     // the probe's samples are kept (KArgs.resume_rng) — not in the opt-in fast mode, whose chunks are streams of their own
     const bool resume = !(p->flags & PT_FLAG_FAST_RNG) && !s->knobs.no_resume;
-    a.resume_rng = resume ? s->ws_rng : nullptr;
+    a.resume_rng = resume ? s->ws_rng.p : nullptr;
     a.resume_spp = 0;
     // a sample window's probe renders the window's first samples from the accumulator's state, in place; with probe_resume = -1 it
     // only costs (from the pixels' seeds: it writes nothing) and the frame launch renders the whole window
     if (window && resume) { a.samples = w->done + probe_spp; a.resume_rng = w->rng; a.resume_spp = w->done; }
-    int* const order_out = w ? w->order : s->ws_order;
-    int* const nsplit_out = w ? w->nsplit : s->ws_nsplit;
+    int* const order_out = w ? w->order : s->ws_order.p;
+    int* const nsplit_out = w ? w->nsplit : s->ws_nsplit.p;
     int rc = launch_variant();
     if (rc) return rc;
     // rough per-iteration instruction counts: traversal (splittable) vs shading + camera + cooperative overhead (not)
     const int forced_logG = s->knobs.wide_logG; // 0: the model picks the group size of the wide phase
-    const unsigned int* ranked = s->ws_cost;
+    const unsigned int* ranked = s->ws_cost.p;
     if (a.cost_max && p->shard_count == 1 && !coop) { // tile_dilate_kernel (a shard's neighbours are other ranks' tiles: its own estimates)
-      hipLaunchKernelGGL(tile_dilate_kernel, dim3((unsigned int)((local_tiles + 255) / 256)), dim3(256), 0, st, s->ws_cost, a.tiles_x, (int)(a.n_tiles / a.tiles_x), s->ws_rank);
+      hipLaunchKernelGGL(tile_dilate_kernel, dim3((unsigned int)((local_tiles + 255) / 256)), dim3(256), 0, st, s->ws_cost.p, a.tiles_x, (int)(a.n_tiles / a.tiles_x), s->ws_rank.p);
       PT_HIP(hipGetLastError());
-      ranked = s->ws_rank;
+      ranked = s->ws_rank.p;
     }
     // rough per-iteration instruction counts: traversal (splittable) vs shading + camera (not)
     hipLaunchKernelGGL(lpt_order_kernel, dim3(1), dim3(1024), 0, st, ranked, local_tiles, order_out, n_waves_resident,
@@ -2241,7 +2209,7 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
     // 1024 spp 375 / 407 -> 380.8 +- 1.5 — at the price of the fast ones and of 4 % on chain-bound shards: not kept.)
     a = main_args;
     if (window) { if (resume) a.resume_spp = w->done + probe_spp; }
-    else if (resume) { a.resume_rng = s->ws_rng; a.resume_spp = probe_spp; }
+    else if (resume) { a.resume_rng = s->ws_rng.p; a.resume_spp = probe_spp; }
     a.order = order_out;
     a.n_split = (coop && !(p->flags & PT_FLAG_NO_SPLIT)) ? nsplit_out : nullptr;
     if (w) *w->has_order = true;
@@ -2259,13 +2227,13 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
       return fail(PT_ERR_TOO_LARGE, "PT_FLAG_FAST_RNG supports up to 8128 samples per pixel and 2^24 pixels per shard");
     const size_t plane = (size_t)pt_framebuffer_floats(p), need = plane * (size_t)chunks;
     if (int rc = reserve_partial(s, need)) return rc; // first render at a new size only (or never: pt_scene_reserve)
-    PT_HIP(hipMemsetAsync(s->ws_partial, 0, need * sizeof(float), st)); // pixels no lane owns add 0
+    PT_HIP(hipMemsetAsync(s->ws_partial.p, 0, need * sizeof(float), st)); // pixels no lane owns add 0
     a.fast_chunks = chunks;
     a.fast_chunk0 = w ? w->done / PT_FAST_CHUNK_SPP : 0; // (a window starts on a chunk boundary: pt_render_accumulate)
     a.samples = std::min(p->samples, (int)PT_FAST_CHUNK_SPP);
     a.samples_total = p->samples;
     a.fast_stride = (long long)plane;
-    a.fb = s->ws_partial;
+    a.fb = s->ws_partial.p;
     a.n_local_pixels = local_tiles * PT_TILE_PIXELS * chunks;
     set_scatter();
     a.n_split = nullptr;
@@ -2274,12 +2242,12 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
     int rc = launch_variant();
     if (rc) return rc;
     if (w) { // a window: its chunks onto the accumulator's running sums, in chunk order, undivided
-      hipLaunchKernelGGL(fast_accum_kernel, dim3((unsigned int)((plane + 255) / 256)), dim3(256), 0, st, s->ws_partial, fb, (long long)plane,
+      hipLaunchKernelGGL(fast_accum_kernel, dim3((unsigned int)((plane + 255) / 256)), dim3(256), 0, st, s->ws_partial.p, fb, (long long)plane,
                          (long long)plane, chunks);
       PT_HIP(hipGetLastError());
       return PT_OK;
     }
-    hipLaunchKernelGGL(fast_reduce_kernel, dim3((unsigned int)((plane + 255) / 256)), dim3(256), 0, st, s->ws_partial, fb,
+    hipLaunchKernelGGL(fast_reduce_kernel, dim3((unsigned int)((plane + 255) / 256)), dim3(256), 0, st, s->ws_partial.p, fb,
                        (long long)plane, (long long)plane, chunks, (float)p->samples);
     PT_HIP(hipGetLastError());
     return PT_OK;
@@ -2368,7 +2336,7 @@ int pt_unshard_tiles(const float* gathered_device, const PtRenderParams* p, floa
 int pt_tonemap_rgb8(const float* fb_device, int32_t width, int32_t height, uint8_t* rgb8_device, void* stream) {
   if (!fb_device || !rgb8_device || width <= 0 || height <= 0) return fail(PT_ERR_INVALID_ARG, "pt_tonemap_rgb8: bad argument");
   dim3 block(256), grid((width + 255) / 256, height);
-  hipLaunchKernelGGL(tonemap_kernel, grid, block, 0, (hipStream_t)stream, fb_device, rgb8_device, width, height);
+  hipLaunchKernelGGL(tonemap_kernel<false>, grid, block, 0, (hipStream_t)stream, fb_device, nullptr, 0, rgb8_device, width, height);
   PT_HIP(hipGetLastError());
   return PT_OK;
 }
@@ -2381,10 +2349,10 @@ struct PtAccum {
   PtRenderParams p{};           // the frame (samples: unused)
   int local_tiles = 0;
   size_t fb_floats = 0, rng_words = 0;
-  float* sum = nullptr;         // plain radiance sums, pt_render's framebuffer layout
-  unsigned int* rng = nullptr;  // generator state per local pixel (ws_rng's indexing)
-  int* order = nullptr;         // heaviest-first tile order of the last probed window (never the scene's ws_order)
-  int* nsplit = nullptr;        // ... and the cooperative kernels' split decided with it
+  DevBuf<float> sum;            // plain radiance sums, pt_render's framebuffer layout
+  DevBuf<unsigned int> rng;     // generator state per local pixel (ws_rng's indexing)
+  DevBuf<int> order;            // heaviest-first tile order of the last probed window (never the scene's ws_order)
+  DevBuf<int> nsplit;           // ... and the cooperative kernels' split decided with it
   bool has_order = false;
   int32_t done = 0;             // samples the state holds (host-side count; adaptive: the unmasked windows' samples)
   bool cam_bound = false;
@@ -2392,20 +2360,20 @@ struct PtAccum {
   // adaptive accumulators (pt_adaptive_create): per-pixel counts and half A, in the frame buffer's layout without the channel
   bool adaptive = false;
   size_t pixels = 0;            // P = fb_floats / 3
-  float* half = nullptr;        // H: radiance sum of half A (fb_floats)
-  float* prev = nullptr;        // the sums before the next window (fb_floats): its contribution for the bookkeeping ...
+  DevBuf<float> half;           // H: radiance sum of half A (fb_floats)
+  DevBuf<float> prev;           // the sums before the next window (fb_floats): its contribution for the bookkeeping ...
   bool prev_synced = false;     // ... equal to `sum` (the bookkeeping pass keeps it so; otherwise a window copies it first)
-  int* cnt = nullptr;           // n per pixel
-  int* cnt_a = nullptr;         // a per pixel: samples in half A
-  uint8_t* tile_on = nullptr;   // masked windows: per local tile, holds an active pixel ...
-  int* active = nullptr;        // ... the active tiles in dequeue order ...
-  int* n_active = nullptr;      // ... and how many (device)
-  unsigned long long* n_sel = nullptr; // pt_adaptive_select's count (device)
+  DevBuf<int> cnt;              // n per pixel
+  DevBuf<int> cnt_a;            // a per pixel: samples in half A
+  DevBuf<uint8_t> tile_on;      // masked windows: per local tile, holds an active pixel ...
+  DevBuf<int> active;           // ... the active tiles in dequeue order ...
+  DevBuf<int> n_active;         // ... and how many (device)
+  DevBuf<unsigned long long> n_sel; // pt_adaptive_select's count (device)
   int64_t max_n = 0;            // bound on every pixel's n (host-side; 0: nothing rendered)
 };
 
 namespace {
-struct AccumHeader { // pt_accum_export's header: 160 bytes, then the sums (float) and the generator states (u32)
+struct AccumHeader { // an exported state's header: 160 bytes, then the sections of state_layout
   uint32_t magic, version;
   int32_t width, height, depth, shard_index, shard_count;
   uint32_t flags;
@@ -2425,21 +2393,72 @@ int accum_params(const PtRenderParams* p, PtRenderParams& q) {
   return PT_OK;
 }
 
+// THE description of an exported state: after the header, in order — format PT_ACCUM_FORMAT: the sums (float), the generator states (u32);
+// PT_ADAPTIVE_FORMAT: the same, then half A (float), n and a (i32).  `at` counts from the start of the state; `dev` is the accumulator's
+// array (NULL without one, and for the arrays a plain accumulator does not have).
+struct StateSection { void* dev; size_t bytes, at; };
+enum { SEC_SUM, SEC_RNG, SEC_HALF, SEC_N, SEC_A }; // their order
+struct StateLayout {
+  int n = 0;
+  StateSection s[5];
+  size_t bytes = sizeof(AccumHeader); // of the whole state
+};
+StateLayout state_layout(const PtRenderParams& q, uint32_t format, const PtAccum* acc = nullptr) {
+  const size_t F = (size_t)pt_framebuffer_floats(&q) * sizeof(float), R = (size_t)pt_shard_tiles(&q) * PT_TILE_PIXELS * sizeof(unsigned int);
+  const size_t P = F / 3; // one i32 per pixel of the frame buffer's layout
+  StateLayout l;
+  auto add = [&](void* dev, size_t bytes) { l.s[l.n++] = {dev, bytes, l.bytes}; l.bytes += bytes; };
+  add(acc ? acc->sum.p : nullptr, F);
+  add(acc ? acc->rng.p : nullptr, R);
+  if (format == PT_ADAPTIVE_FORMAT) {
+    add(acc ? acc->half.p : nullptr, F);
+    add(acc ? acc->cnt.p : nullptr, P);
+    add(acc ? acc->cnt_a.p : nullptr, P);
+  }
+  return l;
+}
+
+// the header of the accumulator's state, in its own format
+AccumHeader header_of(const PtAccum* acc) {
+  AccumHeader h;
+  std::memset(&h, 0, sizeof h);
+  h.magic = PT_ACCUM_MAGIC; h.version = acc->adaptive ? PT_ADAPTIVE_FORMAT : PT_ACCUM_FORMAT;
+  h.width = acc->p.width; h.height = acc->p.height; h.depth = acc->p.depth;
+  h.shard_index = acc->p.shard_index; h.shard_count = acc->p.shard_count; h.flags = acc->p.flags;
+  h.samples_done = acc->done; h.camera_bound = acc->cam_bound ? 1 : 0;
+  h.cam = acc->cam;
+  return h;
+}
+
+// that header, then every section of the format, device to host (pt_accum_export / pt_adaptive_export: `host` holds the layout's bytes)
+int export_state(const PtAccum* acc, void* host, hipStream_t st) {
+  const AccumHeader h = header_of(acc);
+  std::memcpy(host, &h, sizeof h);
+  const StateLayout l = state_layout(acc->p, h.version, acc);
+  for (int k = 0; k < l.n; k++) PT_HIP(hipMemcpyAsync((char*)host + l.s[k].at, l.s[k].dev, l.s[k].bytes, hipMemcpyDeviceToHost, st));
+  PT_HIP(hipStreamSynchronize(st));
+  return PT_OK;
+}
+
+// a state's header against the accumulator it is imported into: magic, a format `who` accepts (an adaptive accumulator: both), the
+// size of that format, the frame parameters
+int check_header(const AccumHeader& h, const PtAccum* acc, int64_t bytes, const char* who) {
+  if (h.magic != PT_ACCUM_MAGIC || (h.version != PT_ACCUM_FORMAT && !(acc->adaptive && h.version == PT_ADAPTIVE_FORMAT)))
+    return fail(PT_ERR_INVALID_ARG, std::string(who) + ": not an exported accumulator state (magic / format version)");
+  if (bytes != (int64_t)state_layout(acc->p, h.version).bytes)
+    return fail(PT_ERR_INVALID_ARG, std::string(who) + ": the state's size does not fit its format and this accumulator's frame");
+  if (h.width != acc->p.width || h.height != acc->p.height || h.depth != acc->p.depth || h.shard_index != acc->p.shard_index ||
+      h.shard_count != acc->p.shard_count || h.flags != acc->p.flags)
+    return fail(PT_ERR_INVALID_ARG, std::string(who) + ": the state was exported from an accumulator with other frame parameters");
+  return PT_OK;
+}
+
 // the triangle-pool kernels' candidate cache for every lane they can launch (launch_render would otherwise grow it on a window)
 int reserve_tricache(const PtScene* s, uint32_t flags) {
   if (s->tri_pooled <= 0 || s->knobs.no_tri_cache || (flags & PT_FLAG_FORCE_STREAM)) return PT_OK;
-  const bool fast = (flags & PT_FLAG_FAST_RNG) != 0;
-  const void* k;
-  if (s->track_uv) k = fast ? (const void*)render_kernel<UV_TRACKED, false, false, false, false, true, false, true, true>
-                            : (const void*)render_kernel<UV_TRACKED, false, false, false, false, false, false, true, true>;
-  else if (s->has_image) k = fast ? (const void*)render_kernel<UV_WINNER, false, false, false, false, true, false, true, true>
-                                  : (const void*)render_kernel<UV_WINNER, false, false, false, false, false, false, true, true>;
-  else k = fast ? (const void*)render_kernel<UV_NONE, false, false, false, false, true, false, true, true>
-                : (const void*)render_kernel<UV_NONE, false, false, false, false, false, false, true, true>;
-  int per_cu = 0;
-  auto cached = s->occupancy.find(k);
-  if (cached != s->occupancy.end()) per_cu = cached->second;
-  else { PT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, kBlock, 0)); s->occupancy[k] = per_cu; }
+  const int uv = s->track_uv ? UV_TRACKED : s->has_image ? UV_WINNER : UV_NONE; // (launch_render: launch_variant)
+  int per_cu = occupancy_of(s, (const void*)tripool_kernel(uv, (flags & PT_FLAG_FAST_RNG) != 0), kBlock, 0);
+  if (per_cu < 0) return PT_ERR_HIP;
   if (s->knobs.blocks_per_cu) per_cu = std::min(per_cu, s->knobs.blocks_per_cu);
   return grow_tricache(s, (size_t)std::max(1, per_cu) * (size_t)std::max(1, s->num_cus) * kBlock);
 }
@@ -2450,20 +2469,10 @@ extern "C" {
 int64_t pt_accum_state_bytes(const PtRenderParams* p) {
   PtRenderParams q;
   if (accum_params(p, q)) return -1;
-  return (int64_t)PT_ACCUM_HEADER_BYTES + 4 * pt_framebuffer_floats(&q) + 4 * (int64_t)pt_shard_tiles(&q) * PT_TILE_PIXELS;
+  return (int64_t)state_layout(q, PT_ACCUM_FORMAT).bytes;
 }
 
-void pt_accum_destroy(PtAccum* acc) {
-  if (!acc) return;
-  if (acc->sum) (void)hipFree(acc->sum);
-  if (acc->rng) (void)hipFree(acc->rng);
-  if (acc->order) (void)hipFree(acc->order);
-  if (acc->nsplit) (void)hipFree(acc->nsplit);
-  for (void* b : {(void*)acc->half, (void*)acc->prev, (void*)acc->cnt, (void*)acc->cnt_a, (void*)acc->tile_on, (void*)acc->active,
-                  (void*)acc->n_active, (void*)acc->n_sel})
-    if (b) (void)hipFree(b);
-  delete acc;
-}
+void pt_accum_destroy(PtAccum* acc) { delete acc; } // (its buffers: DevBuf members)
 
 } // extern "C"
 namespace {
@@ -2478,14 +2487,14 @@ unsigned int blocks_of(long long n) { return (unsigned int)std::max<long long>(1
 
 // an adaptive accumulator at 0 samples: sums, H, n, a zeroed; every generator state the pixel's seed
 int adaptive_clear(PtAccum* acc, hipStream_t st) {
-  PT_HIP(hipMemsetAsync(acc->sum, 0, acc->fb_floats * sizeof(float), st));
-  PT_HIP(hipMemsetAsync(acc->half, 0, acc->fb_floats * sizeof(float), st));
-  PT_HIP(hipMemsetAsync(acc->prev, 0, acc->fb_floats * sizeof(float), st));
+  PT_HIP(hipMemsetAsync(acc->sum.p, 0, acc->fb_floats * sizeof(float), st));
+  PT_HIP(hipMemsetAsync(acc->half.p, 0, acc->fb_floats * sizeof(float), st));
+  PT_HIP(hipMemsetAsync(acc->prev.p, 0, acc->fb_floats * sizeof(float), st));
   acc->prev_synced = true;
-  PT_HIP(hipMemsetAsync(acc->cnt, 0, std::max<size_t>(acc->pixels, 1) * sizeof(int), st));
-  PT_HIP(hipMemsetAsync(acc->cnt_a, 0, std::max<size_t>(acc->pixels, 1) * sizeof(int), st));
+  PT_HIP(hipMemsetAsync(acc->cnt.p, 0, std::max<size_t>(acc->pixels, 1) * sizeof(int), st));
+  PT_HIP(hipMemsetAsync(acc->cnt_a.p, 0, std::max<size_t>(acc->pixels, 1) * sizeof(int), st));
   if (acc->rng_words) {
-    hipLaunchKernelGGL(adaptive_seed_kernel, dim3(blocks_of((long long)acc->rng_words)), dim3(256), 0, st, frame_of(acc), acc->rng, (long long)acc->rng_words);
+    hipLaunchKernelGGL(adaptive_seed_kernel, dim3(blocks_of((long long)acc->rng_words)), dim3(256), 0, st, frame_of(acc), acc->rng.p, (long long)acc->rng_words);
     PT_HIP(hipGetLastError());
   }
   acc->max_n = 0;
@@ -2503,7 +2512,8 @@ int accum_create(const PtScene* scene, const PtRenderParams* p, PtAccum** out, b
   int cur = -1;
   PT_HIP(hipGetDevice(&cur));
   if (cur != scene->device) return fail(PT_ERR_INVALID_ARG, std::string(who) + ": the scene lives on another device");
-  PtAccum* acc = new PtAccum();
+  std::unique_ptr<PtAccum> owner(new PtAccum()); // (an early return frees what was allocated so far)
+  PtAccum* const acc = owner.get();
   acc->scene = scene;
   acc->p = q;
   acc->adaptive = adaptive;
@@ -2511,37 +2521,31 @@ int accum_create(const PtScene* scene, const PtRenderParams* p, PtAccum** out, b
   acc->local_tiles = std::max(0, (n_tiles - q.shard_index + q.shard_count - 1) / q.shard_count);
   acc->fb_floats = (size_t)pt_framebuffer_floats(&q);
   acc->rng_words = (size_t)pt_shard_tiles(&q) * PT_TILE_PIXELS;
-  auto bail = [&](hipError_t e, const char* what) { pt_accum_destroy(acc); return fail(PT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); };
-  hipError_t e;
-  if ((e = hipMalloc((void**)&acc->sum, acc->fb_floats * sizeof(float))) != hipSuccess) return bail(e, "pt_accum_create: hipMalloc");
-  if ((e = hipMalloc((void**)&acc->rng, std::max<size_t>(acc->rng_words, 1) * sizeof(unsigned int))) != hipSuccess) return bail(e, "pt_accum_create: hipMalloc");
-  if ((e = hipMalloc((void**)&acc->order, (size_t)std::max(acc->local_tiles, 1) * sizeof(int))) != hipSuccess) return bail(e, "pt_accum_create: hipMalloc");
-  if ((e = hipMalloc((void**)&acc->nsplit, 2 * sizeof(int))) != hipSuccess) return bail(e, "pt_accum_create: hipMalloc");
-  if ((e = hipMemset(acc->sum, 0, acc->fb_floats * sizeof(float))) != hipSuccess) return bail(e, "pt_accum_create: hipMemset");
-  if ((e = hipMemset(acc->rng, 0, std::max<size_t>(acc->rng_words, 1) * sizeof(unsigned int))) != hipSuccess) return bail(e, "pt_accum_create: hipMemset");
+  auto bad = [&](hipError_t e, const char* what) { return fail(PT_ERR_HIP, std::string(who) + ": " + what + ": " + hipGetErrorString(e)); };
+  hipError_t e = hipSuccess; // (a failed allocation: the others are still tried, the last failure is reported)
+  for (hipError_t r : {acc->sum.alloc(acc->fb_floats), acc->rng.alloc(acc->rng_words), acc->order.alloc((size_t)acc->local_tiles), acc->nsplit.alloc(2)})
+    if (r != hipSuccess) e = r;
+  if (e != hipSuccess) return bad(e, "hipMalloc");
+  if ((e = hipMemset(acc->sum.p, 0, acc->fb_floats * sizeof(float))) != hipSuccess) return bad(e, "hipMemset");
+  if ((e = hipMemset(acc->rng.p, 0, std::max<size_t>(acc->rng_words, 1) * sizeof(unsigned int))) != hipSuccess) return bad(e, "hipMemset");
   if (adaptive) {
     acc->pixels = acc->fb_floats / 3;
-    const size_t P = std::max<size_t>(acc->pixels, 1), T = (size_t)std::max(acc->local_tiles, 1);
-    if ((e = hipMalloc((void**)&acc->half, acc->fb_floats * sizeof(float))) != hipSuccess ||
-        (e = hipMalloc((void**)&acc->prev, acc->fb_floats * sizeof(float))) != hipSuccess ||
-        (e = hipMalloc((void**)&acc->cnt, P * sizeof(int))) != hipSuccess ||
-        (e = hipMalloc((void**)&acc->cnt_a, P * sizeof(int))) != hipSuccess ||
-        (e = hipMalloc((void**)&acc->tile_on, T)) != hipSuccess ||
-        (e = hipMalloc((void**)&acc->active, T * sizeof(int))) != hipSuccess ||
-        (e = hipMalloc((void**)&acc->n_active, sizeof(int))) != hipSuccess ||
-        (e = hipMalloc((void**)&acc->n_sel, sizeof(unsigned long long))) != hipSuccess)
-      return bail(e, "pt_adaptive_create: hipMalloc");
-    if (int rc = adaptive_clear(acc, nullptr)) { pt_accum_destroy(acc); return rc; }
-    if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) return bail(e, "pt_adaptive_create: hipStreamSynchronize");
+    const size_t T = (size_t)acc->local_tiles;
+    for (hipError_t r : {acc->half.alloc(acc->fb_floats), acc->prev.alloc(acc->fb_floats), acc->cnt.alloc(acc->pixels), acc->cnt_a.alloc(acc->pixels),
+                         acc->tile_on.alloc(T), acc->active.alloc(T), acc->n_active.alloc(1), acc->n_sel.alloc(1)})
+      if (r != hipSuccess) e = r;
+    if (e != hipSuccess) return bad(e, "hipMalloc");
+    if (int rc = adaptive_clear(acc, nullptr)) return rc;
+    if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) return bad(e, "hipStreamSynchronize");
   }
   {
     // the scene's launch workspaces a window uses (probe costs, tile ranks; the candidate cache): sized now, not by a window
     std::lock_guard<std::mutex> lock(scene->sched);
     int rc = acc->local_tiles > 0 ? reserve_tiles(scene, acc->local_tiles) : PT_OK;
     if (!rc) rc = reserve_tricache(scene, q.flags);
-    if (rc) { pt_accum_destroy(acc); return rc; }
+    if (rc) return rc;
   }
-  *out = acc;
+  *out = owner.release();
   return PT_OK;
 }
 } // namespace
@@ -2552,7 +2556,7 @@ int pt_accum_create(const PtScene* scene, const PtRenderParams* p, PtAccum** out
 int pt_accum_reset(PtAccum* acc, void* stream) {
   if (!acc) return fail(PT_ERR_INVALID_ARG, "pt_accum_reset: NULL accumulator");
   if (acc->adaptive) { if (int rc = adaptive_clear(acc, (hipStream_t)stream)) return rc; }
-  else PT_HIP(hipMemsetAsync(acc->sum, 0, acc->fb_floats * sizeof(float), (hipStream_t)stream));
+  else PT_HIP(hipMemsetAsync(acc->sum.p, 0, acc->fb_floats * sizeof(float), (hipStream_t)stream));
   acc->done = 0;
   acc->cam_bound = false;
   acc->has_order = false;
@@ -2572,8 +2576,8 @@ int pt_render_accumulate(PtAccum* acc, const PtCamera* cam, int32_t samples, voi
     return fail(PT_ERR_INVALID_ARG, "pt_render_accumulate: PT_FLAG_FAST_RNG windows start on a multiple of PT_FAST_CHUNK_SPP samples (the last window ended off one)");
   PtRenderParams q = acc->p;
   q.samples = samples;
-  Window w{acc->done, acc->rng, acc->order, acc->nsplit, &acc->has_order};
-  if (int rc = launch_render(acc->scene, cam, &q, acc->sum, (hipStream_t)stream, &w)) return rc;
+  Window w{acc->done, acc->rng.p, acc->order.p, acc->nsplit.p, &acc->has_order};
+  if (int rc = launch_render(acc->scene, cam, &q, acc->sum.p, (hipStream_t)stream, &w)) return rc;
   acc->done += samples;
   if (!acc->cam_bound) { acc->cam = *cam; acc->cam_bound = true; }
   return PT_OK;
@@ -2583,13 +2587,9 @@ int pt_accum_resolve(const PtAccum* acc, float* fb_device, void* stream) {
   if (!acc || !fb_device) return fail(PT_ERR_INVALID_ARG, "pt_accum_resolve: NULL argument");
   if (acc->adaptive ? acc->max_n <= 0 : acc->done <= 0) return fail(PT_ERR_INVALID_ARG, "pt_accum_resolve: no samples rendered yet");
   const long long n = (long long)acc->fb_floats;
-  if (acc->adaptive) { // each pixel by its own count
-    hipLaunchKernelGGL(adaptive_resolve_kernel, dim3(blocks_of(n)), dim3(256), 0, (hipStream_t)stream, acc->sum, acc->cnt, fb_device, n);
-    PT_HIP(hipGetLastError());
-    return PT_OK;
-  }
-  hipLaunchKernelGGL(accum_resolve_kernel, dim3((unsigned int)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, acc->sum, fb_device, n,
-                     (float)acc->done);
+  // (adaptive: each pixel by its own count)
+  hipLaunchKernelGGL(accum_resolve_kernel, dim3(blocks_of(n)), dim3(256), 0, (hipStream_t)stream, acc->sum.p, acc->adaptive ? acc->cnt.p : nullptr,
+                     (int)acc->done, fb_device, n);
   PT_HIP(hipGetLastError());
   return PT_OK;
 }
@@ -2599,12 +2599,8 @@ int pt_accum_tonemap_rgb8(const PtAccum* acc, uint8_t* rgb8_device, void* stream
   if (acc->adaptive ? acc->max_n <= 0 : acc->done <= 0) return fail(PT_ERR_INVALID_ARG, "pt_accum_tonemap_rgb8: no samples rendered yet");
   if (acc->p.shard_count != 1) return fail(PT_ERR_INVALID_ARG, "pt_accum_tonemap_rgb8: whole frames only (shard_count == 1)");
   dim3 block(256), grid((acc->p.width + 255) / 256, acc->p.height);
-  if (acc->adaptive) {
-    hipLaunchKernelGGL(adaptive_tonemap_kernel, grid, block, 0, (hipStream_t)stream, acc->sum, acc->cnt, rgb8_device, acc->p.width, acc->p.height);
-    PT_HIP(hipGetLastError());
-    return PT_OK;
-  }
-  hipLaunchKernelGGL(accum_tonemap_kernel, grid, block, 0, (hipStream_t)stream, acc->sum, rgb8_device, acc->p.width, acc->p.height, (float)acc->done);
+  hipLaunchKernelGGL(tonemap_kernel<true>, grid, block, 0, (hipStream_t)stream, acc->sum.p, acc->adaptive ? acc->cnt.p : nullptr, (int)acc->done,
+                     rgb8_device, acc->p.width, acc->p.height);
   PT_HIP(hipGetLastError());
   return PT_OK;
 }
@@ -2613,20 +2609,7 @@ int pt_accum_export(const PtAccum* acc, void* host, int64_t bytes, void* stream)
   if (!acc || !host) return fail(PT_ERR_INVALID_ARG, "pt_accum_export: NULL argument");
   if (acc->adaptive) return fail(PT_ERR_INVALID_ARG, "pt_accum_export: an adaptive accumulator exports with pt_adaptive_export");
   if (bytes != pt_accum_state_bytes(&acc->p)) return fail(PT_ERR_INVALID_ARG, "pt_accum_export: the buffer is not pt_accum_state_bytes() long");
-  AccumHeader h;
-  std::memset(&h, 0, sizeof h);
-  h.magic = PT_ACCUM_MAGIC; h.version = PT_ACCUM_FORMAT;
-  h.width = acc->p.width; h.height = acc->p.height; h.depth = acc->p.depth;
-  h.shard_index = acc->p.shard_index; h.shard_count = acc->p.shard_count; h.flags = acc->p.flags;
-  h.samples_done = acc->done; h.camera_bound = acc->cam_bound ? 1 : 0;
-  h.cam = acc->cam;
-  char* out = (char*)host;
-  std::memcpy(out, &h, sizeof h);
-  const hipStream_t st = (hipStream_t)stream;
-  PT_HIP(hipMemcpyAsync(out + sizeof h, acc->sum, acc->fb_floats * sizeof(float), hipMemcpyDeviceToHost, st));
-  PT_HIP(hipMemcpyAsync(out + sizeof h + acc->fb_floats * sizeof(float), acc->rng, acc->rng_words * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-  PT_HIP(hipStreamSynchronize(st));
-  return PT_OK;
+  return export_state(acc, host, (hipStream_t)stream);
 }
 
 int pt_accum_import(PtAccum* acc, const void* host, int64_t bytes, void* stream) {
@@ -2635,15 +2618,11 @@ int pt_accum_import(PtAccum* acc, const void* host, int64_t bytes, void* stream)
   if (bytes != pt_accum_state_bytes(&acc->p)) return fail(PT_ERR_INVALID_ARG, "pt_accum_import: the state is not pt_accum_state_bytes() long for this accumulator");
   AccumHeader h;
   std::memcpy(&h, host, sizeof h);
-  if (h.magic != PT_ACCUM_MAGIC || h.version != PT_ACCUM_FORMAT) return fail(PT_ERR_INVALID_ARG, "pt_accum_import: not an exported accumulator state (magic / format version)");
-  if (h.width != acc->p.width || h.height != acc->p.height || h.depth != acc->p.depth || h.shard_index != acc->p.shard_index ||
-      h.shard_count != acc->p.shard_count || h.flags != acc->p.flags)
-    return fail(PT_ERR_INVALID_ARG, "pt_accum_import: the state was exported from an accumulator with other frame parameters");
+  if (int rc = check_header(h, acc, bytes, "pt_accum_import")) return rc;
   if (h.samples_done < 0 || (h.camera_bound != 0) != (h.samples_done > 0)) return fail(PT_ERR_INVALID_ARG, "pt_accum_import: inconsistent header");
-  const char* in = (const char*)host;
   const hipStream_t st = (hipStream_t)stream;
-  PT_HIP(hipMemcpyAsync(acc->sum, in + sizeof h, acc->fb_floats * sizeof(float), hipMemcpyHostToDevice, st));
-  PT_HIP(hipMemcpyAsync(acc->rng, in + sizeof h + acc->fb_floats * sizeof(float), acc->rng_words * sizeof(unsigned int), hipMemcpyHostToDevice, st));
+  const StateLayout l = state_layout(acc->p, h.version, acc);
+  for (int k = 0; k < l.n; k++) PT_HIP(hipMemcpyAsync(l.s[k].dev, (const char*)host + l.s[k].at, l.s[k].bytes, hipMemcpyHostToDevice, st));
   PT_HIP(hipStreamSynchronize(st)); // (the caller's buffer may go as soon as this returns)
   acc->done = h.samples_done;
   acc->cam_bound = h.camera_bound != 0;
@@ -2658,8 +2637,7 @@ int pt_adaptive_create(const PtScene* scene, const PtRenderParams* p, PtAccum** 
 int64_t pt_adaptive_state_bytes(const PtRenderParams* p) {
   PtRenderParams q;
   if (accum_params(p, q) || (q.flags & PT_FLAG_FAST_RNG)) return -1;
-  const int64_t F = pt_framebuffer_floats(&q), R = (int64_t)pt_shard_tiles(&q) * PT_TILE_PIXELS, P = F / 3;
-  return (int64_t)PT_ACCUM_HEADER_BYTES + 4 * F + 4 * R + 4 * F + 4 * P + 4 * P;
+  return (int64_t)state_layout(q, PT_ADAPTIVE_FORMAT).bytes;
 }
 
 static int adaptive_only(const PtAccum* acc, const char* who) {
@@ -2681,28 +2659,28 @@ int pt_adaptive_window(PtAccum* acc, const PtCamera* cam, int32_t samples, const
   const AFrame f = frame_of(acc);
   // Every window resumes from the state (pt_adaptive_create seeded it), whatever its pixels' counts: the kernels read the sample index
   // only to stop and for the chain-priority poll, so a window runs from a nominal start of 1 to 1 + samples (with done = 0 it would seed).
-  Window w{1, acc->rng, acc->order, acc->nsplit, &acc->has_order};
+  Window w{1, acc->rng.p, acc->order.p, acc->nsplit.p, &acc->has_order};
   if (mask_device) {
     if (acc->local_tiles <= 0) return PT_OK;
-    hipLaunchKernelGGL(adaptive_tiles_kernel, dim3(blocks_of(acc->local_tiles)), dim3(256), 0, st, f, mask_device, acc->local_tiles, acc->tile_on);
+    hipLaunchKernelGGL(adaptive_tiles_kernel, dim3(blocks_of(acc->local_tiles)), dim3(256), 0, st, f, mask_device, acc->local_tiles, acc->tile_on.p);
     PT_HIP(hipGetLastError());
-    hipLaunchKernelGGL(adaptive_compact_kernel, dim3(1), dim3(1024), 0, st, acc->tile_on, acc->has_order ? acc->order : nullptr, acc->local_tiles,
-                       acc->active, acc->n_active);
+    hipLaunchKernelGGL(adaptive_compact_kernel, dim3(1), dim3(1024), 0, st, acc->tile_on.p, acc->has_order ? acc->order.p : nullptr, acc->local_tiles,
+                       acc->active.p, acc->n_active.p);
     PT_HIP(hipGetLastError());
     int n_active = 0;
-    PT_HIP(hipMemcpyAsync(&n_active, acc->n_active, sizeof(int), hipMemcpyDeviceToHost, st));
+    PT_HIP(hipMemcpyAsync(&n_active, acc->n_active.p, sizeof(int), hipMemcpyDeviceToHost, st));
     PT_HIP(hipStreamSynchronize(st)); // (the launch is sized by the active tiles)
     if (n_active <= 0) return PT_OK;  // an empty mask: nothing to render
-    w.mask = mask_device; w.active = acc->active; w.n_active = n_active;
+    w.mask = mask_device; w.active = acc->active.p; w.n_active = n_active;
   }
   PtRenderParams q = acc->p;
   q.samples = samples;
   // S before the window is `prev`, which the last bookkeeping pass left equal to the sums (copied here only where none ran since)
-  if (!acc->prev_synced) PT_HIP(hipMemcpyAsync(acc->prev, acc->sum, acc->fb_floats * sizeof(float), hipMemcpyDeviceToDevice, st));
+  if (!acc->prev_synced) PT_HIP(hipMemcpyAsync(acc->prev.p, acc->sum.p, acc->fb_floats * sizeof(float), hipMemcpyDeviceToDevice, st));
   acc->prev_synced = false;
-  if (int rc = launch_render(acc->scene, cam, &q, acc->sum, st, &w)) return rc;
-  hipLaunchKernelGGL(adaptive_book_kernel, dim3(blocks_of(f.pixels)), dim3(256), 0, st, f, mask_device, acc->sum, acc->prev, acc->half,
-                     acc->cnt, acc->cnt_a, (int)samples);
+  if (int rc = launch_render(acc->scene, cam, &q, acc->sum.p, st, &w)) return rc;
+  hipLaunchKernelGGL(adaptive_book_kernel, dim3(blocks_of(f.pixels)), dim3(256), 0, st, f, mask_device, acc->sum.p, acc->prev.p, acc->half.p,
+                     acc->cnt.p, acc->cnt_a.p, (int)samples);
   PT_HIP(hipGetLastError());
   acc->prev_synced = true;
   if (!mask_device) acc->done += samples;
@@ -2714,7 +2692,7 @@ int pt_adaptive_window(PtAccum* acc, const PtCamera* cam, int32_t samples, const
 int pt_adaptive_counts(const PtAccum* acc, int32_t* counts_device, void* stream) {
   if (int rc = adaptive_only(acc, "pt_adaptive_counts")) return rc;
   if (!counts_device) return fail(PT_ERR_INVALID_ARG, "pt_adaptive_counts: NULL argument");
-  PT_HIP(hipMemcpyAsync(counts_device, acc->cnt, acc->pixels * sizeof(int), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  PT_HIP(hipMemcpyAsync(counts_device, acc->cnt.p, acc->pixels * sizeof(int), hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return PT_OK;
 }
 
@@ -2722,7 +2700,7 @@ int pt_adaptive_error(const PtAccum* acc, float* err_device, void* stream) {
   if (int rc = adaptive_only(acc, "pt_adaptive_error")) return rc;
   if (!err_device) return fail(PT_ERR_INVALID_ARG, "pt_adaptive_error: NULL argument");
   const AFrame f = frame_of(acc);
-  hipLaunchKernelGGL(adaptive_error_kernel, dim3(blocks_of(f.pixels)), dim3(256), 0, (hipStream_t)stream, f, acc->sum, acc->half, acc->cnt, acc->cnt_a, err_device);
+  hipLaunchKernelGGL(adaptive_error_kernel, dim3(blocks_of(f.pixels)), dim3(256), 0, (hipStream_t)stream, f, acc->sum.p, acc->half.p, acc->cnt.p, acc->cnt_a.p, err_device);
   PT_HIP(hipGetLastError());
   return PT_OK;
 }
@@ -2736,12 +2714,12 @@ int pt_adaptive_select(const PtAccum* acc, float threshold, int32_t min_spp, int
     return fail(PT_ERR_INVALID_ARG, "pt_adaptive_select: PT_ADAPTIVE_DILATE needs whole frames (a shard's neighbours are other shards' pixels)");
   const hipStream_t st = (hipStream_t)stream;
   const AFrame f = frame_of(acc);
-  PT_HIP(hipMemsetAsync(acc->n_sel, 0, sizeof(unsigned long long), st));
-  hipLaunchKernelGGL(adaptive_select_kernel, dim3(blocks_of(f.pixels)), dim3(256), 0, st, f, acc->sum, acc->half, acc->cnt, acc->cnt_a, threshold,
-                     (int)min_spp, (int)max_spp, (flags & PT_ADAPTIVE_DILATE) ? 1 : 0, mask_device, acc->n_sel);
+  PT_HIP(hipMemsetAsync(acc->n_sel.p, 0, sizeof(unsigned long long), st));
+  hipLaunchKernelGGL(adaptive_select_kernel, dim3(blocks_of(f.pixels)), dim3(256), 0, st, f, acc->sum.p, acc->half.p, acc->cnt.p, acc->cnt_a.p, threshold,
+                     (int)min_spp, (int)max_spp, (flags & PT_ADAPTIVE_DILATE) ? 1 : 0, mask_device, acc->n_sel.p);
   PT_HIP(hipGetLastError());
   unsigned long long n = 0;
-  PT_HIP(hipMemcpyAsync(&n, acc->n_sel, sizeof n, hipMemcpyDeviceToHost, st));
+  PT_HIP(hipMemcpyAsync(&n, acc->n_sel.p, sizeof n, hipMemcpyDeviceToHost, st));
   PT_HIP(hipStreamSynchronize(st));
   *n_active = (int64_t)n;
   return PT_OK;
@@ -2751,25 +2729,7 @@ int pt_adaptive_export(const PtAccum* acc, void* host, int64_t bytes, void* stre
   if (int rc = adaptive_only(acc, "pt_adaptive_export")) return rc;
   if (!host) return fail(PT_ERR_INVALID_ARG, "pt_adaptive_export: NULL argument");
   if (bytes != pt_adaptive_state_bytes(&acc->p)) return fail(PT_ERR_INVALID_ARG, "pt_adaptive_export: the buffer is not pt_adaptive_state_bytes() long");
-  AccumHeader h;
-  std::memset(&h, 0, sizeof h);
-  h.magic = PT_ACCUM_MAGIC; h.version = PT_ADAPTIVE_FORMAT;
-  h.width = acc->p.width; h.height = acc->p.height; h.depth = acc->p.depth;
-  h.shard_index = acc->p.shard_index; h.shard_count = acc->p.shard_count; h.flags = acc->p.flags;
-  h.samples_done = acc->done; h.camera_bound = acc->cam_bound ? 1 : 0;
-  h.cam = acc->cam;
-  char* out = (char*)host;
-  std::memcpy(out, &h, sizeof h);
-  const hipStream_t st = (hipStream_t)stream;
-  const size_t F = acc->fb_floats * sizeof(float), R = acc->rng_words * sizeof(unsigned int), P = acc->pixels * sizeof(int);
-  out += sizeof h;
-  PT_HIP(hipMemcpyAsync(out, acc->sum, F, hipMemcpyDeviceToHost, st));
-  PT_HIP(hipMemcpyAsync(out + F, acc->rng, R, hipMemcpyDeviceToHost, st));
-  PT_HIP(hipMemcpyAsync(out + F + R, acc->half, F, hipMemcpyDeviceToHost, st));
-  PT_HIP(hipMemcpyAsync(out + 2 * F + R, acc->cnt, P, hipMemcpyDeviceToHost, st));
-  PT_HIP(hipMemcpyAsync(out + 2 * F + R + P, acc->cnt_a, P, hipMemcpyDeviceToHost, st));
-  PT_HIP(hipStreamSynchronize(st));
-  return PT_OK;
+  return export_state(acc, host, (hipStream_t)stream);
 }
 
 int pt_adaptive_import(PtAccum* acc, const void* host, int64_t bytes, void* stream) {
@@ -2778,16 +2738,10 @@ int pt_adaptive_import(PtAccum* acc, const void* host, int64_t bytes, void* stre
   if (bytes < (int64_t)sizeof(AccumHeader)) return fail(PT_ERR_INVALID_ARG, "pt_adaptive_import: shorter than a state header");
   AccumHeader h;
   std::memcpy(&h, host, sizeof h);
-  if (h.magic != PT_ACCUM_MAGIC || (h.version != PT_ADAPTIVE_FORMAT && h.version != PT_ACCUM_FORMAT))
-    return fail(PT_ERR_INVALID_ARG, "pt_adaptive_import: not an exported accumulator state (magic / format version)");
+  if (int rc = check_header(h, acc, bytes, "pt_adaptive_import")) return rc;
   const bool plain = h.version == PT_ACCUM_FORMAT;
-  if (bytes != (plain ? pt_accum_state_bytes(&acc->p) : pt_adaptive_state_bytes(&acc->p)))
-    return fail(PT_ERR_INVALID_ARG, "pt_adaptive_import: the state's size does not fit its format and this accumulator's frame");
-  if (h.width != acc->p.width || h.height != acc->p.height || h.depth != acc->p.depth || h.shard_index != acc->p.shard_index ||
-      h.shard_count != acc->p.shard_count || h.flags != acc->p.flags)
-    return fail(PT_ERR_INVALID_ARG, "pt_adaptive_import: the state was exported from an accumulator with other frame parameters");
-  const char* in = (const char*)host + sizeof h;
-  const size_t F = acc->fb_floats * sizeof(float), R = acc->rng_words * sizeof(unsigned int);
+  const StateLayout l = state_layout(acc->p, h.version, acc); // (a plain state: the sums and the generator states)
+  const char* in = (const char*)host;
   const AFrame f = frame_of(acc);
   std::vector<int> n, na;
   int64_t max_n = 0;
@@ -2799,8 +2753,8 @@ int pt_adaptive_import(PtAccum* acc, const void* host, int64_t bytes, void* stre
     max_n = h.samples_done;
   } else {
     n.resize(acc->pixels); na.resize(acc->pixels);
-    std::memcpy(n.data(), in + 2 * F + R, acc->pixels * sizeof(int));
-    std::memcpy(na.data(), in + 2 * F + R + acc->pixels * sizeof(int), acc->pixels * sizeof(int));
+    std::memcpy(n.data(), in + l.s[SEC_N].at, l.s[SEC_N].bytes);
+    std::memcpy(na.data(), in + l.s[SEC_A].at, l.s[SEC_A].bytes);
     int64_t min_n = INT32_MAX;
     for (size_t i = 0; i < acc->pixels; i++) {
       if (na[i] < 0 || na[i] > n[i]) return fail(PT_ERR_INVALID_ARG, "pt_adaptive_import: a pixel's counts are not 0 <= a <= n");
@@ -2812,19 +2766,19 @@ int pt_adaptive_import(PtAccum* acc, const void* host, int64_t bytes, void* stre
       return fail(PT_ERR_INVALID_ARG, "pt_adaptive_import: inconsistent header");
   }
   const hipStream_t st = (hipStream_t)stream;
-  PT_HIP(hipMemcpyAsync(acc->sum, in, F, hipMemcpyHostToDevice, st));
+  PT_HIP(hipMemcpyAsync(acc->sum.p, in + l.s[SEC_SUM].at, l.s[SEC_SUM].bytes, hipMemcpyHostToDevice, st));
   if (plain && h.samples_done == 0) { // (a plain state at 0 samples holds no generator states: the seeds)
     if (acc->rng_words) {
-      hipLaunchKernelGGL(adaptive_seed_kernel, dim3(blocks_of((long long)acc->rng_words)), dim3(256), 0, st, f, acc->rng, (long long)acc->rng_words);
+      hipLaunchKernelGGL(adaptive_seed_kernel, dim3(blocks_of((long long)acc->rng_words)), dim3(256), 0, st, f, acc->rng.p, (long long)acc->rng_words);
       PT_HIP(hipGetLastError());
     }
   } else {
-    PT_HIP(hipMemcpyAsync(acc->rng, in + F, R, hipMemcpyHostToDevice, st));
+    PT_HIP(hipMemcpyAsync(acc->rng.p, in + l.s[SEC_RNG].at, l.s[SEC_RNG].bytes, hipMemcpyHostToDevice, st));
   }
-  if (plain) PT_HIP(hipMemsetAsync(acc->half, 0, F, st));
-  else PT_HIP(hipMemcpyAsync(acc->half, in + F + R, F, hipMemcpyHostToDevice, st));
-  PT_HIP(hipMemcpyAsync(acc->cnt, n.data(), acc->pixels * sizeof(int), hipMemcpyHostToDevice, st));
-  PT_HIP(hipMemcpyAsync(acc->cnt_a, na.data(), acc->pixels * sizeof(int), hipMemcpyHostToDevice, st));
+  if (plain) PT_HIP(hipMemsetAsync(acc->half.p, 0, acc->fb_floats * sizeof(float), st));
+  else PT_HIP(hipMemcpyAsync(acc->half.p, in + l.s[SEC_HALF].at, l.s[SEC_HALF].bytes, hipMemcpyHostToDevice, st));
+  PT_HIP(hipMemcpyAsync(acc->cnt.p, n.data(), acc->pixels * sizeof(int), hipMemcpyHostToDevice, st));
+  PT_HIP(hipMemcpyAsync(acc->cnt_a.p, na.data(), acc->pixels * sizeof(int), hipMemcpyHostToDevice, st));
   PT_HIP(hipStreamSynchronize(st)); // (the caller's buffer and the host counts may go as soon as this returns)
   acc->done = h.samples_done;
   acc->max_n = max_n;
@@ -2889,13 +2843,13 @@ int pt_debug_bounce(const PtScene* scene, const PtBounceIn* in, PtBounceOut* out
   dim3 block(64), grid((n + 63) / 64);
   const bool qw = scene->knobs.grid_walk == 2; // PtTuning.grid_walk = 2: the probe walks sphere grids through the pair queue, like the kernels it stands for
   if (scene->track_uv && qw)
-    hipLaunchKernelGGL((bounce_kernel<true, 2>), grid, block, 0, nullptr, scene->blob, scene->n_runs, scene->mats, scene->pool, scene->atlas, din.p, dout.p, n, scene->fast_ok ? 1 : 0);
+    hipLaunchKernelGGL((bounce_kernel<true, 2>), grid, block, 0, nullptr, scene->blob.p, scene->n_runs, scene->mats, scene->pool.p, scene->atlas.p, din.p, dout.p, n, scene->fast_ok ? 1 : 0);
   else if (scene->track_uv)
-    hipLaunchKernelGGL((bounce_kernel<true, 1>), grid, block, 0, nullptr, scene->blob, scene->n_runs, scene->mats, scene->pool, scene->atlas, din.p, dout.p, n, scene->fast_ok ? 1 : 0);
+    hipLaunchKernelGGL((bounce_kernel<true, 1>), grid, block, 0, nullptr, scene->blob.p, scene->n_runs, scene->mats, scene->pool.p, scene->atlas.p, din.p, dout.p, n, scene->fast_ok ? 1 : 0);
   else if (qw)
-    hipLaunchKernelGGL((bounce_kernel<false, 2>), grid, block, 0, nullptr, scene->blob, scene->n_runs, scene->mats, scene->pool, scene->atlas, din.p, dout.p, n, scene->fast_ok ? 1 : 0);
+    hipLaunchKernelGGL((bounce_kernel<false, 2>), grid, block, 0, nullptr, scene->blob.p, scene->n_runs, scene->mats, scene->pool.p, scene->atlas.p, din.p, dout.p, n, scene->fast_ok ? 1 : 0);
   else
-    hipLaunchKernelGGL((bounce_kernel<false, 1>), grid, block, 0, nullptr, scene->blob, scene->n_runs, scene->mats, scene->pool, scene->atlas, din.p, dout.p, n, scene->fast_ok ? 1 : 0);
+    hipLaunchKernelGGL((bounce_kernel<false, 1>), grid, block, 0, nullptr, scene->blob.p, scene->n_runs, scene->mats, scene->pool.p, scene->atlas.p, din.p, dout.p, n, scene->fast_ok ? 1 : 0);
   PT_HIP(hipGetLastError());
   PT_HIP(hipMemcpy(out, dout.p, (size_t)n * sizeof(PtBounceOut), hipMemcpyDeviceToHost));
   return PT_OK;
@@ -2908,7 +2862,7 @@ int pt_debug_schedule(const PtScene* scene, int32_t out[2]) {
   std::lock_guard<std::mutex> lock(scene->sched); // last_had_wide_phase / ws_nsplit belong to the launch path
   if (!scene->last_had_wide_phase) return PT_OK;
   int v[2] = {0, 0};
-  PT_HIP(hipMemcpy(v, scene->ws_nsplit, sizeof v, hipMemcpyDeviceToHost));
+  PT_HIP(hipMemcpy(v, scene->ws_nsplit.p, sizeof v, hipMemcpyDeviceToHost));
   out[0] = v[0]; out[1] = v[0] > 0 ? (1 << v[1]) : 0;
   return PT_OK;
 }
