@@ -21,6 +21,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <numeric>
 #include <type_traits>
 #include <string>
 #include <vector>
@@ -86,63 +87,65 @@ constexpr size_t kMaxLdsBlob = 64 * 1024;   // blob staged in LDS when it fits
 constexpr size_t kMaxLdsWithMaterials = 16 * 1024; // stage the material table too when records + materials are this small
 constexpr size_t kMaxLdsColdScene = 10 * 1024;    // records + materials this small: the 8-wave kernel with LDS-resident cold lane state
 constexpr float kCoopMinTraversal = 2500.0f;        // estimated VALU instructions of one list scan (~110 spheres)
-constexpr int kGridMinTiles = 0;                    // since the grid's retuning it wins at every frame size: see launch_render
+constexpr int kGridMinTiles = 0;                    // since the grid's retuning it wins at every frame size: see choose_variant
 constexpr unsigned kQueueRing = 256;        // launches in flight on one scene may not exceed this
 
+// The kernels' only argument.  Every member starts "off": a launcher writes only what its launch uses.
 struct KArgs {
-  Cam cam;
-  const f4* blob;
-  const f4* mats;
-  const f4* pool;      // tables of the triangle pools (pt_flatten.hpp: put_tri_pool); NULL when the scene has none
-  const uint8_t* atlas;
-  float* fb;
-  int n_runs, blob_f4, mats_f4;
-  int width, height, samples, depth;
-  float inv_w, inv_h; // RN(1 / (float)width), RN(1 / (float)height): camera_ray
-  int pinhole;        // cam_is_pinhole(cam): camera_ray skips the lens arithmetic
-  int shard_index, shard_count;
-  int tiles_x, n_tiles;
-  int n_local_pixels;  // 64 x the tiles this shard owns (incl. padding pixels of edge tiles)
-  unsigned int* queue; // per-launch dequeue counter, zeroed on the stream before the kernel
-  unsigned int* cost;  // non-NULL: cost-probe pass, per local tile ray counts
+  Cam cam = {};
+  const f4* blob = nullptr;
+  const f4* mats = nullptr;
+  const f4* pool = nullptr;    // tables of the triangle pools (pt_flatten.hpp: put_tri_pool); NULL when the scene has none
+  const uint8_t* atlas = nullptr;
+  float* fb = nullptr;
+  int n_runs = 0, blob_f4 = 0, mats_f4 = 0;
+  int width = 0, height = 0, samples = 0, depth = 0;
+  float inv_w = 0.0f, inv_h = 0.0f; // RN(1 / (float)width), RN(1 / (float)height): camera_ray
+  int pinhole = 0;    // cam_is_pinhole(cam): camera_ray skips the lens arithmetic
+  int shard_index = 0, shard_count = 0;
+  int tiles_x = 0, n_tiles = 0;
+  int n_local_pixels = 0;  // 64 x the tiles this shard owns (incl. padding pixels of edge tiles)
+  unsigned int* queue = nullptr; // per-launch dequeue counter, zeroed on the stream before the kernel
+  unsigned int* cost = nullptr;  // non-NULL: cost-probe pass, per local tile ray counts
   // The probe's samples are the frame's FIRST samples: with resume_rng the probe leaves every pixel's plain radiance sum in fb and its
   // generator's state in resume_rng[local pixel]; the frame launch (resume_spp = what the probe rendered) starts every pixel from both, at
   // sample resume_spp — the same stream, the same order of additions (render.hpp:95-101), and no sample is rendered twice.
-  unsigned int* resume_rng;
-  int resume_spp;
+  unsigned int* resume_rng = nullptr;
+  int resume_spp = 0;
   // Sample windows of a PtAccum (pt_render_accumulate): `samples` is the window's END, resume_spp its start, and a finished pixel leaves
   // its plain radiance sum in fb and its generator's state in resume_rng — the probe's branch of lane_store — instead of the mean.
-  int keep_state;
+  int keep_state = 0;
   // Masked windows of an adaptive PtAccum (pt_adaptive_window): one byte per pixel in the frame buffer's layout without the channel
   // ([y][x], or [local tile][64] for shards); lane_acquire skips a pixel whose byte is 0 like a padding pixel.  NULL: every pixel.
-  const uint8_t* mask;
+  const uint8_t* mask = nullptr;
   // Headline-family launches (launch_render): once prio_onset queue positions are taken, a wave sets its issue priority — every 64
   // iterations — by the samples its slowest pixel still has to render: >= prio_t3 -> 3, >= prio_t2 -> 2, >= prio_t1 -> 1, else 0 (render_kernel).
   // prio_t1 = 0: never.
-  int prio_onset, prio_t1, prio_t2, prio_t3;
-  int cost_max;        // probe: 1 = keep the tile's HEAVIEST pixel (x 64) instead of the sum over its pixels
-  const int* order;    // non-NULL: queue position -> local tile, heaviest first
-  const int* n_split;  // non-NULL (COOP kernels): [0] how many leading tiles of `order` go through the wide phase, [1] log2 G
-  int tile_granular;   // PT_FLAG_TILE_GRANULAR
-  int tile_group;      // tile-granular launches: lanes of a wave that take pixels together (64: the whole wave = a tile; 32 / 16: half / quarter tiles)
-  int heavy_pixels;    // > 0 (tile-granular grid kernels, chain-bound launches): the first heavy_pixels queue positions — the heaviest tiles of the
-  int heavy_lanes;     //   cost-sorted order — are taken heavy_lanes pixels at a time, by the first heavy_lanes lanes of a wave (lane_acquire)
-  int scatter_p;       // > 0 (triangle-pool kernels): queue positions are dealt to tiles in runs of 2^scatter_log pixels with this stride (lane_acquire)
-  int scatter_log;
-  int lanes_cap;       // < 64 (triangle-pool kernels, fewer pixels than lanes): only the first lanes_cap lanes of a wave take pixels (lane_acquire)
-  int n_hittables;
-  int coop_prefix;     // >= 0: cooperative traversal allowed, list splittable up to this hittable; -1: disabled
-  int fast_ok; // every rect/box coordinate finite and <= 2^60: rays may use the shared-reciprocal division
+  int prio_onset = 0, prio_t1 = 0, prio_t2 = 0, prio_t3 = 0;
+  int cost_max = 0;    // probe: 1 = keep the tile's HEAVIEST pixel (x 64) instead of the sum over its pixels
+  const int* order = nullptr;  // non-NULL: queue position -> local tile, heaviest first
+  const int* n_split = nullptr; // non-NULL (COOP kernels): [0] how many leading tiles of `order` go through the wide phase, [1] log2 G
+  int tile_granular = 0; // PT_FLAG_TILE_GRANULAR
+  int tile_group = 64;   // tile-granular launches: lanes of a wave that take pixels together (64: the whole wave = a tile; 32 / 16: half / quarter tiles)
+  int heavy_pixels = 0;  // > 0 (tile-granular grid kernels, chain-bound launches): the first heavy_pixels queue positions — the heaviest tiles of the
+  int heavy_lanes = 64;  //   cost-sorted order — are taken heavy_lanes pixels at a time, by the first heavy_lanes lanes of a wave (lane_acquire)
+  int scatter_p = 0;     // > 0 (triangle-pool kernels): queue positions are dealt to tiles in runs of 2^scatter_log pixels with this stride (lane_acquire)
+  int scatter_log = 0;
+  int lanes_cap = 64;    // < 64 (triangle-pool kernels, fewer pixels than lanes): only the first lanes_cap lanes of a wave take pixels (lane_acquire)
+  int n_hittables = 0;
+  int coop_prefix = -1;  // >= 0: cooperative traversal allowed, list splittable up to this hittable; -1: disabled
+  int fast_ok = 0; // every rect/box coordinate finite and <= 2^60: rays may use the shared-reciprocal division
   // PT_FLAG_FAST_RNG (opt-in, not the reference's image): a work unit is one CHUNK of a tile's pixels; `samples` above is
   // then the chunk length, fast_chunks the chunks per pixel, samples_total the caller's spp, fb the partial-sum workspace
   // [chunk][framebuffer layout] (fast_reduce_kernel adds the chunks in order and divides).  0 = the reference's single stream.
-  int fast_chunks, samples_total;
-  int fast_chunk0;       // global index of the launch's first chunk (sample windows start at 64 x fast_chunk0; pt_render: 0)
-  long long fast_stride; // floats per chunk plane of the workspace
+  int fast_chunks = 0, samples_total = 0;
+  int fast_chunk0 = 0;      // global index of the launch's first chunk (sample windows start at 64 x fast_chunk0; pt_render: 0)
+  long long fast_stride = 0; // floats per chunk plane of the workspace
   // the camera rays' candidate cache of the triangle-pool kernels (pt_device.hpp: TriPrimCtx): one line per resident lane; NULL: none
-  unsigned int* tri_cache;
-  float foot[11];        // (llc - origin) xyz, hor / W xyz, ver / H xyz, the bound dd on |d - d_centre| over a pixel's camera rays, dd's rounding term
+  unsigned int* tri_cache = nullptr;
+  float foot[11] = {};      // (llc - origin) xyz, hor / W xyz, ver / H xyz, the bound dd on |d - d_centre| over a pixel's camera rays, dd's rounding term
 };
+static_assert(std::is_trivially_copyable<KArgs>::value, "KArgs is copied into the kernarg segment as it is");
 
 // Per-lane state of the persistent loop.  A lane owns ONE pixel at a time, for all of its samples (the
 // reference's single RNG stream per pixel, render.hpp:130-133, forbids splitting a pixel), but lanes are not
@@ -512,7 +515,7 @@ __device__ __forceinline__ void lane_prepare(Lane& L, const KArgs& a) {
 // MLDS: the material table is staged too (small tables only: it rides behind the records in the same buffer), so
 // the whole bounce — traversal, hit record, material, texture constants — runs out of LDS without a global load.
 // COOP: the traversal can split a ray's list over idle lanes (hit_world_lds); costs ~10 VGPRs and ~7 % of the
-// ordinary-mode throughput, so the launcher picks it only where the makespan floor matters (launch_render).
+// ordinary-mode throughput, so the launcher picks it only where the makespan floor matters (choose_variant).
 // CL: the cold part of the lane state lives in LDS (Cold<true>); small scenes only (8 KB per workgroup).
 // FAST: PT_FLAG_FAST_RNG (opt-in decorrelated mode; its own instantiations, so the parity kernels carry none of it)
 // BADOUEL: the scene has Badouel-strategy triangles (their loop is compiled only into these instantiations)
@@ -1307,7 +1310,6 @@ struct Knobs {
   float model_fixed = 2400.0f, model_chain = 2400.0f; // constants of the makespan model (lpt_order_kernel)
   int scatter_log = 0;     // log2 of the pixels of one tile that a wave takes together (0: every lane a pixel of another tile)
   bool lpt_with_scatter = false; // the cost probe + heaviest-first order also for scattered (triangle-pool) renders
-  int grid_block = kGridBlock; // PT_GRID_BLOCK (build-time experiment: workgroup size of the grid kernels)
   bool no_scatter = false; // triangle-pool kernels hand out whole tiles' pixels to a wave again (lane_acquire)
   bool generic_materials = false;
   int grid_walk = 0;       // PtTuning.grid_walk: 0 the launcher's rule, 1 the wave-synchronous walk, 2 the queued walk
@@ -1416,6 +1418,173 @@ struct PtScene {
   mutable std::map<const void*, int> occupancy; // resident workgroups per CU, per kernel variant (queried once)
   Knobs knobs;                                  // the scene's PtTuning (launch side), as resolved when the scene was created
 };
+
+namespace {
+
+// ---- which kernel variant a launch runs -------------------------------------------------------------------
+
+// A render_kernel instantiation by name: one member per template parameter, with the template's defaults.
+struct KV {
+  int uv = UV_NONE;
+  bool lds = false, mlds = false, coop = false, cl = false, fast = false, badouel = false;
+  int grid = 1;
+  bool tripool = false;
+  int mats = MATS_ALL;
+  int block = kBlock;
+};
+typedef void (*Kernel)(KArgs);
+// (the only place that lists render_kernel's parameters by position)
+template <KV V>
+constexpr Kernel kernel_of = render_kernel<V.uv, V.lds, V.mlds, V.coop, V.cl, V.fast, V.badouel, V.grid, V.tripool, V.mats, V.block>;
+
+// Resident workgroups per CU of a kernel variant: queried once per scene, then from PtScene.occupancy.  < 0: the query failed (pt_last_error).
+int occupancy_of(const PtScene* s, const void* kernel, int block_threads, size_t shmem) {
+  auto cached = s->occupancy.find(kernel);
+  if (cached != s->occupancy.end()) return cached->second;
+  int per_cu = 0;
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block_threads, shmem);
+  if (e != hipSuccess) { fail(PT_ERR_HIP, std::string("occupancy query of a kernel variant: ") + hipGetErrorString(e)); return -1; }
+  s->occupancy[kernel] = per_cu;
+  return per_cu;
+}
+
+// How a scene's kernels obtain u,v (the UV parameter of its kernel variants)
+int uv_of(const PtScene* s) { return s->track_uv ? UV_TRACKED : s->has_image ? UV_WINNER : UV_NONE; }
+
+// The triangle-pool kernel of a scene's UV mode: what choose_variant picks for such a scene, and what reserve_tricache sizes the cache for.
+Kernel tripool_kernel(int uv, bool fast) {
+  switch (uv) {
+    case UV_TRACKED: return fast ? kernel_of<KV{.uv = UV_TRACKED, .fast = true, .tripool = true}> : kernel_of<KV{.uv = UV_TRACKED, .tripool = true}>;
+    case UV_WINNER: return fast ? kernel_of<KV{.uv = UV_WINNER, .fast = true, .tripool = true}> : kernel_of<KV{.uv = UV_WINNER, .tripool = true}>;
+    default: return fast ? kernel_of<KV{.fast = true, .tripool = true}> : kernel_of<KV{.tripool = true}>;
+  }
+}
+
+// The headline family's kernel — no image texture, no grid walk — for the material and hittable kinds MATS; `cold`: cold lane state in LDS
+template <int MATS>
+Kernel headline_kernel(bool lds, bool mlds, bool cold) {
+  if (!lds) return kernel_of<KV{.grid = 0, .mats = MATS}>;
+  if (cold) return kernel_of<KV{.lds = true, .mlds = true, .cl = true, .grid = 0, .mats = MATS}>;
+  return mlds ? kernel_of<KV{.lds = true, .mlds = true, .grid = 0, .mats = MATS}> : kernel_of<KV{.lds = true, .grid = 0, .mats = MATS}>;
+}
+
+// The binned renderer's two kernels that shade (pt_binned.hpp), compiled for a scene's UV mode and material kinds
+struct BinKernels { void (*step)(BinArgs); void (*finish)(BinArgs); };
+template <int UV, int MATS>
+constexpr BinKernels bin_kernels = {bin_step_kernel<UV, MATS>, bin_finish_kernel<UV, MATS>};
+
+// What choose_variant decides for one pass of launch_render: the kernel, and the facts about it that the launch reads.
+struct Variant {
+  int rc = PT_OK;          // != PT_OK: no kernel (pt_last_error says why)
+  Kernel kernel = nullptr;
+  size_t shmem = 0;        // dynamic LDS: the blob image (+ the material table) of the LDS-resident kernels
+  int coop_prefix = -1;    // KArgs.coop_prefix
+  bool tri_pool = false;   // the scene's triangle pools are queried (the TRIPOOL kernels)
+  bool resident = false;   // render_kernel (blob in LDS or read through the scalar cache), not render_kernel_stream
+  bool use_grid = false;   // the kernel walks the scene's sphere grids
+  bool coop = false;       // cooperative kernel
+  bool chain_bound = false; // the headline family — no sphere grid, no cooperative phase: see `launch`
+  bool queued_walk = false; // the kernel walks sphere grids through the pair queue (pt_debug_last_launch)
+};
+
+// The kernel variant of one pass over local_tiles tiles: `fast` — the pass is a PT_FLAG_FAST_RNG launch (the probe of such a render is not);
+// n_local_pixels — the pass's KArgs.n_local_pixels.
+template <int UV>
+Variant choose_variant_uv(const PtScene* s, const PtRenderParams* p, int local_tiles, bool fast, int n_local_pixels) {
+  Variant v;
+  const bool fast_ok = s->fast_ok && !(p->flags & PT_FLAG_NO_FASTDIV);
+  v.coop_prefix = (s->coop_ok && fast_ok && !(p->flags & PT_FLAG_NO_COOP)) ? s->coop_prefix : -1;
+  const size_t blob_bytes = (size_t)s->blob_f4 * 16;
+  // a scene with a triangle pool is queried through per-lane loads from the global blob: the scalar-cache resident kernels,
+  // whatever its size (PT_FLAG_FORCE_STREAM: the streaming kernel, which scans every triangle, as the A/B)
+  v.tri_pool = s->tri_pooled > 0 && !(p->flags & PT_FLAG_FORCE_STREAM);
+  v.resident = (blob_bytes <= kMaxLdsBlob || (p->flags & PT_FLAG_NO_LDS) || v.tri_pool) && !(p->flags & PT_FLAG_FORCE_STREAM);
+  const bool lds = v.resident && !(p->flags & PT_FLAG_NO_LDS) && !v.tri_pool;
+  const bool mlds = lds && blob_bytes + (size_t)s->mats_f4 * 16 <= kMaxLdsWithMaterials;
+  v.shmem = lds ? blob_bytes + (mlds ? (size_t)s->mats_f4 * 16 : 0) : 0;
+  const bool cold = mlds && v.shmem <= kMaxLdsColdScene && !s->knobs.no_cold_lds; // small scene: cold lane state in LDS (7 workgroups x (scene + 8 KB) per CU)
+  // Cooperative kernels (a ray's list split over idle lanes; the heaviest tiles rendered G lanes per pixel) cost ~15 % of
+  // the ordinary-mode throughput, and the part of an iteration that cannot be split (camera, shading, ray context:
+  // ~4 500 cycles of a lone wave's 13 200 on the Cornell-style scene) bounds what they can win: there G = 8 shortens a
+  // pixel's chain by 1.4x for 4.6x the lane time, so they pay only where the scan of the list dominates an iteration
+  // (496-hittable scene, shard 0/8: 522 -> 229 ms).
+  // Sphere runs with a culling grid: the ordinary resident kernels walk it (a ray then tests tens of spheres instead of
+  // hundreds: 496-hittable scene 1 660 -> 3 240 Msamples/s at 1080p), the cooperative kernels scan the lists with lane
+  // groups.  With the grid as first tuned (margin 1.5 r) a lone wave's walk was no shorter than a group's list scan and small
+  // frames / shards kept the cooperative kernels; since the retuning (margin 0.5 r, walk after the big spheres) the walk wins
+  // everywhere (tools/grid_min_tiles.py: 400x225x256 spp 99 ms against 108; shard 0/8 of the 1080p frame at 256 spp 80
+  // against 102; shard 0/8 of 4K at 128 spp 61 against 102).  PT_GRID_MIN_TILES restores a threshold.
+  v.use_grid = s->grid_spheres > 0 && v.resident /* the streaming kernel scans the full lists */ && local_tiles >= s->knobs.grid_min_tiles && !(p->flags & PT_FLAG_FORCE_COOP);
+  v.coop = lds && v.coop_prefix >= 0 && !v.use_grid && (s->traversal_cost >= kCoopMinTraversal || (p->flags & PT_FLAG_FORCE_COOP));
+
+  if (s->has_badouel) { // parity-completeness path: scalar-cache or streaming kernel with the Badouel loop compiled in
+    if (fast) { v.rc = fail(PT_ERR_INVALID_ARG, "PT_FLAG_FAST_RNG is not offered for scenes with Badouel-strategy triangles"); return v; }
+    v.kernel = !v.resident ? render_kernel_stream<UV, false, true> : kernel_of<KV{.uv = UV, .badouel = true}>;
+    return v;
+  }
+  if (fast) { // opt-in decorrelated mode: its own instantiations (no cooperative kernels: a chunk is short)
+    if (v.tri_pool) v.kernel = tripool_kernel(UV, true);
+    else if (!v.resident) v.kernel = render_kernel_stream<UV, true>;
+    else if (!lds) v.kernel = kernel_of<KV{.uv = UV, .fast = true}>;
+    else v.kernel = mlds ? kernel_of<KV{.uv = UV, .lds = true, .mlds = true, .fast = true}> : kernel_of<KV{.uv = UV, .lds = true, .fast = true}>;
+    return v;
+  }
+  if (v.tri_pool) { v.kernel = tripool_kernel(UV, false); return v; }
+  if (!v.resident) { v.kernel = render_kernel_stream<UV>; return v; }
+  if constexpr (UV == UV_NONE) { // no image texture and no sphere grid (the headline scene): kernels without the grid walk
+    if (s->grid_spheres == 0 && !v.coop) {
+      v.chain_bound = true;
+      // lambertian + lightsource over solid textures: kernels without the other materials' code
+      // ... and every hittable a rect or a box (the headline scene): resolve_hit without the other kinds
+      v.kernel = !s->mats_simple    ? headline_kernel<MATS_ALL>(lds, mlds, cold)
+                 : !s->rectbox_only ? headline_kernel<MATS_LAMB_LIGHT_SOLID>(lds, mlds, cold)
+                                    : headline_kernel<MATS_LAMB_LIGHT_SOLID | MATS_RECTBOX_ONLY>(lds, mlds, cold);
+      return v;
+    }
+  }
+  if (!lds) { v.kernel = kernel_of<KV{.uv = UV}>; return v; }
+  if (v.coop) { v.kernel = mlds ? kernel_of<KV{.uv = UV, .lds = true, .mlds = true, .coop = true}> : kernel_of<KV{.uv = UV, .lds = true, .coop = true}>; return v; }
+  if constexpr (UV == UV_NONE) {
+    if (cold) { v.kernel = kernel_of<KV{.lds = true, .mlds = true, .cl = true}>; return v; }
+  }
+  if (v.use_grid) {
+    // Which sphere-grid walk (pt_device.hpp: sphere_scan, GRID = 1 / 2): the pair queue where walks diverge or the launch is bound by its
+    // chains — whole tiles per wave or at least 16 lanes (the rule of `launch`, evaluated for the kernels' four workgroups per CU) — and
+    // not on frames that are both dense (>= 4 M pixels: a tile's rays share their cells) and throughput-bound (>= 6 pixels per resident lane).
+    // The rule is evaluated for the resident lanes the GRID = 2 kernels really have (their occupancy is queried like `launch` does: 31 KB LDS
+    // image + 4 KB of per-wave queues and slots usually allow four workgroups per CU) — round 4 assumed 16 waves per CU here and the cap of
+    // `launch` from the measured occupancy, and the two could disagree.  The queued walk's STATIC 4 KB of LDS (sphere_queue,
+    // sphere_slots) ride on top of the dynamic blob image: where the sum exceeds what a workgroup may have, the walk stays in place.
+    constexpr size_t kQueuedWalkStaticLds = (size_t)PT_MAX_WAVES_PER_BLOCK * (PT_SQ_CAP * 4 + 64 * 8);
+    const Kernel queued = mlds ? kernel_of<KV{.uv = UV, .lds = true, .mlds = true, .grid = 2}> : kernel_of<KV{.uv = UV, .lds = true, .grid = 2}>;
+    int per_cu_queued = 0; // (stays 0 where the queued walk's LDS does not fit: never asked)
+    if (v.shmem + kQueuedWalkStaticLds <= s->lds_per_block) {
+      per_cu_queued = occupancy_of(s, (const void*)queued, kBlock, v.shmem);
+      if (per_cu_queued < 0) { v.rc = PT_ERR_HIP; return v; }
+    }
+    if (s->knobs.blocks_per_cu) per_cu_queued = std::min(per_cu_queued, s->knobs.blocks_per_cu);
+    const bool fits = per_cu_queued >= 1;
+    const double lanes = (double)std::max(1, s->num_cus) * std::max(1, per_cu_queued) * kWavesPerBlock * 64.0;
+    const double rho = (double)n_local_pixels / lanes;
+    const bool few_lanes = rho < 0.875 && !(p->flags & (PT_FLAG_TILE_GRANULAR | PT_FLAG_PIXEL_GRANULAR | PT_FLAG_FAST_RNG)) && s->knobs.lanes_cap >= 0; // 16 rho rounds below 16
+    const bool dense_and_busy = (double)p->width * p->height >= 4.0e6 && rho >= 6.0;
+    v.queued_walk = fits && (s->knobs.grid_walk == 2 || (s->knobs.grid_walk == 0 && !few_lanes && !dense_and_busy && !(s->knobs.lanes_cap > 0 && s->knobs.lanes_cap < 16)));
+    // the sphere-grid walk through the pair queue (pt_device.hpp: sphere_scan says where it pays)
+    if (v.queued_walk) { v.kernel = queued; return v; }
+  }
+  v.kernel = mlds ? kernel_of<KV{.uv = UV, .lds = true, .mlds = true}> : kernel_of<KV{.uv = UV, .lds = true}>;
+  return v;
+}
+
+Variant choose_variant(const PtScene* s, const PtRenderParams* p, int local_tiles, bool fast, int n_local_pixels) {
+  switch (uv_of(s)) {
+    case UV_TRACKED: return choose_variant_uv<UV_TRACKED>(s, p, local_tiles, fast, n_local_pixels);
+    case UV_WINNER: return choose_variant_uv<UV_WINNER>(s, p, local_tiles, fast, n_local_pixels);
+    default: return choose_variant_uv<UV_NONE>(s, p, local_tiles, fast, n_local_pixels);
+  }
+}
+
+} // namespace
 
 extern "C" {
 
@@ -1671,6 +1840,16 @@ static int n_tiles_of(const PtRenderParams* p, int* tiles_x) {
   if (tiles_x) *tiles_x = tx;
   return tx * ty;
 }
+// the tiles shard p->shard_index owns: tile t belongs to shard t % shard_count
+static int local_tiles_of(const PtRenderParams* p) { return (n_tiles_of(p, nullptr) - p->shard_index + p->shard_count - 1) / p->shard_count; }
+// PT_FLAG_FAST_RNG: the chunks a pixel's samples are rendered in
+static int fast_chunks_of(int samples) { return (samples + PT_FAST_CHUNK_SPP - 1) / PT_FAST_CHUNK_SPP; }
+// Scattered queues (lane_acquire: scatter_p) deal positions to the nt tiles with a stride: the smallest P >= max(1, nt / per_wave) coprime to nt
+static unsigned int scatter_stride(unsigned int nt, unsigned int per_wave) {
+  unsigned int P = nt / per_wave > 1 ? nt / per_wave : 1;
+  while (std::gcd(P, nt) != 1) ++P;
+  return P;
+}
 
 uint32_t pt_fast_seed(uint32_t pixel, uint32_t chunk) { return fast_seed(pixel, chunk); }
 
@@ -1706,26 +1885,6 @@ static int reserve_partial(const PtScene* s, size_t floats) {
   return PT_OK;
 }
 
-// Resident workgroups per CU of a kernel variant: queried once per scene, then from PtScene.occupancy.  < 0: the query failed (pt_last_error).
-static int occupancy_of(const PtScene* s, const void* kernel, int block_threads, size_t shmem) {
-  auto cached = s->occupancy.find(kernel);
-  if (cached != s->occupancy.end()) return cached->second;
-  int per_cu = 0;
-  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block_threads, shmem);
-  if (e != hipSuccess) { fail(PT_ERR_HIP, std::string("occupancy query of a kernel variant: ") + hipGetErrorString(e)); return -1; }
-  s->occupancy[kernel] = per_cu;
-  return per_cu;
-}
-
-// The triangle-pool kernel of a scene's UV mode: what launch_uv launches for such a scene, and what reserve_tricache sizes the cache for.
-static auto tripool_kernel(int uv, bool fast) -> void (*)(KArgs) {
-  switch (uv) {
-    case UV_TRACKED: return fast ? render_kernel<UV_TRACKED, false, false, false, false, true, false, true, true> : render_kernel<UV_TRACKED, false, false, false, false, false, false, true, true>;
-    case UV_WINNER: return fast ? render_kernel<UV_WINNER, false, false, false, false, true, false, true, true> : render_kernel<UV_WINNER, false, false, false, false, false, false, true, true>;
-    default: return fast ? render_kernel<UV_NONE, false, false, false, false, true, false, true, true> : render_kernel<UV_NONE, false, false, false, false, false, false, true, true>;
-  }
-}
-
 // The binned triangle-pool renderer (pt_binned.hpp): generations of { step, sort the requests by direction bin, band stage }, until no pixel
 // is live.  How many generations a frame takes is known only on the device (the heaviest pixel's ray count), so the host reads the live
 // count back every few generations: unlike the persistent kernels' launches this render has returned only when the frame is done.
@@ -1733,10 +1892,7 @@ static int reserve_binned(const PtScene* s, size_t n_pixels, size_t n_keys, size
 static int launch_binned(const PtScene* s, KArgs a, const PtRenderParams* p, int local_tiles, hipStream_t st) {
   if (p->depth <= 0) return PT_OK; // every sample black (render.hpp:58,91): the frame is pre-zeroed
   a.n_local_pixels = local_tiles * PT_TILE_PIXELS;
-  a.cost = nullptr; a.cost_max = 0; a.resume_rng = nullptr; a.resume_spp = 0; a.order = nullptr; a.n_split = nullptr;
-  a.prio_onset = a.prio_t1 = a.prio_t2 = a.prio_t3 = 0;
-  a.tile_granular = 1; a.tile_group = 64; a.heavy_pixels = 0; a.heavy_lanes = 64; a.scatter_p = 0; a.scatter_log = 0; a.lanes_cap = 64;
-  a.fast_chunks = 0; a.samples_total = p->samples; a.fast_stride = 0; a.queue = nullptr; a.coop_prefix = -1;
+  a.tile_granular = 1; a.samples_total = p->samples; // (everything else of the persistent kernels' scheduling: off, as a KArgs starts)
   const size_t N = (size_t)a.n_local_pixels, K = (size_t)s->bin_keys;
   size_t bytes = 0;
   if (int rc = reserve_binned(s, N, K, bytes)) return rc;
@@ -1760,14 +1916,8 @@ static int launch_binned(const PtScene* s, KArgs a, const PtRenderParams* p, int
   unsigned int* live_list[2] = {(unsigned int*)take(N * 4), (unsigned int*)take(N * 4)};
   sa.n_keys = (int)K; sa.n_blocks = (int)n_blocks; sa.full_slices = s->bin_full_slices;
   ba.hist = sa.hist; ba.ctl = sa.ctl; ba.pool_run = s->bin_run;
-  ba.scatter_p = 0; ba.dbg_base1 = s->bin_base1;
-  if (!s->knobs.no_scatter) {
-    const unsigned int nt = (unsigned int)local_tiles;
-    unsigned int P = nt / 64 > 1 ? nt / 64 : 1;
-    auto gcd = [](unsigned int x, unsigned int y) { while (y) { const unsigned int t = x % y; x = y; y = t; } return x; };
-    while (gcd(P, nt) != 1) ++P;
-    ba.scatter_p = (int)P;
-  }
+  ba.scatter_p = s->knobs.no_scatter ? 0 : (int)scatter_stride((unsigned int)local_tiles, 64);
+  ba.dbg_base1 = s->bin_base1;
   BandArgs bd;
   bd.pool = s->pool.p; bd.blob = s->blob.p; bd.hdr = s->bin_hdr; bd.goff = s->bin_goff;
   bd.A0 = ba.A0; bd.A1 = ba.A1; bd.A5 = ba.A5; bd.slot = ba.slot; bd.offs = sa.offs; bd.packets = sa.packets; bd.ctl = sa.ctl; bd.sorted = sorted;
@@ -1777,16 +1927,12 @@ static int launch_binned(const PtScene* s, KArgs a, const PtRenderParams* p, int
   PT_HIP(hipMemsetAsync(sa.ctl, 0, 64, st));
   const dim3 step_grid((unsigned int)((N + kBlock - 1) / kBlock)), step_block(kBlock);
   const int band_blocks = std::max(1, s->num_cus) * 6;
+  const BinKernels bk = s->has_image ? (s->mats_simple ? bin_kernels<UV_WINNER, MATS_LAMB_LIGHT_SOLID> : bin_kernels<UV_WINNER, MATS_ALL>)
+                                     : (s->mats_simple ? bin_kernels<UV_NONE, MATS_LAMB_LIGHT_SOLID> : bin_kernels<UV_NONE, MATS_ALL>);
   auto step = [&](int gen) -> int {
     ba.gen = gen;
     ba.live_in = live_list[gen & 1]; ba.live_out = live_list[(gen + 1) & 1];
-    if (s->has_image) {
-      if (s->mats_simple) hipLaunchKernelGGL((bin_step_kernel<UV_WINNER, MATS_LAMB_LIGHT_SOLID>), step_grid, step_block, 0, st, ba);
-      else hipLaunchKernelGGL((bin_step_kernel<UV_WINNER, MATS_ALL>), step_grid, step_block, 0, st, ba);
-    } else {
-      if (s->mats_simple) hipLaunchKernelGGL((bin_step_kernel<UV_NONE, MATS_LAMB_LIGHT_SOLID>), step_grid, step_block, 0, st, ba);
-      else hipLaunchKernelGGL((bin_step_kernel<UV_NONE, MATS_ALL>), step_grid, step_block, 0, st, ba);
-    }
+    hipLaunchKernelGGL(bk.step, step_grid, step_block, 0, st, ba);
     PT_HIP(hipGetLastError());
     hipLaunchKernelGGL(bin_count_kernel, dim3((unsigned int)n_blocks), dim3(1024), 0, st, sa);
     hipLaunchKernelGGL(bin_prefix_kernel, dim3(1), dim3(64), 0, st, sa);
@@ -1813,19 +1959,11 @@ static int launch_binned(const PtScene* s, KArgs a, const PtRenderParams* p, int
   if (live != 0 && gen <= max_gen) { // the tail: persistent waves finish what is left (ctl[3] live pixels in the list the last step wrote)
     ba.gen = gen; ba.live_in = live_list[gen & 1]; ba.live_out = live_list[(gen + 1) & 1];
     PT_HIP(hipMemsetAsync(sa.ctl + 5, 0, 4, st));
-    const void* fk = s->has_image ? (s->mats_simple ? (const void*)bin_finish_kernel<UV_WINNER, MATS_LAMB_LIGHT_SOLID> : (const void*)bin_finish_kernel<UV_WINNER, MATS_ALL>)
-                                  : (s->mats_simple ? (const void*)bin_finish_kernel<UV_NONE, MATS_LAMB_LIGHT_SOLID> : (const void*)bin_finish_kernel<UV_NONE, MATS_ALL>);
-    const int per_cu = occupancy_of(s, fk, kBlock, 0);
+    const int per_cu = occupancy_of(s, (const void*)bk.finish, kBlock, 0);
     if (per_cu < 0) return PT_ERR_HIP;
     const unsigned int blocks = (unsigned int)std::min<long long>((long long)std::max(1, per_cu) * std::max(1, s->num_cus), ((long long)live + kBlock - 1) / kBlock * 64);
     const dim3 fgrid(std::max(1u, blocks)), fblock(kBlock);
-    if (s->has_image) {
-      if (s->mats_simple) hipLaunchKernelGGL((bin_finish_kernel<UV_WINNER, MATS_LAMB_LIGHT_SOLID>), fgrid, fblock, 0, st, ba);
-      else hipLaunchKernelGGL((bin_finish_kernel<UV_WINNER, MATS_ALL>), fgrid, fblock, 0, st, ba);
-    } else {
-      if (s->mats_simple) hipLaunchKernelGGL((bin_finish_kernel<UV_NONE, MATS_LAMB_LIGHT_SOLID>), fgrid, fblock, 0, st, ba);
-      else hipLaunchKernelGGL((bin_finish_kernel<UV_NONE, MATS_ALL>), fgrid, fblock, 0, st, ba);
-    }
+    hipLaunchKernelGGL(bk.finish, fgrid, fblock, 0, st, ba);
     PT_HIP(hipGetLastError());
     live = 0;
   }
@@ -1875,9 +2013,8 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
   a.n_tiles = n_tiles_of(p, &a.tiles_x);
   const bool masked = w && w->mask;
   // tiles this shard owns (a masked window: the tiles it renders)
-  const int local_tiles = masked ? w->n_active : (a.n_tiles - p->shard_index + p->shard_count - 1) / p->shard_count;
-  a.keep_state = 0; a.fast_chunk0 = 0;
-  a.mask = masked ? w->mask : nullptr;
+  const int local_tiles = masked ? w->n_active : local_tiles_of(p);
+  if (masked) a.mask = w->mask;
   // pixels no lane owns (edge tiles, padded last tile, depth 0) read as 0 (a window's sums: zeroed by pt_accum_create / _reset)
   if (!w) PT_HIP(hipMemsetAsync(fb, 0, (size_t)pt_framebuffer_floats(p) * sizeof(float), st));
   if (local_tiles <= 0) return PT_OK;
@@ -1891,92 +2028,39 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
     PT_HIP(hipGetLastError());
     return PT_OK;
   }
-  a.coop_prefix = (s->coop_ok && a.fast_ok && !(p->flags & PT_FLAG_NO_COOP)) ? s->coop_prefix : -1;
   // (sample windows run the persistent kernels: both renderers give the reference's image, and only these resume a pixel)
   if (s->binned && !w && !(p->flags & (PT_FLAG_FORCE_STREAM | PT_FLAG_FAST_RNG))) return launch_binned(s, a, p, local_tiles, st);
-  const size_t blob_bytes = (size_t)s->blob_f4 * 16;
-  // a scene with a triangle pool is queried through per-lane loads from the global blob: the scalar-cache resident kernels,
-  // whatever its size (PT_FLAG_FORCE_STREAM: the streaming kernel, which scans every triangle, as the A/B)
-  const bool tri_pool = s->tri_pooled > 0 && !(p->flags & PT_FLAG_FORCE_STREAM);
-  const bool resident = (blob_bytes <= kMaxLdsBlob || (p->flags & PT_FLAG_NO_LDS) || tri_pool) && !(p->flags & PT_FLAG_FORCE_STREAM);
-  const bool lds = resident && !(p->flags & PT_FLAG_NO_LDS) && !tri_pool;
   a.n_local_pixels = local_tiles * PT_TILE_PIXELS;
-  a.fast_chunks = 0; a.samples_total = p->samples; a.fast_stride = 0;
+  // The parity-mode kernel variant: the probe pass and the frame pass run it (the fast mode chooses its frame launch's own, below)
+  const Variant pv = choose_variant(s, p, local_tiles, false, a.n_local_pixels);
+  if (pv.rc) return pv.rc;
+  const bool tri_pool = pv.tri_pool, use_grid = pv.use_grid, coop = pv.coop; // (the same in every pass)
+  a.coop_prefix = pv.coop_prefix;
+  a.samples_total = p->samples;
   long long launch_units = local_tiles; // waves worth of work in the queue (tiles; fast mode: tiles x chunks)
+  if (const char* e = std::getenv("PT_TILE_GROUP")) { const int g = std::atoi(e); if (g == 16 || g == 32) a.tile_group = g; } // (experiment)
   // default: whole tiles for the resident kernels (coherent primary rays), single pixels for the lock-step
   // streaming kernel (a workgroup waits for its slowest lane); either can be forced
   // (the triangle-pool kernels' iterations are long and per-lane: single pixels, like the streaming kernel)
-  a.heavy_pixels = 0; a.heavy_lanes = 64;
-  a.tile_group = 64;
-  if (const char* e = std::getenv("PT_TILE_GROUP")) { const int g = std::atoi(e); if (g == 16 || g == 32) a.tile_group = g; } // (experiment)
-  a.tile_granular = (p->flags & PT_FLAG_TILE_GRANULAR) ? 1 : (p->flags & PT_FLAG_PIXEL_GRANULAR) ? 0 : ((resident && !tri_pool) ? 1 : 0);
-  a.scatter_p = 0; a.scatter_log = 0;
+  a.tile_granular = (p->flags & PT_FLAG_TILE_GRANULAR) ? 1 : (p->flags & PT_FLAG_PIXEL_GRANULAR) ? 0 : ((pv.resident && !tri_pool) ? 1 : 0);
   auto set_scatter = [&]() { // (after a.n_local_pixels is final: fast mode multiplies it by the chunks per pixel)
     if (!(tri_pool && !a.tile_granular && !s->knobs.no_scatter)) return;
-    const unsigned int nt = (unsigned int)a.n_local_pixels >> 6;
     a.scatter_log = s->knobs.scatter_log;
-    const unsigned int per_wave = 64u >> a.scatter_log; // tiles a wave's 64 pixels come from
-    unsigned int P = nt / per_wave > 1 ? nt / per_wave : 1;
-    auto gcd = [](unsigned int x, unsigned int y) { while (y) { const unsigned int t = x % y; x = y; y = t; } return x; };
-    while (gcd(P, nt) != 1) ++P;
-    a.scatter_p = (int)P;
+    a.scatter_p = (int)scatter_stride((unsigned int)a.n_local_pixels >> 6, 64u >> a.scatter_log /* tiles a wave's 64 pixels come from */);
   };
   set_scatter();
-  a.cost = nullptr;
-  a.cost_max = 0;
-  a.tri_cache = nullptr;
-  for (float& f : a.foot) f = 0.0f;
-  a.resume_rng = nullptr; a.resume_spp = 0;
   const bool window = w && !(p->flags & PT_FLAG_FAST_RNG); // a parity-mode sample window: resumes from / keeps the per-pixel state
   if (window) { a.samples = w->done + p->samples; a.resume_rng = w->rng; a.resume_spp = w->done; a.keep_state = 1; }
-  a.prio_onset = 0; a.prio_t1 = a.prio_t2 = a.prio_t3 = 0;
-  a.order = nullptr;
-  const bool mlds = lds && blob_bytes + (size_t)s->mats_f4 * 16 <= kMaxLdsWithMaterials;
-  const size_t shmem = lds ? blob_bytes + (mlds ? (size_t)s->mats_f4 * 16 : 0) : 0;
-  a.n_split = nullptr;
   int n_waves_resident = 1;
-  // Cooperative kernels (a ray's list split over idle lanes; the heaviest tiles rendered G lanes per pixel) cost ~15 % of
-  // the ordinary-mode throughput, and the part of an iteration that cannot be split (camera, shading, ray context:
-  // ~4 500 cycles of a lone wave's 13 200 on the Cornell-style scene) bounds what they can win: there G = 8 shortens a
-  // pixel's chain by 1.4x for 4.6x the lane time, so they pay only where the scan of the list dominates an iteration
-  // (496-hittable scene, shard 0/8: 522 -> 229 ms).
-  // Sphere runs with a culling grid: the ordinary resident kernels walk it (a ray then tests tens of spheres instead of
-  // hundreds: 496-hittable scene 1 660 -> 3 240 Msamples/s at 1080p), the cooperative kernels scan the lists with lane
-  // groups.  With the grid as first tuned (margin 1.5 r) a lone wave's walk was no shorter than a group's list scan and small
-  // frames / shards kept the cooperative kernels; since the retuning (margin 0.5 r, walk after the big spheres) the walk wins
-  // everywhere (tools/grid_min_tiles.py: 400x225x256 spp 99 ms against 108; shard 0/8 of the 1080p frame at 256 spp 80
-  // against 102; shard 0/8 of 4K at 128 spp 61 against 102).  PT_GRID_MIN_TILES restores a threshold.
-  const bool use_grid = s->grid_spheres > 0 && resident /* the streaming kernel scans the full lists */ && local_tiles >= s->knobs.grid_min_tiles && !(p->flags & PT_FLAG_FORCE_COOP);
-  const bool coop = lds && a.coop_prefix >= 0 && !use_grid && (s->traversal_cost >= kCoopMinTraversal || (p->flags & PT_FLAG_FORCE_COOP));
-  // Which sphere-grid walk (pt_device.hpp: sphere_scan, GRID = 1 / 2): the pair queue where walks diverge or the launch is bound by its
-  // chains — whole tiles per wave or at least 16 lanes (the rule of `launch` below, evaluated for the kernels' four workgroups per CU) — and
-  // not on frames that are both dense (>= 4 M pixels: a tile's rays share their cells) and throughput-bound (>= 6 pixels per resident lane).
-  // The rule is evaluated for the resident lanes the GRID = 2 kernels really have (their occupancy is queried like `launch` does: 31 KB LDS
-  // image + 4 KB of per-wave queues and slots usually allow four workgroups per CU) — round 4 assumed 16 waves per CU here and the cap of
-  // `launch` from the measured occupancy, and the two could disagree.  The queued walk's STATIC 4 KB of LDS (sphere_queue,
-  // sphere_slots) ride on top of the dynamic blob image: where the sum exceeds what a workgroup may have, the walk stays in place.
-  constexpr size_t kQueuedWalkStaticLds = (size_t)PT_MAX_WAVES_PER_BLOCK * (PT_SQ_CAP * 4 + 64 * 8);
-  bool queued_walk = false;
-  auto decide_walk = [&](int per_cu_queued, int waves_per_block) {
-    if (!use_grid) return;
-    const bool fits = shmem + kQueuedWalkStaticLds <= s->lds_per_block && per_cu_queued >= 1;
-    const double lanes = (double)std::max(1, s->num_cus) * std::max(1, per_cu_queued) * waves_per_block * 64.0;
-    const double rho = (double)a.n_local_pixels / lanes;
-    const bool few_lanes = rho < 0.875 && !(p->flags & (PT_FLAG_TILE_GRANULAR | PT_FLAG_PIXEL_GRANULAR | PT_FLAG_FAST_RNG)) && s->knobs.lanes_cap >= 0; // 16 rho rounds below 16
-    const bool dense_and_busy = (double)p->width * p->height >= 4.0e6 && rho >= 6.0;
-    queued_walk = fits && (s->knobs.grid_walk == 2 || (s->knobs.grid_walk == 0 && !few_lanes && !dense_and_busy && !(s->knobs.lanes_cap > 0 && s->knobs.lanes_cap < 16)));
-  };
   // (small frames through the grid kernels: see `launch`; PT_FLAG_TILE_GRANULAR / PT_FLAG_PIXEL_GRANULAR and the fast mode keep what they ask for)
   // (only the kernels that walk a sphere grid: the headline family's iteration — slab pass, wave-uniform — does not get shorter with fewer
   // lanes: its shard 0/8 took 127 ms that way against 40)
   const bool share_small = use_grid && s->knobs.lanes_cap >= 0 && !(p->flags & (PT_FLAG_TILE_GRANULAR | PT_FLAG_PIXEL_GRANULAR | PT_FLAG_FAST_RNG));
-  // (set by launch_uv for the headline family — no sphere grid, no cooperative phase: see `launch`)
-  bool chain_bound_family = false;
-  bool launched_queued_walk = false; // the kernel variant actually launched walks sphere grids through the pair queue (pt_debug_last_launch)
   // Persistent grid: no more workgroups than the chip holds at once; lanes pull pixels from the queue.
-  auto launch = [&](auto kernel, int block_threads = kBlock) -> int {
+  auto launch = [&](const Variant& v, int block_threads = kBlock) -> int {
+    const size_t shmem = v.shmem;
     const int waves_per_block = block_threads / 64;
-    int per_cu = occupancy_of(s, (const void*)kernel, block_threads, shmem);
+    int per_cu = occupancy_of(s, (const void*)v.kernel, block_threads, shmem);
     if (per_cu < 0) return PT_ERR_HIP;
     // (a kernel variant that does not fit a CU at all — its static + dynamic LDS beyond the device's limit — must not be launched and hoped for)
     if (per_cu < 1) return fail(PT_ERR_TOO_LARGE, "pt_render: this scene's kernel variant does not fit a compute unit (LDS " + std::to_string(shmem) + " B dynamic + static)");
@@ -1988,13 +2072,13 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
     // (Grid and triangle-pool kernels: their own occupancy is the best at every shard count — same file.)
     // (Round 5, with the chain priorities of render_kernel: shard 0 of 3 — 1.3 tiles per slot — 61.2 ms at four workgroups per CU, 54.4 / 57.1 at
     // six / eight; shard 0 of 4 — 1.0 — 45.2 / 47.3 / 48.7: the bound moved from 1.6 to 1.15; profiles/r05_ab_chain_priority.txt.)
-    if (chain_bound_family && !s->knobs.blocks_per_cu && a.n_split == 0 && a.scatter_p == 0 &&
+    if (v.chain_bound && !s->knobs.blocks_per_cu && a.n_split == 0 && a.scatter_p == 0 &&
         (double)launch_units < 1.15 * (double)per_cu * waves_per_block * std::max(1, s->num_cus))
       per_cu = std::min(per_cu, 4);
     if (s->knobs.blocks_per_cu) per_cu = std::min(per_cu, s->knobs.blocks_per_cu); // tuning knob
     // longest remaining chain first (render_kernel): the headline family's frame launches in parity mode, from the middle of the queue on
     a.prio_onset = 0; a.prio_t1 = a.prio_t2 = a.prio_t3 = 0;
-    if (chain_bound_family && !a.cost && !a.fast_chunks && a.tile_granular && !s->knobs.no_chain_prio && p->samples >= 16) {
+    if (v.chain_bound && !a.cost && !a.fast_chunks && a.tile_granular && !s->knobs.no_chain_prio && p->samples >= 16) {
       a.prio_onset = a.n_local_pixels / 2;
       a.prio_t3 = p->samples / 2; a.prio_t2 = p->samples / 4; a.prio_t1 = p->samples / 8;
     }
@@ -2050,7 +2134,7 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
       a.lanes_cap = (int)std::min<long long>(64, std::max<long long>(1, ((long long)a.n_local_pixels + waves - 1) / waves));
     }
     n_waves_resident = (int)std::min<long long>(wanted, resident_blocks) * waves_per_block;
-    if (!a.cost) { s->last_launch[0] = (int)std::min<long long>(wanted, resident_blocks); s->last_launch[1] = a.lanes_cap; s->last_launch[2] = a.heavy_pixels; s->last_launch[3] = launched_queued_walk ? 1 : 0; }
+    if (!a.cost) { s->last_launch[0] = (int)std::min<long long>(wanted, resident_blocks); s->last_launch[1] = a.lanes_cap; s->last_launch[2] = a.heavy_pixels; s->last_launch[3] = v.queued_walk ? 1 : 0; }
     dim3 grid((unsigned int)std::min<long long>(wanted, resident_blocks)), block((unsigned int)block_threads);
     // The camera rays' candidate cache (pt_device.hpp: TriPrimCtx): triangle-pool kernels, a pinhole camera (the rays of a pixel share
     // their origin), pixel coordinates that fit 16 bits.  One 1 KB line per lane of the launch; every line starts out belonging to no pixel.
@@ -2085,73 +2169,10 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
     s->next_queue++; // (only once nothing above can fail any more)
     a.queue = s->queues.p + 2 * slot; // [0] ordinary queue, [1] wide-phase queue
     PT_HIP(hipMemsetAsync(a.queue, 0, 2 * sizeof(unsigned int), st));
-    hipLaunchKernelGGL(kernel, grid, block, shmem, st, a);
+    hipLaunchKernelGGL(v.kernel, grid, block, shmem, st, a);
     PT_HIP(hipGetLastError());
     PT_HIP(hipEventRecord(s->ring_done[slot], st));
     return PT_OK;
-  };
-  auto launch_uv = [&](auto uv) -> int {
-    constexpr int UV = decltype(uv)::value;
-    if (s->has_badouel) { // parity-completeness path: scalar-cache or streaming kernel with the Badouel loop compiled in
-      if (a.fast_chunks) return fail(PT_ERR_INVALID_ARG, "PT_FLAG_FAST_RNG is not offered for scenes with Badouel-strategy triangles");
-      if (!resident) return launch(render_kernel_stream<UV, false, true>);
-      return launch(render_kernel<UV, false, false, false, false, false, true>);
-    }
-    if (a.fast_chunks) { // opt-in decorrelated mode: its own instantiations (no cooperative kernels: a chunk is short)
-      if (tri_pool) return launch(tripool_kernel(UV, true));
-      if (!resident) return launch(render_kernel_stream<UV, true>);
-      if (!lds) return launch(render_kernel<UV, false, false, false, false, true>);
-      return mlds ? launch(render_kernel<UV, true, true, false, false, true>) : launch(render_kernel<UV, true, false, false, false, true>);
-    }
-    if (tri_pool) return launch(tripool_kernel(UV, false));
-    if (!resident) return launch(render_kernel_stream<UV>);
-    if constexpr (UV == UV_NONE) { // no image texture and no sphere grid (the headline scene): kernels without the grid walk
-      if (s->grid_spheres == 0 && !coop) {
-        chain_bound_family = true;
-        if (s->mats_simple) { // lambertian + lightsource over solid textures: kernels without the other materials' code
-          if (s->rectbox_only) { // ... and every hittable a rect or a box (the headline scene): resolve_hit without the other kinds
-            constexpr int MSR = MATS_LAMB_LIGHT_SOLID | MATS_RECTBOX_ONLY;
-            if (!lds) return launch(render_kernel<UV, false, false, false, false, false, false, false, false, MSR>);
-            if (mlds && shmem <= kMaxLdsColdScene && !s->knobs.no_cold_lds) return launch(render_kernel<UV, true, true, false, true, false, false, false, false, MSR>);
-            return mlds ? launch(render_kernel<UV, true, true, false, false, false, false, false, false, MSR>)
-                        : launch(render_kernel<UV, true, false, false, false, false, false, false, false, MSR>);
-          }
-          constexpr int MS = MATS_LAMB_LIGHT_SOLID;
-          if (!lds) return launch(render_kernel<UV, false, false, false, false, false, false, false, false, MS>);
-          if (mlds && shmem <= kMaxLdsColdScene && !s->knobs.no_cold_lds) return launch(render_kernel<UV, true, true, false, true, false, false, false, false, MS>);
-          return mlds ? launch(render_kernel<UV, true, true, false, false, false, false, false, false, MS>)
-                      : launch(render_kernel<UV, true, false, false, false, false, false, false, false, MS>);
-        }
-        if (!lds) return launch(render_kernel<UV, false, false, false, false, false, false, false>);
-        if (mlds && shmem <= kMaxLdsColdScene && !s->knobs.no_cold_lds) return launch(render_kernel<UV, true, true, false, true, false, false, false>);
-        return mlds ? launch(render_kernel<UV, true, true, false, false, false, false, false>)
-                    : launch(render_kernel<UV, true, false, false, false, false, false, false>);
-      }
-    }
-    if (!lds) return launch(render_kernel<UV, false, false, false>);
-    if (coop) return mlds ? launch(render_kernel<UV, true, true, true>) : launch(render_kernel<UV, true, false, true>);
-    if constexpr (UV == UV_NONE) { // small scene: cold lane state in LDS (7 workgroups x (scene + 8 KB) per CU)
-      if (mlds && shmem <= kMaxLdsColdScene && !s->knobs.no_cold_lds) return launch(render_kernel<UV, true, true, false, true>);
-    }
-    if (use_grid) { // which walk: decided with the queued-walk kernel's own occupancy
-      int per_cu2 = 0; // (stays 0 where the queued walk's LDS does not fit: never asked)
-      const void* k2 = mlds ? (const void*)render_kernel<UV, true, true, false, false, false, false, 2> : (const void*)render_kernel<UV, true, false, false, false, false, false, 2>;
-      if (shmem + kQueuedWalkStaticLds <= s->lds_per_block) {
-        per_cu2 = occupancy_of(s, k2, kBlock, shmem);
-        if (per_cu2 < 0) return PT_ERR_HIP;
-      }
-      decide_walk(s->knobs.blocks_per_cu ? std::min(per_cu2, s->knobs.blocks_per_cu) : per_cu2, kWavesPerBlock);
-    }
-    if (use_grid && queued_walk) { // the sphere-grid walk through the pair queue (pt_device.hpp: sphere_scan says where it pays)
-      launched_queued_walk = true;
-      return mlds ? launch(render_kernel<UV, true, true, false, false, false, false, 2>) : launch(render_kernel<UV, true, false, false, false, false, false, 2>);
-    }
-    return mlds ? launch(render_kernel<UV, true, true, false>) : launch(render_kernel<UV, true, false, false>);
-  };
-  auto launch_variant = [&]() -> int {
-    if (s->track_uv) return launch_uv(std::integral_constant<int, UV_TRACKED>{});
-    if (s->has_image) return launch_uv(std::integral_constant<int, UV_WINNER>{});
-    return launch_uv(std::integral_constant<int, UV_NONE>{});
   };
   // Heaviest-first tile order from a probe pass (see lpt_order_kernel); pointless for short renders.
   int probe_spp = std::min(4, p->samples / 16);
@@ -2165,6 +2186,7 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
   // (the triangle-pool kernels deal every wave a stratified sample of the frame's tiles — lane_acquire, scatter_p — which balances the
   // waves without knowing the costs: the probe only costs there, 1080p x 32 spp 3.12 -> 2.95 s without it; PT_LPT_SCATTER=1 keeps it)
   const bool probe_pays = !(a.scatter_p > 0) || s->knobs.lpt_with_scatter;
+  bool probed = false; // the probe pass ran
   if (masked) {
     a.order = w->active; // (n_split stays NULL: no wide phase)
   } else if (probe_spp >= 1 && local_tiles >= 64 && !(p->flags & PT_FLAG_NO_LPT) && probe_pays) {
@@ -2184,8 +2206,9 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
     if (window && resume) { a.samples = w->done + probe_spp; a.resume_rng = w->rng; a.resume_spp = w->done; }
     int* const order_out = w ? w->order : s->ws_order.p;
     int* const nsplit_out = w ? w->nsplit : s->ws_nsplit.p;
-    int rc = launch_variant();
+    int rc = launch(pv);
     if (rc) return rc;
+    probed = true;
     // rough per-iteration instruction counts: traversal (splittable) vs shading + camera + cooperative overhead (not)
     const int forced_logG = s->knobs.wide_logG; // 0: the model picks the group size of the wide phase
     const unsigned int* ranked = s->ws_cost.p;
@@ -2222,7 +2245,7 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
   if (p->flags & PT_FLAG_FAST_RNG) {
     // OPT-IN decorrelated mode (include/pt_render.h): (tile, chunk) work units, per-chunk sums into a workspace, then
     // one ordered reduction.  No wide phase (a chunk is short by construction); the tile order of the probe still applies.
-    const int chunks = (p->samples + PT_FAST_CHUNK_SPP - 1) / PT_FAST_CHUNK_SPP;
+    const int chunks = fast_chunks_of(p->samples);
     if (chunks > 127 || local_tiles >= (1 << 18))
       return fail(PT_ERR_TOO_LARGE, "PT_FLAG_FAST_RNG supports up to 8128 samples per pixel and 2^24 pixels per shard");
     const size_t plane = (size_t)pt_framebuffer_floats(p), need = plane * (size_t)chunks;
@@ -2231,7 +2254,6 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
     a.fast_chunks = chunks;
     a.fast_chunk0 = w ? w->done / PT_FAST_CHUNK_SPP : 0; // (a window starts on a chunk boundary: pt_render_accumulate)
     a.samples = std::min(p->samples, (int)PT_FAST_CHUNK_SPP);
-    a.samples_total = p->samples;
     a.fast_stride = (long long)plane;
     a.fb = s->ws_partial.p;
     a.n_local_pixels = local_tiles * PT_TILE_PIXELS * chunks;
@@ -2239,7 +2261,11 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
     a.n_split = nullptr;
     launch_units = (long long)local_tiles * chunks;
     s->last_had_wide_phase = false;
-    int rc = launch_variant();
+    Variant fv = choose_variant(s, p, local_tiles, true, a.n_local_pixels);
+    if (fv.rc) return fv.rc;
+    // (sticky: what the probe pass of this call ran stays set for its frame launch — the four-workgroup rule of `launch`, pt_debug_last_launch)
+    if (probed) { fv.chain_bound |= pv.chain_bound; fv.queued_walk |= pv.queued_walk; }
+    int rc = launch(fv);
     if (rc) return rc;
     if (w) { // a window: its chunks onto the accumulator's running sums, in chunk order, undivided
       hipLaunchKernelGGL(fast_accum_kernel, dim3((unsigned int)((plane + 255) / 256)), dim3(256), 0, st, s->ws_partial.p, fb, (long long)plane,
@@ -2253,10 +2279,7 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
     return PT_OK;
   }
   s->last_had_wide_phase = a.n_split != nullptr;
-  int rc = launch_variant();
-  if (rc) return rc;
-  PT_HIP(hipGetLastError());
-  return PT_OK;
+  return launch(pv);
 }
 
 int pt_scene_reserve(const PtScene* scene, const PtRenderParams* p) {
@@ -2267,12 +2290,10 @@ int pt_scene_reserve(const PtScene* scene, const PtRenderParams* p) {
   PT_HIP(hipGetDevice(&cur));
   if (cur != scene->device) return fail(PT_ERR_INVALID_ARG, "pt_scene_reserve: the scene lives on another device");
   std::lock_guard<std::mutex> lock(scene->sched);
-  int tiles_x;
-  const int n_tiles = n_tiles_of(p, &tiles_x);
-  const int local_tiles = (n_tiles - p->shard_index + p->shard_count - 1) / p->shard_count;
+  const int local_tiles = local_tiles_of(p);
   if (local_tiles > 0 && (rc = reserve_tiles(scene, local_tiles))) return rc;
   if (p->flags & PT_FLAG_FAST_RNG) {
-    const int chunks = (p->samples + PT_FAST_CHUNK_SPP - 1) / PT_FAST_CHUNK_SPP;
+    const int chunks = fast_chunks_of(p->samples);
     if ((rc = reserve_partial(scene, (size_t)pt_framebuffer_floats(p) * (size_t)chunks))) return rc;
   }
   return PT_OK;
@@ -2456,8 +2477,7 @@ int check_header(const AccumHeader& h, const PtAccum* acc, int64_t bytes, const 
 // the triangle-pool kernels' candidate cache for every lane they can launch (launch_render would otherwise grow it on a window)
 int reserve_tricache(const PtScene* s, uint32_t flags) {
   if (s->tri_pooled <= 0 || s->knobs.no_tri_cache || (flags & PT_FLAG_FORCE_STREAM)) return PT_OK;
-  const int uv = s->track_uv ? UV_TRACKED : s->has_image ? UV_WINNER : UV_NONE; // (launch_render: launch_variant)
-  int per_cu = occupancy_of(s, (const void*)tripool_kernel(uv, (flags & PT_FLAG_FAST_RNG) != 0), kBlock, 0);
+  int per_cu = occupancy_of(s, (const void*)tripool_kernel(uv_of(s), (flags & PT_FLAG_FAST_RNG) != 0), kBlock, 0);
   if (per_cu < 0) return PT_ERR_HIP;
   if (s->knobs.blocks_per_cu) per_cu = std::min(per_cu, s->knobs.blocks_per_cu);
   return grow_tricache(s, (size_t)std::max(1, per_cu) * (size_t)std::max(1, s->num_cus) * kBlock);
@@ -2517,8 +2537,7 @@ int accum_create(const PtScene* scene, const PtRenderParams* p, PtAccum** out, b
   acc->scene = scene;
   acc->p = q;
   acc->adaptive = adaptive;
-  const int n_tiles = n_tiles_of(&q, nullptr);
-  acc->local_tiles = std::max(0, (n_tiles - q.shard_index + q.shard_count - 1) / q.shard_count);
+  acc->local_tiles = std::max(0, local_tiles_of(&q));
   acc->fb_floats = (size_t)pt_framebuffer_floats(&q);
   acc->rng_words = (size_t)pt_shard_tiles(&q) * PT_TILE_PIXELS;
   auto bad = [&](hipError_t e, const char* what) { return fail(PT_ERR_HIP, std::string(who) + ": " + what + ": " + hipGetErrorString(e)); };
@@ -2842,14 +2861,8 @@ int pt_debug_bounce(const PtScene* scene, const PtBounceIn* in, PtBounceOut* out
   PT_HIP(hipMemcpy(din.p, in, (size_t)n * sizeof(PtBounceIn), hipMemcpyHostToDevice));
   dim3 block(64), grid((n + 63) / 64);
   const bool qw = scene->knobs.grid_walk == 2; // PtTuning.grid_walk = 2: the probe walks sphere grids through the pair queue, like the kernels it stands for
-  if (scene->track_uv && qw)
-    hipLaunchKernelGGL((bounce_kernel<true, 2>), grid, block, 0, nullptr, scene->blob.p, scene->n_runs, scene->mats, scene->pool.p, scene->atlas.p, din.p, dout.p, n, scene->fast_ok ? 1 : 0);
-  else if (scene->track_uv)
-    hipLaunchKernelGGL((bounce_kernel<true, 1>), grid, block, 0, nullptr, scene->blob.p, scene->n_runs, scene->mats, scene->pool.p, scene->atlas.p, din.p, dout.p, n, scene->fast_ok ? 1 : 0);
-  else if (qw)
-    hipLaunchKernelGGL((bounce_kernel<false, 2>), grid, block, 0, nullptr, scene->blob.p, scene->n_runs, scene->mats, scene->pool.p, scene->atlas.p, din.p, dout.p, n, scene->fast_ok ? 1 : 0);
-  else
-    hipLaunchKernelGGL((bounce_kernel<false, 1>), grid, block, 0, nullptr, scene->blob.p, scene->n_runs, scene->mats, scene->pool.p, scene->atlas.p, din.p, dout.p, n, scene->fast_ok ? 1 : 0);
+  const auto kernel = scene->track_uv ? (qw ? bounce_kernel<true, 2> : bounce_kernel<true, 1>) : (qw ? bounce_kernel<false, 2> : bounce_kernel<false, 1>);
+  hipLaunchKernelGGL(kernel, grid, block, 0, nullptr, scene->blob.p, scene->n_runs, scene->mats, scene->pool.p, scene->atlas.p, din.p, dout.p, n, scene->fast_ok ? 1 : 0);
   PT_HIP(hipGetLastError());
   PT_HIP(hipMemcpy(out, dout.p, (size_t)n * sizeof(PtBounceOut), hipMemcpyDeviceToHost));
   return PT_OK;
