@@ -244,8 +244,15 @@ __device__ __forceinline__ RayCtx make_ctx(const Ray& r, bool scene_fast_ok) {
   c.a = dot(r.d, r.d);
   const float lo = 9.094947017729282e-13f, hi = 1.099511627776e12f, ohi = 1.152921504606846976e18f; // 2^-40 2^40 2^60
   float ax = __builtin_fabsf(r.d.x), ay = __builtin_fabsf(r.d.y), az = __builtin_fabsf(r.d.z);
-  c.reg = scene_fast_ok && ax >= lo && ax <= hi && ay >= lo && ay <= hi && az >= lo && az <= hi &&
-          __builtin_fabsf(r.o.x) <= ohi && __builtin_fabsf(r.o.y) <= ohi && __builtin_fabsf(r.o.z) <= ohi;
+  // every |d_c| in [lo, hi] and every |o_c| <= ohi, as the smallest and the largest of each triple (v_min3 / v_max3 and three comparisons; the
+  // nine comparisons of the components took nine v_cmp and eight s_or).  v_min / v_max DROP a NaN operand, so a NaN component would go
+  // unnoticed beside two regular ones; the fourth comparison is "ordered" on two values that are NaN exactly when a component is:
+  // d.d = c.a (squares and sums of non-NaN values are never NaN — an infinite one gives +inf) and o.x + o.y + o.z (NaN for a NaN component;
+  // also for infinities of both signs, whose ray max|o_c| <= ohi rejects anyway).  An infinite component fails max <= hi / ohi as before.
+  const float dmin = __builtin_fminf(__builtin_fminf(ax, ay), az), dmax = __builtin_fmaxf(__builtin_fmaxf(ax, ay), az);
+  const float omax = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(r.o.x), __builtin_fabsf(r.o.y)), __builtin_fabsf(r.o.z));
+  const float osum = (r.o.x + r.o.y) + r.o.z;
+  c.reg = scene_fast_ok && dmin >= lo && dmax <= hi && omax <= ohi && !__builtin_isunordered(c.a, osum);
   c.yx = rcp_rn_guarded(r.d.x); // only used when the ray is regular
   c.yy = rcp_rn_guarded(r.d.y);
   c.yz = rcp_rn_guarded(r.d.z);
@@ -1929,6 +1936,58 @@ __device__ __forceinline__ bool tri_pool_scan(glb_f4p pool, cst_f4p cblob, int h
   return true;
 }
 
+// A run of rects or boxes in the kernels of scenes that hold nothing else (RECTBOX), as ONE guarded loop per alternative in a row —
+// rects, boxes of a regular wave, boxes by plain division — with the trip counts of the alternatives not taken set to 0, instead of
+// hit_records' if / else chain.  The arithmetic per record is hit_records' own.  Why: every alternative updates (closest, hit), and the
+// structured form of an if / else that writes a value on both sides merges the sides through a register that is UNDEFINED on one of
+// them; a value with such a definition cannot share its register with the incoming one, so the headline kernel kept (closest, hit) in
+// three register pairs and copied them at every exit of every loop of the traversal (24 v_mov at the slab pool's exit alone).  A guarded
+// loop merges only "unchanged" with "updated": one pair throughout.  (The counts go through an empty asm so that the optimiser cannot
+// work out that at most one of them is non-zero and rebuild the chain.)
+template <typename P>
+__device__ __forceinline__ void hit_records_rectbox(P recs, int kind, int n, int goff, const RayCtx& c, bool fast, HitState& h) {
+  int n_rect = kind == DK_RECT ? n : 0, n_fast = (kind != DK_RECT && fast) ? n : 0, n_plain = (kind != DK_RECT && !fast) ? n : 0;
+#ifdef __HIP_DEVICE_COMPILE__
+  asm volatile("" : "+s"(n_rect), "+s"(n_fast), "+s"(n_plain));
+#endif
+  int off = 0;
+  for (int i = 0; i < n_rect; ++i, off += SZ_RECT) {
+    f4 R0 = recs[off], R1 = recs[off + 1];
+    float t, ca, cb;
+    const bool acc = rect_any(fast, as_i(R1.z), R0.x, R0.y, R0.z, R0.w, R1.x, c, h.closest, t, ca, cb);
+    if (acc) {
+      h.closest = t;
+      h.hit = hit_pack(DK_RECT, 0, goff + off);
+    }
+  }
+  off = 0;
+#ifndef PT_NO_CMPX
+  const unsigned long long exec_all = __builtin_amdgcn_ballot_w64(true); // EXEC as it is around the scan
+  for (int i = 0; i < n_fast; ++i, off += SZ_BOX) {
+    int hit_base = hit_pack(DK_BOX, 0, goff + off);
+    asm volatile("" : "+v"(hit_base)); // in a VGPR: the side's v_or takes the side bits as its literal
+    box_cmpx(recs[off], recs[off + 1], c, exec_all, hit_base, h.closest, h.hit);
+  }
+#else
+  for (int i = 0; i < n_fast; ++i, off += SZ_BOX) {
+    float t, bu = 0.0f, bv = 0.0f;
+    int side = 0;
+    const bool acc = box_fast<false>(recs[off], recs[off + 1], c, h.closest, t, side, bu, bv);
+    h.closest = acc ? t : h.closest;
+    h.hit = acc ? hit_pack(DK_BOX, side, goff + off) : h.hit;
+  }
+#endif
+  off = 0;
+  for (int i = 0; i < n_plain; ++i, off += SZ_BOX) {
+    float t, bu = 0.0f, bv = 0.0f;
+    int side = 0;
+    if (box_plain<false>(recs[off], recs[off + 1], c, PT_TMIN, h.closest, t, side, bu, bv)) {
+      h.closest = t;
+      h.hit = hit_pack(DK_BOX, side, goff + off);
+    }
+  }
+}
+
 // RECTBOX: the scene holds rects and boxes only (MATS_RECTBOX_ONLY kernels): the sphere / triangle / medium loops are not compiled in —
 // less code, and nothing of theirs (the medium's sqrt(d.d), say) can be hoisted into the per-iteration prologue of a kernel that never runs it.
 template <bool IMG, int TRIP = 1, int TTRIP = TRIP, bool WHOLE = true, bool BADOUEL = false, int GRID = 1, bool TRIPOOL = false, bool RECTBOX = false, bool DEFER = false, typename P>
@@ -2160,10 +2219,25 @@ __device__ __forceinline__ void hit_world_range(P blob, cst_f4p cblob, int ri0, 
 #endif
     f4 runf = cblob[ri];
     const int off = as_i(runf.y), kind = as_i(runf.x);
-    if (kind & DK_ABSORBED) continue; // a sphere run that an earlier run's lists have tested already (pt_flatten.hpp "absorbed sphere runs")
+    if (!RECTBOX && (kind & DK_ABSORBED)) continue; // a sphere run that an earlier run's lists have tested already (pt_flatten.hpp "absorbed sphere runs")
 #ifdef PT_ABLATE_TAIL /* measurement-only build (a WRONG image): what would the runs behind the first cost if they were free? */
     if (ri > 0) continue;
 #endif
+    if constexpr (RECTBOX) {
+      // every run is a rect or a box run and carries the pool's aux record; the pool and the run's own scan one after the other, each
+      // under its own guard (hit_records_rectbox says why), the scan with no records where the pool has covered the run
+      static_assert(!IMG, "scenes of rects and boxes only have no image texture that tracks u, v");
+      const f4 aux = cblob[off - 1]; // (largest |coordinate|, span, pool offset, entries)
+      int span = fast ? as_i(aux.y) : 0;
+#ifdef __HIP_DEVICE_COMPILE__
+      asm volatile("" : "+s"(span));
+#endif
+      if (span != 0) { // head of a slab pool: the pool covers this run and the next span - 1
+        slab_pool(blob, cblob, as_i(aux.z), as_i(aux.w), aux.x, c, h);
+        ri += span - 1;
+      }
+      hit_records_rectbox(blob + off, kind, span != 0 ? 0 : as_i(runf.z), off, c, fast, h);
+    } else {
     if constexpr (!IMG) {
       if (fast && (kind == DK_RECT || kind == DK_BOX)) { // head of a slab pool: the pool covers this run and the next span - 1
         const f4 aux = cblob[off - 1];                   // (largest |coordinate|, span, pool offset, entries)
@@ -2176,6 +2250,7 @@ __device__ __forceinline__ void hit_world_range(P blob, cst_f4p cblob, int ri0, 
     }
     // (four triangles per trip in the grid kernels — 96 VGPRs — measured: nothing, 347-351 ms either way on the 496-hittable scene)
     hit_records<IMG, 1, 1, true, BADOUEL, GRID, TRIPOOL, RECTBOX, DEFER>(blob + off, cblob, kind, as_i(runf.z), off, c, fast, rng, h, (glb_f4p)pool, dfr, pc);
+    }
   }
 }
 template <bool IMG, bool BADOUEL = false, int GRID = 1, bool TRIPOOL = false, bool RECTBOX = false, typename P>
@@ -2397,10 +2472,14 @@ __device__ __forceinline__ Rec resolve_hit(P blob, int hit, const Ray& r, float 
   const int kind = hit_kind(hit);
   f4 R0 = blob[off], R1 = blob[off + 1];
   if constexpr (RECTBOX) {
-    int axis;
-    if (kind == DK_RECT) { axis = as_i(R1.z); rec.mat = as_i(R1.y); rec.hittable = as_i(R1.w); }
-    else { axis = hit_side(hit) >> 1; rec.mat = as_i(R0.w); rec.hittable = as_i(R1.w); }
-    V3 n = axis == 0 ? mk(0, 0, 1) : axis == 1 ? mk(0, 1, 0) : mk(1, 0, 0);
+    // the plane's axis, the material and the three constants of the normal by selects on the kind and the side bits: as branches, a wave
+    // with rects and all box sides among its hits switched EXEC about twenty times for them.  (The products with the normal's zeros stay:
+    // dot(d, n) is the reference's, NaN for an infinite d included.)
+    const bool is_rect = kind == DK_RECT;
+    const int axis = is_rect ? as_i(R1.z) : hit_side(hit) >> 1;
+    rec.mat = as_i(is_rect ? R1.y : R0.w);
+    rec.hittable = as_i(R1.w);
+    const V3 n = mk(axis == 0 || axis == 1 ? 0.0f : 1.0f, axis == 1 ? 1.0f : 0.0f, axis == 0 ? 1.0f : 0.0f);
     set_face_normal(rec, r, n);
     return rec;
   }

@@ -470,16 +470,22 @@ struct HitUv {
 };
 
 // emitted / scatter / sky for the nearest hit (render.hpp:60-88) and the sample bookkeeping (:100).
-template <int UV, bool FAST = false, int MATS = MATS_ALL, typename Lane, typename PB, typename PM>
+// SKY_FIRST (the headline family: kernels without a grid walk, a cooperative phase or a pool): the sky's colour is computed ahead of the hit
+// branch, for every lane.  Everything that reads the ray and the attenuation this iteration came in with is then computed BEFORE any
+// branch writes the next ones, so the branches write the lane state in place, under their own EXEC mask (some lane of 64 nearly always
+// misses everything, so a wave walks through the sky's code anyway; lanes with a hit drop the value) — computed inside the miss branch,
+// behind the hit branch in program order, it kept the old ray and attenuation alive across the hit branch and the whole lane state was
+// built in a second register set and moved back at the loop's back-edge (45 v_mov per iteration).  The price: where NO lane of a wave
+// misses — a closed scene — the sky's code ran for nothing: ~17 issue slots of an iteration's ~900 when every live ray is regular, ~30 on
+// the general path.  The other kernel families keep the sky inside the miss branch: their iterations are several
+// times as long, and the cooperative kernels and irregular waves would pay the general path.
+template <int UV, bool FAST = false, int MATS = MATS_ALL, bool SKY_FIRST = false, typename Lane, typename PB, typename PM>
 __device__ __forceinline__ void lane_shade(Lane& L, const KArgs& a, const HitState& h, PB recs, PM mats, bool regular = false) {
   if (!L.live) return;
   if (a.cost) L.cold.count_ray(); // cost-probe pass (wave-uniform)
   V3 out = mk(0.0f, 0.0f, 0.0f);
-  bool cont;
-  if (h.hit < 0) {
-    out = sky_color(L.ray, L.att, regular);
-    cont = false;
-  } else {
+  bool cont = false;
+  auto hit_branch = [&]() {
     Rec rec = resolve_hit<(MATS & MATS_RECTBOX_ONLY) != 0>(recs, h.hit, L.ray, h.closest); // per-lane gather of the one record that was hit
     // UV_TRACKED kernels carried u,v through the scan (stale values included); UV_WINNER derives them from the final hit
     // when an image texture asks; UV_NONE: the scene has no image texture, nothing reads them
@@ -489,6 +495,13 @@ __device__ __forceinline__ void lane_shade(Lane& L, const KArgs& a, const HitSta
       out = mk(0.0f, 0.0f, 0.0f);
       cont = false;
     }
+  };
+  if constexpr (SKY_FIRST) {
+    out = sky_color(L.ray, L.att, regular);
+    if (h.hit >= 0) hit_branch();
+  } else {
+    if (h.hit < 0) out = sky_color(L.ray, L.att, regular);
+    else hit_branch();
   }
   if (!cont) {
     L.need_new = true;
@@ -534,6 +547,7 @@ template <int UV, bool LDS, bool MLDS, bool COOP, bool CL = false, bool FAST = f
 __global__ __launch_bounds__(BLOCK, TRIPOOL ? PT_MIN_WAVES_TRIPOOL : CL ? PT_MIN_WAVES_CL : COOP ? (UV ? PT_MIN_WAVES_COOP_IMG : PT_MIN_WAVES_COOP) : (UV ? PT_MIN_WAVES_IMG : PT_MIN_WAVES))
 void render_kernel(KArgs a) {
   constexpr bool IMG = UV == UV_TRACKED;
+  constexpr bool kSkyFirst = GRID == 0 && !COOP && !FAST && !TRIPOOL; // the headline family (lane_shade)
   typedef LaneT<CL> Lane;
   static_assert(!CL || BLOCK == kBlock, "the LDS-resident cold lane state is laid out for kBlock threads");
   static_assert(BLOCK % 64 == 0 && BLOCK / 64 <= PT_MAX_WAVES_PER_BLOCK, "per-wave LDS arrays are sized for PT_MAX_WAVES_PER_BLOCK waves");
@@ -600,11 +614,18 @@ void render_kernel(KArgs a) {
         }
       }
     }
-    lane_prepare<FAST>(L, a);
-    if (__builtin_amdgcn_ballot_w64(L.live) == 0) {
-      if (__builtin_amdgcn_ballot_w64(!L.retired) == 0) break; // queue drained for the whole wave
-      continue;                                                 // only padding pixels this time: pull again
-    }
+    // Pull until some lane has a ray to trace.  (A loop of its own around lane_prepare, not a `continue` of the outer one: on a path that
+    // skips the traversal and the shading, the compiler's structured control flow leaves the lane state that the shading writes undefined,
+    // which kept it from being written in place — the whole lane state went through a second register set on every iteration.  A pull that
+    // brings only padding pixels used to pass the priority poll above again and count as an iteration of prio_it; now it does neither, so
+    // the poll's 64-iteration cadence counts traced iterations only: a shift of a few iterations for the waves that meet edge tiles.)
+    bool drained = false;
+    do {
+      lane_prepare<FAST>(L, a);
+      if (__builtin_amdgcn_ballot_w64(L.live) != 0) break;
+      drained = __builtin_amdgcn_ballot_w64(!L.retired) == 0; // queue drained for the whole wave; else only padding pixels this time: pull again
+    } while (!drained);
+    if (drained) break;
 #ifdef PT_STAMPS
     PT_STAMP(t1);
 #endif
@@ -626,8 +647,8 @@ void render_kernel(KArgs a) {
       asm volatile("" ::"v"(h.closest), "v"(h.hit));
       PT_STAMP(t2);
 #endif
-      if constexpr (MLDS) lane_shade<UV, FAST, MATS>(L, a, h, (lds_f4p)smem, (lds_f4p)smem + a.blob_f4, regular);
-      else lane_shade<UV, FAST, MATS>(L, a, h, (lds_f4p)smem, a.mats, regular);
+      if constexpr (MLDS) lane_shade<UV, FAST, MATS, kSkyFirst>(L, a, h, (lds_f4p)smem, (lds_f4p)smem + a.blob_f4, regular);
+      else lane_shade<UV, FAST, MATS, kSkyFirst>(L, a, h, (lds_f4p)smem, a.mats, regular);
 #ifdef PT_STAMPS
       asm volatile("" ::"v"(L.att.x), "v"(L.ray.d.x));
       PT_STAMP(t3);
@@ -651,7 +672,7 @@ void render_kernel(KArgs a) {
         hit_world<IMG, BADOUEL, GRID, TRIPOOL, (MATS & MATS_RECTBOX_ONLY) != 0>((cst_f4p)a.blob, (cst_f4p)a.blob, a.n_runs, c, fast, L.rng, h, a.pool, &pc);
       } else
       hit_world<IMG, BADOUEL, GRID, TRIPOOL, (MATS & MATS_RECTBOX_ONLY) != 0>((cst_f4p)a.blob, (cst_f4p)a.blob, a.n_runs, c, fast, L.rng, h, a.pool);
-      lane_shade<UV, FAST, MATS>(L, a, h, a.blob, a.mats, fast);
+      lane_shade<UV, FAST, MATS, kSkyFirst>(L, a, h, a.blob, a.mats, fast);
     }
   }
 #ifdef PT_STAMPS_WALK
