@@ -77,6 +77,7 @@ __device__ __forceinline__ int as_i(float f) { return __float_as_int(f); }
 #define PT_STRIDED_K 4 /* spheres per trip of the cooperative (strided) scan: 4 or 2 */
 #endif
 #define PT_INF (__builtin_inff())
+#define PT_KEY_NONE 0x7fc00000u      /* slab pool: the candidate key "none" (slab_chunk_pass) */
 #define PT_PI 3.1415926535897932385f /* rtweekend.hpp:22 */
 #define PT_TMIN 0.001f               /* render.hpp:40 */
 
@@ -1170,9 +1171,10 @@ __device__ __forceinline__ void sphere_scan(P recs, cst_f4p cblob, int n, int go
 // order like floats; truncation only lowers L); +inf = none.  More than three live candidates: another pass over the
 // chunk for the lanes concerned, restricted to keys above the last one handled.
 template <bool FILTER, typename P>
-__device__ __forceinline__ bool slab_chunk_pass(P xrecs, P slrecs, cst_f4p srecs, int cn, float bmax, const RayCtx& c, V3 om, V3 op, float& kdone,
+__device__ __forceinline__ unsigned long long slab_chunk_pass(P xrecs, P slrecs, cst_f4p srecs, int cn, float bmax, const RayCtx& c, V3 om, V3 op, float& kdone,
                                                 HitState& h) {
-  const float none = PT_INF;
+  const float none = as_f(PT_KEY_NONE);
+  auto ku = [](float k) { return (unsigned int)as_i(k); }; // keys compare as unsigned integers
   float k1 = none, k2 = none, k3 = none;
   // two entries per trip (the table is padded to an even count with an all-NaN entry: `L <= NaN` is false), one
   // s_load_dwordx16 for both; wave-uniform, the bounds are SGPR operands
@@ -1191,10 +1193,10 @@ __device__ __forceinline__ bool slab_chunk_pass(P xrecs, P slrecs, cst_f4p srecs
     float key;
     asm("v_bfi_b32 %0, 15, %1, %2" : "=v"(key) : "s"(j), "v"(L)); // (j & 15) | (L & ~15)
     bool cand = L <= tf;
-    if (FILTER) cand = cand & (key > kdone);
+    if (FILTER) cand = cand & (ku(key) > ku(kdone));
     const float kk = cand ? key : none;
-    // sorted insert into (k1 <= k2 <= k3), in place, as unsigned integers (positive floats and +inf order the same way; the
-    // float min / med3 would first canonicalise their operands: two more instructions per entry)
+    // sorted insert into (k1 <= k2 <= k3), in place, as unsigned integers (the float min / med3 would first canonicalise their
+    // operands: two more instructions per entry)
     asm("v_med3_u32 %0, %1, %0, %2" : "+v"(k3) : "v"(k2), "v"(kk));
     asm("v_med3_u32 %0, %1, %0, %2" : "+v"(k2) : "v"(k1), "v"(kk));
     asm("v_min_u32_e32 %0, %0, %1" : "+v"(k1) : "v"(kk));
@@ -1209,9 +1211,14 @@ __device__ __forceinline__ bool slab_chunk_pass(P xrecs, P slrecs, cst_f4p srecs
   // Every trip of the loop consumes the nearest key of every lane that still has a live one (tested exactly, or dropped by
   // the proof below); a key beyond closest ends the lane's scan (keys ascend).  A lane that consumed all three keys it
   // could hold may have a fourth candidate: it asks for another pass (`more`).
-  const bool had3 = k3 < none;
+  // Liveness enters here, once per pass: a lane that is not live asks for nothing and its nearest key becomes the sentinel, which
+  // fails both gates below by itself — the lane never votes and never pops, so its k2 / k3 are never looked at.
+  k1 = c.live ? k1 : none;
+  k3 = c.live ? k3 : none;
+  const unsigned long long had3 = __builtin_amdgcn_ballot_w64(ku(k3) != PT_KEY_NONE);
+  unsigned long long vote;
 #pragma unroll 1
-  for (;;) {
+  do {
     // A ray that leaves a face of a box has that box as its nearest candidate whenever the slab margins reach `min` along the
     // face's axis (a few per cent of the lanes: nearly every wave), and the exact test then rejects all six sides: a whole
     // trip for nothing.  For nearest keys with L == min (origin inside, on or next to the box) a proof is tried first.
@@ -1224,12 +1231,14 @@ __device__ __forceinline__ bool slab_chunk_pass(P xrecs, P slrecs, cst_f4p srecs
     // then no side of the box can be accepted and the key is dropped without a trip: the ray leaves through the far plane
     // of axis k before it reaches any other plane of the box.
     {
-      bool inside = (k1 < none) & ((as_i(k1) & ~15) == (as_i(PT_TMIN) & ~15)) & c.live;
+      // the gate is ONE comparison: L == min up to the four index bits; the sentinel differs from min's pattern in its high bits
+      bool inside = (ku(k1) ^ (unsigned int)as_i(PT_TMIN)) < 16u;
 #ifdef PT_NO_POOL_PROOF
       inside = false; // A/B build
 #endif
       if (__builtin_amdgcn_ballot_w64(inside)) {
-        const int offs = inside ? (as_i(k1) & 15) * 2 : 0;
+        // (every lane reads the entry its nearest key names, voting or not: a key's index bits name an entry of this chunk, the sentinel's entry 0)
+        const int offs = (as_i(k1) & 15) * 2;
         const f4 S0 = slrecs[offs], S1 = slrecs[offs + 1]; // the slab entry: true bounds, a rect's plane in both
         const float e = 0x1p-20f, tlo = PT_TMIN * (1.0f - 0x1p-20f);
         auto ends = [&](float o, float y, float lo, float hi, float& lw, float& us, float& ws) { // returns (1) for this axis
@@ -1258,36 +1267,47 @@ __device__ __forceinline__ bool slab_chunk_pass(P xrecs, P slrecs, cst_f4p srecs
         k1 = gone ? k2 : k1; k2 = gone ? k3 : k2; k3 = gone ? none : k3;
       }
     }
-    const bool active = (k1 < none) & (as_f(as_i(k1) & ~15) <= h.closest) & c.live;
-    if (!__builtin_amdgcn_ballot_w64(active)) break;
+    // ONE ordered comparison: false for the sentinel (a NaN) whatever closest is, +inf included
+    // the compare's own SGPR pair: the ballot, the branch and the EXEC mask of the trip
+    asm("v_cmp_le_f32_e64 %0, %1, %2" : "=s"(vote) : "v"(as_i(k1) & ~15), "v"(h.closest));
+    const bool active = __builtin_amdgcn_inverse_ballot_w64(vote);
 #ifdef PT_STAMPS_POOL
     { // diagnostic build (make stamps EXTRA=-DPT_STAMPS_POOL): trips per pool scan, lanes busy per trip, repeated passes
       const unsigned long long busy = __builtin_amdgcn_ballot_w64(active);
-      if ((threadIdx.x & 63) == 0) {
+      if (vote != 0 && (threadIdx.x & 63) == 0) {
         atomicAdd(&g_stamps[5], 1ull);
         atomicAdd(&g_stamps[7], (unsigned long long)__builtin_popcountll(busy));
         if (FILTER) atomicAdd(&g_stamps[6], 1ull);
       }
     }
 #endif
-    const int offl = active ? (as_i(k1) & 15) * 2 : 0;
-    const f4 X0 = xrecs[offl], X1 = xrecs[offl + 1];
     if (active) {
+      const int offl = (as_i(k1) & 15) * 2;
+      const f4 X0 = xrecs[offl], X1 = xrecs[offl + 1];
       const unsigned long long exec_now = __builtin_amdgcn_ballot_w64(true);
       int hit_base = as_i(X0.w);
       // (a later holder that is a SPHERE — an absorbed run's, tested through an earlier run's lists — is strict itself: in list order this
       // hittable takes an equal t first and the sphere then fails t < max, so the candidate keeps the non-strict comparison)
       const bool holder_later = ((h.hit >= 0) & (hit_off(h.hit) > hit_off(hit_base))) && hit_kind(h.hit) != DK_SPHERE;
       float cl = holder_later ? as_f(as_i(h.closest) - 1) : h.closest;
-      int hit_now = h.hit;
-      box_cmpx(X0, X1, c, exec_now, hit_base, cl, hit_now);
-      h.closest = hit_now != h.hit ? cl : h.closest;
-      h.hit = hit_now;
-      kdone = k1;
+      // the trip writes the hit in place; the holder's id is the copy (the compiler copies the other way round, and back after the trip)
+      int holder;
+      asm("v_mov_b32_e32 %0, %1" : "=v"(holder) : "v"(h.hit));
+      box_cmpx(X0, X1, c, exec_now, hit_base, cl, h.hit);
+      // closest takes the trip's t where the hit changed hands, and the key is popped inside the block that consumed it: one statement, each
+      // register written in place, the pops between the comparison and the select that waits for its VCC (EXEC is the block's own throughout)
+      asm("v_cmp_ne_u32_e32 vcc, %[hit], %[holder]\n\t"
+          "v_mov_b32_e32 %[kd], %[k1]\n\t"
+          "v_mov_b32_e32 %[k1], %[k2]\n\t"
+          "v_cndmask_b32_e32 %[closest], %[closest], %[cl], vcc\n\t"
+          "v_mov_b32_e32 %[k2], %[k3]\n\t"
+          "v_mov_b32_e32 %[k3], %[none]"
+          : [kd] "+v"(kdone), [k1] "+v"(k1), [k2] "+v"(k2), [k3] "+v"(k3), [closest] "+v"(h.closest)
+          : [hit] "v"(h.hit), [holder] "v"(holder), [cl] "v"(cl), [none] "v"(none)
+          : "vcc");
     }
-    k1 = active ? k2 : k1; k2 = active ? k3 : k2; k3 = active ? none : k3;
-  }
-  return had3 & !(k1 < none) & c.live;
+  } while (vote != 0);
+  return had3 & __builtin_amdgcn_ballot_w64(ku(k1) == PT_KEY_NONE);
 }
 
 // pool table at blob[pool_off]: n slab entries (2 f4 each; padded to an even count), then n exact entries (2 f4 each)
@@ -1308,9 +1328,9 @@ __device__ __forceinline__ void slab_pool(P blob, cst_f4p cblob, int pool_off, i
     const cst_f4p srecs = cblob + pool_off + 2 * base; // the slab entries through the scalar cache (wave-uniform reads) ...
     const P slrecs = blob + pool_off + 2 * base;       // ... and where the lanes read them individually
     float kdone = 0.0f;
-    bool more = slab_chunk_pass<false>(xrecs, slrecs, srecs, cn, bmax, c, om, op, kdone, h);
-    while (__builtin_amdgcn_ballot_w64(more)) {
-      if (!more) kdone = PT_INF; // lanes that are done: no key passes the filter
+    unsigned long long more = slab_chunk_pass<false>(xrecs, slrecs, srecs, cn, bmax, c, om, op, kdone, h);
+    while (more) {
+      if (!__builtin_amdgcn_inverse_ballot_w64(more)) kdone = as_f(PT_KEY_NONE); // lanes that are done: no key passes the filter
       more = slab_chunk_pass<true>(xrecs, slrecs, srecs, cn, bmax, c, om, op, kdone, h);
     }
   }

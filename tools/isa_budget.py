@@ -64,8 +64,9 @@ def function_ranges(src):
                 j += 1
             first, last = i + 1, j + 1
             if name == "slab_chunk_pass":
-                a = next(k for k in range(i, j) if "const bool had3" in lines[k]) + 1
-                b = next(k for k in range(i, j) if "const bool active" in lines[k]) + 1
+                # the candidate loop starts where `had3` is taken; the trip's part at the gate's comparison (`vote`; `active` in older trees)
+                a = next(k for k in range(i, j) if re.search(r"\bhad3 =", lines[k])) + 1
+                b = next(k for k in range(a, j) if re.search(r"\((vote|active)\) :|const bool active", lines[k])) + 1
                 out[path.name] += [(first, a - 1, where["slab_chunk_pass:pass"]), (a, b - 1, where["slab_chunk_pass:proof"]), (b, last, where["slab_chunk_pass:trip"])]
             else:
                 out[path.name].append((first, last, where[name]))
