@@ -1170,12 +1170,74 @@ __device__ __forceinline__ void sphere_scan(P recs, cst_f4p cblob, int n, int go
 // Keys: the float L with its low four bits replaced by the entry's index in the chunk of 16 (L >= min > 0, so the keys
 // order like floats; truncation only lowers L); +inf = none.  More than three live candidates: another pass over the
 // chunk for the lanes concerned, restricted to keys above the last one handled.
-template <bool FILTER, typename P>
-__device__ __forceinline__ unsigned long long slab_chunk_pass(P xrecs, P slrecs, cst_f4p srecs, int cn, float bmax, const RayCtx& c, V3 om, V3 op, float& kdone,
+//
+// Two forms of the slab pass, one per kernel (never both: the LDS kernels run at a register and instruction budget that has no room for dead code).
+// SCALAR form (blob read through the scalar cache): the bounds are wave-uniform SGPR operands, a = fma(lo, y, om), b = fma(hi, y, op) with
+// om = -(o + S) y, op = -(o - S) y, and each axis' interval is (min(a, b), max(a, b)).
+// SIGN-RESOLVED form (OCT: the records pointer is the LDS image, the pool has its octant table — pt_flatten.hpp): which of a, b is the smaller is
+// known from the sign of y alone, so the lane reads (near, far) = (s ? hi : lo, s ? lo : hi), s = sign bit of y_c, from the table record of its
+// direction octant (two ds_read_b128 per entry; the eight octants of an entry lie on all 64 banks once: no conflict), pairs them with the addends
+// An = -(o + copysign(S, y)) y and Af = -(o - copysign(S, y)) y, and takes entry = max3 of the three fma(near, y, An), exit = min3 of the three
+// fma(far, y, Af): six v_min / v_max per entry fewer.  Why the keys (k1, k2, k3) are the scalar form's, bit for bit:
+//  - y > 0 (s = 0): lo <= hi gives lo y <= hi y exactly; S >= 0 gives RN(o + S) >= RN(o - S), so -(o + S) y <= -(o - S) y exactly and, rounding being
+//    monotonic, om <= op; the exact sums are ordered and so are their roundings: a <= b.  near = lo with An = -(o + S) y IS a, far with Af IS b.
+//  - y < 0 (s = 1): every inequality turns round, a >= b; near = hi with An = -(o - S) y IS b, far = lo with Af = -(o + S) y IS a.
+//    (y is never 0 or NaN for a regular ray — 2^-40 <= |d| <= 2^40 — and nothing is infinite or NaN: scene and origin are <= 2^60.)
+//  - a rect's lo == hi on its own axis: near == far, a and b differ by the addends only and the argument above orders them as it does for a box.
+//  - the pad entry: near = far = NaN in every octant, entry = max(NaN.., min) = min, exit = NaN, `L <= NaN` is false: never a candidate, as today.
+//  - +-0.  The values agree, the SIGN of a zero may not: the scalar form's 0 - (o +- S) is +0 where the product form's -(o +- S) is -0, which
+//    shows in an fma whose product is an exact zero (bound 0), and min / max of two zeros of either sign returns one or the other.  No comparison
+//    sees it: the entry side ends in L = max(., min) with min > 0, which no zero survives; the exit side is read by `L <= exit` alone, false for
+//    +0 and -0 alike (L >= min > 0), and a zero that loses a v_min3 against a negative value or a v_max3 against a positive one is gone.  The
+//    key is made of L's bits: identical.  (tests/cpp/slab_forms_main.c compares L, the decision and the key of both forms, 10^8 cases and the corners.)
+// Idle lanes and lanes of an irregular wave never get here with a vote (c.live, `fast`); their octant is three sign bits of whatever y holds: an
+// address inside the table whatever the value.
+template <bool FILTER, int FORM, typename P>
+__device__ __forceinline__ unsigned long long slab_chunk_pass(P xrecs, P slrecs, cst_f4p srecs, P otab, int cn, float bmax, const RayCtx& c, V3 om, V3 op, float& kdone,
                                                 HitState& h) {
+  constexpr bool OCT = FORM > 0; // 0: the scalar form; 1 / 2: the sign-resolved form, one / two entries per trip
   const float none = as_f(PT_KEY_NONE);
   auto ku = [](float k) { return (unsigned int)as_i(k); }; // keys compare as unsigned integers
   float k1 = none, k2 = none, k3 = none;
+  auto insert = [&](float L, float tf, int j) {
+    float key;
+    asm("v_bfi_b32 %0, 15, %1, %2" : "=v"(key) : "s"(j), "v"(L)); // (j & 15) | (L & ~15)
+    bool cand = L <= tf;
+    if (FILTER) cand = cand & (ku(key) > ku(kdone));
+    const float kk = cand ? key : none;
+    // sorted insert into (k1 <= k2 <= k3), in place, as unsigned integers (the float min / med3 would first canonicalise their
+    // operands: two more instructions per entry)
+    asm("v_med3_u32 %0, %1, %0, %2" : "+v"(k3) : "v"(k2), "v"(kk));
+    asm("v_med3_u32 %0, %1, %0, %2" : "+v"(k2) : "v"(k1), "v"(kk));
+    asm("v_min_u32_e32 %0, %0, %1" : "+v"(k1) : "v"(kk));
+  };
+  if constexpr (OCT) {
+    // sign-resolved form: om = An, op = Af (slab_pool); otab = this lane's octant record of the chunk's first entry, 16 F4 per entry
+    auto entry = [&](f4 N, f4 F, int j) {
+      const float nx = __builtin_fmaf(N.x, c.yx, om.x), ny = __builtin_fmaf(N.y, c.yy, om.y), nz = __builtin_fmaf(N.z, c.yz, om.z);
+      const float fx = __builtin_fmaf(F.x, c.yx, op.x), fy = __builtin_fmaf(F.y, c.yy, op.y), fz = __builtin_fmaf(F.z, c.yz, op.z);
+      const float L = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(nx, ny), nz), PT_TMIN);
+      insert(L, __builtin_fminf(__builtin_fminf(fx, fy), fz), j);
+    };
+    // two entries per trip, as the scalar form (the table holds the pad entry too).  The trip's address is ONE instruction on the chunk's base
+    // and the scalar counter; a pointer carried through the loop costs a copy per pass on top of its increment (the base is needed again).
+    // (FORM 1, the kernels that carry every hittable kind: ONE entry per trip — the bounds are eight vector registers per entry in flight where the
+    // scalar form held them in SGPRs, and two entries' worth spill at those kernels' budgets; the pad entry is then never read)
+#pragma unroll 1
+    for (int j = 0; j < cn; j += FORM) {
+      unsigned int at;
+      asm("v_lshl_add_u32 %0, %1, 8, %2" : "=v"(at) : "s"(j), "v"((unsigned int)(uintptr_t)otab));
+      const P e = (P)(uintptr_t)at;
+      if constexpr (FORM == 2) {
+        const f4 N0 = e[0], F0 = e[1], N1 = e[16], F1 = e[17];
+        entry(N0, F0, j);
+        entry(N1, F1, j + 1);
+      } else {
+        const f4 N0 = e[0], F0 = e[1];
+        entry(N0, F0, j);
+      }
+    }
+  } else {
   // two entries per trip (the table is padded to an even count with an all-NaN entry: `L <= NaN` is false), one
   // s_load_dwordx16 for both; wave-uniform, the bounds are SGPR operands
   typedef float f16v __attribute__((ext_vector_type(16)));
@@ -1189,17 +1251,7 @@ __device__ __forceinline__ unsigned long long slab_chunk_pass(P xrecs, P slrecs,
     const float az = __builtin_fmaf(lz, c.yz, om.z), bz = __builtin_fmaf(hz, c.yz, op.z);
     const float tn = __builtin_fmaxf(__builtin_fmaxf(__builtin_fminf(ax, bx), __builtin_fminf(ay, by)), __builtin_fminf(az, bz));
     const float tf = __builtin_fminf(__builtin_fminf(__builtin_fmaxf(ax, bx), __builtin_fmaxf(ay, by)), __builtin_fmaxf(az, bz));
-    const float L = __builtin_fmaxf(tn, PT_TMIN);
-    float key;
-    asm("v_bfi_b32 %0, 15, %1, %2" : "=v"(key) : "s"(j), "v"(L)); // (j & 15) | (L & ~15)
-    bool cand = L <= tf;
-    if (FILTER) cand = cand & (ku(key) > ku(kdone));
-    const float kk = cand ? key : none;
-    // sorted insert into (k1 <= k2 <= k3), in place, as unsigned integers (the float min / med3 would first canonicalise their
-    // operands: two more instructions per entry)
-    asm("v_med3_u32 %0, %1, %0, %2" : "+v"(k3) : "v"(k2), "v"(kk));
-    asm("v_med3_u32 %0, %1, %0, %2" : "+v"(k2) : "v"(k1), "v"(kk));
-    asm("v_min_u32_e32 %0, %0, %1" : "+v"(k1) : "v"(kk));
+    insert(__builtin_fmaxf(tn, PT_TMIN), tf, j);
   };
   // (four entries per trip of this scalar loop — two s_load_dwordx16 in flight — measured 2.3 % SLOWER on the headline scene, 150.2
   // against 146.9 ms, three alternating runs each: profiles/r03_ab_slab_unroll4.log)
@@ -1207,6 +1259,7 @@ __device__ __forceinline__ unsigned long long slab_chunk_pass(P xrecs, P slrecs,
     const f16v e = pairs[j >> 1];
     entry(e[0], e[1], e[2], e[4], e[5], e[6], j);
     entry(e[8], e[9], e[10], e[12], e[13], e[14], j + 1);
+  }
   }
   // Every trip of the loop consumes the nearest key of every lane that still has a live one (tested exactly, or dropped by
   // the proof below); a key beyond closest ends the lane's scan (keys ascend).  A lane that consumed all three keys it
@@ -1238,13 +1291,22 @@ __device__ __forceinline__ unsigned long long slab_chunk_pass(P xrecs, P slrecs,
 #endif
       if (__builtin_amdgcn_ballot_w64(inside)) {
         // (every lane reads the entry its nearest key names, voting or not: a key's index bits name an entry of this chunk, the sentinel's entry 0)
-        const int offs = (as_i(k1) & 15) * 2;
-        const f4 S0 = slrecs[offs], S1 = slrecs[offs + 1]; // the slab entry: true bounds, a rect's plane in both
+        // the entry's true bounds (a rect's plane in both).  Sign-resolved form: the lane's (near, far) of them from the octant table, so the
+        // interval's ends need no min / max (the argument above the pass, with S = 0; a zero's sign reaches only |.|, `< min` and `>`: no outcome)
+        f4 S0, S1;
+        if constexpr (OCT) {
+          unsigned int at;
+          asm("v_lshl_add_u32 %0, %1, 8, %2" : "=v"(at) : "v"(as_i(k1) & 15), "v"((unsigned int)(uintptr_t)otab));
+          S0 = ((P)(uintptr_t)at)[0]; S1 = ((P)(uintptr_t)at)[1];
+        } else {
+          const int offs = (as_i(k1) & 15) * 2;
+          S0 = slrecs[offs]; S1 = slrecs[offs + 1];
+        }
         const float e = 0x1p-20f, tlo = PT_TMIN * (1.0f - 0x1p-20f);
         auto ends = [&](float o, float y, float lo, float hi, float& lw, float& us, float& ws) { // returns (1) for this axis
           const float a = (lo - o) * y, b = (hi - o) * y;
-          lw = __builtin_fminf(a, b);
-          const float up = __builtin_fmaxf(a, b);
+          lw = OCT ? a : __builtin_fminf(a, b);
+          const float up = OCT ? b : __builtin_fmaxf(a, b);
           // slab_pool's shift S = 9u |o| + 7u B as it can come out of RN(o +- S) and of rounding (o +- S) y: up to
           // ulp(o +- S)/2 <= u (|o| + S) and u |o +- S| more; the fma's own rounding is in the 2^-20 below
           const float S = __builtin_fmaf(__builtin_fabsf(o), 0x1.7p-21f, 0x1.dp-22f * bmax); // 11.5u |o| + 7.25u B
@@ -1310,15 +1372,36 @@ __device__ __forceinline__ unsigned long long slab_chunk_pass(P xrecs, P slrecs,
   return had3 & __builtin_amdgcn_ballot_w64(ku(k1) == PT_KEY_NONE);
 }
 
-// pool table at blob[pool_off]: n slab entries (2 f4 each; padded to an even count), then n exact entries (2 f4 each)
-template <typename P>
+// pool table at blob[pool_off]: n slab entries (2 f4 each; padded to an even count), then n exact entries (2 f4 each), then — where the scene has
+// them, and every scene an LDS kernel is chosen for has (pt_render.hip: choose_variant) — the octant table, 16 f4 per slab entry
+// LDS_FORM: which form a kernel takes when its records pointer is the LDS image (slab_chunk_pass: FORM); every other pointer: the scalar form.
+// The kernels of rect / box-only scenes (the headline family): 2.  The kernels that carry every hittable kind: 1 — except the queued sphere-grid
+// walk's (GRID = 2), which keep the scalar form: they hold five more values across a scan, and the bounds in vector registers push their
+// scratch from 20 to 28 bytes at the 96-register budget (tests/test_kernel_resources_cpu.py holds 24).  One form per kernel, never two.
+template <int LDS_FORM, typename P>
 __device__ __forceinline__ void slab_pool(P blob, cst_f4p cblob, int pool_off, int n, float bmax, const RayCtx& c, HitState& h) {
+  constexpr int FORM = __is_same(P, lds_f4p) ? LDS_FORM : 0;
+  constexpr bool OCT = FORM > 0;
   const float kP = 0x1.2p-21f;           // 9u
   const float bP = 0x1.cp-22f * bmax;    // 7u B
   const V3 pp = mk(__builtin_fmaf(__builtin_fabsf(c.r.o.x), kP, bP), __builtin_fmaf(__builtin_fabsf(c.r.o.y), kP, bP),
                    __builtin_fmaf(__builtin_fabsf(c.r.o.z), kP, bP));
   const V3 yv = mk(c.yx, c.yy, c.yz);
-  const V3 om = (mk(0.0f, 0.0f, 0.0f) - (c.r.o + pp)) * yv, op = (mk(0.0f, 0.0f, 0.0f) - (c.r.o - pp)) * yv; // the fma addends of the slab test
+  V3 om, op; // the fma addends of the slab test
+  P otab = blob;
+  if constexpr (OCT) {
+    // S takes y's sign, the addends are products with -y (a source modifier): An = -(o + copysign(S, y)) y, Af = -(o - copysign(S, y)) y
+    const V3 ps = mk(__builtin_copysignf(pp.x, c.yx), __builtin_copysignf(pp.y, c.yy), __builtin_copysignf(pp.z, c.yz));
+    const V3 ny = mk(-c.yx, -c.yy, -c.yz);
+    om = (c.r.o + ps) * ny;
+    op = (c.r.o - ps) * ny;
+    // the lane's octant record: q = sx | sy << 1 | sz << 2, two f4 per octant
+    const unsigned int q2 = (((unsigned int)as_i(c.yx) >> 30) & 2u) | (((unsigned int)as_i(c.yy) >> 29) & 4u) | (((unsigned int)as_i(c.yz) >> 28) & 8u);
+    otab = blob + pool_off + 2 * (n + (n & 1)) + 2 * n + (int)q2;
+  } else {
+    om = (mk(0.0f, 0.0f, 0.0f) - (c.r.o + pp)) * yv;
+    op = (mk(0.0f, 0.0f, 0.0f) - (c.r.o - pp)) * yv;
+  }
 #ifdef PT_STAMPS_POOL
   if ((threadIdx.x & 63) == 0) atomicAdd(&g_stamps[4], 1ull);
 #endif
@@ -1327,11 +1410,12 @@ __device__ __forceinline__ void slab_pool(P blob, cst_f4p cblob, int pool_off, i
     const P xrecs = blob + pool_off + 2 * (n + (n & 1)) + 2 * base;
     const cst_f4p srecs = cblob + pool_off + 2 * base; // the slab entries through the scalar cache (wave-uniform reads) ...
     const P slrecs = blob + pool_off + 2 * base;       // ... and where the lanes read them individually
+    const P ochunk = otab + 16 * base;                 // sign-resolved form: the lane's octant record of the chunk's first entry
     float kdone = 0.0f;
-    unsigned long long more = slab_chunk_pass<false>(xrecs, slrecs, srecs, cn, bmax, c, om, op, kdone, h);
+    unsigned long long more = slab_chunk_pass<false, FORM>(xrecs, slrecs, srecs, ochunk, cn, bmax, c, om, op, kdone, h);
     while (more) {
       if (!__builtin_amdgcn_inverse_ballot_w64(more)) kdone = as_f(PT_KEY_NONE); // lanes that are done: no key passes the filter
-      more = slab_chunk_pass<true>(xrecs, slrecs, srecs, cn, bmax, c, om, op, kdone, h);
+      more = slab_chunk_pass<true, FORM>(xrecs, slrecs, srecs, ochunk, cn, bmax, c, om, op, kdone, h);
     }
   }
 }
@@ -2253,7 +2337,7 @@ __device__ __forceinline__ void hit_world_range(P blob, cst_f4p cblob, int ri0, 
       asm volatile("" : "+s"(span));
 #endif
       if (span != 0) { // head of a slab pool: the pool covers this run and the next span - 1
-        slab_pool(blob, cblob, as_i(aux.z), as_i(aux.w), aux.x, c, h);
+        slab_pool<2>(blob, cblob, as_i(aux.z), as_i(aux.w), aux.x, c, h);
         ri += span - 1;
       }
       hit_records_rectbox(blob + off, kind, span != 0 ? 0 : as_i(runf.z), off, c, fast, h);
@@ -2262,7 +2346,7 @@ __device__ __forceinline__ void hit_world_range(P blob, cst_f4p cblob, int ri0, 
       if (fast && (kind == DK_RECT || kind == DK_BOX)) { // head of a slab pool: the pool covers this run and the next span - 1
         const f4 aux = cblob[off - 1];                   // (largest |coordinate|, span, pool offset, entries)
         if (as_i(aux.y) != 0) {
-          slab_pool(blob, cblob, as_i(aux.z), as_i(aux.w), aux.x, c, h);
+          slab_pool<GRID == 2 ? 0 : 1>(blob, cblob, as_i(aux.z), as_i(aux.w), aux.x, c, h);
           ri += as_i(aux.y) - 1;
           continue;
         }

@@ -60,6 +60,7 @@ struct Flat {
   bool has_badouel = false; // some triangle uses the Badouel strategy (its own device kind and kernel instantiations)
   int grid_spheres = 0;     // spheres that sit in a culling grid (pt_scene_create: their scan is cheap)
   int pooled = 0;           // rects and boxes that sit in a slab pool (pt_device.hpp: slab_pool)
+  bool pool_octants = false; // every slab pool carries its octant table (the sign-resolved slab pass of the LDS kernels); all pools or none
   int tri_pooled = 0;       // triangles that sit in a triangle pool (pt_tripool.hpp; pt_device.hpp: tri_pool_scan)
   double tri_cells_per_triangle = 0; // statistics of the (last) triangle pool, for the tests
   int tri_wide = 0, tri_maps = 0;   // triangles whose band covers every direction; direction maps built
@@ -371,11 +372,13 @@ inline int32_t put_tri_pool(std::vector<F4>& b, PoolLayout& pool, TriPool& tp, c
   return hdr;
 }
 
-inline int flatten(const PtSceneDesc* sc, Flat& out, std::string& err, bool allow_grid = true, int box_cull = 1, GridTuning tune = GridTuning(),
-                   bool allow_tri_pool = true, TriPoolTuning tri_tune = TriPoolTuning(), bool sphere_merge = true) {
+// one layout of the scene; pool_octants: the slab pools carry their octant tables (flatten decides)
+inline int flatten_layout(const PtSceneDesc* sc, Flat& out, std::string& err, bool allow_grid, int box_cull, GridTuning tune,
+                          bool allow_tri_pool, TriPoolTuning tri_tune, bool sphere_merge, bool pool_octants) {
   int rc = validate(sc, err);
   if (rc) return rc;
   out = Flat();
+  out.pool_octants = pool_octants;
   // materials with their texture inlined
   out.mats.reserve((size_t)sc->n_materials * 4);
   for (int i = 0; i < sc->n_materials; i++) {
@@ -489,6 +492,11 @@ inline int flatten(const PtSceneDesc* sc, Flat& out, std::string& err, bool allo
     // [n slab entries (lo, -)(hi, -), padded to an even count][n exact entries (lo', hit id)(hi', -)] in front of its first run; every rect / box run
     // carries an aux F4 at its first record - 1: (largest |coordinate| of the pool, runs the pool spans (0: not a pool head),
     // pool offset, n).
+    // pool_octants: between the exact entries and the aux record sits the pool's OCTANT TABLE, [slab entry, the pad included][octant q][near, far]:
+    // for a ray whose direction has the sign bits q = sx | sy << 1 | sz << 2, (near.xyz, 0) holds per axis the bound its line meets first
+    // (s_c ? hi_c : lo_c) and (far.xyz, 0) the other one.  16 F4 = 256 bytes per entry, 32 bytes per octant: the eight octants of an entry lie
+    // on all 64 LDS banks once, so a wave whose lanes each read their own octant's record (ds_read_b128) meets no bank conflict.  The table's
+    // offset is pool offset + 2 (n + (n & 1)) + 2 n: no field names it.
     if (run.kind == DK_BOX || run.kind == DK_RECT) {
       const bool prev_rectish = ri > 0 && (runs[ri - 1].kind == DK_BOX || runs[ri - 1].kind == DK_RECT);
       int span = 0, n = 0, n_box = 0;
@@ -511,7 +519,7 @@ inline int flatten(const PtSceneDesc* sc, Flat& out, std::string& err, bool allo
         pool_first = run.first;
         pool_at = b.size();
         const int ns = n + (n & 1); // slab entries, padded to an even count with an entry no ray can be a candidate for (NaN bounds)
-        b.resize(b.size() + 2 * (size_t)ns + 2 * (size_t)n);
+        b.resize(b.size() + 2 * (size_t)ns + 2 * (size_t)n + (pool_octants ? 16 * (size_t)ns : 0));
         pool_x = pool_at + 2 * (size_t)ns;
         if (ns > n) { const float q = std::nanf(""); b[pool_at + 2 * n] = {q, q, q, 0}; b[pool_at + 2 * n + 1] = {q, q, q, 0}; }
         const float ninf = -INFINITY;
@@ -526,6 +534,17 @@ inline int flatten(const PtSceneDesc* sc, Flat& out, std::string& err, bool allo
           for (float v : {lo.x, lo.y, lo.z, hi.x, hi.y, hi.z}) bmax = std::max(bmax, std::fabs(v));
           b[pool_at + 2 * e] = lo; b[pool_at + 2 * e + 1] = hi;
           b[pool_x + 2 * e] = lo; b[pool_x + 2 * e + 1] = xhi; // .w of the first = hit id: filled in with the record
+        }
+        if (pool_octants) {
+          const size_t oct = pool_x + 2 * (size_t)n;
+          for (int e = 0; e < ns; e++) {
+            const F4 lo = b[pool_at + 2 * e], hi = b[pool_at + 2 * e + 1]; // (the pad entry: NaN in both)
+            for (int q = 0; q < 8; q++) {
+              const bool sx = q & 1, sy = q & 2, sz = q & 4;
+              b[oct + 16 * (size_t)e + 2 * q] = {sx ? hi.x : lo.x, sy ? hi.y : lo.y, sz ? hi.z : lo.z, 0};
+              b[oct + 16 * (size_t)e + 2 * q + 1] = {sx ? lo.x : hi.x, sy ? lo.y : hi.y, sz ? lo.z : hi.z, 0};
+            }
+          }
         }
         pool_n = n;
         out.pooled += n;
@@ -607,6 +626,22 @@ inline int flatten(const PtSceneDesc* sc, Flat& out, std::string& err, bool allo
   }
   if (b.size() >= (1u << kHitOffBits)) { err = "scene too large for 25-bit record offsets (33.5 M records of 16 bytes)"; return PT_ERR_TOO_LARGE; }
   return PT_OK;
+}
+
+// The blob the kernels read.  Octant tables of the slab pools (only the LDS-resident kernels read them: pt_device.hpp slab_chunk_pass): ALL
+// pools of a scene get theirs when the blob including them still fits the LDS image, NONE otherwise — Flat::pool_octants says which, and a
+// scene with pools and no tables renders through the scalar-cache kernels (pt_render.hip: choose_variant).  A scene whose records alone
+// exceed the image is laid out once, without them.  pool_octants = false: never (experiments: the scene as it was before the tables).
+constexpr size_t kLdsImageBytes = 64 * 1024; // pt_render.hip: kMaxLdsBlob
+inline int flatten(const PtSceneDesc* sc, Flat& out, std::string& err, bool allow_grid = true, int box_cull = 1, GridTuning tune = GridTuning(),
+                   bool allow_tri_pool = true, TriPoolTuning tri_tune = TriPoolTuning(), bool sphere_merge = true, bool pool_octants = true) {
+  size_t records_f4 = 0;
+  for (int i = 0; sc && sc->hittables && i < sc->n_hittables; i++) records_f4 += (size_t)std::max(0, record_size(device_kind(sc->hittables[i])));
+  const bool with_tables = pool_octants && records_f4 * 16 <= kLdsImageBytes;
+  int rc = flatten_layout(sc, out, err, allow_grid, box_cull, tune, allow_tri_pool, tri_tune, sphere_merge, with_tables);
+  if (rc == PT_OK && with_tables && out.pooled > 0 && out.blob.size() * 16 > kLdsImageBytes)
+    rc = flatten_layout(sc, out, err, allow_grid, box_cull, tune, allow_tri_pool, tri_tune, sphere_merge, false);
+  return rc;
 }
 
 } // namespace ptf

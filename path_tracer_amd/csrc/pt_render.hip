@@ -83,7 +83,7 @@ constexpr int kWavesPerBlock = kBlock / 64;
 #define PT_GRID_BLOCK 256
 #endif
 constexpr int kGridBlock = PT_GRID_BLOCK;   // workgroup size of the LDS-resident kernels that walk a sphere grid (render_kernel: BLOCK)
-constexpr size_t kMaxLdsBlob = 64 * 1024;   // blob staged in LDS when it fits
+constexpr size_t kMaxLdsBlob = ptf::kLdsImageBytes;   // blob staged in LDS when it fits (64 KB; the flattener budgets the slab pools' octant tables by it)
 constexpr size_t kMaxLdsWithMaterials = 16 * 1024; // stage the material table too when records + materials are this small
 constexpr size_t kMaxLdsColdScene = 10 * 1024;    // records + materials this small: the 8-wave kernel with LDS-resident cold lane state
 constexpr float kCoopMinTraversal = 2500.0f;        // estimated VALU instructions of one list scan (~110 spheres)
@@ -1298,12 +1298,16 @@ static int flatten_tuned(const PtSceneDesc* desc, const PtTuning& t, ptf::Flat& 
   if (t.tri_cell > 0.0f) tri.cell = t.tri_cell;
   if (const char* e = std::getenv("PT_TRI_GRID_BUDGET")) tri.grid_budget = (float)std::atof(e); // (experiments only: not a PtTuning field)
   const bool merge = t.sphere_merge >= 0;
-  int rc = ptf::flatten(desc, flat, err, allow_grid, box_cull, tune, allow_tri, tri, merge);
+  // (the octant tables of the slab pools are ptf::flatten's own decision — all pools or none, by the same LDS budget; PT_NO_POOL_OCTANTS, for
+  // tests only and no PtTuning field like PT_TRI_GRID_BUDGET, lays the scene out as it was before the tables: it then renders through the
+  // scalar-cache kernels)
+  const bool octants = !std::getenv("PT_NO_POOL_OCTANTS");
+  int rc = ptf::flatten(desc, flat, err, allow_grid, box_cull, tune, allow_tri, tri, merge, octants);
   if (rc) return rc;
   if (flat.grid_spheres > 0 && flat.blob.size() * 16 > kMaxLdsBlob) {
     ptf::Flat plain;
     std::string err2;
-    if (flat.tri_pooled == 0 && ptf::flatten(desc, plain, err2, false, box_cull, tune, allow_tri, tri, merge) == PT_OK && plain.blob.size() * 16 <= kMaxLdsBlob) flat = std::move(plain);
+    if (flat.tri_pooled == 0 && ptf::flatten(desc, plain, err2, false, box_cull, tune, allow_tri, tri, merge, octants) == PT_OK && plain.blob.size() * 16 <= kMaxLdsBlob) flat = std::move(plain);
   }
   return PT_OK;
 }
@@ -1409,6 +1413,7 @@ struct PtScene {
   float traversal_cost = 0.0f; // estimated VALU instructions of one ray's scan of the list (sphere runs through their lists)
   int grid_spheres = 0;        // spheres that sit in a culling grid (the resident non-cooperative kernels walk it)
   int tri_pooled = 0;          // triangles that sit in a triangle pool (the TRIPOOL kernels query it)
+  bool pools_need_scalar = false; // the scene has slab pools WITHOUT octant tables (ptf::flatten): only the scalar-cache kernels scan such pools
   bool rectbox_only = false;   // every hittable is a rect or a box (kernels compiled with MATS_RECTBOX_ONLY: resolve_hit)
   bool mats_simple = false;    // every material is lambertian or lightsource over a solid texture (kernels compiled with MATS_LAMB_LIGHT_SOLID)
   size_t blob_bytes = 0, atlas_bytes = 0;
@@ -1520,7 +1525,9 @@ Variant choose_variant_uv(const PtScene* s, const PtRenderParams* p, int local_t
   // whatever its size (PT_FLAG_FORCE_STREAM: the streaming kernel, which scans every triangle, as the A/B)
   v.tri_pool = s->tri_pooled > 0 && !(p->flags & PT_FLAG_FORCE_STREAM);
   v.resident = (blob_bytes <= kMaxLdsBlob || (p->flags & PT_FLAG_NO_LDS) || v.tri_pool) && !(p->flags & PT_FLAG_FORCE_STREAM);
-  const bool lds = v.resident && !(p->flags & PT_FLAG_NO_LDS) && !v.tri_pool;
+  // The LDS kernels hold only the sign-resolved slab pass, which reads a pool's octant table (pt_device.hpp: slab_chunk_pass): a scene whose pools
+  // have none — the tables would have pushed its blob past the LDS image — takes the scalar-cache kernels it would take under PT_FLAG_NO_LDS.
+  const bool lds = v.resident && !(p->flags & PT_FLAG_NO_LDS) && !v.tri_pool && !s->pools_need_scalar;
   const bool mlds = lds && blob_bytes + (size_t)s->mats_f4 * 16 <= kMaxLdsWithMaterials;
   v.shmem = lds ? blob_bytes + (mlds ? (size_t)s->mats_f4 * 16 : 0) : 0;
   const bool cold = mlds && v.shmem <= kMaxLdsColdScene && !s->knobs.no_cold_lds; // small scene: cold lane state in LDS (7 workgroups x (scene + 8 KB) per CU)
@@ -1772,6 +1779,7 @@ int pt_scene_create_tuned(const PtSceneDesc* desc, const PtTuning* tuning, PtSce
     }
   }
   s->grid_spheres = flat.grid_spheres;
+  s->pools_need_scalar = flat.pooled > 0 && !flat.pool_octants;
   s->rectbox_only = desc->n_hittables > 0 && !s->knobs.generic_materials;
 #ifdef PT_NO_RECTBOX /* A/B build */
   s->rectbox_only = false;
