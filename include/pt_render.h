@@ -487,6 +487,49 @@ int pt_adaptive_export(const PtAccum* acc, void* host, int64_t bytes, void* stre
 /* Restore a PT_ADAPTIVE_FORMAT checkpoint, or upgrade a plain PT_ACCUM_FORMAT one (synchronises `stream`). */
 int pt_adaptive_import(PtAccum* acc, const void* host, int64_t bytes, void* stream);
 
+/* ---- first-hit feature buffers (AOVs): guide images for denoisers, mattes for compositing --------------------------------------------
+ * Added without an ABI version change, like PtAccum: a caller detects the feature by the presence of these symbols.
+ *
+ * DEFINITION.  The AOV pass of n samples is the reference's render at DEPTH 1, with the first bounce's record kept instead of thrown
+ * away.  Pixel p owns one xorshift32 stream, seeded with its linear id exactly as pt_render seeds it (render.hpp:130-132).  Sample s
+ * draws its camera ray from the stream (render.hpp:96-99), runs ONE iteration of the bounce loop (render.hpp:58-89: traversal, emitted,
+ * scatter — with every draw a constant_medium or the scatter takes) and leaves the stream where that bounce left it.  In terms of the
+ * probes below: pt_debug_camera_rays -> pt_debug_bounce (attenuation in = 1,1,1) -> PtBounceOut.rng_state -> the next sample.  Sample
+ * 0's camera ray is the beauty pass's first camera ray; later ones are other draws over the same pixel footprint, lens and shutter.
+ * The pass needs nothing from the beauty pass and costs one ray per sample.
+ *
+ * Per-sample terms, each a field of that sample's PtBounceOut, with hit = (status != PT_BOUNCE_MISS):
+ *   albedo    color: the new attenuation if scattered, the emitted colour if absorbed, the sky if missed
+ *   normal    hit ? normal : 0
+ *   depth     hit ? t : 0
+ *   coverage  hit ? 1 : 0
+ *   direct    status == PT_BOUNCE_SCATTERED ? 0 : color — the depth-1 radiance: the bits pt_render writes with depth = 1
+ *   id        `hittable` of SAMPLE 0 only (-1: miss)
+ * Each float channel is a binary32 sum from +0 in sample order, divided once by (float)samples, correctly rounded (render.hpp:102).
+ *
+ * Layout.  3-channel planes are laid out like pt_render's frame buffer ([y][x][3], y = 0 the bottom scan-line, or [local tile][64][3]
+ * for shards), 1-channel planes like pt_adaptive_counts ([height][width], or [local tile][64]); pt_aov_plane_elems gives the element
+ * counts.  Padding pixels of a shard get 0, and -1 in `id`.  A NULL plane is not written.
+ *
+ * Rejected (PT_ERR_INVALID_ARG, before any device call): a NULL scene, camera, params or buffers; a struct_size other than
+ * sizeof(PtAovBuffers); all six planes NULL; samples < 1 or > 1 << 24 (coverage stays exact); width or height <= 0; bad shard fields;
+ * PT_FLAG_FAST_RNG or PT_FLAG_SINGLE_STREAM.  `depth` and the scheduling flags are ignored.
+ *
+ * Asynchronous on `stream` like pt_render; allocates nothing and touches none of the scene's launch workspaces, so it may sit between
+ * any two renders of the scene on their stream without disturbing them.                                                              */
+typedef struct PtAovBuffers { /* device pointers; NULL = plane not wanted */
+  int32_t struct_size, reserved;
+  float* albedo;   /* 3 ch */
+  float* normal;   /* 3 ch */
+  float* direct;   /* 3 ch */
+  float* depth;    /* 1 ch */
+  float* coverage; /* 1 ch */
+  int32_t* id;     /* 1 ch */
+} PtAovBuffers;
+/* Host function, no GPU: elements of a plane of `channels` (1 or 3) channels for these parameters (samples ignored); < 0 for invalid ones. */
+int64_t pt_aov_plane_elems(const PtRenderParams* p, int32_t channels);
+int pt_render_aov(const PtScene* scene, const PtCamera* cam, const PtRenderParams* p, const PtAovBuffers* buffers, void* stream);
+
 /* ---- function-level probes (parity tests call these; not used by render) ---- */
 
 /* One iteration of the bounce loop render.hpp:58-89 per record: hit_world,
@@ -562,6 +605,10 @@ int pt_debug_schedule(const PtScene* scene, int32_t out[2]);
  * cost-sorted order that are handed out 16 pixels at a time (PtTuning.heavy_tiles' rule; 0 = none), out[3] = 1 if the sphere-grid walk
  * through the LDS pair queue was picked.  For tests of those rules.                                                                  */
 int pt_debug_last_launch(const PtScene* scene, int32_t out[4]);
+
+/* Which aov_kernel the LAST pt_render_aov of this scene launched: out[0] = its sphere-grid walk (1 wave-synchronous, 2 through the LDS pair
+ * queue; scenes without a sphere grid: 1), out[1] = 1 if u,v are tracked through the scan; both 0 before the first pass.  For tests.  */
+int pt_debug_last_aov(const PtScene* scene, int32_t out[2]);
 
 /* Device math used by the kernel, elementwise over host arrays.
  * op: 0 sin 1 cos 2 log 3 pow5 4 atan2(a,b) 5 asin 6 fmod(a,1) 7 sqrt 8 div(a,b)

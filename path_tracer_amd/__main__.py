@@ -10,6 +10,10 @@ each; the final --out PNG is byte-identical to the one written without these opt
 With --noise-threshold T the frame is rendered adaptively (render.render_adaptive): --min-spp samples of every pixel, then windows of
 --adaptive-step samples of the pixels whose noise estimate is above T, up to --spp; --counts-out writes the per-pixel counts as a grey
 PNG (row 0 at the top, --spp = white).  A negative T renders every pixel to --spp: the same out.png as without the options.
+With --aov-dir DIR the first-hit feature buffers a denoiser takes (render.render_aov: a pass of its own, --aov-spp camera rays per pixel)
+are written next to the frame: DIR/albedo.png, DIR/normal.png (as (n + 1) / 2), DIR/coverage.png and DIR/aov.npz with all six planes
+(albedo, normal, direct, depth, coverage, id; row 0 = the bottom scan-line, as the frame buffer); out.png is byte-identical to the one
+written without the options.
 """
 import argparse
 import os
@@ -18,6 +22,20 @@ import time
 from . import render as R
 from . import scenes
 from .png import write_png
+
+
+def write_aovs(aov_dir, planes) -> None:
+    """DIR/albedo.png, normal.png ((n + 1) / 2) and coverage.png — linear values (guide images, not pictures: no gamma), clamped to
+    [0, 0.999] and scaled by 256 like out.png, row 0 = top like out.png — and DIR/aov.npz with the six planes as rendered."""
+    import numpy as np
+    import torch
+
+    os.makedirs(aov_dir, exist_ok=True)
+    grey = planes["coverage"].unsqueeze(-1).expand(-1, -1, 3)
+    for name, fb in (("albedo", planes["albedo"]), ("normal", (planes["normal"] + 1.0) * 0.5), ("coverage", grey)):
+        rgb8 = (fb.clamp(0.0, 0.999) * 256.0).to(torch.uint8).flip(0).contiguous()
+        write_png(os.path.join(aov_dir, f"{name}.png"), rgb8.cpu().numpy())
+    np.savez(os.path.join(aov_dir, "aov.npz"), **{k: v.cpu().numpy() for k, v in planes.items()})
 
 
 def main() -> None:
@@ -41,7 +59,15 @@ def main() -> None:
     ap.add_argument("--min-spp", type=int, default=None, metavar="N", help="adaptive sampling: samples of every pixel (default 16)")
     ap.add_argument("--adaptive-step", type=int, default=None, metavar="N", help="adaptive sampling: samples per window (default --min-spp)")
     ap.add_argument("--counts-out", default=None, metavar="PATH", help="adaptive sampling: grey PNG of the per-pixel sample counts")
+    ap.add_argument("--aov-dir", default=None, metavar="DIR",
+                    help="also write first-hit feature buffers for a denoiser: DIR/albedo.png, normal.png, coverage.png, aov.npz")
+    ap.add_argument("--aov-spp", type=int, default=None, metavar="N", help="feature buffers: camera rays per pixel (default 16)")
     a = ap.parse_args()
+    if a.aov_spp is not None and a.aov_dir is None:
+        ap.error("--aov-spp needs --aov-dir")
+    a.aov_spp = 16 if a.aov_spp is None else a.aov_spp
+    if not 1 <= a.aov_spp <= 1 << 24:
+        ap.error(f"--aov-spp must be in 1 .. {1 << 24}")
     if a.preview_every < 0:
         ap.error("--preview-every must be >= 0")
     adaptive = a.noise_threshold is not None
@@ -100,6 +126,8 @@ def main() -> None:
         rgb8 = R.tonemap_rgb8(fb)
     torch.cuda.synchronize()
     write_png(a.out, rgb8.cpu().numpy())
+    if a.aov_dir:
+        write_aovs(a.aov_dir, R.render_aov(a.width, a.height, a.aov_spp, packed, cam))
     if mean_spp is not None:
         n = int(counts.sum())
         print(f"{a.scene}: {packed.n_hittables} hittables, {a.width}x{a.height}, adaptive {a.min_spp}..{a.spp} spp (threshold "

@@ -123,6 +123,12 @@ class PtCameraRay(C.Structure):
     _fields_ = [("origin", C.c_float * 3), ("dir", C.c_float * 3), ("time", C.c_float), ("rng_state", C.c_uint32)]
 
 
+class PtAovBuffers(C.Structure):
+    """include/pt_render.h PtAovBuffers: device pointers of the planes pt_render_aov writes (NULL = plane not wanted)."""
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("albedo", C.c_void_p), ("normal", C.c_void_p),
+                ("direct", C.c_void_p), ("depth", C.c_void_p), ("coverage", C.c_void_p), ("id", C.c_void_p)]
+
+
 assert C.sizeof(PtHittable) == 64 and C.sizeof(PtMaterial) == 32 and C.sizeof(PtTexture) == 48
 assert C.sizeof(PtCamera) == 96 and C.sizeof(PtRenderParams) == 32
 
@@ -188,6 +194,10 @@ SIGNATURES = {
     "pt_adaptive_state_bytes": (C.c_int64, [C.POINTER(PtRenderParams)]),
     "pt_adaptive_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "pt_adaptive_import": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    # first-hit feature buffers (AOVs): likewise optional (AOV_SYMBOLS)
+    "pt_aov_plane_elems": (C.c_int64, [C.POINTER(PtRenderParams), C.c_int32]),
+    "pt_debug_last_aov": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "pt_render_aov": (C.c_int, [_SCENE_P, C.POINTER(PtCamera), C.POINTER(PtRenderParams), C.POINTER(PtAovBuffers), C.c_void_p]),
 }
 
 # Entry points a library may lack and still load for everything else (include/pt_render.h: the feature is detected by their presence);
@@ -200,6 +210,10 @@ PT_ACCUM_HEADER_BYTES = 160
 ADAPTIVE_SYMBOLS = frozenset(n for n in SIGNATURES if n.startswith("pt_adaptive_"))
 PT_ADAPTIVE_FORMAT = 2
 PT_ADAPTIVE_DILATE = 1
+# first-hit feature buffers (include/pt_render.h: pt_render_aov); has_aov() tells whether the loaded library has them
+AOV_SYMBOLS = frozenset({"pt_aov_plane_elems", "pt_render_aov", "pt_debug_last_aov"})
+AOV_PLANES = ("albedo", "normal", "direct", "depth", "coverage", "id")  # PtAovBuffers' planes, in the struct's order
+AOV_CHANNELS = {"albedo": 3, "normal": 3, "direct": 3, "depth": 1, "coverage": 1, "id": 1}
 
 LIB_NAME = "libpt_render.so"
 _lib = None
@@ -244,7 +258,7 @@ def load_library() -> C.CDLL:
         pass  # torch-free hosts bind to /opt/rocm/lib through the library's RUNPATH
     lib = C.CDLL(str(path))
     for name, (res, args) in SIGNATURES.items():
-        if override_is_older_build(path, lib, name) or (name in ACCUM_SYMBOLS | ADAPTIVE_SYMBOLS and not hasattr(lib, name)):
+        if override_is_older_build(path, lib, name) or (name in ACCUM_SYMBOLS | ADAPTIVE_SYMBOLS | AOV_SYMBOLS and not hasattr(lib, name)):
             continue
         fn = getattr(lib, name)  # AttributeError if the library does not export what the header declares
         fn.restype = res
@@ -266,6 +280,12 @@ def has_adaptive(lib=None) -> bool:
     """Does the loaded library offer adaptive sampling (the pt_adaptive_* entry points)?"""
     lib = lib or load_library()
     return has_accumulator(lib) and all(hasattr(lib, n) for n in ADAPTIVE_SYMBOLS)
+
+
+def has_aov(lib=None) -> bool:
+    """Does the loaded library offer the first-hit feature buffers (pt_render_aov)?"""
+    lib = lib or load_library()
+    return all(hasattr(lib, n) for n in AOV_SYMBOLS)
 
 
 def check(code: int, where: str) -> None:

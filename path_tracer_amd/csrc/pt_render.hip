@@ -75,6 +75,9 @@ namespace {
 #ifndef PT_MIN_WAVES_COOP_IMG
 #define PT_MIN_WAVES_COOP_IMG 5 /* 96 VGPRs + 60 B/lane of spills; spill-free needs 116 VGPRs = 4 waves: 496-hittable scene -9 % (A/B) */
 #endif
+#ifndef PT_MIN_WAVES_AOV
+#define PT_MIN_WAVES_AOV 4 /* aov_kernel (pt_render_aov): 128 VGPRs + 92 - 116 B/lane of scratch (spills around the traversal, inside the per-sample loop), 20 KB of static LDS per workgroup.  Left to itself the compiler takes 168 - 173 VGPRs, no scratch, 2 waves; measured at 1080p x 16 samples with 2 / 3 / 4 waves: Cornell-style scene 0.68 / 0.55 / 0.50 ms, 496-hittable scene 2.93 / 2.11 / 1.93, 100 k triangles 324 / 242 / 210 — the spills cost less than the occupancy buys (profiles/aov_bench.txt: the A/B and the resource table) */
+#endif
 // How a kernel obtains the u,v an image texture looks up (DESIGN.md §3 "u,v of the final hit")
 enum { UV_NONE = 0, UV_WINNER = 1, UV_TRACKED = 2 };
 constexpr int kBlock = 256;                 // 4 wavefronts = 4 tiles per workgroup
@@ -895,6 +898,102 @@ __global__ __launch_bounds__(1024) void lpt_order_kernel(const unsigned int* __r
   for (int i = threadIdx.x; i < n; i += blockDim.x) order[atomicAdd(&s_cursor[cls(cost[i])], 1u)] = i;
 }
 
+// ---- first-hit feature buffers (include/pt_render.h: pt_render_aov) ---------------------------------------------
+// The AOV pass of n samples is the reference's render at depth 1 with the first bounce's record kept: pixel p owns one xorshift32 stream
+// seeded with its linear id (render.hpp:130-132); sample s draws its camera ray from it (render.hpp:96-99), runs ONE iteration of the
+// bounce loop (render.hpp:58-89: traversal, emitted, scatter — bounce_kernel's body, with every culling structure the scene has) and
+// leaves the stream where that bounce left it.  A pass of its own: it shares no code path, no register budget and no workspace with
+// render_kernel (DESIGN.md §1 "First-hit feature buffers", §3 "The AOV pass").  One wave per 8x8 tile, lane ly * 8 + lx; every plane's term is added in sample order
+// from +0 and divided once by (float)samples (render.hpp:102).
+struct AovArgs {
+  Cam cam = {};
+  const f4* blob = nullptr;
+  const f4* mats = nullptr;
+  const f4* pool = nullptr;
+  const uint8_t* atlas = nullptr;
+  float* albedo = nullptr;   // [pixel][3]; every plane: NULL = not wanted
+  float* normal = nullptr;   // [pixel][3]
+  float* direct = nullptr;   // [pixel][3]
+  float* depth = nullptr;    // [pixel]
+  float* coverage = nullptr; // [pixel]
+  int* id = nullptr;         // [pixel]
+  int n_runs = 0;
+  int width = 0, height = 0, samples = 0;
+  float inv_w = 0.0f, inv_h = 0.0f;
+  int pinhole = 0, fast_ok = 0;
+  int shard_index = 0, shard_count = 1;
+  int tiles_x = 0, n_tiles = 0;
+  int local_tiles = 0; // tiles of the planes: every tile of a whole frame; pt_shard_tiles() for a shard (its last one may be padding)
+};
+static_assert(std::is_trivially_copyable<AovArgs>::value, "AovArgs is copied into the kernarg segment as it is");
+
+template <bool IMG, int WALK>
+__global__ __launch_bounds__(kBlock, PT_MIN_WAVES_AOV) void aov_kernel(AovArgs a) {
+  const int l = (int)blockIdx.x * kWavesPerBlock + (int)(threadIdx.x >> 6); // local tile: one per wave
+  if (l >= a.local_tiles) return;                                           // (wave-uniform)
+  const int lane = threadIdx.x & 63;
+  const long long g = (long long)l * a.shard_count + a.shard_index; // global tile (pt_render.h: round-robin shards)
+  const bool sharded = a.shard_count != 1;
+  const bool tile_in_frame = g < a.n_tiles;
+  V3 alb = mk(0.0f, 0.0f, 0.0f), nrm = mk(0.0f, 0.0f, 0.0f), dir = mk(0.0f, 0.0f, 0.0f);
+  float dep = 0.0f, cov = 0.0f;
+  int first_id = -1;
+  bool in_frame = false;
+  long long at = (long long)l * PT_TILE_PIXELS + lane; // the pixel's element in the per-pixel layout: [local tile][64], or [y][x]
+  if (tile_in_frame) { // (wave-uniform: a shard's padding tile traces nothing)
+    const int tx = (int)(g % a.tiles_x), ty = (int)(g / a.tiles_x);
+    const int px = tx * PT_TILE + (lane & 7), py = ty * PT_TILE + (lane >> 3);
+    in_frame = px < a.width && py < a.height;
+    // every lane of the wave stays active through the traversal, which exchanges data between lanes (grid walk, triangle pool: see
+    // bounce_kernel): a padding lane repeats an in-frame pixel of its tile — same seed, same work — and stores nothing of it
+    const int x = min(px, a.width - 1), y = min(py, a.height - 1);
+    if (!sharded) at = (long long)y * a.width + x;
+    uint32_t rng = (uint32_t)((unsigned long long)y * (unsigned long long)a.width + (unsigned long long)x); // render.hpp:130-132
+    for (int s = 0; s < a.samples; ++s) {
+      Ray ray = camera_ray(a.cam, x, y, a.width, a.height, a.inv_w, a.inv_h, rng, a.pinhole != 0);
+      V3 att = mk(1.0f, 1.0f, 1.0f);
+      RayCtx c = make_ctx(ray, a.fast_ok != 0);
+      HitState h;
+      hit_world<IMG, true, WALK, true>(a.blob, (cst_f4p)a.blob, a.n_runs, c, wave_all_regular(c, true), rng, h, a.pool);
+      const float closest = h.closest, hu = h.u, hv = h.v;
+      const int hit = h.hit;
+      V3 color, n_term = mk(0.0f, 0.0f, 0.0f), d_term;
+      float t_term = 0.0f, c_term = 0.0f;
+      int hittable = -1;
+      if (hit < 0) {
+        color = sky_color(ray, att);
+        d_term = color;
+      } else {
+        const Rec rec = resolve_hit(a.blob, hit, ray, closest);
+        hittable = rec.hittable;
+        n_term = rec.normal; t_term = closest; c_term = 1.0f;
+        float pu = hu, pv = hv;
+        if (!IMG) winner_uv(a.blob, hit, ray, closest, rec, pu, pv);
+        V3 out = mk(0.0f, 0.0f, 0.0f);
+        auto uv = [&](float& u, float& v) { u = pu; v = pv; };
+        if (shade(a.mats, a.atlas, rec, uv, ray, att, rng, out)) { color = att; d_term = mk(0.0f, 0.0f, 0.0f); } // scattered: the new attenuation
+        else { color = out; d_term = out; }                                                                       // absorbed: the emitted colour
+      }
+      alb = alb + color; nrm = nrm + n_term; dir = dir + d_term;
+      dep = dep + t_term; cov = cov + c_term;
+      if (s == 0) first_id = hittable;
+    }
+    const float n = (float)a.samples;
+    alb = alb / n; nrm = nrm / n; dir = dir / n; dep = dep / n; cov = cov / n; // render.hpp:102
+  }
+  // whole frames: pixels outside the frame have no element; shards: padding pixels get 0, and -1 in `id`
+  if (!in_frame) {
+    if (!sharded) return;
+    alb = nrm = dir = mk(0.0f, 0.0f, 0.0f); dep = cov = 0.0f; first_id = -1;
+  }
+  if (a.albedo) store_rgb(a.albedo + at * 3, alb);
+  if (a.normal) store_rgb(a.normal + at * 3, nrm);
+  if (a.direct) store_rgb(a.direct + at * 3, dir);
+  if (a.depth) a.depth[at] = dep;
+  if (a.coverage) a.coverage[at] = cov;
+  if (a.id) a.id[at] = first_id;
+}
+
 // ---- probes ---------------------------------------------------------------------------------
 template <bool IMG, int WALK = 1>
 __global__ void bounce_kernel(const f4* __restrict__ blob, int n_runs, const f4* __restrict__ mats, const f4* __restrict__ pool,
@@ -1409,6 +1508,7 @@ struct PtScene {
   int n_hittables = 0;
   mutable bool last_had_wide_phase = false;
   mutable int last_launch[4] = {0, 0, 0, 0}; // what the launcher decided for the last frame launch: workgroups, lanes_cap, heavy_pixels, queued walk (pt_debug_last_launch)
+  mutable int last_aov[2] = {0, 0}; // the last AOV pass's kernel: sphere-grid walk (1 / 2), u,v tracked (pt_debug_last_aov)
   mutable int nsplit_override = 0; // PT_SPLIT_TILES tuning knob (host copy must outlive the async upload)
   float traversal_cost = 0.0f; // estimated VALU instructions of one ray's scan of the list (sphere runs through their lists)
   int grid_spheres = 0;        // spheres that sit in a culling grid (the resident non-cooperative kernels walk it)
@@ -2311,6 +2411,70 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
   return launch(pv);
 }
 
+// ---- first-hit feature buffers: the AOV pass (aov_kernel) -------------------------------------------------------------------------
+// What pt_render_aov refuses, checked on the host before any device call (`depth` and the scheduling flags mean nothing to the pass).
+static int check_aov_params(const PtRenderParams* p) {
+  if (!p) return fail(PT_ERR_INVALID_ARG, "render params are NULL");
+  if (p->width <= 0 || p->height <= 0) return fail(PT_ERR_INVALID_ARG, "width and height must be > 0");
+  if (p->shard_count < 1 || p->shard_index < 0 || p->shard_index >= p->shard_count)
+    return fail(PT_ERR_INVALID_ARG, "need 0 <= shard_index < shard_count");
+  if (p->flags & (PT_FLAG_FAST_RNG | PT_FLAG_SINGLE_STREAM))
+    return fail(PT_ERR_INVALID_ARG, "the AOV pass is defined on the reference's stream per pixel: no PT_FLAG_FAST_RNG, no PT_FLAG_SINGLE_STREAM");
+  return PT_OK;
+}
+
+// The launch: which aov_kernel (IMG: u,v tracked through the scan, as the scene's render kernels do; WALK: the sphere-grid walk the
+// launcher would pick for a frame of these parameters), one wave per tile of the planes.  Nothing is allocated and none of the scene's
+// launch workspaces is read or written.
+static int launch_aov(const PtScene* s, const PtCamera* cam, const PtRenderParams* p, const PtAovBuffers* b, hipStream_t st) {
+  int cur = -1;
+  PT_HIP(hipGetDevice(&cur));
+  if (cur != s->device) return fail(PT_ERR_INVALID_ARG, "pt_render_aov: the scene lives on another device (hipSetDevice to the scene's device first)");
+  AovArgs a;
+  std::memcpy(&a.cam, cam, sizeof(Cam));
+  a.blob = s->blob.p; a.mats = s->mats; a.pool = s->pool.p; a.atlas = s->atlas.p;
+  a.albedo = b->albedo; a.normal = b->normal; a.direct = b->direct; a.depth = b->depth; a.coverage = b->coverage; a.id = b->id;
+  a.n_runs = s->n_runs;
+  a.width = p->width; a.height = p->height; a.samples = p->samples;
+  a.inv_w = 1.0f / (float)p->width; a.inv_h = 1.0f / (float)p->height; // host IEEE division: correctly rounded
+  a.pinhole = cam_is_pinhole(a.cam) ? 1 : 0;
+  a.fast_ok = s->fast_ok ? 1 : 0;
+  a.shard_index = p->shard_index; a.shard_count = p->shard_count;
+  a.n_tiles = n_tiles_of(p, &a.tiles_x);
+  a.local_tiles = p->shard_count == 1 ? a.n_tiles : (a.n_tiles + p->shard_count - 1) / p->shard_count;
+  std::lock_guard<std::mutex> lock(s->sched); // (choose_variant caches its occupancy queries on the scene; last_aov)
+  bool queued_walk = false;
+  if (s->grid_spheres > 0) {
+    PtRenderParams q = *p; // (the scheduling flags are ignored: the walk of an ordinary frame launch)
+    q.flags = 0; q.depth = 1;
+    const int local_tiles = local_tiles_of(&q);
+    const Variant v = choose_variant(s, &q, local_tiles, false, local_tiles * PT_TILE_PIXELS);
+    if (v.rc) return v.rc;
+    queued_walk = v.queued_walk;
+  }
+  const auto kernel = s->track_uv ? (queued_walk ? aov_kernel<true, 2> : aov_kernel<true, 1>) : (queued_walk ? aov_kernel<false, 2> : aov_kernel<false, 1>);
+  hipLaunchKernelGGL(kernel, dim3((a.local_tiles + kWavesPerBlock - 1) / kWavesPerBlock), dim3(kBlock), 0, st, a);
+  PT_HIP(hipGetLastError());
+  s->last_aov[0] = queued_walk ? 2 : 1; s->last_aov[1] = s->track_uv ? 1 : 0;
+  return PT_OK;
+}
+
+int64_t pt_aov_plane_elems(const PtRenderParams* p, int32_t channels) {
+  if (check_aov_params(p) || (channels != 1 && channels != 3)) return -1;
+  if (p->shard_count == 1) return (int64_t)p->width * p->height * channels;
+  return (int64_t)((n_tiles_of(p, nullptr) + p->shard_count - 1) / p->shard_count) * PT_TILE_PIXELS * channels;
+}
+
+int pt_render_aov(const PtScene* scene, const PtCamera* cam, const PtRenderParams* p, const PtAovBuffers* buffers, void* stream) {
+  if (!scene || !cam || !p || !buffers) return fail(PT_ERR_INVALID_ARG, "pt_render_aov: NULL argument");
+  if (int rc = check_aov_params(p)) return rc;
+  if (p->samples < 1 || p->samples > (1 << 24)) return fail(PT_ERR_INVALID_ARG, "pt_render_aov: need 1 <= samples <= 2^24 (coverage stays exact)");
+  if (buffers->struct_size != (int32_t)sizeof(PtAovBuffers)) return fail(PT_ERR_INVALID_ARG, "pt_render_aov: PtAovBuffers.struct_size is not this library's");
+  if (!buffers->albedo && !buffers->normal && !buffers->direct && !buffers->depth && !buffers->coverage && !buffers->id)
+    return fail(PT_ERR_INVALID_ARG, "pt_render_aov: no plane asked for");
+  return launch_aov(scene, cam, p, buffers, (hipStream_t)stream);
+}
+
 int pt_scene_reserve(const PtScene* scene, const PtRenderParams* p) {
   if (!scene) return fail(PT_ERR_INVALID_ARG, "pt_scene_reserve: NULL scene");
   int rc = check_params(p);
@@ -2913,6 +3077,13 @@ int pt_debug_last_launch(const PtScene* scene, int32_t out[4]) {
   if (!scene || !out) return fail(PT_ERR_INVALID_ARG, "pt_debug_last_launch: NULL argument");
   std::lock_guard<std::mutex> lock(scene->sched);
   for (int k = 0; k < 4; k++) out[k] = scene->last_launch[k];
+  return PT_OK;
+}
+
+int pt_debug_last_aov(const PtScene* scene, int32_t out[2]) {
+  if (!scene || !out) return fail(PT_ERR_INVALID_ARG, "pt_debug_last_aov: NULL argument");
+  std::lock_guard<std::mutex> lock(scene->sched);
+  out[0] = scene->last_aov[0]; out[1] = scene->last_aov[1];
   return PT_OK;
 }
 

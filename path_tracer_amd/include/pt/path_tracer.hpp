@@ -361,6 +361,37 @@ void render(frame_buffer& frame_buf, std::vector<hittable_t>& hittables, camera&
   render(width, height, samples, frame_buf, hittables, cam);
 }
 
+// First-hit feature buffers (include/pt_render.h: pt_render_aov) — guide images for a denoiser, mattes for compositing: the render at
+// depth 1 with the first bounce's record kept, `samples` camera rays per pixel from the pixel's own stream, a pass that needs nothing
+// from render().  The planes are DEVICE buffers the caller owns, as in the C ABI (this header does no device allocation): albedo, normal,
+// direct hold aov_plane_elems(..., 3) floats, laid out like render()'s frame buffer; depth, coverage and id aov_plane_elems(..., 1)
+// elements, [height][width] ([local tile][64] for shards).  nullptr = plane not wanted.
+struct aov_buffers {
+  float* albedo = nullptr;
+  float* normal = nullptr;
+  float* direct = nullptr;
+  float* depth = nullptr;
+  float* coverage = nullptr;
+  int32_t* id = nullptr;
+};
+inline int64_t aov_plane_elems(int width, int height, int channels, int shard_index = 0, int shard_count = 1) {
+  const PtRenderParams p{width, height, 1, 1, shard_index, shard_count, 0, 0};
+  return pt_aov_plane_elems(&p, channels);
+}
+// asynchronous on `stream` (the scene must outlive the pass)
+inline void render_aov(int width, int height, int samples, const aov_buffers& planes, const device_scene& scene, const camera& cam,
+                       int shard_index = 0, int shard_count = 1, void* stream = nullptr) {
+  const PtRenderParams p{width, height, samples, 1, shard_index, shard_count, 0, 0};
+  const PtAovBuffers b{(int32_t)sizeof(PtAovBuffers), 0, planes.albedo, planes.normal, planes.direct, planes.depth, planes.coverage, planes.id};
+  check(pt_render_aov(scene.s, &cam.c, &p, &b, stream), "pt_render_aov");
+}
+// from a list of hittables: the planes are complete on return (the temporary scene's release waits for the device)
+inline void render_aov(int width, int height, int samples, const aov_buffers& planes, const std::vector<hittable_t>& hittables,
+                       const camera& cam, int shard_index = 0, int shard_count = 1) {
+  device_scene scene(hittables);
+  render_aov(width, height, samples, planes, scene, cam, shard_index, shard_count, nullptr);
+}
+
 // Progressive rendering: one frame in sample windows; RAII over pt_accum_create / pt_accum_destroy (include/pt_render.h, PtAccum).
 // After windows totalling N samples, resolve() holds the bits render() gives at samples = N.  The scene must outlive the accumulator;
 // windows run on the default stream (or `stream`) and are ordered like renders of the scene.

@@ -124,6 +124,41 @@ def render(width: int, height: int, samples: int, scene, cam: camera, depth: int
     return out
 
 
+def render_aov(width: int, height: int, samples: int, scene, cam: camera, *, planes=abi.AOV_PLANES, shard_index: int = 0,
+               shard_count: int = 1) -> dict:
+    """First-hit feature buffers (include/pt_render.h: pt_render_aov) — guide images for a denoiser, mattes for compositing: the
+    reference's render at depth 1 with the first bounce's record kept, `samples` camera rays per pixel from the pixel's own stream, a
+    pass of its own that needs nothing from render().  Asynchronous on torch's current stream.  `scene`: as for render().
+    Returns {plane: tensor} for the `planes` asked for: albedo, normal, direct float32 [H][W][3] (y = 0 the bottom row), depth,
+    coverage float32 [H][W], id int32 [H][W] — for shard_count > 1 this shard's tiles, [tiles][64][3] and [tiles][64]."""
+    import torch
+
+    if not torch.cuda.is_available():
+        raise RuntimeError("path_tracer_amd.render_aov needs a HIP device: there is no CPU path in the product")
+    lib = abi.load_library()
+    if not abi.has_aov(lib):
+        raise ImportError(f"{abi.library_path()} predates the feature buffers (no pt_render_aov entry point)")
+    planes = tuple(planes)
+    unknown = [k for k in planes if k not in abi.AOV_CHANNELS]
+    if unknown or not planes or len(set(planes)) != len(planes):
+        raise ValueError(f"planes must be a non-empty selection of {abi.AOV_PLANES} without repeats, not {planes}")
+    ds = _as_device_scene(scene, cache_key=("cuda", torch.cuda.current_device(), torch.cuda.current_stream().cuda_stream))
+    p = _params(width, height, samples, 1, shard_index, shard_count, 0)
+    n = lib.pt_aov_plane_elems(C.byref(p), 1)
+    if n < 0:
+        abi.check(abi.PT_ERR_INVALID_ARG, "pt_aov_plane_elems")
+    shape = (height, width) if shard_count == 1 else (n // abi.PT_TILE_PIXELS, abi.PT_TILE_PIXELS)
+    bufs = abi.PtAovBuffers(struct_size=C.sizeof(abi.PtAovBuffers))
+    out = {}
+    for k in planes:
+        out[k] = torch.empty(shape + ((3,) if abi.AOV_CHANNELS[k] == 3 else ()), dtype=torch.int32 if k == "id" else torch.float32, device="cuda")
+        setattr(bufs, k, out[k].data_ptr())
+    abi.check(lib.pt_render_aov(ds.handle, C.byref(cam.c), C.byref(p), C.byref(bufs), _stream_ptr(torch)), "pt_render_aov")
+    for t in out.values():
+        t._pt_scene = ds  # a scene built from a list of hittables lives as long as the planes it is still rendering into
+    return out
+
+
 def render_host(width: int, height: int, samples: int, scene, cam: camera, depth: int = 50, *, flags: int = 0,
                 shard_index: int = 0, shard_count: int = 1) -> np.ndarray:
     """Torch-free path: pt_render_host renders into a numpy array (allocates, copies back, syncs)."""
