@@ -280,7 +280,8 @@ const char* pt_build_id(void);
  *   lanes_cap          sphere-grid kernels on frames that do not fill the chip: lanes of a wave that take pixels (PT_LANES_CAP=n; 0: 16 x
  *                      pixels per resident lane, whole tiles from 24 on; -1 or PT_LANES_CAP=0: whole tiles always)
  *   grid_walk          which sphere-grid walk: 1 wave-synchronous (each lane tests its candidate in place), 2 through the LDS pair queue
- *                      (64 pairs per batch); 0: the launcher's rule (PT_GRID_WALK)
+ *                      (64 pairs per batch); 0: the launcher's rule (PT_GRID_WALK).  Only the LDS-resident ordinary kernels have walk 2:
+ *                      the scalar-cache, fast-mode and cold-state kernels (scenes up to 10 KB without image textures) walk in place
  *   heavy_tiles        sphere-grid kernels on launches bound by their heaviest tiles' chains (1.5 ... 6 pixels per resident lane): the first
  *                      n tiles of the cost-sorted order are handed out 16 pixels at a time, a quarter tile per wave (PT_HEAVY_TILES=n;
  *                      0: one tile per SIMD of the chip in that range, none outside; -1: never)
@@ -605,6 +606,14 @@ int pt_debug_schedule(const PtScene* scene, int32_t out[2]);
  * cost-sorted order that are handed out 16 pixels at a time (PtTuning.heavy_tiles' rule; 0 = none), out[3] = 1 if the sphere-grid walk
  * through the LDS pair queue was picked.  For tests of those rules.                                                                  */
 int pt_debug_last_launch(const PtScene* scene, int32_t out[4]);
+
+/* Which kernel instantiations the LAST pt_render / pt_render_accumulate of this scene launched: out[0..11] the cost-probe pass,
+ * out[12..23] the frame pass.  Word 0 of a pass is the kernel family — 0 no such pass, 1 render_kernel, 2 render_kernel_stream,
+ * 3 the single-stream kernel (PT_FLAG_SINGLE_STREAM), 4 the binned renderer's step / finish pair — and the words after it are that
+ * family's template arguments in the template's order (csrc/pt_device.hpp; unused words 0): render_kernel UV, LDS, MLDS, COOP, CL, FAST,
+ * BADOUEL, GRID, TRIPOOL, MATS, BLOCK; render_kernel_stream UV, FAST, BADOUEL; binned UV, MATS.  The launcher takes a kernel and its
+ * tag from one constant (csrc/pt_render.hip: picked_of), so the tag is the kernel that ran.  For tests (tests/kernel_variant_cases.py). */
+int pt_debug_last_kernels(const PtScene* scene, int32_t out[24]);
 
 /* Which aov_kernel the LAST pt_render_aov of this scene launched: out[0] = its sphere-grid walk (1 wave-synchronous, 2 through the LDS pair
  * queue; scenes without a sphere grid: 1), out[1] = 1 if u,v are tracked through the scan; both 0 before the first pass.  For tests.  */

@@ -166,6 +166,7 @@ SIGNATURES = {
                                        C.POINTER(C.c_uint32), C.POINTER(PtCameraRay), C.c_int32]),
     "pt_debug_schedule": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "pt_debug_last_launch": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "pt_debug_last_kernels": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "pt_debug_flatten": (C.c_int, [C.POINTER(PtSceneDesc), _FP, C.c_int64, C.POINTER(C.c_int32),
                                    C.POINTER(C.c_int32), _FP, C.c_int64, C.POINTER(C.c_int32)]),
     "pt_debug_math": (C.c_int, [C.c_int32, _FP, _FP, _FP, C.c_int64]),

@@ -1465,6 +1465,11 @@ struct Knobs {
   }
 };
 
+// Which kernel instantiation a pass launched (pt_debug_last_kernels): w[0] the family, then that family's template arguments in the
+// template's order — render_kernel: the eleven KV members; render_kernel_stream: UV, FAST, BADOUEL; the binned pair: UV, MATS.
+enum { KFAM_NONE = 0, KFAM_RENDER = 1, KFAM_STREAM = 2, KFAM_SINGLE = 3, KFAM_BINNED = 4 };
+struct KTag { int w[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; };
+
 struct EventPair { // RAII: no leak on an early return
   hipEvent_t e0 = nullptr, e1 = nullptr;
   ~EventPair() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
@@ -1508,6 +1513,7 @@ struct PtScene {
   int n_hittables = 0;
   mutable bool last_had_wide_phase = false;
   mutable int last_launch[4] = {0, 0, 0, 0}; // what the launcher decided for the last frame launch: workgroups, lanes_cap, heavy_pixels, queued walk (pt_debug_last_launch)
+  mutable KTag last_kernels[2];     // the kernels of the last pt_render / pt_render_accumulate: [0] the probe pass, [1] the frame pass (pt_debug_last_kernels)
   mutable int last_aov[2] = {0, 0}; // the last AOV pass's kernel: sphere-grid walk (1 / 2), u,v tracked (pt_debug_last_aov)
   mutable int nsplit_override = 0; // PT_SPLIT_TILES tuning knob (host copy must outlive the async upload)
   float traversal_cost = 0.0f; // estimated VALU instructions of one ray's scan of the list (sphere runs through their lists)
@@ -1562,6 +1568,12 @@ typedef void (*Kernel)(KArgs);
 // (the only place that lists render_kernel's parameters by position)
 template <KV V>
 constexpr Kernel kernel_of = render_kernel<V.uv, V.lds, V.mlds, V.coop, V.cl, V.fast, V.badouel, V.grid, V.tripool, V.mats, V.block>;
+// A kernel and the tag that names it, from ONE constant: the launcher picks kernels only through these, so the two cannot disagree.
+struct Picked { Kernel kernel; KTag tag; };
+template <KV V>
+constexpr Picked picked_of = {kernel_of<V>, {{KFAM_RENDER, V.uv, V.lds, V.mlds, V.coop, V.cl, V.fast, V.badouel, V.grid, V.tripool, V.mats, V.block}}};
+template <int UV, bool FAST = false, bool BADOUEL = false>
+constexpr Picked stream_of = {render_kernel_stream<UV, FAST, BADOUEL>, {{KFAM_STREAM, UV, FAST, BADOUEL}}};
 
 // Resident workgroups per CU of a kernel variant: queried once per scene, then from PtScene.occupancy.  < 0: the query failed (pt_last_error).
 int occupancy_of(const PtScene* s, const void* kernel, int block_threads, size_t shmem) {
@@ -1578,31 +1590,33 @@ int occupancy_of(const PtScene* s, const void* kernel, int block_threads, size_t
 int uv_of(const PtScene* s) { return s->track_uv ? UV_TRACKED : s->has_image ? UV_WINNER : UV_NONE; }
 
 // The triangle-pool kernel of a scene's UV mode: what choose_variant picks for such a scene, and what reserve_tricache sizes the cache for.
-Kernel tripool_kernel(int uv, bool fast) {
+Picked tripool_kernel(int uv, bool fast) {
   switch (uv) {
-    case UV_TRACKED: return fast ? kernel_of<KV{.uv = UV_TRACKED, .fast = true, .tripool = true}> : kernel_of<KV{.uv = UV_TRACKED, .tripool = true}>;
-    case UV_WINNER: return fast ? kernel_of<KV{.uv = UV_WINNER, .fast = true, .tripool = true}> : kernel_of<KV{.uv = UV_WINNER, .tripool = true}>;
-    default: return fast ? kernel_of<KV{.fast = true, .tripool = true}> : kernel_of<KV{.tripool = true}>;
+    case UV_TRACKED: return fast ? picked_of<KV{.uv = UV_TRACKED, .fast = true, .tripool = true}> : picked_of<KV{.uv = UV_TRACKED, .tripool = true}>;
+    case UV_WINNER: return fast ? picked_of<KV{.uv = UV_WINNER, .fast = true, .tripool = true}> : picked_of<KV{.uv = UV_WINNER, .tripool = true}>;
+    default: return fast ? picked_of<KV{.fast = true, .tripool = true}> : picked_of<KV{.tripool = true}>;
   }
 }
 
 // The headline family's kernel — no image texture, no grid walk — for the material and hittable kinds MATS; `cold`: cold lane state in LDS
 template <int MATS>
-Kernel headline_kernel(bool lds, bool mlds, bool cold) {
-  if (!lds) return kernel_of<KV{.grid = 0, .mats = MATS}>;
-  if (cold) return kernel_of<KV{.lds = true, .mlds = true, .cl = true, .grid = 0, .mats = MATS}>;
-  return mlds ? kernel_of<KV{.lds = true, .mlds = true, .grid = 0, .mats = MATS}> : kernel_of<KV{.lds = true, .grid = 0, .mats = MATS}>;
+Picked headline_kernel(bool lds, bool mlds, bool cold) {
+  if (!lds) return picked_of<KV{.grid = 0, .mats = MATS}>;
+  if (cold) return picked_of<KV{.lds = true, .mlds = true, .cl = true, .grid = 0, .mats = MATS}>;
+  return mlds ? picked_of<KV{.lds = true, .mlds = true, .grid = 0, .mats = MATS}> : picked_of<KV{.lds = true, .grid = 0, .mats = MATS}>;
 }
 
 // The binned renderer's two kernels that shade (pt_binned.hpp), compiled for a scene's UV mode and material kinds
-struct BinKernels { void (*step)(BinArgs); void (*finish)(BinArgs); };
+struct BinKernels { void (*step)(BinArgs); void (*finish)(BinArgs); KTag tag; };
 template <int UV, int MATS>
-constexpr BinKernels bin_kernels = {bin_step_kernel<UV, MATS>, bin_finish_kernel<UV, MATS>};
+constexpr BinKernels bin_kernels = {bin_step_kernel<UV, MATS>, bin_finish_kernel<UV, MATS>, {{KFAM_BINNED, UV, MATS}}};
 
 // What choose_variant decides for one pass of launch_render: the kernel, and the facts about it that the launch reads.
 struct Variant {
   int rc = PT_OK;          // != PT_OK: no kernel (pt_last_error says why)
   Kernel kernel = nullptr;
+  KTag tag;                // ... and its name (pt_debug_last_kernels): both set by pick() alone
+  void pick(const Picked& k) { kernel = k.kernel; tag = k.tag; }
   size_t shmem = 0;        // dynamic LDS: the blob image (+ the material table) of the LDS-resident kernels
   int coop_prefix = -1;    // KArgs.coop_prefix
   bool tri_pool = false;   // the scene's triangle pools are queried (the TRIPOOL kernels)
@@ -1647,33 +1661,38 @@ Variant choose_variant_uv(const PtScene* s, const PtRenderParams* p, int local_t
 
   if (s->has_badouel) { // parity-completeness path: scalar-cache or streaming kernel with the Badouel loop compiled in
     if (fast) { v.rc = fail(PT_ERR_INVALID_ARG, "PT_FLAG_FAST_RNG is not offered for scenes with Badouel-strategy triangles"); return v; }
-    v.kernel = !v.resident ? render_kernel_stream<UV, false, true> : kernel_of<KV{.uv = UV, .badouel = true}>;
+    v.pick(!v.resident ? stream_of<UV, false, true> : picked_of<KV{.uv = UV, .badouel = true}>);
     return v;
   }
   if (fast) { // opt-in decorrelated mode: its own instantiations (no cooperative kernels: a chunk is short)
-    if (v.tri_pool) v.kernel = tripool_kernel(UV, true);
-    else if (!v.resident) v.kernel = render_kernel_stream<UV, true>;
-    else if (!lds) v.kernel = kernel_of<KV{.uv = UV, .fast = true}>;
-    else v.kernel = mlds ? kernel_of<KV{.uv = UV, .lds = true, .mlds = true, .fast = true}> : kernel_of<KV{.uv = UV, .lds = true, .fast = true}>;
+    if (v.tri_pool) v.pick(tripool_kernel(UV, true));
+    else if (!v.resident) v.pick(stream_of<UV, true>);
+    else if (!lds) v.pick(picked_of<KV{.uv = UV, .fast = true}>);
+    else v.pick(mlds ? picked_of<KV{.uv = UV, .lds = true, .mlds = true, .fast = true}> : picked_of<KV{.uv = UV, .lds = true, .fast = true}>);
     return v;
   }
-  if (v.tri_pool) { v.kernel = tripool_kernel(UV, false); return v; }
-  if (!v.resident) { v.kernel = render_kernel_stream<UV>; return v; }
+  if (v.tri_pool) { v.pick(tripool_kernel(UV, false)); return v; }
+  if (!v.resident) { v.pick(stream_of<UV>); return v; }
   if constexpr (UV == UV_NONE) { // no image texture and no sphere grid (the headline scene): kernels without the grid walk
     if (s->grid_spheres == 0 && !v.coop) {
       v.chain_bound = true;
       // lambertian + lightsource over solid textures: kernels without the other materials' code
       // ... and every hittable a rect or a box (the headline scene): resolve_hit without the other kinds
-      v.kernel = !s->mats_simple    ? headline_kernel<MATS_ALL>(lds, mlds, cold)
-                 : !s->rectbox_only ? headline_kernel<MATS_LAMB_LIGHT_SOLID>(lds, mlds, cold)
-                                    : headline_kernel<MATS_LAMB_LIGHT_SOLID | MATS_RECTBOX_ONLY>(lds, mlds, cold);
+      v.pick(!s->mats_simple    ? headline_kernel<MATS_ALL>(lds, mlds, cold)
+             : !s->rectbox_only ? headline_kernel<MATS_LAMB_LIGHT_SOLID>(lds, mlds, cold)
+                                : headline_kernel<MATS_LAMB_LIGHT_SOLID | MATS_RECTBOX_ONLY>(lds, mlds, cold));
       return v;
     }
   }
-  if (!lds) { v.kernel = kernel_of<KV{.uv = UV}>; return v; }
-  if (v.coop) { v.kernel = mlds ? kernel_of<KV{.uv = UV, .lds = true, .mlds = true, .coop = true}> : kernel_of<KV{.uv = UV, .lds = true, .coop = true}>; return v; }
+  if (!lds) { v.pick(picked_of<KV{.uv = UV}>); return v; }
+  // (UV_TRACKED scenes are never cooperative — track_uv is has_image && !coop_ok, and coop_prefix then stays -1 — so no such kernel is compiled)
+  if constexpr (UV != UV_TRACKED) {
+    if (v.coop) { v.pick(mlds ? picked_of<KV{.uv = UV, .lds = true, .mlds = true, .coop = true}> : picked_of<KV{.uv = UV, .lds = true, .coop = true}>); return v; }
+  }
   if constexpr (UV == UV_NONE) {
-    if (cold) { v.kernel = kernel_of<KV{.lds = true, .mlds = true, .cl = true}>; return v; }
+    // (deliberately BEFORE the choice of walk: the cold-state kernel has the in-place walk only, so a scene this small keeps it even under
+    // PtTuning.grid_walk = 2 — the pair queue's static LDS and extra live values would cost the occupancy CL buys)
+    if (cold) { v.pick(picked_of<KV{.lds = true, .mlds = true, .cl = true}>); return v; }
   }
   if (v.use_grid) {
     // Which sphere-grid walk (pt_device.hpp: sphere_scan, GRID = 1 / 2): the pair queue where walks diverge or the launch is bound by its
@@ -1684,10 +1703,10 @@ Variant choose_variant_uv(const PtScene* s, const PtRenderParams* p, int local_t
     // `launch` from the measured occupancy, and the two could disagree.  The queued walk's STATIC 4 KB of LDS (sphere_queue,
     // sphere_slots) ride on top of the dynamic blob image: where the sum exceeds what a workgroup may have, the walk stays in place.
     constexpr size_t kQueuedWalkStaticLds = (size_t)PT_MAX_WAVES_PER_BLOCK * (PT_SQ_CAP * 4 + 64 * 8);
-    const Kernel queued = mlds ? kernel_of<KV{.uv = UV, .lds = true, .mlds = true, .grid = 2}> : kernel_of<KV{.uv = UV, .lds = true, .grid = 2}>;
+    const Picked queued = mlds ? picked_of<KV{.uv = UV, .lds = true, .mlds = true, .grid = 2}> : picked_of<KV{.uv = UV, .lds = true, .grid = 2}>;
     int per_cu_queued = 0; // (stays 0 where the queued walk's LDS does not fit: never asked)
     if (v.shmem + kQueuedWalkStaticLds <= s->lds_per_block) {
-      per_cu_queued = occupancy_of(s, (const void*)queued, kBlock, v.shmem);
+      per_cu_queued = occupancy_of(s, (const void*)queued.kernel, kBlock, v.shmem);
       if (per_cu_queued < 0) { v.rc = PT_ERR_HIP; return v; }
     }
     if (s->knobs.blocks_per_cu) per_cu_queued = std::min(per_cu_queued, s->knobs.blocks_per_cu);
@@ -1698,9 +1717,9 @@ Variant choose_variant_uv(const PtScene* s, const PtRenderParams* p, int local_t
     const bool dense_and_busy = (double)p->width * p->height >= 4.0e6 && rho >= 6.0;
     v.queued_walk = fits && (s->knobs.grid_walk == 2 || (s->knobs.grid_walk == 0 && !few_lanes && !dense_and_busy && !(s->knobs.lanes_cap > 0 && s->knobs.lanes_cap < 16)));
     // the sphere-grid walk through the pair queue (pt_device.hpp: sphere_scan says where it pays)
-    if (v.queued_walk) { v.kernel = queued; return v; }
+    if (v.queued_walk) { v.pick(queued); return v; }
   }
-  v.kernel = mlds ? kernel_of<KV{.uv = UV, .lds = true, .mlds = true}> : kernel_of<KV{.uv = UV, .lds = true}>;
+  v.pick(mlds ? picked_of<KV{.uv = UV, .lds = true, .mlds = true}> : picked_of<KV{.uv = UV, .lds = true}>);
   return v;
 }
 
@@ -2056,7 +2075,8 @@ static int launch_binned(const PtScene* s, KArgs a, const PtRenderParams* p, int
   PT_HIP(hipMemsetAsync(sa.ctl, 0, 64, st));
   const dim3 step_grid((unsigned int)((N + kBlock - 1) / kBlock)), step_block(kBlock);
   const int band_blocks = std::max(1, s->num_cus) * 6;
-  const BinKernels bk = s->has_image ? (s->mats_simple ? bin_kernels<UV_WINNER, MATS_LAMB_LIGHT_SOLID> : bin_kernels<UV_WINNER, MATS_ALL>)
+  // (a scene with an image texture has a material that is not "simple" — mats_simple wants solid textures only — so UV_WINNER comes with MATS_ALL alone)
+  const BinKernels bk = s->has_image ? bin_kernels<UV_WINNER, MATS_ALL>
                                      : (s->mats_simple ? bin_kernels<UV_NONE, MATS_LAMB_LIGHT_SOLID> : bin_kernels<UV_NONE, MATS_ALL>);
   auto step = [&](int gen) -> int {
     ba.gen = gen;
@@ -2097,6 +2117,7 @@ static int launch_binned(const PtScene* s, KArgs a, const PtRenderParams* p, int
     live = 0;
   }
   s->last_generations = gen;
+  s->last_kernels[1] = bk.tag;
   s->last_launch[0] = (int)step_grid.x; s->last_launch[1] = 64; s->last_launch[2] = 0; s->last_launch[3] = 0;
   if (live != 0) return fail(PT_ERR_HIP, "pt_render: the binned renderer did not finish within samples x depth generations");
   return PT_OK;
@@ -2131,6 +2152,7 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
     return fail(PT_ERR_INVALID_ARG, "pt_render: the scene lives on device " + std::to_string(s->device) + " but the current device is " +
                                         std::to_string(cur) + " (hipSetDevice to the scene's device first)");
   std::lock_guard<std::mutex> lock(s->sched);
+  s->last_kernels[0] = s->last_kernels[1] = KTag{}; // (a pass that does not run leaves family 0)
   KArgs a;
   std::memcpy(&a.cam, cam, sizeof(Cam));
   a.blob = s->blob.p; a.mats = s->mats; a.pool = s->pool.p; a.atlas = s->atlas.p; a.fb = fb;
@@ -2155,6 +2177,7 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
     if (p->depth <= 0) return PT_OK;
     hipLaunchKernelGGL(render_single_stream_kernel, dim3(1), dim3(64), 0, st, a);
     PT_HIP(hipGetLastError());
+    s->last_kernels[1].w[0] = KFAM_SINGLE;
     return PT_OK;
   }
   // (sample windows run the persistent kernels: both renderers give the reference's image, and only these resume a pixel)
@@ -2300,6 +2323,7 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
     PT_HIP(hipMemsetAsync(a.queue, 0, 2 * sizeof(unsigned int), st));
     hipLaunchKernelGGL(v.kernel, grid, block, shmem, st, a);
     PT_HIP(hipGetLastError());
+    s->last_kernels[a.cost ? 0 : 1] = v.tag;
     PT_HIP(hipEventRecord(s->ring_done[slot], st));
     return PT_OK;
   };
@@ -2670,7 +2694,7 @@ int check_header(const AccumHeader& h, const PtAccum* acc, int64_t bytes, const 
 // the triangle-pool kernels' candidate cache for every lane they can launch (launch_render would otherwise grow it on a window)
 int reserve_tricache(const PtScene* s, uint32_t flags) {
   if (s->tri_pooled <= 0 || s->knobs.no_tri_cache || (flags & PT_FLAG_FORCE_STREAM)) return PT_OK;
-  int per_cu = occupancy_of(s, (const void*)tripool_kernel(uv_of(s), (flags & PT_FLAG_FAST_RNG) != 0), kBlock, 0);
+  int per_cu = occupancy_of(s, (const void*)tripool_kernel(uv_of(s), (flags & PT_FLAG_FAST_RNG) != 0).kernel, kBlock, 0);
   if (per_cu < 0) return PT_ERR_HIP;
   if (s->knobs.blocks_per_cu) per_cu = std::min(per_cu, s->knobs.blocks_per_cu);
   return grow_tricache(s, (size_t)std::max(1, per_cu) * (size_t)std::max(1, s->num_cus) * kBlock);
@@ -3077,6 +3101,14 @@ int pt_debug_last_launch(const PtScene* scene, int32_t out[4]) {
   if (!scene || !out) return fail(PT_ERR_INVALID_ARG, "pt_debug_last_launch: NULL argument");
   std::lock_guard<std::mutex> lock(scene->sched);
   for (int k = 0; k < 4; k++) out[k] = scene->last_launch[k];
+  return PT_OK;
+}
+
+int pt_debug_last_kernels(const PtScene* scene, int32_t out[24]) {
+  if (!scene || !out) return fail(PT_ERR_INVALID_ARG, "pt_debug_last_kernels: NULL argument");
+  std::lock_guard<std::mutex> lock(scene->sched);
+  for (int pass = 0; pass < 2; pass++)
+    for (int k = 0; k < 12; k++) out[12 * pass + k] = scene->last_kernels[pass].w[k];
   return PT_OK;
 }
 

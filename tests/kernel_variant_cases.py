@@ -1,0 +1,259 @@
+"""One recipe per kernel instantiation the launcher can pick (csrc/pt_render.hip: choose_variant, launch_binned, launch_aov), shared by
+tests/test_kernel_resources_cpu.py — the table's tags must be exactly the instantiations the library compiles — and
+tests/test_gpu_kernel_variants.py — every recipe renders against the oracle and pt_debug_last_kernels must report its tag.
+
+A tag is (kernel name, template arguments in the template's order):
+  ("render_kernel", UV, LDS, MLDS, COOP, CL, FAST, BADOUEL, GRID, TRIPOOL, MATS, BLOCK)     UV: 0 none, 1 of the winner, 2 tracked
+  ("render_kernel_stream", UV, FAST, BADOUEL)
+  ("render_single_stream_kernel",)
+  ("bin_step_kernel", UV, MATS)          (the binned renderer's step / finish pair)
+  ("aov_kernel", IMG, WALK)
+A recipe is a scene builder of this file, a PtTuning (as keywords of abi.tuning) or the environment test_gpu_fuzz.tri_pools sets while
+the scene is created, and render flags; its comment names the scene fact that selects the kernel.  A new kernel variant needs its
+instantiation in the launcher and its row here — the CPU test fails until both exist."""
+import collections
+import ctypes as C
+
+import numpy as np
+
+from path_tracer_amd import abi, scenes
+from path_tracer_amd.scene import (TextureAtlas, box, checker_texture, dielectric_material, image_texture, lambertian_material,
+                                   lightsource_material, metal_material, pack, sphere, triangle, xy_rect, xz_rect)
+
+MATS_ALL, MATS_SIMPLE, MATS_RECTBOX = 287, 9, 65545  # pt_device.hpp: MATS_ALL, MATS_LAMB_LIGHT_SOLID, ... | MATS_RECTBOX_ONLY
+BLOCK = 256
+FAMILY = {1: ("render_kernel", 11), 2: ("render_kernel_stream", 3), 3: ("render_single_stream_kernel", 0), 4: ("bin_step_kernel", 2)}
+
+NO_LDS, STREAM, NO_COOP, COOP = abi.PT_FLAG_NO_LDS, abi.PT_FLAG_FORCE_STREAM, abi.PT_FLAG_NO_COOP, abi.PT_FLAG_FORCE_COOP
+FAST, SINGLE = abi.PT_FLAG_FAST_RNG, abi.PT_FLAG_SINGLE_STREAM
+
+
+def rk(uv=0, lds=0, mlds=0, coop=0, cl=0, fast=0, badouel=0, grid=1, tripool=0, mats=MATS_ALL):
+    return ("render_kernel", uv, lds, mlds, coop, cl, fast, badouel, grid, tripool, mats, BLOCK)
+
+
+def st(uv=0, fast=0, badouel=0):
+    return ("render_kernel_stream", uv, fast, badouel)
+
+
+def decode(words):
+    """One pass's 12 words of pt_debug_last_kernels as a tag; None: no such pass."""
+    words = [int(x) for x in words]
+    if words[0] == 0:
+        assert not any(words), words
+        return None
+    name, n = FAMILY[words[0]]
+    assert not any(words[1 + n:]), words
+    return (name, *words[1:1 + n])
+
+
+def last_kernels(ds):
+    """(probe-pass tag, frame-pass tag) of a DeviceScene's last render (pt_debug_last_kernels); None: no such pass."""
+    out = (C.c_int32 * 24)()
+    abi.check(ds.lib.pt_debug_last_kernels(ds.handle, out), "pt_debug_last_kernels")
+    return decode(out[:12]), decode(out[12:])
+
+
+RK_MEMBERS = ("uv", "lds", "mlds", "coop", "cl", "fast", "badouel", "grid", "tripool", "mats", "block")
+
+
+def ran(tag, name="render_kernel", **members):
+    """Is `tag` an instantiation of kernel `name` with these template arguments (render_kernel: by KV member; render_kernel_stream: uv, fast,
+    badouel)?  For the tests that name the kernel they mean to reach: assert K.ran(frame, lds=1, cl=1), frame."""
+    if tag is None or tag[0] != name:
+        return False
+    names = RK_MEMBERS if name == "render_kernel" else ("uv", "fast", "badouel")
+    got = dict(zip(names, tag[1:]))
+    return all(got[k] == v for k, v in members.items())
+
+
+def render_host_tagged(w, h, spp, ps, c, depth=50, *, flags=0, tuning=None):
+    """R.render_host of a packed scene — its device scene created here, with `tuning` or under the environment of the moment, as
+    render_host itself does — and with the frame the (probe-pass tag, frame-pass tag) of that render."""
+    from path_tracer_amd import render as R
+    ds = R.DeviceScene(ps, tuning)
+    try:
+        fb = R.render_host(w, h, spp, ds, c, depth, flags=flags)
+        return fb, last_kernels(ds)
+    finally:
+        ds.close()
+
+
+# ---- scenes: small, deterministic, cheap for the oracle (open to the sky: most paths end after a few bounces) ------------------------
+
+CAM = dict(vup=(0, 1, 0), aperture=0.0, time0=0.0, time1=1.0)
+_COLS = [(0.8, 0.8, 0.8), (0.9, 0.2, 0.2), (0.2, 0.9, 0.2), (0.2, 0.2, 0.9)]
+
+
+def _image(atlas, freq=1.5):
+    y, x = np.mgrid[0:13, 0:17]
+    rgb = np.stack([(x * 13 + y * 5) % 256, (x * 3 + 17 * y) % 256, (x * y * 7) % 256], axis=-1).astype(np.uint8)
+    return image_texture.from_array(rgb, freq, atlas)
+
+
+def _extras(hs, extra, image, where, size, atlas):
+    """What moves a scene to another kernel family: extra = "sphere" (a lambertian sphere: not rect / box only), "metal" (a material
+    beyond lambertian + light); image = "sphere" (an image texture on a sphere: u,v of the winner), "triangle" (on a triangle: u,v tracked
+    through the scan)."""
+    x, y, z = where
+    if extra == "sphere":
+        hs.append(sphere((x, y, z), size, lambertian_material(_COLS[1])))
+    if extra == "metal":
+        hs.append(sphere((x, y, z), size, metal_material((0.8, 0.7, 0.6), 0.1)))
+    if image == "sphere":
+        hs.append(sphere((x + 2.5 * size, y, z), size, lambertian_material(_image(atlas))))
+    if image == "triangle":
+        hs.append(triangle((x + 1.5 * size, y - size, z), (x + 3.5 * size, y - size, z), (x + 2.5 * size, y + size, z + 0.3 * size),
+                           lambertian_material(_image(atlas))))
+
+
+def cornell(extra=None):
+    """The headline scene: rects and boxes, lambertian + light over solid colours; 8 hittables — records + materials far below 10 KB."""
+    hs, cam = scenes.cornell_box()
+    hs = list(hs)
+    _extras(hs, extra, None, (190, 240, 150), 60.0, None)
+    return pack(hs), cam
+
+
+def boxes(extra=None, n=150):
+    """n boxes in one slab pool: 96 bytes of records and 256 of octant table each — over the 16 KB that would hold the material table
+    in LDS too, within the 64 KB LDS image."""
+    mats = [lambertian_material(c) for c in _COLS] + [lightsource_material((4, 4, 4))]
+    hs = []
+    for i in range(n):
+        x, y, z = i % 8 - 4, (i // 8) % 5 - 2, -4 - 2 * (i // 40)
+        hs.append(box((x, y, z), (x + 0.55, y + 0.55, z + 0.55), mats[i % 5]))
+    _extras(hs, extra, None, (0.3, 0.3, -2.0), 0.4, None)
+    return pack(hs), dict(CAM, look_from=(0.3, 0.4, 3), look_at=(0, 0, -6), vfov=65.0, focus_dist=5.0)
+
+
+def field(n, image=None):
+    """n small spheres (>= 48: they get a culling grid) of six shared materials on a checkered ground, a big glass ball inside the
+    field and a triangle behind it.  n = 56: records + grid + materials under 10 KB; n = 300: over 16 KB, within 64 KB."""
+    rng = scenes.HostRNG(77 + n)
+    atlas = TextureAtlas() if image else None
+    mats = [lambertian_material(_COLS[1]), lambertian_material(_COLS[3]), metal_material((0.8, 0.8, 0.9), 0.1), dielectric_material(1.5, (1, 1, 1)),
+            lightsource_material((3, 3, 2)), lambertian_material(checker_texture((0.1, 0.1, 0.1), (0.9, 0.9, 0.9)))]
+    hs = [sphere((0, -500, 0), 500, mats[5])]
+    side = 4.0 if n < 100 else 9.0
+    for i in range(n):
+        c = (side * (float(rng.float_t()) - 0.5), 0.15 + 0.4 * float(rng.float_t()), side * (float(rng.float_t()) - 0.5))
+        r = 0.1 + 0.08 * float(rng.float_t())
+        if i % 4 == 1:
+            hs.append(sphere(c, (c[0], c[1] + 0.3 * float(rng.float_t()), c[2]), 0.0, 1.0, r, mats[i % 5]))
+        else:
+            hs.append(sphere(c, r, mats[i % 5]))
+        if i % 37 == 5:
+            hs.append(sphere(c, r, mats[(i + 1) % 5]))  # an exact duplicate later in the list: loses every tie
+    hs.append(sphere((0.0, 0.8, 0.0), 0.8, mats[3]))
+    hs.append(triangle((-1.5, 0, -side / 2 - 0.5), (1.5, 0, -side / 2 - 0.5), (0, 1.8, -side / 2 - 0.3), mats[0]))
+    _extras(hs, None, image, (-1.2, 0.6, 1.2), 0.5, atlas)
+    cam = dict(CAM, look_from=(0.9 * side, 0.35 * side, 0.8 * side), look_at=(0, 0.3, 0), vfov=40.0, aperture=0.03, focus_dist=1.25 * side)
+    return (pack(hs, atlas) if image else pack(hs)), cam
+
+
+def tris(image=None, extra=None, badouel=False, n=300):
+    """n small triangles in one run (>= 256: a triangle pool under tri_pools()) over a ground sphere, an emissive rect behind; with
+    badouel, every third triangle takes the Badouel strategy (such scenes get no pool: the kernels with that loop compiled in)."""
+    rng = scenes.HostRNG(4100)
+    atlas = TextureAtlas() if image else None
+    mats = [lambertian_material(c) for c in _COLS]
+    hs = [sphere((0, -1000, 0), 1000, mats[0])]
+    for i in range(n):
+        v0 = np.array([4 * float(rng.float_t()) - 2, 2 * float(rng.float_t()), 4 * float(rng.float_t()) - 2])
+        e1, e2 = (np.array([float(rng.float_t()) - 0.5 for _ in range(3)]) * 0.6 for _ in range(2))
+        hs.append(triangle(tuple(v0), tuple(v0 + e1), tuple(v0 + e2), mats[i % 4], "badouel" if badouel and i % 3 == 0 else "moller_trumbore"))
+        if i % 50 == 7:
+            hs.append(hs[-1])  # coplanar duplicate: the later one wins the tie
+    hs.append(xy_rect(-2, 2, 0.5, 2.5, -2.6, lightsource_material((6, 6, 6))))
+    _extras(hs, extra, image, (-0.8, 0.5, 2.4), 0.35, atlas)
+    cam = dict(CAM, look_from=(0, 1.8, 7), look_at=(0, 0.9, 0), vfov=40.0, focus_dist=7.0)
+    return (pack(hs, atlas) if image else pack(hs)), cam
+
+
+SCENES = {"cornell": cornell, "boxes": boxes, "field": field, "tris": tris}
+
+# ---- the table ------------------------------------------------------------------------------------------------------------------------
+
+Row = collections.namedtuple("Row", "tag probe scene args tuning env flags fact")
+ROWS = []
+POOL_ENV = dict(PT_LPT_SCATTER=1)  # (with tri_pools(): the cost probe also for the scattered launches of the triangle-pool kernels)
+
+
+def row(tag, scene, *args, tuning=None, env=None, flags=0, probe="same", fact=None, **kw):
+    """probe: the parity-mode tag the cost-probe pass of a frame of >= 64 tiles must report ("same": the row's own; None: the renderer
+    has no such pass); fact: "grid" / "tri_pool" — what the kernel's extra code exists for must be there."""
+    ROWS.append(Row(tag, tag if probe == "same" else probe, scene, (args, kw), tuning, env, flags, fact))
+
+
+# The headline family (no image texture, no sphere grid, not cooperative: GRID = 0), for each of the three material / hittable sets:
+# MATS_RECTBOX: rects and boxes only, lambertian + light; MATS_SIMPLE: the same materials and a sphere; MATS_ALL: a metal sphere.
+for mats, extra in ((MATS_RECTBOX, None), (MATS_SIMPLE, "sphere"), (MATS_ALL, "metal")):
+    row(rk(lds=1, mlds=1, cl=1, grid=0, mats=mats), "cornell", extra)                                     # records + materials <= 10 KB: cold lane state in LDS
+    row(rk(lds=1, mlds=1, grid=0, mats=mats), "cornell", extra, tuning=dict(cold_state=-1))               # ... PtTuning.cold_state = -1 keeps it in registers
+    row(rk(grid=0, mats=mats), "cornell", extra, flags=NO_LDS)                                            # PT_FLAG_NO_LDS: blob through the scalar cache
+    row(rk(lds=1, grid=0, mats=mats), "boxes", extra, flags=NO_COOP)                                      # 150 pooled boxes: > 16 KB, so the materials stay in memory (NO_COOP: 150 boxes would go cooperative)
+
+# Sphere fields without an image texture (UV = 0)
+row(rk(lds=1, mlds=1, cl=1), "field", 56, tuning=dict(grid_walk=2), fact="grid")                           # <= 10 KB with a grid: the cold-state kernel comes before the choice of walk, and has the in-place walk only
+row(rk(lds=1, mlds=1, grid=1), "field", 56, tuning=dict(cold_state=-1, grid_walk=1), fact="grid")         # cold_state = -1, walk 1
+row(rk(lds=1, mlds=1, grid=2), "field", 56, tuning=dict(cold_state=-1, grid_walk=2), fact="grid")         # ... walk 2: the pair queue
+row(rk(lds=1, mlds=1, coop=1), "field", 56, flags=COOP)                                                    # PT_FLAG_FORCE_COOP (decided before the cold state)
+row(rk(lds=1, grid=1), "field", 300, tuning=dict(grid_walk=1), fact="grid")                               # 300 spheres: > 16 KB
+row(rk(lds=1, grid=2), "field", 300, tuning=dict(grid_walk=2), fact="grid")
+row(rk(lds=1, coop=1), "field", 300, flags=COOP)
+row(rk(), "field", 300, flags=NO_LDS, fact="grid")                                                         # scalar cache, grid walked in place
+row(rk(lds=1, mlds=1, fast=1), "field", 56, flags=FAST, probe=rk(lds=1, mlds=1, cl=1), fact="grid")
+row(rk(lds=1, fast=1), "field", 300, tuning=dict(grid_walk=1), flags=FAST, probe=rk(lds=1, grid=1), fact="grid")
+row(rk(fast=1), "field", 300, flags=FAST | NO_LDS, probe=rk(), fact="grid")
+row(st(0), "field", 300, flags=STREAM)                                                                     # PT_FLAG_FORCE_STREAM
+row(st(0, fast=1), "field", 300, flags=STREAM | FAST, probe=st(0))
+
+# ... with an image texture on a sphere (UV = 1: u,v of the final winner) and on a triangle (UV = 2: tracked through the scan; such
+# scenes are never cooperative)
+for uv, image in ((1, "sphere"), (2, "triangle")):
+    row(rk(uv, lds=1, mlds=1, grid=1), "field", 56, image, tuning=dict(grid_walk=1), fact="grid")          # (no cold-state kernel with image textures)
+    row(rk(uv, lds=1, mlds=1, grid=2), "field", 56, image, tuning=dict(grid_walk=2), fact="grid")
+    row(rk(uv, lds=1, grid=1), "field", 300, image, tuning=dict(grid_walk=1), fact="grid")
+    row(rk(uv, lds=1, grid=2), "field", 300, image, tuning=dict(grid_walk=2), fact="grid")
+    row(rk(uv), "field", 300, image, flags=NO_LDS, fact="grid")
+    if uv == 1:
+        row(rk(uv, lds=1, mlds=1, coop=1), "field", 56, image, flags=COOP)
+        row(rk(uv, lds=1, coop=1), "field", 300, image, flags=COOP)
+    row(rk(uv, lds=1, mlds=1, fast=1), "field", 56, image, tuning=dict(grid_walk=1), flags=FAST, probe=rk(uv, lds=1, mlds=1, grid=1), fact="grid")
+    row(rk(uv, lds=1, fast=1), "field", 300, image, tuning=dict(grid_walk=1), flags=FAST, probe=rk(uv, lds=1, grid=1), fact="grid")
+    row(rk(uv, fast=1), "field", 300, image, flags=FAST | NO_LDS, probe=rk(uv), fact="grid")
+    row(st(uv), "field", 300, image, flags=STREAM)
+    row(st(uv, fast=1), "field", 300, image, flags=STREAM | FAST, probe=st(uv))
+
+# Triangles: a pooled run (tri_pools(): from 256 triangles on), Badouel-strategy triangles (no pool), the binned renderer
+for uv, image in ((0, None), (1, "sphere"), (2, "triangle")):
+    row(rk(uv, tripool=1), "tris", image, env=POOL_ENV, fact="tri_pool")
+    row(rk(uv, fast=1, tripool=1), "tris", image, env=POOL_ENV, flags=FAST, probe=rk(uv, tripool=1), fact="tri_pool")
+    row(rk(uv, badouel=1), "tris", image, badouel=True)
+    row(st(uv, badouel=1), "tris", image, badouel=True, flags=STREAM)
+row(("bin_step_kernel", 0, MATS_SIMPLE), "tris", tuning=dict(tri_min_run=256, tri_binned=1), probe=None)          # PtTuning.tri_binned; lambertian + light
+row(("bin_step_kernel", 0, MATS_ALL), "tris", None, "metal", tuning=dict(tri_min_run=256, tri_binned=1), probe=None)
+row(("bin_step_kernel", 1, MATS_ALL), "tris", "sphere", tuning=dict(tri_min_run=256, tri_binned=1), probe=None)   # (an image texture is never "simple")
+
+row(("render_single_stream_kernel",), "cornell", flags=SINGLE, probe=None)                                       # PT_FLAG_SINGLE_STREAM
+
+# The AOV pass: IMG = u,v tracked (an image texture on a triangle), WALK = the sphere-grid walk an ordinary frame would take
+AOV_ROWS = [
+    Row(("aov_kernel", 0, 1), None, "field", ((56,), {}), dict(grid_walk=1), None, 0, "grid"),
+    Row(("aov_kernel", 0, 2), None, "field", ((300,), {}), dict(grid_walk=2), None, 0, "grid"),
+    Row(("aov_kernel", 1, 1), None, "tris", (("triangle",), dict(n=40)), None, None, 0, None),
+    Row(("aov_kernel", 1, 2), None, "field", ((300, "triangle"), {}), dict(grid_walk=2), None, 0, "grid"),
+]
+
+ALL_TAGS = [r.tag for r in ROWS + AOV_ROWS]
+
+
+def row_id(r):
+    short = {"render_kernel": "rk", "render_kernel_stream": "stream", "render_single_stream_kernel": "single", "bin_step_kernel": "binned", "aov_kernel": "aov"}[r.tag[0]]
+    return "-".join([short] + [str(x) for x in r.tag[1:-1 if r.tag[0] == "render_kernel" else None]])
+
+
+def build(r):
+    args, kw = r.args
+    return SCENES[r.scene](*args, **kw)

@@ -48,6 +48,15 @@ def flatten(lib, ps):
     return blob, n_runs.value
 
 
+def flatten_tuned(lib, ps, tuning):
+    """(blob, n_runs) of pt_debug_flatten_tuned: the flattening under an explicit PtTuning"""
+    n_f4, n_runs = C.c_int32(), C.c_int32()
+    assert lib.pt_debug_flatten_tuned(C.byref(ps.desc), C.byref(tuning), None, 0, C.byref(n_f4), C.byref(n_runs), None, 0, None) == 0
+    blob = np.zeros((n_f4.value, 4), np.float32)
+    assert lib.pt_debug_flatten_tuned(C.byref(ps.desc), C.byref(tuning), blob.ctypes.data_as(C.POINTER(C.c_float)), len(blob), None, None, None, 0, None) == 0
+    return blob, n_runs.value
+
+
 def pools(blob, n_runs):
     """[(pool offset, entries, first record of the head run)] of the blob's slab pools, from the aux records of their head runs"""
     out = []

@@ -29,6 +29,18 @@ def test_library_exports_every_declared_symbol(lib):
     assert set(names) == set(abi.SIGNATURES), "abi.py and pt_render.h disagree on the entry points"
 
 
+def test_last_kernels_probe_is_declared_and_refuses_null(lib):
+    """pt_debug_last_kernels: the header's prototype, abi.py's signature, and NULL arguments refused on the host with `out` untouched
+    (what it reports is tests/test_gpu_kernel_variants.py)."""
+    text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
+    assert re.search(r"^int pt_debug_last_kernels\(const PtScene\* scene, int32_t out\[24\]\);", text, re.M)
+    assert abi.SIGNATURES["pt_debug_last_kernels"] == (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)])
+    out = (C.c_int32 * 24)(*([7] * 24))
+    assert lib.pt_debug_last_kernels(None, out) == abi.PT_ERR_INVALID_ARG and list(out) == [7] * 24
+    assert lib.pt_debug_last_kernels(C.c_void_p(0xdead0), None) == abi.PT_ERR_INVALID_ARG  # (never dereferenced)
+    assert b"pt_debug_last_kernels" in lib.pt_last_error()
+
+
 def test_abi_version_and_errors(lib):
     assert lib.pt_abi_version() == abi.PT_ABI_VERSION
     assert lib.pt_error_string(abi.PT_OK) == b"ok"

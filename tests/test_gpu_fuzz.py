@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+import kernel_variant_cases as K
 from conftest import assert_bit_identical
 from path_tracer_amd import abi, scenes
 from path_tracer_amd import render as R
@@ -220,13 +221,34 @@ def test_random_sphere_fields_through_the_culling_grid(orc, lib, seed, walk, mon
     c = scenes.make_camera(cam, w, h)
     orc.set_math(True)
     ref = orc.render(ps, c.c, w, h, spp)
-    # frames this small keep the cooperative kernels (lists) by default: PT_FLAG_NO_COOP / NO_LDS select the kernels that
-    # walk the grid (LDS-resident and scalar-cache), FAST_RNG has its own instantiations of them
-    for name, flags in (("grid, LDS", abi.PT_FLAG_NO_COOP), ("grid, scalar cache", abi.PT_FLAG_NO_LDS), ("default", 0),
-                        ("grid, pixel-granular", abi.PT_FLAG_NO_COOP | abi.PT_FLAG_PIXEL_GRANULAR), ("stream", abi.PT_FLAG_FORCE_STREAM)):
-        assert_bit_identical(R.render_host(w, h, spp, ps, c, flags=flags), ref, f"sphere field seed {seed} {name}")
+    # The grid is walked at every frame size, so the default and PT_FLAG_NO_COOP run the same LDS-resident kernel: with the walk of `walk`
+    # — except that a field whose records, grid and materials fit 10 KB takes the cold-state kernel, which has the in-place walk only
+    # (csrc/pt_render.hip: choose_variant_uv; such a field reaches the pair queue below, with PT_NO_COLD_LDS).  PT_FLAG_NO_LDS: the
+    # scalar-cache kernel, in-place walk only; FAST_RNG has its own instantiations (in-place walk).
+    import ctypes as C
+    st = (C.c_int32 * 8)()
+    abi.check(lib.pt_debug_tri_pool(C.byref(ps.desc), st), "pt_debug_tri_pool")
+    blob, mats, in_grid = st[6] * 16, ps.n_materials * 64, st[7]
+    # (seed 3006 draws radii so spread that no sphere counts as small: no grid, the headline kernels without the walk — kept as the control)
+    assert (in_grid >= 48 or seed == 6) and blob <= 64 * 1024, "the field must get its grid and fit the LDS image"
+    cold = blob + mats <= 10 * 1024
+    resident = dict(lds=1, mlds=int(blob + mats <= 16 * 1024), cl=int(cold), coop=0, grid=0 if in_grid == 0 else 1 if cold else walk)
+    for name, flags, kernel in (("grid, LDS", abi.PT_FLAG_NO_COOP, resident), ("grid, scalar cache", abi.PT_FLAG_NO_LDS, dict(lds=0, grid=int(in_grid > 0))),
+                                ("default", 0, resident if in_grid else dict(lds=1)), ("grid, pixel-granular", abi.PT_FLAG_NO_COOP | abi.PT_FLAG_PIXEL_GRANULAR, resident),
+                                ("stream", abi.PT_FLAG_FORCE_STREAM, None)):
+        fb, (_, frame) = K.render_host_tagged(w, h, spp, ps, c, flags=flags)
+        assert K.ran(frame, **kernel) if kernel else K.ran(frame, "render_kernel_stream", uv=0), (name, frame)
+        assert_bit_identical(fb, ref, f"sphere field seed {seed} {name}")
+    if cold and in_grid:
+        monkeypatch.setenv("PT_NO_COLD_LDS", "1")
+        fb, (_, frame) = K.render_host_tagged(w, h, spp, ps, c)
+        assert K.ran(frame, lds=1, mlds=1, cl=0, grid=walk), frame
+        assert_bit_identical(fb, ref, f"sphere field seed {seed}, cold state in registers: walk {walk}")
+        monkeypatch.delenv("PT_NO_COLD_LDS")
     F = abi.PT_FLAG_FAST_RNG
-    assert_bit_identical(R.render_host(w, h, 70, ps, c, flags=F), orc.render(ps, c.c, w, h, 70, flags=F), f"sphere field seed {seed} fast mode")
+    fb, (_, frame) = K.render_host_tagged(w, h, 70, ps, c, flags=F)
+    assert K.ran(frame, lds=1, fast=1), frame
+    assert_bit_identical(fb, orc.render(ps, c.c, w, h, 70, flags=F), f"sphere field seed {seed} fast mode")
 
 
 def random_box_field(seed: int):
@@ -295,14 +317,19 @@ def test_random_box_fields_through_the_slab_culling(orc, lib, seed):
     c = scenes.make_camera(cam, w, h)
     orc.set_math(True)
     ref = orc.render(ps, c.c, w, h, spp)
-    # frames this small go to the cooperative kernels by default (straight-line box runs): NO_COOP / NO_LDS select the
+    # by default a field of some twenty boxes and more goes to the cooperative kernels (straight-line box runs): NO_COOP / NO_LDS select the
     # kernels with the culled box runs (LDS-resident and scalar-cache)
-    for name, flags in (("culled, LDS", abi.PT_FLAG_NO_COOP), ("culled, scalar cache", abi.PT_FLAG_NO_LDS), ("default", 0),
-                        ("culled, pixel-granular", abi.PT_FLAG_NO_COOP | abi.PT_FLAG_PIXEL_GRANULAR), ("stream", abi.PT_FLAG_FORCE_STREAM),
-                        ("plain division", abi.PT_FLAG_NO_FASTDIV | abi.PT_FLAG_NO_COOP)):
-        assert_bit_identical(R.render_host(w, h, spp, ps, c, flags=flags), ref, f"box field seed {seed} {name}")
+    lds, scalar = dict(lds=1, coop=0, fast=0), dict(lds=0, coop=0, fast=0)
+    for name, flags, kernel in (("culled, LDS", abi.PT_FLAG_NO_COOP, lds), ("culled, scalar cache", abi.PT_FLAG_NO_LDS, scalar), ("default", 0, dict(lds=1)),
+                                ("culled, pixel-granular", abi.PT_FLAG_NO_COOP | abi.PT_FLAG_PIXEL_GRANULAR, lds), ("stream", abi.PT_FLAG_FORCE_STREAM, None),
+                                ("plain division", abi.PT_FLAG_NO_FASTDIV | abi.PT_FLAG_NO_COOP, lds)):
+        fb, (_, frame) = K.render_host_tagged(w, h, spp, ps, c, flags=flags)
+        assert K.ran(frame, **kernel) if kernel else K.ran(frame, "render_kernel_stream", uv=0), (name, frame)
+        assert_bit_identical(fb, ref, f"box field seed {seed} {name}")
     F = abi.PT_FLAG_FAST_RNG | abi.PT_FLAG_NO_COOP
-    assert_bit_identical(R.render_host(w, h, 70, ps, c, flags=F), orc.render(ps, c.c, w, h, 70, flags=F), f"box field seed {seed} fast mode")
+    fb, (_, frame) = K.render_host_tagged(w, h, 70, ps, c, flags=F)
+    assert K.ran(frame, lds=1, fast=1), frame
+    assert_bit_identical(fb, orc.render(ps, c.c, w, h, 70, flags=F), f"box field seed {seed} fast mode")
 
 
 def random_triangle_field(seed: int, images: int = 0, offset=None, cam_dist=None, vfov=None):
@@ -465,8 +492,11 @@ def test_random_triangle_fields_through_the_triangle_pool(orc, lib, seed):
     for name, flags in (("pool", 0), ("pool, tile-granular", abi.PT_FLAG_TILE_GRANULAR), ("full scan (stream)", abi.PT_FLAG_FORCE_STREAM),
                         ("plain division: every ray irregular -> full scan in the pool kernel", abi.PT_FLAG_NO_FASTDIV)):
         assert_bit_identical(R.render_host(w, h, spp, ds, c, flags=flags), ref, f"triangle field seed {seed} {name}")
+        frame = K.last_kernels(ds)[1]
+        assert K.ran(frame, "render_kernel_stream", uv=0) if flags == abi.PT_FLAG_FORCE_STREAM else K.ran(frame, uv=0, tripool=1, fast=0), (name, frame)
     F = abi.PT_FLAG_FAST_RNG
     assert_bit_identical(R.render_host(w, h, 70, ds, c, flags=F), orc.render(ps, c.c, w, h, 70, flags=F), f"triangle field seed {seed} fast mode")
+    assert K.ran(K.last_kernels(ds)[1], uv=0, tripool=1, fast=1), K.last_kernels(ds)
 
 
 @pytest.mark.parametrize("seed,tail", [(8000, "0"), (8001, "0.4"), (8003, "0"), (8004, "0.9"), (8006, "0.2"), (8009, "0"), (8012, "0.5")])

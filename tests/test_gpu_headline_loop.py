@@ -5,6 +5,8 @@ frame size whose edge tiles have padding pixels (61 x 35: lanes that scan along 
 import numpy as np
 import pytest
 
+import kernel_variant_cases as K
+import pool_octant_scenes as P
 import scenes_small as S
 from conftest import assert_bit_identical
 from path_tracer_amd import abi, scenes
@@ -16,11 +18,18 @@ SIZES = [(64, 36), (61, 35)]
 SPP = 8
 
 
-def _check(orc, ps, cam, w, h, spp=SPP, depth=50, flags=0, what=""):
+# the headline family's kernel of a small scene (csrc/pt_render.hip: headline_kernel): blob and materials in LDS, cold lane state in LDS, no grid walk
+HEADLINE = dict(lds=1, mlds=1, cl=1, coop=0, grid=0, tripool=0)
+
+
+def _check(orc, ps, cam, w, h, spp=SPP, depth=50, flags=0, what="", mats=K.MATS_RECTBOX):
+    """mats: the material / hittable set of the headline kernel the frame must have run (pt_debug_last_kernels)"""
     c = scenes.make_camera(cam, w, h)
     orc.set_math(True)
     ref = orc.render(ps, c.c, w, h, spp, depth)
-    assert_bit_identical(R.render_host(w, h, spp, ps, c, depth, flags=flags), ref, f"{what} {w}x{h}x{spp} depth {depth}")
+    fb, (probe, frame) = K.render_host_tagged(w, h, spp, ps, c, depth, flags=flags)
+    assert K.ran(frame, mats=mats, **HEADLINE) and probe is None, (probe, frame)
+    assert_bit_identical(fb, ref, f"{what} {w}x{h}x{spp} depth {depth}")
 
 
 @pytest.mark.parametrize("size", SIZES)
@@ -40,9 +49,10 @@ def test_cornell_exhausted_bounces(orc, size, depth):
 
 @pytest.mark.parametrize("size", SIZES)
 def test_ties(orc, size):
-    """(c) equal t, the holder_later rule (this scene has spheres and triangles too: the generic kernels; test_rect_box_only_ties: the headline family's)"""
+    """(c) equal t, the holder_later rule (this scene has spheres and triangles too, all lambertian over solid colours: the headline kernel for
+    every hittable kind, MATS_LAMB_LIGHT_SOLID; test_rect_box_only_ties: the rect / box-only kernel's)"""
     ps, cam = S.ties_scene()
-    _check(orc, ps, cam, *size, what="ties")
+    _check(orc, ps, cam, *size, what="ties", mats=K.MATS_SIMPLE)
 
 
 def _rectbox_ties_scene(n_boxes):
@@ -65,9 +75,10 @@ def _rectbox_ties_scene(n_boxes):
 
 @pytest.mark.parametrize("n_boxes", [4, 2])
 @pytest.mark.parametrize("size", SIZES)
-def test_rect_box_only_ties(orc, size, n_boxes):
+def test_rect_box_only_ties(orc, lib, size, n_boxes):
     """(c') the same ties in the kernels this scene family runs: one (closest, hit) through the pool, its re-pass and the guarded loops"""
     ps, cam = _rectbox_ties_scene(n_boxes)
+    assert len(P.pools(*P.flatten(lib, ps))) == (1 if n_boxes == 4 else 0), "four boxes get a slab pool, two do not"
     _check(orc, ps, cam, *size, what=f"rect / box ties, {n_boxes} boxes")
     _check(orc, ps, cam, *size, flags=abi.PT_FLAG_NO_FASTDIV, what=f"rect / box ties, {n_boxes} boxes, plain division")
 
@@ -87,13 +98,18 @@ def test_cornell_plain_division(orc, size):
 
 
 def test_cornell_probe_and_resume(orc):
-    """(f) pt_render with enough samples for the cost probe (>= 16 spp): the probe + resume branch of lane_acquire / lane_store"""
+    """(f) pt_render with enough samples (>= 16 spp) and tiles (>= 64) for the cost probe: the probe + resume branch of lane_acquire /
+    lane_store.  64 x 36 is 40 tiles — the launcher does not probe it, as pt_debug_last_kernels shows; 64 x 72 is 72, and the same
+    kernel runs as the probe and as the frame pass that resumes its samples."""
     import torch
 
-    w, h, spp = 64, 36, 40
     ps, cam = S.cornell_scene()
-    c = scenes.make_camera(cam, w, h)
-    fb = R.render(w, h, spp, ps, c)
-    torch.cuda.synchronize()
+    ds = R.DeviceScene(ps)
     orc.set_math(True)
-    assert_bit_identical(fb.cpu().numpy(), orc.render(ps, c.c, w, h, spp), f"cornell {w}x{h}x{spp} through pt_render")
+    for (w, h, spp), probed in (((64, 36, 40), False), ((64, 72, 40), True)):
+        c = scenes.make_camera(cam, w, h)
+        fb = R.render(w, h, spp, ds, c)
+        torch.cuda.synchronize()
+        probe, frame = K.last_kernels(ds)
+        assert K.ran(frame, mats=K.MATS_RECTBOX, **HEADLINE) and probe == (frame if probed else None), (probe, frame)
+        assert_bit_identical(fb.cpu().numpy(), orc.render(ps, c.c, w, h, spp), f"cornell {w}x{h}x{spp} through pt_render")

@@ -13,6 +13,8 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+import kernel_variant_cases as K
+import pool_octant_scenes as P
 import scenes_small as S
 from conftest import assert_bit_identical, bits, psnr_8bit
 from dist_util import unshard_reference
@@ -446,8 +448,13 @@ def test_small_scenes_with_slab_pools_forced(orc, lib, name, w, h, spp):
         del os.environ["PT_POOL_ALWAYS"]
     orc.set_math(True)
     ref = orc.render(ps, c.c, w, h, spp)
+    blob, n_runs = P.flatten_tuned(lib, ps, abi.tuning(slab_pools=1))
+    assert (len(P.pools(blob, n_runs)) >= 1) == (name != "badouel"), "the forced pools must be there (badouel has a single box: no stretch to pool)"
     for what, flags in (("LDS", abi.PT_FLAG_NO_COOP), ("scalar cache", abi.PT_FLAG_NO_LDS), ("default", 0)):
         assert_bit_identical(R.render_host(w, h, spp, ds, c, flags=flags), ref, f"{name} pools forced, {what}")
+        frame = K.last_kernels(ds)[1]
+        # the resident kernels with the blob in LDS / read through the scalar cache (badouel: the one kernel with that loop, scalar cache)
+        assert K.ran(frame, lds=int(what != "scalar cache" and name != "badouel"), badouel=int(name == "badouel"), coop=0), (what, frame)
     rng = np.random.default_rng(5)
     centre, extent = {"ties": ((0, 0, -2), 3.0), "mixed": ((0, 0.3, -1), 3.0), "cornell": ((278, 278, 278), 700.0), "badouel": ((0, 0.3, -2), 3.0)}[name]
     recs = random_bounce_inputs(rng, 6000, np.float32(centre), np.float32(extent))
@@ -514,8 +521,9 @@ def test_streaming_kernel_agrees(name):
     """The LDS-tile streaming kernel (used when the scene exceeds LDS) gives the resident kernel's frame."""
     ps, cam = S.ALL[name]()
     c = scenes.make_camera(cam, 64, 40)
-    a = R.render_host(64, 40, 8, ps, c)
-    b = R.render_host(64, 40, 8, ps, c, flags=abi.PT_FLAG_FORCE_STREAM)
+    a, (_, ka) = K.render_host_tagged(64, 40, 8, ps, c)
+    b, (_, kb) = K.render_host_tagged(64, 40, 8, ps, c, flags=abi.PT_FLAG_FORCE_STREAM)
+    assert K.ran(ka) and K.ran(kb, "render_kernel_stream", badouel=int(name == "badouel")), (ka, kb)
     assert_bit_identical(a, b, name)
 
 
@@ -530,8 +538,10 @@ def test_streaming_kernel_cooperative_tail(orc, name, size):
     c = scenes.make_camera(cam, w, h)
     orc.set_math(True)
     ref = orc.render(ps, c.c, w, h, 6)
-    assert_bit_identical(R.render_host(w, h, 6, ps, c, flags=abi.PT_FLAG_FORCE_STREAM | abi.PT_FLAG_PIXEL_GRANULAR), ref, f"{name} {w}x{h}")
-    assert_bit_identical(R.render_host(w, h, 6, ps, c, flags=abi.PT_FLAG_FORCE_STREAM | abi.PT_FLAG_NO_COOP), ref, f"{name} {w}x{h} no coop")
+    ds = R.DeviceScene(ps)
+    for what, flags in (("", abi.PT_FLAG_PIXEL_GRANULAR), (" no coop", abi.PT_FLAG_NO_COOP)):
+        assert_bit_identical(R.render_host(w, h, 6, ds, c, flags=abi.PT_FLAG_FORCE_STREAM | flags), ref, f"{name} {w}x{h}{what}")
+        assert K.ran(K.last_kernels(ds)[1], "render_kernel_stream", fast=0, badouel=0), K.last_kernels(ds)
 
 
 def test_streaming_kernel_cooperative_tail_many_tiles(orc):
@@ -539,9 +549,11 @@ def test_streaming_kernel_cooperative_tail_many_tiles(orc):
     side, against the oracle."""
     ps, cam = S.triangles_scene(3000)
     orc.set_math(True)
+    ds = R.DeviceScene(ps)
     for w, h in ((3, 2), (16, 2), (48, 27)):
         c = scenes.make_camera(cam, w, h)
-        assert_bit_identical(R.render_host(w, h, 5, ps, c, flags=abi.PT_FLAG_FORCE_STREAM), orc.render(ps, c.c, w, h, 5), f"{w}x{h}")
+        assert_bit_identical(R.render_host(w, h, 5, ds, c, flags=abi.PT_FLAG_FORCE_STREAM), orc.render(ps, c.c, w, h, 5), f"{w}x{h}")
+        assert K.ran(K.last_kernels(ds)[1], "render_kernel_stream", uv=0), K.last_kernels(ds)
 
 
 def test_sphere_runs_masks_chunks_and_mixed_shutter_intervals(orc):
@@ -586,18 +598,30 @@ def test_streaming_kernel_sphere_tiles(orc):
     c = scenes.make_camera(cam, 40, 24)
     orc.set_math(True)
     ref = orc.render(ps, c.c, 40, 24, 4)
-    assert_bit_identical(R.render_host(40, 24, 4, ps, c, flags=abi.PT_FLAG_FORCE_STREAM), ref, "streamed sphere tiles")
-    assert_bit_identical(R.render_host(40, 24, 4, ps, c), ref, "resident")
+    fb, (_, frame) = K.render_host_tagged(40, 24, 4, ps, c, flags=abi.PT_FLAG_FORCE_STREAM)
+    assert K.ran(frame, "render_kernel_stream", uv=0), frame
+    assert_bit_identical(fb, ref, "streamed sphere tiles")
+    # 1 500 spheres are 70 KB of records: past the 64 KB LDS image, so the launcher streams this scene by itself ...
+    fb, (_, frame) = K.render_host_tagged(40, 24, 4, ps, c)
+    assert K.ran(frame, "render_kernel_stream", uv=0), frame
+    assert_bit_identical(fb, ref, "the launcher's own choice: streamed")
+    # ... and the resident kernel it can be compared with is the scalar-cache one
+    fb, (_, frame) = K.render_host_tagged(40, 24, 4, ps, c, flags=abi.PT_FLAG_NO_LDS)
+    assert K.ran(frame, lds=0), frame
+    assert_bit_identical(fb, ref, "resident (scalar cache)")
 
 
 def test_streaming_kernel_many_tiles(orc):
     """3 000 triangles = 9 000 records: several LDS tiles per run, partial last tile, small runs either side."""
     ps, cam = S.triangles_scene(3000)
     c = scenes.make_camera(cam, 48, 27)
-    fb = R.render_host(48, 27, 3, ps, c, flags=abi.PT_FLAG_FORCE_STREAM)
+    fb, (_, frame) = K.render_host_tagged(48, 27, 3, ps, c, flags=abi.PT_FLAG_FORCE_STREAM)
+    assert K.ran(frame, "render_kernel_stream", uv=0), frame
     orc.set_math(True)
     assert_bit_identical(fb, orc.render(ps, c.c, 48, 27, 3), "streamed 3000 triangles")
-    assert_bit_identical(fb, R.render_host(48, 27, 3, ps, c, flags=abi.PT_FLAG_NO_LDS), "stream vs scalar")
+    scalar, (_, frame) = K.render_host_tagged(48, 27, 3, ps, c, flags=abi.PT_FLAG_NO_LDS)
+    assert K.ran(frame, lds=0), frame
+    assert_bit_identical(fb, scalar, "stream vs scalar")
 
 
 @pytest.mark.parametrize("name", ["cornell", "mixed", "triangles"])
@@ -639,10 +663,14 @@ def test_cooperative_traversal_agrees(orc, name, size):
     w, h = size
     ps, cam = S.ALL[name]()
     c = scenes.make_camera(cam, w, h)
-    a = R.render_host(w, h, 24, ps, c, flags=abi.PT_FLAG_FORCE_COOP)
-    b = R.render_host(w, h, 24, ps, c, flags=abi.PT_FLAG_NO_COOP)
+    a, (_, ka) = K.render_host_tagged(w, h, 24, ps, c, flags=abi.PT_FLAG_FORCE_COOP)
+    b, (_, kb) = K.render_host_tagged(w, h, 24, ps, c, flags=abi.PT_FLAG_NO_COOP)
+    # the cooperative kernel, except for 'mixed' (u,v tracked: no such kernel exists); never with PT_FLAG_NO_COOP
+    assert K.ran(ka, lds=1, coop=int(name != "mixed"), uv=2 if name == "mixed" else 0) and K.ran(kb, lds=1, coop=0), (ka, kb)
     assert_bit_identical(a, b, f"{name} {w}x{h}")
-    assert_bit_identical(a, R.render_host(w, h, 24, ps, c, flags=abi.PT_FLAG_FORCE_COOP | abi.PT_FLAG_NO_SPLIT), "no split")
+    c_, (_, kc) = K.render_host_tagged(w, h, 24, ps, c, flags=abi.PT_FLAG_FORCE_COOP | abi.PT_FLAG_NO_SPLIT)
+    assert kc == ka, (kc, ka)
+    assert_bit_identical(a, c_, "no split")
     orc.set_math(True)
     assert_bit_identical(a, orc.render(ps, c.c, w, h, 24), f"{name} {w}x{h} vs oracle")
 
@@ -718,10 +746,12 @@ def test_lds_resident_cold_lane_state_agrees(orc, name, monkeypatch):
     ps, cam = S.ALL[name]()
     for (w, h, spp) in ((96, 54, 20), (13, 9, 3)):
         c = scenes.make_camera(cam, w, h)
-        a = R.render_host(w, h, spp, ps, c)
+        a, (_, ka) = K.render_host_tagged(w, h, spp, ps, c)
         monkeypatch.setenv("PT_NO_COLD_LDS", "1")
-        b = R.render_host(w, h, spp, ps, c)
+        b, (_, kb) = K.render_host_tagged(w, h, spp, ps, c)
         monkeypatch.delenv("PT_NO_COLD_LDS")
+        # the same headline kernel with CL = true and CL = false
+        assert K.ran(ka, lds=1, mlds=1, cl=1, grid=0) and kb == ka[:5] + (0,) + ka[6:], (ka, kb)
         assert_bit_identical(a, b, f"{name} {w}x{h}")
         orc.set_math(True)
         assert_bit_identical(a, orc.render(ps, c.c, w, h, spp), f"{name} {w}x{h} vs oracle")
@@ -1198,14 +1228,21 @@ def test_sphere_grid_is_exact(orc, monkeypatch, walk):
     for vi, view in enumerate(views):
         c = scenes.make_camera(view, 64, 36)
         ref = orc.render(ps, c.c, 64, 36, 6)
-        # NO_COOP / NO_LDS: the kernels that walk the grid (a frame this small would otherwise keep the cooperative ones)
-        for flags in (abi.PT_FLAG_NO_COOP, abi.PT_FLAG_NO_LDS, abi.PT_FLAG_NO_COOP | abi.PT_FLAG_PIXEL_GRANULAR, 0, abi.PT_FLAG_FORCE_COOP,
-                      abi.PT_FLAG_FORCE_STREAM, abi.PT_FLAG_FORCE_COOP | abi.PT_FLAG_NO_SPLIT):
-            assert_bit_identical(R.render_host(64, 36, 6, ps, c, flags=flags), ref, f"view {vi} flags {flags}")
+        # The grid is walked at every frame size (kGridMinTiles = 0), so flags = 0 and PT_FLAG_NO_COOP run the same kernel: the LDS-resident
+        # one with the walk of `walk` (the scene's blob is over 16 KB: materials in memory, no cold-state kernel).  PT_FLAG_NO_LDS: the
+        # scalar-cache kernel, which has the in-place walk only; FORCE_COOP: lane groups over the lists; FORCE_STREAM: the full lists.
+        resident = dict(lds=1, mlds=0, coop=0, grid=walk)
+        for flags, kernel in ((abi.PT_FLAG_NO_COOP, resident), (abi.PT_FLAG_NO_LDS, dict(lds=0, grid=1)),
+                              (abi.PT_FLAG_NO_COOP | abi.PT_FLAG_PIXEL_GRANULAR, resident), (0, resident), (abi.PT_FLAG_FORCE_COOP, dict(lds=1, coop=1)),
+                              (abi.PT_FLAG_FORCE_STREAM, None), (abi.PT_FLAG_FORCE_COOP | abi.PT_FLAG_NO_SPLIT, dict(lds=1, coop=1))):
+            fb, (_, frame) = K.render_host_tagged(64, 36, 6, ps, c, flags=flags)
+            assert K.ran(frame, **kernel) if kernel else K.ran(frame, "render_kernel_stream", uv=0), (flags, frame)
+            assert_bit_identical(fb, ref, f"view {vi} flags {flags}")
     c = scenes.make_camera(cam, 48, 27)
-    fast = R.render_host(48, 27, 70, ps, c, flags=abi.PT_FLAG_FAST_RNG)
+    fast, (_, frame) = K.render_host_tagged(48, 27, 70, ps, c, flags=abi.PT_FLAG_FAST_RNG)
+    assert K.ran(frame, lds=1, fast=1), frame
     assert_bit_identical(fast, orc.render(ps, c.c, 48, 27, 70, flags=abi.PT_FLAG_FAST_RNG), "grid + fast mode")
-    # a frame large enough for the launcher to pick the grid kernels by itself (>= 4096 tiles), sampled pixels
+    # a larger frame (5 200 tiles), sampled pixels
     c = scenes.make_camera(cam, 640, 520)
     big = R.render_host(640, 520, 4, ps, c)
     xy = np.stack([np.random.default_rng(1).integers(0, 640, 3000), np.random.default_rng(2).integers(0, 520, 3000)], axis=1).astype(np.int32)

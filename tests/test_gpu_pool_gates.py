@@ -8,6 +8,7 @@ that reach the scan without being live (61 x 35 has padding pixels in its edge t
 import numpy as np
 import pytest
 
+import kernel_variant_cases as K
 import scenes_small as S
 from conftest import assert_bit_identical
 from path_tracer_amd import abi, scenes
@@ -20,11 +21,18 @@ SIZES = [(64, 36), (61, 35)]
 SPP = 8
 
 
-def _check(orc, ps, cam, w, h, spp=SPP, depth=50, flags=0, what="", scene=None):
+def _check(orc, ps, cam, w, h, spp=SPP, depth=50, flags=0, what="", scene=None, mats=K.MATS_RECTBOX):
+    """mats: the material / hittable set of the LDS-resident headline kernel the frame must have run (pt_debug_last_kernels)"""
     c = scenes.make_camera(cam, w, h)
     orc.set_math(True)
     ref = orc.render(ps, c.c, w, h, spp, depth)
-    assert_bit_identical(R.render_host(w, h, spp, scene if scene is not None else ps, c, depth, flags=flags), ref, f"{what} {w}x{h}x{spp} depth {depth}")
+    if scene is not None:
+        fb = R.render_host(w, h, spp, scene, c, depth, flags=flags)
+        frame = K.last_kernels(scene)[1]
+    else:
+        fb, (_, frame) = K.render_host_tagged(w, h, spp, ps, c, depth, flags=flags)
+    assert K.ran(frame, lds=1, grid=0, mats=mats), frame
+    assert_bit_identical(fb, ref, f"{what} {w}x{h}x{spp} depth {depth}")
 
 
 def _box_field(n_small, seed=5):
@@ -101,10 +109,11 @@ def test_closed_room(orc, size):
 
 @pytest.mark.parametrize("size", SIZES)
 def test_generic_family_pool(orc, size):
-    """ties_scene (spheres and triangles beside the rects and boxes: the generic kernels' copy of the loop), its four rects / boxes in a pool"""
+    """ties_scene (spheres and triangles beside the rects and boxes: the copy of the loop in the kernels for every hittable kind — lambertian
+    over solid colours only, so MATS_LAMB_LIGHT_SOLID), its four rects / boxes in a pool"""
     ps, cam = S.ties_scene()
     ds = R.DeviceScene(ps, tuning=abi.tuning(slab_pools=1))
-    _check(orc, ps, cam, *size, what="ties, pool forced", scene=ds)
+    _check(orc, ps, cam, *size, what="ties, pool forced", scene=ds, mats=K.MATS_SIMPLE)
     ds.close()
 
 

@@ -13,6 +13,7 @@ import functools
 import numpy as np
 import pytest
 
+import kernel_variant_cases as K
 import pool_octant_scenes as P
 import scenes_small as S
 from conftest import assert_bit_identical
@@ -69,7 +70,9 @@ def _reference(name, size, spp):
 @pytest.mark.parametrize("name", ["cornell", "field7", "field8", "field21", "far", "closed_room"])
 def test_frame_is_the_oracles(orc, name, size, flags):
     ps, cam = _scene(name)
-    got = R.render_host(*size, SPP, ps, scenes.make_camera(cam, *size), DEPTH, flags=flags)
+    got, (_, frame) = K.render_host_tagged(*size, SPP, ps, scenes.make_camera(cam, *size), DEPTH, flags=flags)
+    # the rect / box-only headline kernel in both forms: the LDS one (sign-resolved slab pass), the scalar-cache one (scalar form)
+    assert K.ran(frame, lds=int(flags == 0), grid=0, mats=K.MATS_RECTBOX), frame
     assert_bit_identical(got, _reference(name, size, SPP), f"{name} {size[0]}x{size[1]}x{SPP} depth {DEPTH} flags {flags}")
 
 
@@ -80,7 +83,8 @@ def test_scene_without_tables_renders_through_the_scalar_cache_kernels(orc, lib,
     blob, n_runs = P.flatten(lib, ps)
     (off, n, first), = P.pools(blob, n_runs)
     assert n == 260 and first - 1 == off + 4 * n and len(blob) * 16 <= 64 * 1024, "a pool, no octant table, a blob that fits LDS"
-    got = R.render_host(*size, 2, ps, scenes.make_camera(cam, *size), DEPTH, flags=flags)
+    got, (_, frame) = K.render_host_tagged(*size, 2, ps, scenes.make_camera(cam, *size), DEPTH, flags=flags)
+    assert K.ran(frame, lds=0, grid=0, mats=K.MATS_RECTBOX), frame  # the scalar-cache kernel, with and without PT_FLAG_NO_LDS
     assert_bit_identical(got, _reference("many_boxes", size, 2), f"260 boxes {size[0]}x{size[1]}x2 flags {flags}")
 
 

@@ -7,6 +7,8 @@ from pathlib import Path
 
 import pytest
 
+import kernel_variant_cases as K
+
 ROOT = Path(__file__).resolve().parent.parent
 CSRC = ROOT / "path_tracer_amd" / "csrc"
 
@@ -75,7 +77,8 @@ def test_grid_walk_and_triangle_pool_kernels(usage):
     # the binned renderer's kernels (opt-in, csrc/pt_binned.hpp): the step at four waves and the band stage without scratch
     step = [v for k, v in usage.items() if "bin_step_kernel" in k]
     band = [v for k, v in usage.items() if "band_kernel" in k]
-    assert len(step) == 4 and all(v["ScratchSize [bytes/lane]"] == 0 and v["Occupancy [waves/SIMD]"] >= 4 for v in step), step
+    # (three pairs: UV_NONE with both material sets, UV_WINNER with the generic one — an image texture is never "simple")
+    assert len(step) == 3 and all(v["ScratchSize [bytes/lane]"] == 0 and v["Occupancy [waves/SIMD]"] >= 4 for v in step), step
     assert len(band) == 1 and band[0]["ScratchSize [bytes/lane]"] == 0 and band[0]["Occupancy [waves/SIMD]"] >= 4, band
 
 
@@ -105,3 +108,24 @@ def test_streaming_and_cooperative_kernels_without_image_textures(usage):
             assert v["ScratchSize [bytes/lane]"] == 0, (k, v)
         if re.search(r"render_kernelILi0ELb1ELb[01]ELb1ELb0ELb0ELb0E", k):
             assert v["ScratchSize [bytes/lane]"] <= 64 and v["Occupancy [waves/SIMD]"] >= 5, (k, v)
+
+
+def test_every_compiled_variant_has_a_case_and_every_case_a_kernel(usage):
+    """tests/kernel_variant_cases.py against the compiled library: the instantiations of render_kernel, render_kernel_stream, the binned
+    renderer's step / finish pair and aov_kernel, decoded from their mangled names (template arguments: L[ib]<n>E groups), plus the
+    single-stream kernel, are exactly the table's tags.  An instantiation the launcher gained without a row — so without an oracle
+    comparison in tests/test_gpu_kernel_variants.py — fails here, and so does a row whose kernel is no longer compiled."""
+    compiled, finish = [], []
+    for name in usage:
+        m = re.search(r"\d+(render_kernel_stream|render_kernel|bin_step_kernel|bin_finish_kernel|aov_kernel)I((?:L[ib]\d+E)+)E", name)
+        if m:
+            tag = (m.group(1), *(int(x) for x in re.findall(r"L[ib](\d+)E", m.group(2))))
+            (finish if tag[0] == "bin_finish_kernel" else compiled).append(tag)
+        elif "render_single_stream_kernel" in name:
+            compiled.append(("render_single_stream_kernel",))
+    assert len(compiled) == len(set(compiled)) and len(K.ALL_TAGS) == len(set(K.ALL_TAGS)), "a tag appears twice"
+    assert sorted(t[1:] for t in finish) == sorted(t[1:] for t in compiled if t[0] == "bin_step_kernel"), "the binned step / finish kernels come in pairs"
+    missing, stale = sorted(set(compiled) - set(K.ALL_TAGS)), sorted(set(K.ALL_TAGS) - set(compiled))
+    assert not missing, f"compiled kernel variants without a row in tests/kernel_variant_cases.py: {missing}"
+    assert not stale, f"rows of tests/kernel_variant_cases.py whose kernel is not compiled: {stale}"
+    assert len([t for t in compiled if t[0] == "render_kernel"]) == 50 and len([t for t in compiled if t[0] == "render_kernel_stream"]) == 9
