@@ -531,6 +531,88 @@ typedef struct PtAovBuffers { /* device pointers; NULL = plane not wanted */
 int64_t pt_aov_plane_elems(const PtRenderParams* p, int32_t channels);
 int pt_render_aov(const PtScene* scene, const PtCamera* cam, const PtRenderParams* p, const PtAovBuffers* buffers, void* stream);
 
+/* ---- denoiser: the edge-avoiding a-trous wavelet filter, guided by the feature buffers ---------------------------------------------
+ * Added without an ABI version change, like PtAccum: a caller detects the feature by the presence of these symbols.
+ *
+ * The filter of Dammertz, Sewtz, Hanika and Lensch (HPG 2010) over a finished frame, defined here operation by operation: every value
+ * is IEEE binary32, every operation below is rounded once, nothing is fused, and the order of operations is the one written.
+ *
+ * Scope.  Whole frames only: color, albedo, normal and out are [height][width][3], depth is [height][width], y = 0 the bottom row — the
+ * layouts pt_render and pt_render_aov write with shard_count = 1.  The filter reads neighbours, so a multi-GPU job filters after
+ * pt_unshard_tiles; there is no shard parameter.  No scene is involved.  albedo, normal and depth are optional (NULL).  `out` may be
+ * `color`.  The call is asynchronous on `stream` like pt_render_aov and allocates nothing: the caller supplies `scratch`,
+ * pt_denoise_scratch_floats(width, height) floats of device memory, 16-byte aligned.
+ *
+ * Terms.  A term is OFF — contributes x = 0 — when its sigma is <= 0 or its plane is NULL (normal, depth, albedo).
+ *
+ * DEFINITION.  c_0 = color (with PT_DENOISE_DEMODULATE: c_0 = color / (albedo + 1e-3f) per channel).  Iteration i = 0 ... iterations - 1
+ * has step s = 2^i and makes c_(i+1) from c_i; for pixel p = (x, y):
+ *   sum = (0, 0, 0), wsum = 0
+ *   for dy = -2 ... 2 (outer), for dx = -2 ... 2 (inner): tap q = (x + s dx, y + s dy); a tap outside the frame is skipped
+ *     h   = K[dy + 2] * K[dx + 2],  K = {1/16, 1/4, 3/8, 1/4, 1/16}                                      (exact)
+ *     x_c = ((dr * dr + dg * dg) + db * db) * k_c(i)      d. = c_i(p) - c_i(q) per channel;  k_c(i) = 1.0f / (sg * sg), sg = sigma_color * 2^-i
+ *     x_n = ((dnx * dnx + dny * dny) + dnz * dnz) * k_n   dn = normal(p) - normal(q);        k_n = 1.0f / (sigma_normal * sigma_normal)
+ *     x_d = (dz * dz) / (sd2 * (z_p * z_p) + 1e-12f)      dz = depth(p) - depth(q), z_p = depth(p);  sd2 = sigma_depth * sigma_depth
+ *     x_a = ((dar * dar + dag * dag) + dab * dab) * k_a   da = albedo(p) - albedo(q);        k_a = 1.0f / (sigma_albedo * sigma_albedo)
+ *     x   = ((x_c + x_n) + x_d) + x_a
+ *     if !(x < 80.0f) the tap is skipped (NaN included); otherwise w = h * pt_exp_neg(x),
+ *       sum.ch = sum.ch + w * c_i(q).ch for ch = r, g, b (the product rounded, then the sum), wsum = wsum + w
+ *   c_(i+1)(p) = sum / wsum per channel (correctly rounded division); where wsum == 0 — no tap was accepted — c_(i+1)(p) = c_i(p)
+ * out = c_iterations (with PT_DENOISE_DEMODULATE: out = c_iterations * (albedo + 1e-3f) per channel).
+ * The colour sigma halves per iteration (the paper's schedule: what one level has smoothed, the next must not take for an edge) by an
+ * exact scaling; the depth term is relative to the centre's depth, so the scene's scale does not matter; with demodulation, texture
+ * detail (checker, image textures) lives in the albedo and is not blurred.
+ *
+ * pt_exp_neg(x), 0 <= x < 80, is e^-x by:  k = rintf(x * 0x1.715476p+0f)  (round half to even; 0 <= k <= 115);
+ *   r = (x - k * 0x1.62e4p-1f) - k * 0x1.7f7d1cp-20f  (the first product is exact: the constant has 16 significant bits);  t = -r;
+ *   q = 0x1.6c16c2p-10f; q = q * t + 0x1.111112p-7f; q = q * t + 0x1.555556p-5f; q = q * t + 0x1.555556p-3f; q = q * t + 0.5f;
+ *   q = q * t + 1.0f; q = q * t + 1.0f  (the degree-6 Taylor polynomial of e^t, every product and every sum rounded);  result = ldexpf(q, -k)
+ *   (exact: the result is a normal number).  Truncation on |r| <= ln2 / 2: 0.3466^7 / 5040 = 1.2e-7; with the rounding of the reduction
+ *   and of the polynomial the relative error against e^-x stays under 1e-6 (derived, then swept: tests/test_denoise_cpu.py).
+ *
+ * Containment.  With the colour term on, a tap whose colour is NaN or inf has x = NaN or inf and is skipped, and a pixel whose own colour
+ * is not finite accepts no tap, its centre included (inf - inf = NaN), and keeps its value: a NaN or inf pixel stays where it is and
+ * never spreads.  Every finite pixel accepts at least its centre tap (x = 0, w = 3/8 * 3/8).  The same holds for a non-finite guide value
+ * whose term is on.
+ *
+ * Rejected (PT_ERR_INVALID_ARG, on the host, before any device call): a NULL params, color, out or scratch; a struct_size other than
+ * sizeof(PtDenoiseParams); width or height <= 0; iterations outside 1 ... PT_DENOISE_MAX_ITERATIONS; a sigma that is not finite; a
+ * sigma > 0 whose k (for sigma_color: any of its k_c(i); for sigma_depth: sd2) is not a finite binary32 number > 0; PT_DENOISE_DEMODULATE
+ * without an albedo plane; flags other than PT_DENOISE_DEMODULATE and PT_DENOISE_NO_LDS; `out` or `scratch` overlapping a guide plane; `scratch` overlapping
+ * `color` or `out`, or not 16-byte aligned.  More than 2^30 pixels: PT_ERR_TOO_LARGE.                                                 */
+#define PT_DENOISE_DEMODULATE 1u
+#define PT_DENOISE_NO_LDS 2u /* A/B switch, same bits: every iteration reads its taps from global memory (default: the steps 1 and 2 read an LDS-staged tile) */
+#define PT_DENOISE_MAX_ITERATIONS 8
+/* The defaults (pt_denoise_params_init), chosen for what progressive and adaptive renders stop at — 8 to 64 samples per pixel, where one
+ * path that reaches a light moves a pixel by a unit of radiance or more: five levels (a 65 x 65 footprint); the halving colour sigma
+ * from 32 in demodulated units (2 at the last level: the early levels are led by the guides, the colour term takes over as the noise
+ * shrinks; lower it for cleaner input); normals within ~0.5 of each other; depth within ~20 %; no albedo term (demodulation has taken
+ * the albedo out already); demodulation on.  tests/test_denoise_cpu.py holds them to a measured quality (profiles/denoise_bench.txt). */
+#define PT_DENOISE_DEFAULT_ITERATIONS 5
+#define PT_DENOISE_DEFAULT_SIGMA_COLOR 32.0f
+#define PT_DENOISE_DEFAULT_SIGMA_NORMAL 0.5f
+#define PT_DENOISE_DEFAULT_SIGMA_DEPTH 0.2f
+#define PT_DENOISE_DEFAULT_SIGMA_ALBEDO 0.0f
+#define PT_DENOISE_DEFAULT_FLAGS PT_DENOISE_DEMODULATE
+typedef struct PtDenoiseParams {
+  int32_t struct_size; /* sizeof(PtDenoiseParams) of the caller's header */
+  int32_t width, height;
+  int32_t iterations;  /* 1 ... PT_DENOISE_MAX_ITERATIONS */
+  float sigma_color, sigma_normal, sigma_depth, sigma_albedo; /* <= 0: term off */
+  uint32_t flags;      /* PT_DENOISE_DEMODULATE, PT_DENOISE_NO_LDS */
+  int32_t reserved;
+} PtDenoiseParams;
+/* Host function, no GPU: struct_size + the defaults above for a frame of width x height. */
+void pt_denoise_params_init(PtDenoiseParams* params, int32_t width, int32_t height);
+/* Host function, no GPU: floats of `scratch` for a frame of width x height — one colour plane (the iterations ping-pong between it and
+ * `out`) and two 16-byte guide records per pixel, (normal, depth) and (albedo, 0), packed by a prepass; < 0 for invalid sizes. */
+int64_t pt_denoise_scratch_floats(int32_t width, int32_t height);
+int pt_denoise(const PtDenoiseParams* params, const float* color, const float* albedo, const float* normal, const float* depth,
+               float* out, float* scratch, void* stream);
+/* How the LAST pt_denoise of this process read its taps, per iteration: out[i] = 0 iteration not run, 1 from global memory, 2 from an
+ * LDS-staged tile (the steps 1 and 2, unless PT_DENOISE_NO_LDS: profiles/denoise_bench.txt).  The bits do not depend on it.  For tests. */
+int pt_debug_last_denoise(int32_t out[8]);
+
 /* ---- function-level probes (parity tests call these; not used by render) ---- */
 
 /* One iteration of the bounce loop render.hpp:58-89 per record: hit_world,

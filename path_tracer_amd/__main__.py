@@ -14,6 +14,10 @@ With --aov-dir DIR the first-hit feature buffers a denoiser takes (render.render
 are written next to the frame: DIR/albedo.png, DIR/normal.png (as (n + 1) / 2), DIR/coverage.png and DIR/aov.npz with all six planes
 (albedo, normal, direct, depth, coverage, id; row 0 = the bottom scan-line, as the frame buffer); out.png is byte-identical to the one
 written without the options.
+With --denoise-out FILE the frame is also filtered by the edge-avoiding a-trous denoiser (render.denoise; --denoise-iterations and the
+--denoise-sigma-* options; the defaults are include/pt_render.h's) over feature buffers of --aov-spp camera rays per pixel — the ones
+--aov-dir writes, or a pass of its own — and FILE gets the filtered frame through the same output stage; out.png is byte-identical to
+the one written without the option.
 """
 import argparse
 import os
@@ -62,8 +66,23 @@ def main() -> None:
     ap.add_argument("--aov-dir", default=None, metavar="DIR",
                     help="also write first-hit feature buffers for a denoiser: DIR/albedo.png, normal.png, coverage.png, aov.npz")
     ap.add_argument("--aov-spp", type=int, default=None, metavar="N", help="feature buffers: camera rays per pixel (default 16)")
+    ap.add_argument("--denoise-out", default=None, metavar="FILE",
+                    help="also write the frame filtered by the a-trous denoiser (guided by feature buffers of --aov-spp rays per pixel)")
+    ap.add_argument("--denoise-iterations", type=int, default=None, metavar="N", help="denoiser: a-trous levels, 1 .. 8 (default 5)")
+    for term in ("color", "normal", "depth", "albedo"):
+        ap.add_argument(f"--denoise-sigma-{term}", type=float, default=None, metavar="S",
+                        help=f"denoiser: sigma of the {term} term, <= 0 turns it off (default: include/pt_render.h)")
     a = ap.parse_args()
-    if a.aov_spp is not None and a.aov_dir is None:
+    denoise_kw = {k: v for k, v in (("iterations", a.denoise_iterations), ("sigma_color", a.denoise_sigma_color),
+                                    ("sigma_normal", a.denoise_sigma_normal), ("sigma_depth", a.denoise_sigma_depth),
+                                    ("sigma_albedo", a.denoise_sigma_albedo)) if v is not None}
+    if denoise_kw and a.denoise_out is None:
+        ap.error("--denoise-iterations and --denoise-sigma-* need --denoise-out")
+    if a.denoise_iterations is not None and not 1 <= a.denoise_iterations <= 8:
+        ap.error("--denoise-iterations must be in 1 .. 8")
+    if any(v != v or v in (float("inf"), float("-inf")) for k, v in denoise_kw.items() if k != "iterations"):
+        ap.error("--denoise-sigma-* must be finite")
+    if a.aov_spp is not None and a.aov_dir is None and a.denoise_out is None:
         ap.error("--aov-spp needs --aov-dir")
     a.aov_spp = 16 if a.aov_spp is None else a.aov_spp
     if not 1 <= a.aov_spp <= 1 << 24:
@@ -120,14 +139,18 @@ def main() -> None:
             torch.cuda.synchronize()
             ms += e0.elapsed_time(e1)
             write_png(os.path.join(a.preview_dir, f"preview_{acc.samples}.png"), rgb8.cpu().numpy())
+        fb = acc.resolve() if a.denoise_out else None
         acc.close()
     else:
         fb, ms = R.render(a.width, a.height, a.spp, packed, cam, a.depth, timed=True)
         rgb8 = R.tonemap_rgb8(fb)
     torch.cuda.synchronize()
     write_png(a.out, rgb8.cpu().numpy())
+    planes = R.render_aov(a.width, a.height, a.aov_spp, packed, cam) if a.aov_dir or a.denoise_out else None
     if a.aov_dir:
-        write_aovs(a.aov_dir, R.render_aov(a.width, a.height, a.aov_spp, packed, cam))
+        write_aovs(a.aov_dir, planes)
+    if a.denoise_out:
+        write_png(a.denoise_out, R.tonemap_rgb8(R.denoise(fb, **planes, **denoise_kw)).cpu().numpy())
     if mean_spp is not None:
         n = int(counts.sum())
         print(f"{a.scene}: {packed.n_hittables} hittables, {a.width}x{a.height}, adaptive {a.min_spp}..{a.spp} spp (threshold "

@@ -129,6 +129,13 @@ class PtAovBuffers(C.Structure):
                 ("direct", C.c_void_p), ("depth", C.c_void_p), ("coverage", C.c_void_p), ("id", C.c_void_p)]
 
 
+class PtDenoiseParams(C.Structure):
+    """include/pt_render.h PtDenoiseParams: the a-trous denoiser's parameters (pt_denoise); a sigma <= 0 turns its term off."""
+    _fields_ = [("struct_size", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("iterations", C.c_int32),
+                ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("sigma_albedo", C.c_float),
+                ("flags", C.c_uint32), ("reserved", C.c_int32)]
+
+
 assert C.sizeof(PtHittable) == 64 and C.sizeof(PtMaterial) == 32 and C.sizeof(PtTexture) == 48
 assert C.sizeof(PtCamera) == 96 and C.sizeof(PtRenderParams) == 32
 
@@ -199,6 +206,11 @@ SIGNATURES = {
     "pt_aov_plane_elems": (C.c_int64, [C.POINTER(PtRenderParams), C.c_int32]),
     "pt_debug_last_aov": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "pt_render_aov": (C.c_int, [_SCENE_P, C.POINTER(PtCamera), C.POINTER(PtRenderParams), C.POINTER(PtAovBuffers), C.c_void_p]),
+    # the a-trous denoiser: likewise optional (DENOISE_SYMBOLS)
+    "pt_denoise_params_init": (None, [C.POINTER(PtDenoiseParams), C.c_int32, C.c_int32]),
+    "pt_denoise_scratch_floats": (C.c_int64, [C.c_int32, C.c_int32]),
+    "pt_denoise": (C.c_int, [C.POINTER(PtDenoiseParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pt_debug_last_denoise": (C.c_int, [C.POINTER(C.c_int32)]),
 }
 
 # Entry points a library may lack and still load for everything else (include/pt_render.h: the feature is detected by their presence);
@@ -215,6 +227,14 @@ PT_ADAPTIVE_DILATE = 1
 AOV_SYMBOLS = frozenset({"pt_aov_plane_elems", "pt_render_aov", "pt_debug_last_aov"})
 AOV_PLANES = ("albedo", "normal", "direct", "depth", "coverage", "id")  # PtAovBuffers' planes, in the struct's order
 AOV_CHANNELS = {"albedo": 3, "normal": 3, "direct": 3, "depth": 1, "coverage": 1, "id": 1}
+# the a-trous denoiser (include/pt_render.h: pt_denoise); has_denoise() tells whether the loaded library has it
+DENOISE_SYMBOLS = frozenset({"pt_denoise_params_init", "pt_denoise_scratch_floats", "pt_denoise", "pt_debug_last_denoise"})
+PT_DENOISE_DEMODULATE = 1
+PT_DENOISE_NO_LDS = 2  # A/B switch, same bits: every iteration reads its taps from global memory
+PT_DENOISE_MAX_ITERATIONS = 8
+# the header's PT_DENOISE_DEFAULT_* (pt_denoise_params_init)
+PT_DENOISE_DEFAULT_ITERATIONS = 5
+PT_DENOISE_DEFAULT_SIGMA_COLOR, PT_DENOISE_DEFAULT_SIGMA_NORMAL, PT_DENOISE_DEFAULT_SIGMA_DEPTH, PT_DENOISE_DEFAULT_SIGMA_ALBEDO = 32.0, 0.5, 0.2, 0.0
 
 LIB_NAME = "libpt_render.so"
 _lib = None
@@ -259,7 +279,7 @@ def load_library() -> C.CDLL:
         pass  # torch-free hosts bind to /opt/rocm/lib through the library's RUNPATH
     lib = C.CDLL(str(path))
     for name, (res, args) in SIGNATURES.items():
-        if override_is_older_build(path, lib, name) or (name in ACCUM_SYMBOLS | ADAPTIVE_SYMBOLS | AOV_SYMBOLS and not hasattr(lib, name)):
+        if override_is_older_build(path, lib, name) or (name in ACCUM_SYMBOLS | ADAPTIVE_SYMBOLS | AOV_SYMBOLS | DENOISE_SYMBOLS and not hasattr(lib, name)):
             continue
         fn = getattr(lib, name)  # AttributeError if the library does not export what the header declares
         fn.restype = res
@@ -287,6 +307,12 @@ def has_aov(lib=None) -> bool:
     """Does the loaded library offer the first-hit feature buffers (pt_render_aov)?"""
     lib = lib or load_library()
     return all(hasattr(lib, n) for n in AOV_SYMBOLS)
+
+
+def has_denoise(lib=None) -> bool:
+    """Does the loaded library offer the a-trous denoiser (pt_denoise)?"""
+    lib = lib or load_library()
+    return all(hasattr(lib, n) for n in DENOISE_SYMBOLS)
 
 
 def check(code: int, where: str) -> None:

@@ -1316,6 +1316,150 @@ __global__ void adaptive_select_kernel(AFrame f, const float* __restrict__ sum, 
   if ((threadIdx.x & 63) == 0 && b) atomicAdd(n_active, (unsigned long long)__builtin_popcountll(b));
 }
 
+// ---- denoiser: the edge-avoiding a-trous filter (include/pt_render.h: pt_denoise) ----------------------------------------------------
+// Image space only: nothing of the render kernels is involved.  The header states every operation; this is that text in HIP, with
+// -ffp-contract=off (no product is fused into a sum) and the correctly rounded division of the build's flags.
+__device__ __forceinline__ float exp_neg(float x) { // pt_exp_neg: 0 <= x < 80
+  const float k = __builtin_rintf(x * 0x1.715476p+0f);
+  const float t = -((x - k * 0x1.62e4p-1f) - k * 0x1.7f7d1cp-20f);
+  float q = 0x1.6c16c2p-10f;
+  q = q * t + 0x1.111112p-7f;
+  q = q * t + 0x1.555556p-5f;
+  q = q * t + 0x1.555556p-3f;
+  q = q * t + 0.5f;
+  q = q * t + 1.0f;
+  q = q * t + 1.0f;
+  return ldexpf(q, -(int)k);
+}
+
+enum { DN_COLOR = 1, DN_NORMAL = 2, DN_DEPTH = 4, DN_ALBEDO = 8, DN_DEMOD_IN = 16, DN_REMOD_OUT = 32 };
+
+struct ATrousArgs {
+  const float* in;  // c_i: [height][width][3] (iteration 0: the caller's colour, or its copy in scratch)
+  float* out;       // c_(i+1)
+  const f4* g_nd;   // per pixel (normal, depth); read when ND
+  const f4* g_al;   // per pixel (albedo, 0); read when AL
+  int width, height, step;
+  unsigned terms;   // DN_*: which terms are on, and whether this launch demodulates what it reads / remodulates what it writes
+  float k_c, k_n, sd2, k_a;
+};
+
+// The prepass: the guide planes the caller handed over, packed into one or two 16-byte records per pixel, so that a tap reads its guides
+// with one or two global_load_dwordx4 instead of up to seven scalar-sized loads from three planes.  A NULL plane packs as 0.
+__global__ __launch_bounds__(256) void atrous_pack_kernel(const float* __restrict__ normal, const float* __restrict__ depth,
+                                                          const float* __restrict__ albedo, f4* __restrict__ g_nd, f4* __restrict__ g_al, long long pixels) {
+  const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= pixels) return;
+  if (g_nd) {
+    f4 r = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (normal) { r.x = normal[p * 3]; r.y = normal[p * 3 + 1]; r.z = normal[p * 3 + 2]; }
+    if (depth) r.w = depth[p];
+    g_nd[p] = r;
+  }
+  if (g_al) {
+    const f4 r = {albedo[p * 3], albedo[p * 3 + 1], albedo[p * 3 + 2], 0.0f};
+    g_al[p] = r;
+  }
+}
+
+// One iteration, one thread per pixel, a 32 x 8 pixel workgroup (a wave is two rows of 32, so a tap's 64 colour reads from global memory
+// are two runs of 384 contiguous bytes).  ND / AL: the launch reads the (normal, depth) / (albedo) records at all.  STEP = 0: every tap
+// is read from global memory, at the step of the arguments.  STEP = 1, 2: the step is STEP and the workgroup first stages its tile with
+// the halo of 2 STEP pixels in LDS — colour (demodulated once per staged pixel instead of once per tap) and the guide records — and the
+// taps read LDS.  Same operations on the same values in the same order either way: the bits do not depend on the path.
+template <int STEP>
+struct ATrousTile {
+  static constexpr int R = 2 * STEP, TW = 32 + 2 * R, TH = 8 + 2 * R, N = TW * TH;
+};
+
+template <bool ND, bool AL, int STEP>
+__global__ __launch_bounds__(256) void atrous_kernel(ATrousArgs a) {
+  using T = ATrousTile<STEP>;
+  const int lx = threadIdx.x & 31, ly = threadIdx.x >> 5;
+  const int x = blockIdx.x * 32 + lx, y = blockIdx.y * 8 + ly;
+  const bool demod = AL && (a.terms & DN_DEMOD_IN);
+  const int step = STEP ? STEP : a.step;
+  __shared__ float s_r[STEP ? T::N : 1], s_g[STEP ? T::N : 1], s_b[STEP ? T::N : 1];
+  __shared__ f4 s_nd[STEP && ND ? T::N : 1], s_al[STEP && AL ? T::N : 1];
+  if constexpr (STEP > 0) {
+    const int x0 = blockIdx.x * 32 - T::R, y0 = blockIdx.y * 8 - T::R;
+    for (int i = threadIdx.x; i < T::N; i += 256) {
+      const int gx = x0 + i % T::TW, gy = y0 + i / T::TW;
+      float cr = 0.0f, cg = 0.0f, cb = 0.0f;
+      f4 nd = {0.0f, 0.0f, 0.0f, 0.0f}, al = {0.0f, 0.0f, 0.0f, 0.0f};
+      if (gx >= 0 && gx < a.width && gy >= 0 && gy < a.height) { // (a slot outside the frame is never read: its tap is skipped)
+        const long long q = (long long)gy * a.width + gx;
+        cr = a.in[q * 3]; cg = a.in[q * 3 + 1]; cb = a.in[q * 3 + 2];
+        if (ND) nd = a.g_nd[q];
+        if (AL) al = a.g_al[q];
+        if (demod) { cr = cr / (al.x + 1e-3f); cg = cg / (al.y + 1e-3f); cb = cb / (al.z + 1e-3f); }
+      }
+      s_r[i] = cr; s_g[i] = cg; s_b[i] = cb;
+      if (ND) s_nd[i] = nd;
+      if (AL) s_al[i] = al;
+    }
+    __syncthreads();
+  }
+  if (x >= a.width || y >= a.height) return;
+  const long long p = (long long)y * a.width + x;
+  const int lp = (ly + T::R) * T::TW + lx + T::R; // the pixel's slot in the tile (STEP > 0)
+  const bool t_c = a.terms & DN_COLOR, t_n = ND && (a.terms & DN_NORMAL), t_d = ND && (a.terms & DN_DEPTH), t_a = AL && (a.terms & DN_ALBEDO);
+  f4 ndp = {0.0f, 0.0f, 0.0f, 0.0f}, alp = {0.0f, 0.0f, 0.0f, 0.0f};
+  float pr, pg, pb;
+  if constexpr (STEP > 0) {
+    if (ND) ndp = s_nd[lp];
+    if (AL) alp = s_al[lp];
+    pr = s_r[lp]; pg = s_g[lp]; pb = s_b[lp];
+  } else {
+    if (ND) ndp = a.g_nd[p];
+    if (AL) alp = a.g_al[p];
+    pr = a.in[p * 3]; pg = a.in[p * 3 + 1]; pb = a.in[p * 3 + 2];
+    if (demod) { pr = pr / (alp.x + 1e-3f); pg = pg / (alp.y + 1e-3f); pb = pb / (alp.z + 1e-3f); }
+  }
+  const float den = a.sd2 * (ndp.w * ndp.w) + 1e-12f;
+  float sr = 0.0f, sg = 0.0f, sb = 0.0f, ws = 0.0f;
+#pragma unroll
+  for (int dy = -2; dy <= 2; dy++) {
+    const int qy = y + dy * step;
+    if (qy < 0 || qy >= a.height) continue;
+#pragma unroll
+    for (int dx = -2; dx <= 2; dx++) {
+      const int qx = x + dx * step;
+      if (qx < 0 || qx >= a.width) continue;
+      constexpr float K[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
+      const float h = K[dy + 2] * K[dx + 2];
+      float cr, cg, cb;
+      f4 ndq = ndp, alq = alp;
+      if constexpr (STEP > 0) {
+        const int lq = lp + dy * STEP * T::TW + dx * STEP; // inside the tile: |dy STEP|, |dx STEP| <= R
+        cr = s_r[lq]; cg = s_g[lq]; cb = s_b[lq];
+        if (ND) ndq = s_nd[lq];
+        if (AL) alq = s_al[lq];
+      } else {
+        const long long q = (long long)qy * a.width + qx;
+        cr = a.in[q * 3]; cg = a.in[q * 3 + 1]; cb = a.in[q * 3 + 2];
+        if (ND) ndq = a.g_nd[q];
+        if (AL) alq = a.g_al[q];
+        if (demod) { cr = cr / (alq.x + 1e-3f); cg = cg / (alq.y + 1e-3f); cb = cb / (alq.z + 1e-3f); }
+      }
+      float xc = 0.0f, xn = 0.0f, xd = 0.0f, xa = 0.0f;
+      if (t_c) { const float dr = pr - cr, dg = pg - cg, db = pb - cb; xc = ((dr * dr + dg * dg) + db * db) * a.k_c; }
+      if (t_n) { const float dnx = ndp.x - ndq.x, dny = ndp.y - ndq.y, dnz = ndp.z - ndq.z; xn = ((dnx * dnx + dny * dny) + dnz * dnz) * a.k_n; }
+      if (t_d) { const float dz = ndp.w - ndq.w; xd = (dz * dz) / den; }
+      if (t_a) { const float dar = alp.x - alq.x, dag = alp.y - alq.y, dab = alp.z - alq.z; xa = ((dar * dar + dag * dag) + dab * dab) * a.k_a; }
+      const float xs = ((xc + xn) + xd) + xa;
+      if (!(xs < 80.0f)) continue;
+      const float w = h * exp_neg(xs);
+      sr = sr + w * cr; sg = sg + w * cg; sb = sb + w * cb;
+      ws = ws + w;
+    }
+  }
+  float orr = pr, og = pg, ob = pb;
+  if (ws != 0.0f) { orr = sr / ws; og = sg / ws; ob = sb / ws; }
+  if (AL && (a.terms & DN_REMOD_OUT)) { orr = orr * (alp.x + 1e-3f); og = og * (alp.y + 1e-3f); ob = ob * (alp.z + 1e-3f); }
+  a.out[p * 3] = orr; a.out[p * 3 + 1] = og; a.out[p * 3 + 2] = ob;
+}
+
 thread_local std::string g_last_error;
 
 // ---- tuning: include/pt_render.h PtTuning.  Resolved ONCE per scene (pt_scene_create / pt_debug_flatten), never on the launch path.
@@ -2576,6 +2720,143 @@ int pt_tonemap_rgb8(const float* fb_device, int32_t width, int32_t height, uint8
   dim3 block(256), grid((width + 255) / 256, height);
   hipLaunchKernelGGL(tonemap_kernel<false>, grid, block, 0, (hipStream_t)stream, fb_device, nullptr, 0, rgb8_device, width, height);
   PT_HIP(hipGetLastError());
+  return PT_OK;
+}
+
+// ---- denoiser: pt_denoise (atrous_pack_kernel, atrous_kernel) ---------------------------------------------------------------------
+constexpr int kDenoiseLdsMaxStep = 2; // the largest step whose taps are read from an LDS-staged tile (profiles/denoise_bench.txt: the A/B)
+static std::mutex g_denoise_mutex;
+static int32_t g_last_denoise[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // the last pt_denoise's read path per iteration (pt_debug_last_denoise)
+
+void pt_denoise_params_init(PtDenoiseParams* params, int32_t width, int32_t height) {
+  if (!params) return;
+  std::memset(params, 0, sizeof *params);
+  params->struct_size = (int32_t)sizeof(PtDenoiseParams);
+  params->width = width; params->height = height;
+  params->iterations = PT_DENOISE_DEFAULT_ITERATIONS;
+  params->sigma_color = PT_DENOISE_DEFAULT_SIGMA_COLOR; params->sigma_normal = PT_DENOISE_DEFAULT_SIGMA_NORMAL;
+  params->sigma_depth = PT_DENOISE_DEFAULT_SIGMA_DEPTH; params->sigma_albedo = PT_DENOISE_DEFAULT_SIGMA_ALBEDO;
+  params->flags = PT_DENOISE_DEFAULT_FLAGS;
+}
+
+// floats of the scratch's colour plane: 3 per pixel, rounded up so that the guide records behind it stay 16-byte aligned
+static int64_t denoise_color_floats(int64_t pixels) { return (pixels * 3 + 3) / 4 * 4; }
+
+int64_t pt_denoise_scratch_floats(int32_t width, int32_t height) {
+  if (width <= 0 || height <= 0 || (int64_t)width * height > ((int64_t)1 << 30)) return -1;
+  const int64_t pixels = (int64_t)width * height;
+  return denoise_color_floats(pixels) + 8 * pixels;
+}
+
+// k = 1.0f / (sigma * sigma) in binary32, as the header defines it (host arithmetic: IEEE, no excess precision on this target)
+static float denoise_k(float sigma) {
+  volatile float s2 = sigma * sigma;
+  volatile float k = 1.0f / s2;
+  return k;
+}
+static bool denoise_k_ok(float k) { return std::isfinite(k) && k > 0.0f; }
+
+int pt_denoise(const PtDenoiseParams* params, const float* color, const float* albedo, const float* normal, const float* depth,
+               float* out, float* scratch, void* stream) {
+  if (!params || !color || !out || !scratch) return fail(PT_ERR_INVALID_ARG, "pt_denoise: NULL params, color, out or scratch");
+  if (params->struct_size != (int32_t)sizeof(PtDenoiseParams)) return fail(PT_ERR_INVALID_ARG, "pt_denoise: PtDenoiseParams.struct_size is not this library's");
+  if (params->width <= 0 || params->height <= 0) return fail(PT_ERR_INVALID_ARG, "pt_denoise: width and height must be > 0");
+  if (params->iterations < 1 || params->iterations > PT_DENOISE_MAX_ITERATIONS) return fail(PT_ERR_INVALID_ARG, "pt_denoise: need 1 <= iterations <= 8");
+  const float sigmas[4] = {params->sigma_color, params->sigma_normal, params->sigma_depth, params->sigma_albedo};
+  for (float s : sigmas)
+    if (!std::isfinite(s)) return fail(PT_ERR_INVALID_ARG, "pt_denoise: a sigma is not finite");
+  if (params->flags & ~(PT_DENOISE_DEMODULATE | PT_DENOISE_NO_LDS)) return fail(PT_ERR_INVALID_ARG, "pt_denoise: unknown flags");
+  const bool demod = params->flags & PT_DENOISE_DEMODULATE;
+  if (demod && !albedo) return fail(PT_ERR_INVALID_ARG, "pt_denoise: PT_DENOISE_DEMODULATE needs the albedo plane");
+  const int n_it = params->iterations;
+  unsigned terms = 0;
+  float k_c[PT_DENOISE_MAX_ITERATIONS] = {}, k_n = 0.0f, sd2 = 0.0f, k_a = 0.0f;
+  if (params->sigma_color > 0.0f) {
+    terms |= DN_COLOR;
+    for (int i = 0; i < n_it; i++) {
+      k_c[i] = denoise_k(std::ldexp(params->sigma_color, -i)); // sigma_color * 2^-i: exact (or rounded once into the denormals, whose k is refused)
+      if (!denoise_k_ok(k_c[i])) return fail(PT_ERR_INVALID_ARG, "pt_denoise: 1 / sigma_color^2 leaves binary32 at one of the iterations");
+    }
+  }
+  if (params->sigma_normal > 0.0f && normal) {
+    terms |= DN_NORMAL;
+    k_n = denoise_k(params->sigma_normal);
+    if (!denoise_k_ok(k_n)) return fail(PT_ERR_INVALID_ARG, "pt_denoise: 1 / sigma_normal^2 leaves binary32");
+  }
+  if (params->sigma_depth > 0.0f && depth) {
+    terms |= DN_DEPTH;
+    volatile float s2 = params->sigma_depth * params->sigma_depth;
+    sd2 = s2;
+    if (!denoise_k_ok(sd2)) return fail(PT_ERR_INVALID_ARG, "pt_denoise: sigma_depth^2 leaves binary32");
+  }
+  if (params->sigma_albedo > 0.0f && albedo) {
+    terms |= DN_ALBEDO;
+    k_a = denoise_k(params->sigma_albedo);
+    if (!denoise_k_ok(k_a)) return fail(PT_ERR_INVALID_ARG, "pt_denoise: 1 / sigma_albedo^2 leaves binary32");
+  }
+  const int64_t pixels = (int64_t)params->width * params->height;
+  if (pixels > ((int64_t)1 << 30)) return fail(PT_ERR_TOO_LARGE, "pt_denoise: more than 2^30 pixels");
+  const int64_t scratch_floats = pt_denoise_scratch_floats(params->width, params->height);
+  if ((uintptr_t)scratch % 16) return fail(PT_ERR_INVALID_ARG, "pt_denoise: scratch must be 16-byte aligned");
+  auto overlap = [](const void* a, int64_t a_floats, const void* b, int64_t b_floats) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a && b && a0 < b0 + (uintptr_t)b_floats * 4 && b0 < a0 + (uintptr_t)a_floats * 4;
+  };
+  const struct { const float* p; int64_t floats; } guides[3] = {{albedo, pixels * 3}, {normal, pixels * 3}, {depth, pixels}};
+  for (const auto& g : guides)
+    if (overlap(out, pixels * 3, g.p, g.floats) || overlap(scratch, scratch_floats, g.p, g.floats))
+      return fail(PT_ERR_INVALID_ARG, "pt_denoise: out and scratch must not overlap a guide plane");
+  if (overlap(scratch, scratch_floats, color, pixels * 3) || overlap(scratch, scratch_floats, out, pixels * 3))
+    return fail(PT_ERR_INVALID_ARG, "pt_denoise: scratch must not overlap color or out");
+
+  hipStream_t st = (hipStream_t)stream;
+  float* const plane = scratch; // the colour plane the iterations ping-pong with `out`
+  f4* const g_nd = reinterpret_cast<f4*>(scratch + denoise_color_floats(pixels));
+  f4* const g_al = g_nd + pixels;
+  const bool nd = terms & (DN_NORMAL | DN_DEPTH), al = demod || (terms & DN_ALBEDO);
+  std::lock_guard<std::mutex> lock(g_denoise_mutex);
+  std::memset(g_last_denoise, 0, sizeof g_last_denoise);
+  if (nd || al) {
+    hipLaunchKernelGGL(atrous_pack_kernel, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, st, (terms & DN_NORMAL) ? normal : nullptr,
+                       (terms & DN_DEPTH) ? depth : nullptr, albedo, nd ? g_nd : nullptr, al ? g_al : nullptr, (long long)pixels);
+    PT_HIP(hipGetLastError());
+  }
+  // Iteration i writes `out` when an even number of iterations follows it and the scratch plane otherwise, so the last one writes `out`.
+  // With an odd count the first would read `color` while writing `out`: where the two overlap it reads a copy in the scratch plane.
+  const float* src = color;
+  if (n_it % 2 == 1 && overlap(out, pixels * 3, color, pixels * 3)) {
+    PT_HIP(hipMemcpyAsync(plane, color, (size_t)pixels * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    src = plane;
+  }
+  // the kernel of an iteration: taps from an LDS-staged tile at the steps 1 and 2 (unless PT_DENOISE_NO_LDS), from global memory beyond
+  using Kernel = void (*)(ATrousArgs);
+  static const Kernel kernels[3][2][2] = {
+      {{atrous_kernel<false, false, 0>, atrous_kernel<false, true, 0>}, {atrous_kernel<true, false, 0>, atrous_kernel<true, true, 0>}},
+      {{atrous_kernel<false, false, 1>, atrous_kernel<false, true, 1>}, {atrous_kernel<true, false, 1>, atrous_kernel<true, true, 1>}},
+      {{atrous_kernel<false, false, 2>, atrous_kernel<false, true, 2>}, {atrous_kernel<true, false, 2>, atrous_kernel<true, true, 2>}}};
+  const bool lds_ok = !(params->flags & PT_DENOISE_NO_LDS);
+  const dim3 grid((unsigned)((params->width + 31) / 32), (unsigned)((params->height + 7) / 8));
+  for (int i = 0; i < n_it; i++) {
+    ATrousArgs a;
+    a.in = src;
+    a.out = (n_it - 1 - i) % 2 == 0 ? out : plane;
+    a.g_nd = g_nd; a.g_al = g_al;
+    a.width = params->width; a.height = params->height; a.step = 1 << i;
+    a.terms = terms | (demod && i == 0 ? DN_DEMOD_IN : 0) | (demod && i == n_it - 1 ? DN_REMOD_OUT : 0);
+    a.k_c = k_c[i]; a.k_n = k_n; a.sd2 = sd2; a.k_a = k_a;
+    const int staged = lds_ok && a.step <= kDenoiseLdsMaxStep ? a.step : 0;
+    hipLaunchKernelGGL(kernels[staged][nd ? 1 : 0][al ? 1 : 0], grid, dim3(256), 0, st, a);
+    PT_HIP(hipGetLastError());
+    g_last_denoise[i] = staged ? 2 : 1;
+    src = a.out;
+  }
+  return PT_OK;
+}
+
+int pt_debug_last_denoise(int32_t out[8]) {
+  if (!out) return fail(PT_ERR_INVALID_ARG, "pt_debug_last_denoise: NULL argument");
+  std::lock_guard<std::mutex> lock(g_denoise_mutex);
+  std::memcpy(out, g_last_denoise, sizeof g_last_denoise);
   return PT_OK;
 }
 

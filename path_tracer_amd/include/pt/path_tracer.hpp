@@ -392,6 +392,25 @@ inline void render_aov(int width, int height, int samples, const aov_buffers& pl
   render_aov(width, height, samples, planes, scene, cam, shard_index, shard_count, nullptr);
 }
 
+// The edge-avoiding a-trous denoiser over a finished whole frame (include/pt_render.h: pt_denoise), guided by render_aov's planes.
+// color, out ([height][width][3]; out may be color), the optional guides albedo, normal ([height][width][3]) and depth ([height][width])
+// and scratch (denoise_scratch_floats(width, height) floats, 16-byte aligned) are DEVICE buffers the caller owns; a sigma <= 0 turns
+// its term off.  The defaults are the header's (pt_denoise_params_init).
+struct denoise_params {
+  int iterations = PT_DENOISE_DEFAULT_ITERATIONS;
+  float sigma_color = PT_DENOISE_DEFAULT_SIGMA_COLOR, sigma_normal = PT_DENOISE_DEFAULT_SIGMA_NORMAL;
+  float sigma_depth = PT_DENOISE_DEFAULT_SIGMA_DEPTH, sigma_albedo = PT_DENOISE_DEFAULT_SIGMA_ALBEDO;
+  bool demodulate = true; // filter color / (albedo + 1e-3) and multiply the albedo back: needs the albedo plane
+};
+inline int64_t denoise_scratch_floats(int width, int height) { return pt_denoise_scratch_floats(width, height); }
+// asynchronous on `stream`
+inline void denoise(int width, int height, const float* color, const float* albedo, const float* normal, const float* depth, float* out,
+                    float* scratch, const denoise_params& dp = {}, void* stream = nullptr) {
+  const PtDenoiseParams p{(int32_t)sizeof(PtDenoiseParams), width, height, dp.iterations, dp.sigma_color, dp.sigma_normal, dp.sigma_depth,
+                          dp.sigma_albedo, dp.demodulate ? PT_DENOISE_DEMODULATE : 0u, 0};
+  check(pt_denoise(&p, color, albedo, normal, depth, out, scratch, stream), "pt_denoise");
+}
+
 // Progressive rendering: one frame in sample windows; RAII over pt_accum_create / pt_accum_destroy (include/pt_render.h, PtAccum).
 // After windows totalling N samples, resolve() holds the bits render() gives at samples = N.  The scene must outlive the accumulator;
 // windows run on the default stream (or `stream`) and are ordered like renders of the scene.

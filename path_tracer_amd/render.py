@@ -159,6 +159,50 @@ def render_aov(width: int, height: int, samples: int, scene, cam: camera, *, pla
     return out
 
 
+def denoise(fb, *, albedo=None, normal=None, depth=None, iterations: int = abi.PT_DENOISE_DEFAULT_ITERATIONS,
+            sigma_color: float = abi.PT_DENOISE_DEFAULT_SIGMA_COLOR, sigma_normal: float = abi.PT_DENOISE_DEFAULT_SIGMA_NORMAL,
+            sigma_depth: float = abi.PT_DENOISE_DEFAULT_SIGMA_DEPTH, sigma_albedo: float = abi.PT_DENOISE_DEFAULT_SIGMA_ALBEDO,
+            demodulate: bool = True, no_lds: bool = False, out=None, **other_planes):
+    """The edge-avoiding a-trous filter over a finished frame (include/pt_render.h: pt_denoise), guided by the feature buffers:
+    denoise(fb, **render_aov(...)) — the planes the filter does not take (direct, coverage, id) are ignored.  `fb`: [H][W][3] float32
+    on the GPU, as render() returns it for a whole frame; albedo, normal [H][W][3], depth [H][W]: each optional; a sigma <= 0 turns
+    its term off; `demodulate` (needs albedo) filters color / (albedo + 1e-3) and multiplies the albedo back, so textures stay sharp.
+    `no_lds`: the A/B switch PT_DENOISE_NO_LDS (every tap from global memory; the same bits).
+    Asynchronous on torch's current stream; torch allocates the scratch.  Returns the filtered frame — `out` if given, which may be
+    `fb` itself."""
+    import torch
+
+    if not torch.cuda.is_available():
+        raise RuntimeError("path_tracer_amd.denoise needs a HIP device: there is no CPU path in the product")
+    lib = abi.load_library()
+    if not abi.has_denoise(lib):
+        raise ImportError(f"{abi.library_path()} predates the denoiser (no pt_denoise entry point)")
+    unknown = set(other_planes) - set(abi.AOV_PLANES)
+    if unknown:
+        raise TypeError(f"denoise() got unexpected keyword arguments {sorted(unknown)}")
+
+    def plane(t, shape, what):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()):
+            raise ValueError(f"{what} must be a contiguous float32 CUDA tensor of shape {shape}")
+        return C.c_void_p(t.data_ptr()) if t is not None else None
+
+    if fb.dim() != 3 or fb.shape[2] != 3:
+        raise ValueError("fb must be a whole frame [H][W][3] (gather and unshard a multi-GPU frame first)")
+    h, w, _ = (int(n) for n in fb.shape)
+    if out is None:
+        out = torch.empty((h, w, 3), dtype=torch.float32, device=fb.device)
+    n = lib.pt_denoise_scratch_floats(w, h)
+    if n < 0:
+        abi.check(abi.PT_ERR_INVALID_ARG, "pt_denoise_scratch_floats")
+    scratch = torch.empty(n, dtype=torch.float32, device=fb.device)
+    p = abi.PtDenoiseParams(C.sizeof(abi.PtDenoiseParams), w, h, int(iterations), float(sigma_color), float(sigma_normal), float(sigma_depth),
+                            float(sigma_albedo), (abi.PT_DENOISE_DEMODULATE if demodulate else 0) | (abi.PT_DENOISE_NO_LDS if no_lds else 0), 0)
+    abi.check(lib.pt_denoise(C.byref(p), plane(fb, (h, w, 3), "fb"), plane(albedo, (h, w, 3), "albedo"), plane(normal, (h, w, 3), "normal"),
+                             plane(depth, (h, w), "depth"), plane(out, (h, w, 3), "out"), C.c_void_p(scratch.data_ptr()), _stream_ptr(torch)),
+              "pt_denoise")
+    return out
+
+
 def render_host(width: int, height: int, samples: int, scene, cam: camera, depth: int = 50, *, flags: int = 0,
                 shard_index: int = 0, shard_count: int = 1) -> np.ndarray:
     """Torch-free path: pt_render_host renders into a numpy array (allocates, copies back, syncs)."""
@@ -336,6 +380,14 @@ class Accumulator:
             raise ValueError("out must be a contiguous float32 CUDA tensor of pt_framebuffer_floats() elements")
         abi.check(self.lib.pt_accum_resolve(self.handle, C.c_void_p(out.data_ptr()), _stream_ptr(torch)), "pt_accum_resolve")
         return out
+
+    def denoise(self, aov_spp: int = 16, **kw):
+        """resolve(), the feature buffers of the accumulator's own scene and bound camera (render_aov at `aov_spp` camera rays per
+        pixel) and denoise() over them: denoise(resolve(), **render_aov(...), **kw).  Whole frames only."""
+        if self.shard_count != 1:
+            raise ValueError("Accumulator.denoise: whole frames only (the filter reads neighbours: gather and unshard first)")
+        guides = render_aov(self.width, self.height, aov_spp, self._ds, self.cam, planes=("albedo", "normal", "depth"))
+        return denoise(self.resolve(), **guides, **kw)
 
     def tonemap_rgb8(self):
         """resolve() + tonemap_rgb8() in one pass (whole frames): uint8 [H][W][3], row 0 = top."""
