@@ -683,11 +683,24 @@ int pt_debug_flatten_pool(const PtSceneDesc* desc, const PtTuning* tuning, float
  * without that phase).  For tuning the makespan model (csrc/pt_render.hip: lpt_order_kernel) and for tests.            */
 int pt_debug_schedule(const PtScene* scene, int32_t out[2]);
 
-/* What the launcher decided for the LAST frame launch of this scene (csrc/pt_render.hip: launch): out[0] = workgroups launched,
+/* What the launcher decided for the LAST frame launch of this scene (csrc/pt_render.hip: plan_pass): out[0] = workgroups launched,
  * out[1] = lanes of a wave that take pixels (PtTuning.lanes_cap's rule; 64 = whole tiles), out[2] = queue positions at the head of the
  * cost-sorted order that are handed out 16 pixels at a time (PtTuning.heavy_tiles' rule; 0 = none), out[3] = 1 if the sphere-grid walk
  * through the LDS pair queue was picked.  For tests of those rules.                                                                  */
 int pt_debug_last_launch(const PtScene* scene, int32_t out[4]);
+
+/* The launcher's geometry rules for ONE pass (csrc/pt_render.hip: plan_pass), host-only: no scene, no device call, so the rules can be
+ * checked without a GPU and on a "chip" of any size.  Detected by its presence, like the entry points above that were added later.
+ * facts[0] = CUs, [1] = the kernel's resident workgroups per CU, [2] = threads per workgroup; the kernel variant: [3] chain-bound (the
+ * headline family), [4] walks a sphere grid, [5] walks it through the pair queue; [6] = PtRenderParams.flags; PtTuning fields as a scene
+ * takes them: [7] blocks_per_cu, [8] lanes_cap, [9] heavy_tiles, [10] != 0: chain_priority = -1; [11] = work units in the queue (tiles;
+ * PT_FLAG_FAST_RNG: tiles x chunks), [12] = local pixels (64 x tiles; fast mode: x chunks), [13] = PtRenderParams.samples; the pass:
+ * [14] != 0 the cost probe, [15] != 0 a tile order exists, [16] != 0 a wide phase exists, [17] != 0 whole tiles per wave, [18] = the
+ * scatter stride of the triangle-pool kernels (0: none), [19] = fast-mode chunks per pixel (0: parity mode).
+ * out[0] = workgroups, [1] = their waves, [2] = lanes of a wave that take pixels, [3] = whole tiles per wave after that cap, [4] / [5] =
+ * queue positions of the narrow head and the lanes that take them, [6] = queue position from which the chain priorities act, [7..9] =
+ * their thresholds for priority 1, 2, 3, [10..13] = what pt_debug_last_launch reports after a frame pass of these facts.               */
+int pt_debug_plan_pass(const int64_t facts[20], int32_t out[14]);
 
 /* Which kernel instantiations the LAST pt_render / pt_render_accumulate of this scene launched: out[0..11] the cost-probe pass,
  * out[12..23] the frame pass.  Word 0 of a pass is the kernel family — 0 no such pass, 1 render_kernel, 2 render_kernel_stream,

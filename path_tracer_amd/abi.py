@@ -211,6 +211,8 @@ SIGNATURES = {
     "pt_denoise_scratch_floats": (C.c_int64, [C.c_int32, C.c_int32]),
     "pt_denoise": (C.c_int, [C.POINTER(PtDenoiseParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pt_debug_last_denoise": (C.c_int, [C.POINTER(C.c_int32)]),
+    # the launcher's geometry rules for one pass, host-only: likewise optional (PLAN_SYMBOLS)
+    "pt_debug_plan_pass": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
 }
 
 # Entry points a library may lack and still load for everything else (include/pt_render.h: the feature is detected by their presence);
@@ -229,6 +231,12 @@ AOV_PLANES = ("albedo", "normal", "direct", "depth", "coverage", "id")  # PtAovB
 AOV_CHANNELS = {"albedo": 3, "normal": 3, "direct": 3, "depth": 1, "coverage": 1, "id": 1}
 # the a-trous denoiser (include/pt_render.h: pt_denoise); has_denoise() tells whether the loaded library has it
 DENOISE_SYMBOLS = frozenset({"pt_denoise_params_init", "pt_denoise_scratch_floats", "pt_denoise", "pt_debug_last_denoise"})
+# the launcher's planner as an entry point (include/pt_render.h: pt_debug_plan_pass): the order of its facts and of its output words
+PLAN_SYMBOLS = frozenset({"pt_debug_plan_pass"})
+PLAN_FACTS = ("num_cus", "per_cu", "block_threads", "chain_bound", "use_grid", "queued_walk", "flags", "blocks_per_cu", "lanes_cap", "heavy_tiles",
+              "no_chain_prio", "launch_units", "n_local_pixels", "samples", "probe", "has_order", "has_split", "tile_granular", "scatter_p", "fast_chunks")
+PLAN_WORDS = ("workgroups", "n_waves_resident", "lanes_cap", "tile_granular", "heavy_pixels", "heavy_lanes", "prio_onset", "prio_t1", "prio_t2",
+              "prio_t3", "last_workgroups", "last_lanes_cap", "last_heavy_pixels", "last_queued_walk")
 PT_DENOISE_DEMODULATE = 1
 PT_DENOISE_NO_LDS = 2  # A/B switch, same bits: every iteration reads its taps from global memory
 PT_DENOISE_MAX_ITERATIONS = 8
@@ -279,7 +287,7 @@ def load_library() -> C.CDLL:
         pass  # torch-free hosts bind to /opt/rocm/lib through the library's RUNPATH
     lib = C.CDLL(str(path))
     for name, (res, args) in SIGNATURES.items():
-        if override_is_older_build(path, lib, name) or (name in ACCUM_SYMBOLS | ADAPTIVE_SYMBOLS | AOV_SYMBOLS | DENOISE_SYMBOLS and not hasattr(lib, name)):
+        if override_is_older_build(path, lib, name) or (name in ACCUM_SYMBOLS | ADAPTIVE_SYMBOLS | AOV_SYMBOLS | DENOISE_SYMBOLS | PLAN_SYMBOLS and not hasattr(lib, name)):
             continue
         fn = getattr(lib, name)  # AttributeError if the library does not export what the header declares
         fn.restype = res

@@ -1581,7 +1581,7 @@ struct Knobs {
   bool no_scatter = false; // triangle-pool kernels hand out whole tiles' pixels to a wave again (lane_acquire)
   bool generic_materials = false;
   int grid_walk = 0;       // PtTuning.grid_walk: 0 the launcher's rule, 1 the wave-synchronous walk, 2 the queued walk
-  int lanes_cap = 0;       // PtTuning.lanes_cap: grid kernels on small frames (launch): 0 the rule, -1 whole tiles always, n forced
+  int lanes_cap = 0;       // PtTuning.lanes_cap: grid kernels on small frames (plan_pass): 0 the rule, -1 whole tiles always, n forced
   bool no_tri_cache = false;  // PtTuning.tri_cache = -1: camera rays enumerate their direction-map list like every other ray
   bool no_chain_prio = false; // PtTuning.chain_priority = -1: no issue priorities in the headline family's frame launches
   bool no_resume = false;  // PtTuning.probe_resume = -1: the probe's samples are rendered again by the frame launch
@@ -1767,7 +1767,7 @@ struct Variant {
   bool resident = false;   // render_kernel (blob in LDS or read through the scalar cache), not render_kernel_stream
   bool use_grid = false;   // the kernel walks the scene's sphere grids
   bool coop = false;       // cooperative kernel
-  bool chain_bound = false; // the headline family — no sphere grid, no cooperative phase: see `launch`
+  bool chain_bound = false; // the headline family — no sphere grid, no cooperative phase: see `plan_pass`
   bool queued_walk = false; // the kernel walks sphere grids through the pair queue (pt_debug_last_launch)
 };
 
@@ -1840,11 +1840,11 @@ Variant choose_variant_uv(const PtScene* s, const PtRenderParams* p, int local_t
   }
   if (v.use_grid) {
     // Which sphere-grid walk (pt_device.hpp: sphere_scan, GRID = 1 / 2): the pair queue where walks diverge or the launch is bound by its
-    // chains — whole tiles per wave or at least 16 lanes (the rule of `launch`, evaluated for the kernels' four workgroups per CU) — and
+    // chains — whole tiles per wave or at least 16 lanes (the rule of `plan_pass`, evaluated for the kernels' four workgroups per CU) — and
     // not on frames that are both dense (>= 4 M pixels: a tile's rays share their cells) and throughput-bound (>= 6 pixels per resident lane).
-    // The rule is evaluated for the resident lanes the GRID = 2 kernels really have (their occupancy is queried like `launch` does: 31 KB LDS
+    // The rule is evaluated for the resident lanes the GRID = 2 kernels really have (their occupancy is queried like `plan_pass` does: 31 KB LDS
     // image + 4 KB of per-wave queues and slots usually allow four workgroups per CU) — round 4 assumed 16 waves per CU here and the cap of
-    // `launch` from the measured occupancy, and the two could disagree.  The queued walk's STATIC 4 KB of LDS (sphere_queue,
+    // `plan_pass` from the measured occupancy, and the two could disagree.  The queued walk's STATIC 4 KB of LDS (sphere_queue,
     // sphere_slots) ride on top of the dynamic blob image: where the sum exceeds what a workgroup may have, the walk stays in place.
     constexpr size_t kQueuedWalkStaticLds = (size_t)PT_MAX_WAVES_PER_BLOCK * (PT_SQ_CAP * 4 + 64 * 8);
     const Picked queued = mlds ? picked_of<KV{.uv = UV, .lds = true, .mlds = true, .grid = 2}> : picked_of<KV{.uv = UV, .lds = true, .grid = 2}>;
@@ -2118,13 +2118,17 @@ void pt_scene_destroy(PtScene* s) {
   delete s; // (its buffers: DevBuf members)
 }
 
+// the shard of a frame's parameters: what check_params and check_aov_params ask after their own conditions on the sizes
+static int check_shard(const PtRenderParams* p) {
+  if (p->shard_count < 1 || p->shard_index < 0 || p->shard_index >= p->shard_count)
+    return fail(PT_ERR_INVALID_ARG, "need 0 <= shard_index < shard_count");
+  return PT_OK;
+}
 static int check_params(const PtRenderParams* p) {
   if (!p) return fail(PT_ERR_INVALID_ARG, "render params are NULL");
   if (p->width <= 0 || p->height <= 0 || p->samples <= 0 || p->depth < 0)
     return fail(PT_ERR_INVALID_ARG, "width, height, samples must be > 0 and depth >= 0");
-  if (p->shard_count < 1 || p->shard_index < 0 || p->shard_index >= p->shard_count)
-    return fail(PT_ERR_INVALID_ARG, "need 0 <= shard_index < shard_count");
-  return PT_OK;
+  return check_shard(p);
 }
 
 static int n_tiles_of(const PtRenderParams* p, int* tiles_x) {
@@ -2132,6 +2136,8 @@ static int n_tiles_of(const PtRenderParams* p, int* tiles_x) {
   if (tiles_x) *tiles_x = tx;
   return tx * ty;
 }
+// the tiles of a shard's compact buffer: the same for every shard of a frame (the last ones' final tile may be padding)
+static int tiles_per_shard(int n_tiles, int shard_count) { return (n_tiles + shard_count - 1) / shard_count; }
 // the tiles shard p->shard_index owns: tile t belongs to shard t % shard_count
 static int local_tiles_of(const PtRenderParams* p) { return (n_tiles_of(p, nullptr) - p->shard_index + p->shard_count - 1) / p->shard_count; }
 // PT_FLAG_FAST_RNG: the chunks a pixel's samples are rendered in
@@ -2147,8 +2153,7 @@ uint32_t pt_fast_seed(uint32_t pixel, uint32_t chunk) { return fast_seed(pixel, 
 
 int32_t pt_shard_tiles(const PtRenderParams* p) {
   if (check_params(p)) return -1;
-  int n = n_tiles_of(p, nullptr);
-  return (n + p->shard_count - 1) / p->shard_count;
+  return tiles_per_shard(n_tiles_of(p, nullptr), p->shard_count);
 }
 
 int64_t pt_framebuffer_floats(const PtRenderParams* p) {
@@ -2275,6 +2280,209 @@ static int reserve_binned(const PtScene* s, size_t N, size_t K, size_t& bytes) {
   return PT_OK;
 }
 
+} // extern "C"
+
+namespace {
+
+// ---- one pass of launch_render: its launch geometry (plan_pass), its enqueue (enqueue_pass) ---------------------------------------
+
+// What plan_pass decides from: plain values, no pointer into the scene (pt_debug_plan_pass feeds it the same way without a device).
+struct PassFacts {
+  int num_cus = 0;         // PtScene.num_cus
+  int per_cu = 0;          // the kernel's resident workgroups per CU as queried (occupancy_of): >= 1
+  int block_threads = kBlock;
+  bool chain_bound = false, use_grid = false, queued_walk = false; // the pass's Variant (a fast-mode pass after a probe: or the probe's)
+  uint32_t flags = 0;      // PtRenderParams.flags
+  int blocks_per_cu = 0, lanes_cap = 0, heavy_tiles = 0; // Knobs of the same names
+  bool no_chain_prio = false;
+  long long launch_units = 0; // waves worth of work in the queue (tiles; fast mode: tiles x chunks)
+  int n_local_pixels = 0;  // KArgs.n_local_pixels
+  int samples = 0;         // PtRenderParams.samples (a window's length)
+  bool probe = false;      // the cost-probe pass (KArgs.cost)
+  bool has_order = false;  // a tile order exists (KArgs.order)
+  bool has_split = false;  // a wide phase exists (KArgs.n_split)
+  int tile_granular = 0, scatter_p = 0, fast_chunks = 0; // KArgs of the same names, as the pass sequence set them
+};
+
+// What it decides: the launch's size and the KArgs members that follow from it (enqueue_pass writes them into the pass's KArgs).
+struct PassPlan {
+  int workgroups = 1;
+  int n_waves_resident = 1; // the waves of the launch (lpt_order_kernel's makespan model takes the probe pass's)
+  int lanes_cap = 64, tile_granular = 0;
+  int heavy_pixels = 0, heavy_lanes = 64;
+  int prio_onset = 0, prio_t1 = 0, prio_t2 = 0, prio_t3 = 0;
+  int last_launch[4] = {0, 0, 0, 0}; // PtScene.last_launch of a frame pass (pt_debug_last_launch)
+};
+
+// Persistent grid: no more workgroups than the chip holds at once; lanes pull pixels from the queue.
+PassPlan plan_pass(const PassFacts& f) {
+  PassPlan pl;
+  const int block_threads = f.block_threads;
+  const int waves_per_block = block_threads / 64;
+  int per_cu = f.per_cu;
+  // (small frames through the grid kernels: below; PT_FLAG_TILE_GRANULAR / PT_FLAG_PIXEL_GRANULAR and the fast mode keep what they ask for)
+  // (only the kernels that walk a sphere grid: the headline family's iteration — slab pass, wave-uniform — does not get shorter with fewer
+  // lanes: its shard 0/8 took 127 ms that way against 40)
+  const bool share_small = f.use_grid && f.lanes_cap >= 0 && !(f.flags & (PT_FLAG_TILE_GRANULAR | PT_FLAG_PIXEL_GRANULAR | PT_FLAG_FAST_RNG));
+  // A headline-family launch with fewer than ~1.15 tiles per wave slot (shard 0 of 4 ... 6 of the 1080p frame) is bound by its heaviest
+  // tiles' sequential chains, and a chain's iteration takes as long as the waves that share its SIMD make it: four waves per SIMD that
+  // take two tiles each, heaviest first, finish before eight that take one.  Cornell-style 1080p x 1024 spp, kernel ms of shard 0 of
+  // N = 3 / 4 / 6 at 8 and at 4 workgroups per CU: 63.3 / 57.8 / 43.4 and 60.3 / 51.1 / 42.8 (profiles/r04_blocks_sweep.txt); whole frames
+  // and halves (>= 2 tiles per slot) keep the full occupancy, and a launch with half a tile per slot takes four per CU by itself.
+  // (Grid and triangle-pool kernels: their own occupancy is the best at every shard count — same file.)
+  // (Round 5, with the chain priorities of render_kernel: shard 0 of 3 — 1.3 tiles per slot — 61.2 ms at four workgroups per CU, 54.4 / 57.1 at
+  // six / eight; shard 0 of 4 — 1.0 — 45.2 / 47.3 / 48.7: the bound moved from 1.6 to 1.15; profiles/r05_ab_chain_priority.txt.)
+  if (f.chain_bound && !f.blocks_per_cu && !f.has_split && f.scatter_p == 0 &&
+      (double)f.launch_units < 1.15 * (double)per_cu * waves_per_block * std::max(1, f.num_cus))
+    per_cu = std::min(per_cu, 4);
+  if (f.blocks_per_cu) per_cu = std::min(per_cu, f.blocks_per_cu); // tuning knob
+  // longest remaining chain first (render_kernel): the headline family's frame launches in parity mode, from the middle of the queue on
+  if (f.chain_bound && !f.probe && !f.fast_chunks && f.tile_granular && !f.no_chain_prio && f.samples >= 16) {
+    pl.prio_onset = f.n_local_pixels / 2;
+    pl.prio_t3 = f.samples / 2; pl.prio_t2 = f.samples / 4; pl.prio_t1 = f.samples / 8;
+  }
+  const int resident_blocks = std::max(1, per_cu) * std::max(1, f.num_cus);
+  // one wave per tile is enough, except in the wide phase, where a split tile keeps G waves busy (how many tiles are
+  // split is decided on the device, so such a launch simply fills the chip; surplus waves find the queues empty and exit)
+  long long wanted = f.has_split ? (long long)resident_blocks : (f.launch_units + waves_per_block - 1) / waves_per_block;
+  pl.lanes_cap = 64;
+  pl.tile_granular = f.tile_granular;
+  // Frames (or shards) that do not fill the chip several times over are bound by their pixels' sequential chains, not by throughput —
+  // BASELINE config 1 is 1 406 tiles for 4 096 resident waves, a shard of an 8-GPU job about one tile per wave — and a wave that steps
+  // 64 pixels together pays, every iteration, for the LONGEST walk, the largest candidate count and every material among them.  Such a
+  // launch fills the chip and gives each wave only `lanes_cap` lanes' worth of pixels at a time (one pixel per lane, refilled from the
+  // queue: consecutive positions = neighbouring pixels of one tile row, so the walks stay coherent): fewer lanes per wave = a shorter
+  // iteration for the pixels that set the frame time.  Measured on one box (profiles/r04_ab_lanes_cap.txt; rho = pixels per resident
+  // lane): config 1 (rho 0.34) 24.5 ms at 64 lanes, 22.0 at 24, 19.2 at 8, 17.9 at 4; shard 0/8 of the 1080p frame (rho 1.0) 70.9 / 61.6 /
+  // 60.1 / 76.4 ms at 64 / 32 / 16 / 8; shard 0/8 of the 4K frame (rho 4.0) 201.7 / 209.8 / 218.1 at 64 / 48 / 32: lanes = 16 rho fits all
+  // three (rounded to the nearest multiple of 4).  Which lane renders a pixel changes nothing in the image (a pixel's seed is its id).
+  if (share_small && f.scatter_p == 0) {
+    const long long lanes = (long long)resident_blocks * waves_per_block * 64;
+    long long cap = (16 * (long long)f.n_local_pixels + lanes / 2) / lanes; // 16 rho
+    cap = std::min<long long>(64, std::max<long long>(4, (cap + 2) / 4 * 4)); // (the nearest multiple of 4: half a tile row)
+    if (cap > 24) cap = 64; // (rho 2: 93.9 ms at 32 lanes against 90.9 at 64 — from there on the frame is throughput)
+    if (f.lanes_cap > 0) cap = std::min(64, f.lanes_cap); // PtTuning.lanes_cap: forced
+    if (cap < 64) {
+      pl.lanes_cap = (int)cap;
+      pl.tile_granular = 0;
+      wanted = std::min<long long>(resident_blocks, ((long long)f.n_local_pixels + cap * waves_per_block - 1) / (cap * waves_per_block));
+      wanted = std::max<long long>(wanted, 1);
+    }
+  }
+  // Between the launches that the rule above serves (fewer than 1.5 pixels per resident lane) and the ones that are throughput (6 and
+  // more) lie the shards of a multi-GPU job on a big frame — one of 8 GPUs on the 4K frame: 4 pixels per lane — whose time is their
+  // heaviest tiles' chains: whole tiles everywhere, except that the head of the cost-sorted queue (one tile per SIMD of the chip) is handed
+  // out 16 pixels at a time (lane_acquire: heavy_pixels).  Kernel ms of shard 0 of N, whole tiles / with the narrow head — 4K x 512 spp
+  // N = 8 / 6 / 5 / 4: 196.8 / 203.9 / 220.4 / 209.1 -> 162.7 / 169.1 / 217.2 / 208.8; 1080p x 512 spp N = 2 / 3 / 4: 189.3 / 189.2 / 176.2 ->
+  // 165.4 / 159.2 / 155.3; whole frames lose (1080p: 382 -> 435 ms), hence the upper bound (profiles/r04_heavy_tiles.txt).
+  // Needs the cost-sorted order (the probe pass ran) — and changes nothing in the image: a pixel's seed is its id.
+  if (share_small && pl.lanes_cap == 64 && pl.tile_granular && f.has_order && f.scatter_p == 0 && !f.probe && f.heavy_tiles >= 0) {
+    const double lanes = (double)resident_blocks * waves_per_block * 64.0, rho = (double)f.n_local_pixels / lanes;
+    long long tiles = f.heavy_tiles > 0 ? f.heavy_tiles : (rho >= 1.5 && rho < 6.0 ? 4LL * std::max(1, f.num_cus) : 0);
+    tiles = std::min<long long>(tiles, f.n_local_pixels / 64 / 2);
+    if (tiles > 0) { pl.heavy_pixels = (int)(tiles * 64); pl.heavy_lanes = 16; }
+  }
+  if (f.scatter_p > 0) { // triangle-pool kernels: fill the chip and share the pixels out evenly (lane_acquire)
+    wanted = std::min<long long>(resident_blocks, ((long long)f.n_local_pixels + block_threads - 1) / block_threads * 64); // (at least one pixel per wave)
+    wanted = std::max<long long>(wanted, 1);
+    const long long waves = std::min<long long>(wanted, resident_blocks) * waves_per_block;
+    pl.lanes_cap = (int)std::min<long long>(64, std::max<long long>(1, ((long long)f.n_local_pixels + waves - 1) / waves));
+  }
+  pl.workgroups = (int)std::min<long long>(wanted, resident_blocks);
+  pl.n_waves_resident = (int)std::min<long long>(wanted, resident_blocks) * waves_per_block;
+  pl.last_launch[0] = pl.workgroups; pl.last_launch[1] = pl.lanes_cap; pl.last_launch[2] = pl.heavy_pixels; pl.last_launch[3] = f.queued_walk ? 1 : 0;
+  return pl;
+}
+
+// the footprint of a pixel in direction space (camera.hpp:93-100 with lens_radius 0: d = llc + s hor + t ver - origin, s in [x / W, (x + 1) / W]):
+// KArgs.foot of the camera rays' candidate cache
+void pixel_footprint(const Cam& cm, float inv_w, float inv_h, float foot[11]) {
+  float base[3], hw[3], vh[3];
+  double dmax = 0, lh = 0, lv = 0;
+  for (int k = 0; k < 3; k++) {
+    base[k] = cm.llc[k] - cm.origin[k]; hw[k] = cm.horizontal[k] * inv_w; vh[k] = cm.vertical[k] * inv_h;
+    foot[k] = base[k]; foot[3 + k] = hw[k]; foot[6 + k] = vh[k];
+    lh += (double)hw[k] * hw[k]; lv += (double)vh[k] * vh[k];
+    dmax += std::fabs((double)cm.llc[k]) + std::fabs((double)cm.origin[k]) + std::fabs((double)cm.horizontal[k]) + std::fabs((double)cm.vertical[k]);
+  }
+  lh = std::sqrt(lh); lv = std::sqrt(lv);
+  // half a pixel each way (the jitter may round to the pixel's far edge), + the binary32 rounding of the camera's own arithmetic and of the centre ray
+  foot[9] = (float)((0.5 * (lh + lv)) * 1.001 + 1e-5 * dmax);
+  // ... and that rounding term alone, per component (the cache's choice of bins: pt_device.hpp, tri_pool_scan)
+  foot[10] = (float)(1e-5 * dmax);
+}
+
+// One pass onto the stream: kernel `v` over the pass's KArgs `a` (a copy: what the plan decided is written into it here), sized by `pl`.
+int enqueue_pass(const PtScene* s, const PtRenderParams* p, const Variant& v, const PassPlan& pl, int block_threads, KArgs a, hipStream_t st) {
+  a.lanes_cap = pl.lanes_cap; a.tile_granular = pl.tile_granular;
+  a.heavy_pixels = pl.heavy_pixels; a.heavy_lanes = pl.heavy_lanes;
+  a.prio_onset = pl.prio_onset; a.prio_t1 = pl.prio_t1; a.prio_t2 = pl.prio_t2; a.prio_t3 = pl.prio_t3;
+  const dim3 grid((unsigned int)pl.workgroups), block((unsigned int)block_threads);
+  // The camera rays' candidate cache (pt_device.hpp: TriPrimCtx): triangle-pool kernels, a pinhole camera (the rays of a pixel share
+  // their origin), pixel coordinates that fit 16 bits.  One 1 KB line per lane of the launch; every line starts out belonging to no pixel.
+  a.tri_cache = nullptr;
+  // (sized ahead by pt_accum_create — reserve_tricache; grown here otherwise, BEFORE the queue slot below is taken, and a failed
+  // allocation only costs the cache: the image does not depend on it)
+  const size_t cache_lanes = (size_t)grid.x * block.x;
+  if (v.tri_pool && a.cam.lens_radius == 0.0f && !s->knobs.no_tri_cache && p->width <= 65535 && p->height <= 65535 &&
+      grow_tricache(s, cache_lanes) == PT_OK) {
+    PT_HIP(hipMemsetAsync(s->ws_tricache.p, 0xff, cache_lanes * PT_TRI_CACHE_WORDS * 4, st));
+    a.tri_cache = s->ws_tricache.p;
+    pixel_footprint(a.cam, a.inv_w, a.inv_h, a.foot);
+  }
+  // Queue counters come from a ring of kQueueRing slots.  A slot is reused only after the launch that last used it has
+  // finished (more than kQueueRing launches in flight on one scene would otherwise share a dequeue counter and lose or
+  // duplicate pixels): the NEW launch's stream waits for that launch's event on the device — the host does not block, so
+  // pt_render stays asynchronous however many renders are queued (round 3 synchronised the host here, with the scene's
+  // scheduling mutex held).
+  const unsigned int slot = s->next_queue % kQueueRing;
+  if (s->ring_done[slot]) PT_HIP(hipStreamWaitEvent(st, s->ring_done[slot], 0));
+  else PT_HIP(hipEventCreateWithFlags(&s->ring_done[slot], hipEventDisableTiming));
+  s->next_queue++; // (only once nothing above can fail any more)
+  a.queue = s->queues.p + 2 * slot; // [0] ordinary queue, [1] wide-phase queue
+  PT_HIP(hipMemsetAsync(a.queue, 0, 2 * sizeof(unsigned int), st));
+  hipLaunchKernelGGL(v.kernel, grid, block, v.shmem, st, a);
+  PT_HIP(hipGetLastError());
+  s->last_kernels[a.cost ? 0 : 1] = v.tag;
+  PT_HIP(hipEventRecord(s->ring_done[slot], st));
+  return PT_OK;
+}
+
+// One pass of launch_render: the kernel's occupancy, the plan, the enqueue.  chain_bound / queued_walk: the variant's own, or — a fast-mode
+// pass after a probe — also what the probe pass of this call ran (the four-workgroup rule of plan_pass, pt_debug_last_launch).
+int run_pass(const PtScene* s, const PtRenderParams* p, const Variant& v, bool chain_bound, bool queued_walk, long long launch_units,
+             const KArgs& a, hipStream_t st, PassPlan* plan_out = nullptr) {
+  PassFacts f;
+  f.num_cus = s->num_cus;
+  f.per_cu = occupancy_of(s, (const void*)v.kernel, f.block_threads, v.shmem);
+  if (f.per_cu < 0) return PT_ERR_HIP;
+  // (a kernel variant that does not fit a CU at all — its static + dynamic LDS beyond the device's limit — must not be launched and hoped for)
+  if (f.per_cu < 1) return fail(PT_ERR_TOO_LARGE, "pt_render: this scene's kernel variant does not fit a compute unit (LDS " + std::to_string(v.shmem) + " B dynamic + static)");
+  f.chain_bound = chain_bound; f.use_grid = v.use_grid; f.queued_walk = queued_walk;
+  f.flags = p->flags;
+  f.blocks_per_cu = s->knobs.blocks_per_cu; f.lanes_cap = s->knobs.lanes_cap; f.heavy_tiles = s->knobs.heavy_tiles; f.no_chain_prio = s->knobs.no_chain_prio;
+  f.launch_units = launch_units; f.n_local_pixels = a.n_local_pixels; f.samples = p->samples;
+  f.probe = a.cost != nullptr; f.has_order = a.order != nullptr; f.has_split = a.n_split != nullptr;
+  f.tile_granular = a.tile_granular; f.scatter_p = a.scatter_p; f.fast_chunks = a.fast_chunks;
+  const PassPlan pl = plan_pass(f);
+  if (plan_out) *plan_out = pl;
+  if (!f.probe) std::copy(pl.last_launch, pl.last_launch + 4, s->last_launch);
+  return enqueue_pass(s, p, v, pl, f.block_threads, a, st);
+}
+
+// The frame block that KArgs and AovArgs share: the scene's tables, the camera, the frame's sizes and reciprocals, shard and tile counts
+template <typename Args>
+void set_frame(Args& a, const PtScene* s, const PtCamera* cam, const PtRenderParams* p) {
+  std::memcpy(&a.cam, cam, sizeof(Cam));
+  a.blob = s->blob.p; a.mats = s->mats; a.pool = s->pool.p; a.atlas = s->atlas.p;
+  a.n_runs = s->n_runs;
+  a.width = p->width; a.height = p->height; a.samples = p->samples;
+  a.inv_w = 1.0f / (float)p->width; a.inv_h = 1.0f / (float)p->height; // host IEEE division: correctly rounded
+  a.pinhole = cam_is_pinhole(a.cam) ? 1 : 0;
+  a.shard_index = p->shard_index; a.shard_count = p->shard_count;
+  a.n_tiles = n_tiles_of(p, &a.tiles_x);
+}
+
 // One sample window of a PtAccum (pt_render_accumulate): p->samples is the window's length, fb the accumulator's radiance sums.
 struct Window {
   int done;          // samples the state already holds: the window renders [done, done + p->samples)
@@ -2289,7 +2497,16 @@ struct Window {
   int n_active = 0;
 };
 
-static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderParams* p, float* fb, hipStream_t st, const Window* w = nullptr) {
+// (after a pass's n_local_pixels is final: fast mode multiplies it by the chunks per pixel)
+void set_scatter(KArgs& a, int scatter_log) {
+  a.scatter_log = scatter_log;
+  a.scatter_p = (int)scatter_stride((unsigned int)a.n_local_pixels >> 6, 64u >> a.scatter_log /* tiles a wave's 64 pixels come from */);
+}
+
+// A render, a sample window or a masked window as a sequence of passes: the early exits (single stream, binned renderer), the optional
+// cost probe with the tile order it leaves, then the frame pass — or, in the opt-in fast mode, the chunk pass and its reduction.  Every
+// pass takes its KArgs from `base` by value; which kernel it runs is choose_variant's, how it is sized plan_pass's (through run_pass).
+int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderParams* p, float* fb, hipStream_t st, const Window* w = nullptr) {
   int cur = -1;
   PT_HIP(hipGetDevice(&cur));
   if (cur != s->device)
@@ -2297,181 +2514,49 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
                                         std::to_string(cur) + " (hipSetDevice to the scene's device first)");
   std::lock_guard<std::mutex> lock(s->sched);
   s->last_kernels[0] = s->last_kernels[1] = KTag{}; // (a pass that does not run leaves family 0)
-  KArgs a;
-  std::memcpy(&a.cam, cam, sizeof(Cam));
-  a.blob = s->blob.p; a.mats = s->mats; a.pool = s->pool.p; a.atlas = s->atlas.p; a.fb = fb;
-  a.n_runs = s->n_runs; a.blob_f4 = s->blob_f4; a.mats_f4 = s->mats_f4; a.n_hittables = s->n_hittables;
-  a.width = p->width; a.height = p->height; a.samples = p->samples; a.depth = p->depth;
-  a.inv_w = 1.0f / (float)p->width; a.inv_h = 1.0f / (float)p->height; // host IEEE division: correctly rounded
-  a.pinhole = cam_is_pinhole(a.cam) ? 1 : 0;
-  a.shard_index = p->shard_index; a.shard_count = p->shard_count;
-  a.n_tiles = n_tiles_of(p, &a.tiles_x);
+  KArgs base;
+  set_frame(base, s, cam, p);
+  base.fb = fb;
+  base.blob_f4 = s->blob_f4; base.mats_f4 = s->mats_f4; base.n_hittables = s->n_hittables;
+  base.depth = p->depth;
   const bool masked = w && w->mask;
   // tiles this shard owns (a masked window: the tiles it renders)
   const int local_tiles = masked ? w->n_active : local_tiles_of(p);
-  if (masked) a.mask = w->mask;
+  if (masked) base.mask = w->mask;
   // pixels no lane owns (edge tiles, padded last tile, depth 0) read as 0 (a window's sums: zeroed by pt_accum_create / _reset)
   if (!w) PT_HIP(hipMemsetAsync(fb, 0, (size_t)pt_framebuffer_floats(p) * sizeof(float), st));
   if (local_tiles <= 0) return PT_OK;
-  a.fast_ok = (s->fast_ok && !(p->flags & PT_FLAG_NO_FASTDIV)) ? 1 : 0;
+  base.fast_ok = (s->fast_ok && !(p->flags & PT_FLAG_NO_FASTDIV)) ? 1 : 0;
   if (p->flags & PT_FLAG_SINGLE_STREAM) { // the reference's single-task executor: one sequential chain, one lane
     if (p->shard_count != 1) return fail(PT_ERR_INVALID_ARG, "PT_FLAG_SINGLE_STREAM needs shard_count == 1");
     if ((long long)p->width * p->height * p->samples > (1ll << 22))
       return fail(PT_ERR_TOO_LARGE, "PT_FLAG_SINGLE_STREAM is sequential by definition: width * height * samples <= 2^22");
     if (p->depth <= 0) return PT_OK;
-    hipLaunchKernelGGL(render_single_stream_kernel, dim3(1), dim3(64), 0, st, a);
+    hipLaunchKernelGGL(render_single_stream_kernel, dim3(1), dim3(64), 0, st, base);
     PT_HIP(hipGetLastError());
     s->last_kernels[1].w[0] = KFAM_SINGLE;
     return PT_OK;
   }
   // (sample windows run the persistent kernels: both renderers give the reference's image, and only these resume a pixel)
-  if (s->binned && !w && !(p->flags & (PT_FLAG_FORCE_STREAM | PT_FLAG_FAST_RNG))) return launch_binned(s, a, p, local_tiles, st);
-  a.n_local_pixels = local_tiles * PT_TILE_PIXELS;
+  if (s->binned && !w && !(p->flags & (PT_FLAG_FORCE_STREAM | PT_FLAG_FAST_RNG))) return launch_binned(s, base, p, local_tiles, st);
+  base.n_local_pixels = local_tiles * PT_TILE_PIXELS;
   // The parity-mode kernel variant: the probe pass and the frame pass run it (the fast mode chooses its frame launch's own, below)
-  const Variant pv = choose_variant(s, p, local_tiles, false, a.n_local_pixels);
+  const Variant pv = choose_variant(s, p, local_tiles, false, base.n_local_pixels);
   if (pv.rc) return pv.rc;
   const bool tri_pool = pv.tri_pool, use_grid = pv.use_grid, coop = pv.coop; // (the same in every pass)
-  a.coop_prefix = pv.coop_prefix;
-  a.samples_total = p->samples;
-  long long launch_units = local_tiles; // waves worth of work in the queue (tiles; fast mode: tiles x chunks)
-  if (const char* e = std::getenv("PT_TILE_GROUP")) { const int g = std::atoi(e); if (g == 16 || g == 32) a.tile_group = g; } // (experiment)
+  base.coop_prefix = pv.coop_prefix;
+  base.samples_total = p->samples;
+  if (const char* e = std::getenv("PT_TILE_GROUP")) { const int g = std::atoi(e); if (g == 16 || g == 32) base.tile_group = g; } // (experiment)
   // default: whole tiles for the resident kernels (coherent primary rays), single pixels for the lock-step
   // streaming kernel (a workgroup waits for its slowest lane); either can be forced
   // (the triangle-pool kernels' iterations are long and per-lane: single pixels, like the streaming kernel)
-  a.tile_granular = (p->flags & PT_FLAG_TILE_GRANULAR) ? 1 : (p->flags & PT_FLAG_PIXEL_GRANULAR) ? 0 : ((pv.resident && !tri_pool) ? 1 : 0);
-  auto set_scatter = [&]() { // (after a.n_local_pixels is final: fast mode multiplies it by the chunks per pixel)
-    if (!(tri_pool && !a.tile_granular && !s->knobs.no_scatter)) return;
-    a.scatter_log = s->knobs.scatter_log;
-    a.scatter_p = (int)scatter_stride((unsigned int)a.n_local_pixels >> 6, 64u >> a.scatter_log /* tiles a wave's 64 pixels come from */);
-  };
-  set_scatter();
+  base.tile_granular = (p->flags & PT_FLAG_TILE_GRANULAR) ? 1 : (p->flags & PT_FLAG_PIXEL_GRANULAR) ? 0 : ((pv.resident && !tri_pool) ? 1 : 0);
+  // the triangle-pool kernels' queues deal positions to the tiles with a stride (lane_acquire: scatter_p; set_scatter, per pass)
+  const bool scattered = tri_pool && !base.tile_granular && !s->knobs.no_scatter;
   const bool window = w && !(p->flags & PT_FLAG_FAST_RNG); // a parity-mode sample window: resumes from / keeps the per-pixel state
-  if (window) { a.samples = w->done + p->samples; a.resume_rng = w->rng; a.resume_spp = w->done; a.keep_state = 1; }
-  int n_waves_resident = 1;
-  // (small frames through the grid kernels: see `launch`; PT_FLAG_TILE_GRANULAR / PT_FLAG_PIXEL_GRANULAR and the fast mode keep what they ask for)
-  // (only the kernels that walk a sphere grid: the headline family's iteration — slab pass, wave-uniform — does not get shorter with fewer
-  // lanes: its shard 0/8 took 127 ms that way against 40)
-  const bool share_small = use_grid && s->knobs.lanes_cap >= 0 && !(p->flags & (PT_FLAG_TILE_GRANULAR | PT_FLAG_PIXEL_GRANULAR | PT_FLAG_FAST_RNG));
-  // Persistent grid: no more workgroups than the chip holds at once; lanes pull pixels from the queue.
-  auto launch = [&](const Variant& v, int block_threads = kBlock) -> int {
-    const size_t shmem = v.shmem;
-    const int waves_per_block = block_threads / 64;
-    int per_cu = occupancy_of(s, (const void*)v.kernel, block_threads, shmem);
-    if (per_cu < 0) return PT_ERR_HIP;
-    // (a kernel variant that does not fit a CU at all — its static + dynamic LDS beyond the device's limit — must not be launched and hoped for)
-    if (per_cu < 1) return fail(PT_ERR_TOO_LARGE, "pt_render: this scene's kernel variant does not fit a compute unit (LDS " + std::to_string(shmem) + " B dynamic + static)");
-    // A headline-family launch with fewer than ~1.15 tiles per wave slot (shard 0 of 4 ... 6 of the 1080p frame) is bound by its heaviest
-    // tiles' sequential chains, and a chain's iteration takes as long as the waves that share its SIMD make it: four waves per SIMD that
-    // take two tiles each, heaviest first, finish before eight that take one.  Cornell-style 1080p x 1024 spp, kernel ms of shard 0 of
-    // N = 3 / 4 / 6 at 8 and at 4 workgroups per CU: 63.3 / 57.8 / 43.4 and 60.3 / 51.1 / 42.8 (profiles/r04_blocks_sweep.txt); whole frames
-    // and halves (>= 2 tiles per slot) keep the full occupancy, and a launch with half a tile per slot takes four per CU by itself.
-    // (Grid and triangle-pool kernels: their own occupancy is the best at every shard count — same file.)
-    // (Round 5, with the chain priorities of render_kernel: shard 0 of 3 — 1.3 tiles per slot — 61.2 ms at four workgroups per CU, 54.4 / 57.1 at
-    // six / eight; shard 0 of 4 — 1.0 — 45.2 / 47.3 / 48.7: the bound moved from 1.6 to 1.15; profiles/r05_ab_chain_priority.txt.)
-    if (v.chain_bound && !s->knobs.blocks_per_cu && a.n_split == 0 && a.scatter_p == 0 &&
-        (double)launch_units < 1.15 * (double)per_cu * waves_per_block * std::max(1, s->num_cus))
-      per_cu = std::min(per_cu, 4);
-    if (s->knobs.blocks_per_cu) per_cu = std::min(per_cu, s->knobs.blocks_per_cu); // tuning knob
-    // longest remaining chain first (render_kernel): the headline family's frame launches in parity mode, from the middle of the queue on
-    a.prio_onset = 0; a.prio_t1 = a.prio_t2 = a.prio_t3 = 0;
-    if (v.chain_bound && !a.cost && !a.fast_chunks && a.tile_granular && !s->knobs.no_chain_prio && p->samples >= 16) {
-      a.prio_onset = a.n_local_pixels / 2;
-      a.prio_t3 = p->samples / 2; a.prio_t2 = p->samples / 4; a.prio_t1 = p->samples / 8;
-    }
-    const int resident_blocks = std::max(1, per_cu) * std::max(1, s->num_cus);
-    // Queue counters come from a ring of kQueueRing slots.  A slot is reused only after the launch that last used it has
-    // finished (more than kQueueRing launches in flight on one scene would otherwise share a dequeue counter and lose or
-    // duplicate pixels): the NEW launch's stream waits for that launch's event on the device — the host does not block, so
-    // pt_render stays asynchronous however many renders are queued (round 3 synchronised the host here, with the scene's
-    // scheduling mutex held).
-    // one wave per tile is enough, except in the wide phase, where a split tile keeps G waves busy (how many tiles are
-    // split is decided on the device, so such a launch simply fills the chip; surplus waves find the queues empty and exit)
-    long long wanted = a.n_split ? (long long)resident_blocks : (launch_units + waves_per_block - 1) / waves_per_block;
-    a.lanes_cap = 64;
-    // Frames (or shards) that do not fill the chip several times over are bound by their pixels' sequential chains, not by throughput —
-    // BASELINE config 1 is 1 406 tiles for 4 096 resident waves, a shard of an 8-GPU job about one tile per wave — and a wave that steps
-    // 64 pixels together pays, every iteration, for the LONGEST walk, the largest candidate count and every material among them.  Such a
-    // launch fills the chip and gives each wave only `lanes_cap` lanes' worth of pixels at a time (one pixel per lane, refilled from the
-    // queue: consecutive positions = neighbouring pixels of one tile row, so the walks stay coherent): fewer lanes per wave = a shorter
-    // iteration for the pixels that set the frame time.  Measured on one box (profiles/r04_ab_lanes_cap.txt; rho = pixels per resident
-    // lane): config 1 (rho 0.34) 24.5 ms at 64 lanes, 22.0 at 24, 19.2 at 8, 17.9 at 4; shard 0/8 of the 1080p frame (rho 1.0) 70.9 / 61.6 /
-    // 60.1 / 76.4 ms at 64 / 32 / 16 / 8; shard 0/8 of the 4K frame (rho 4.0) 201.7 / 209.8 / 218.1 at 64 / 48 / 32: lanes = 16 rho fits all
-    // three (rounded to the nearest multiple of 4).  Which lane renders a pixel changes nothing in the image (a pixel's seed is its id).
-    if (share_small && a.scatter_p == 0) {
-      const long long lanes = (long long)resident_blocks * waves_per_block * 64;
-      long long cap = (16 * (long long)a.n_local_pixels + lanes / 2) / lanes; // 16 rho
-      cap = std::min<long long>(64, std::max<long long>(4, (cap + 2) / 4 * 4)); // (the nearest multiple of 4: half a tile row)
-      if (cap > 24) cap = 64; // (rho 2: 93.9 ms at 32 lanes against 90.9 at 64 — from there on the frame is throughput)
-      if (s->knobs.lanes_cap > 0) cap = std::min(64, s->knobs.lanes_cap); // PtTuning.lanes_cap: forced
-      if (cap < 64) {
-        a.lanes_cap = (int)cap;
-        a.tile_granular = 0;
-        wanted = std::min<long long>(resident_blocks, ((long long)a.n_local_pixels + cap * waves_per_block - 1) / (cap * waves_per_block));
-        wanted = std::max<long long>(wanted, 1);
-      }
-    }
-    // Between the launches that the rule above serves (fewer than 1.5 pixels per resident lane) and the ones that are throughput (6 and
-    // more) lie the shards of a multi-GPU job on a big frame — one of 8 GPUs on the 4K frame: 4 pixels per lane — whose time is their
-    // heaviest tiles' chains: whole tiles everywhere, except that the head of the cost-sorted queue (one tile per SIMD of the chip) is handed
-    // out 16 pixels at a time (lane_acquire: heavy_pixels).  Kernel ms of shard 0 of N, whole tiles / with the narrow head — 4K x 512 spp
-    // N = 8 / 6 / 5 / 4: 196.8 / 203.9 / 220.4 / 209.1 -> 162.7 / 169.1 / 217.2 / 208.8; 1080p x 512 spp N = 2 / 3 / 4: 189.3 / 189.2 / 176.2 ->
-    // 165.4 / 159.2 / 155.3; whole frames lose (1080p: 382 -> 435 ms), hence the upper bound (profiles/r04_heavy_tiles.txt).
-    // Needs the cost-sorted order (the probe pass ran) — and changes nothing in the image: a pixel's seed is its id.
-    if (share_small && a.lanes_cap == 64 && a.tile_granular && a.order && a.scatter_p == 0 && !a.cost && s->knobs.heavy_tiles >= 0) {
-      const double lanes = (double)resident_blocks * waves_per_block * 64.0, rho = (double)a.n_local_pixels / lanes;
-      long long tiles = s->knobs.heavy_tiles > 0 ? s->knobs.heavy_tiles : (rho >= 1.5 && rho < 6.0 ? 4LL * std::max(1, s->num_cus) : 0);
-      tiles = std::min<long long>(tiles, a.n_local_pixels / 64 / 2);
-      if (tiles > 0) { a.heavy_pixels = (int)(tiles * 64); a.heavy_lanes = 16; }
-    }
-    if (a.scatter_p > 0) { // triangle-pool kernels: fill the chip and share the pixels out evenly (lane_acquire)
-      wanted = std::min<long long>(resident_blocks, ((long long)a.n_local_pixels + block_threads - 1) / block_threads * 64); // (at least one pixel per wave)
-      wanted = std::max<long long>(wanted, 1);
-      const long long waves = std::min<long long>(wanted, resident_blocks) * waves_per_block;
-      a.lanes_cap = (int)std::min<long long>(64, std::max<long long>(1, ((long long)a.n_local_pixels + waves - 1) / waves));
-    }
-    n_waves_resident = (int)std::min<long long>(wanted, resident_blocks) * waves_per_block;
-    if (!a.cost) { s->last_launch[0] = (int)std::min<long long>(wanted, resident_blocks); s->last_launch[1] = a.lanes_cap; s->last_launch[2] = a.heavy_pixels; s->last_launch[3] = v.queued_walk ? 1 : 0; }
-    dim3 grid((unsigned int)std::min<long long>(wanted, resident_blocks)), block((unsigned int)block_threads);
-    // The camera rays' candidate cache (pt_device.hpp: TriPrimCtx): triangle-pool kernels, a pinhole camera (the rays of a pixel share
-    // their origin), pixel coordinates that fit 16 bits.  One 1 KB line per lane of the launch; every line starts out belonging to no pixel.
-    a.tri_cache = nullptr;
-    // (sized ahead by pt_accum_create — reserve_tricache; grown here otherwise, BEFORE the queue slot below is taken, and a failed
-    // allocation only costs the cache: the image does not depend on it)
-    const size_t cache_lanes = (size_t)grid.x * block.x;
-    if (tri_pool && a.cam.lens_radius == 0.0f && !s->knobs.no_tri_cache && p->width <= 65535 && p->height <= 65535 &&
-        grow_tricache(s, cache_lanes) == PT_OK) {
-      const size_t lanes = cache_lanes;
-      PT_HIP(hipMemsetAsync(s->ws_tricache.p, 0xff, lanes * PT_TRI_CACHE_WORDS * 4, st));
-      a.tri_cache = s->ws_tricache.p;
-      // the footprint of a pixel in direction space (camera.hpp:93-100 with lens_radius 0: d = llc + s hor + t ver - origin, s in [x / W, (x + 1) / W])
-      const Cam& cm = a.cam;
-      float base[3], hw[3], vh[3];
-      double dmax = 0, lh = 0, lv = 0;
-      for (int k = 0; k < 3; k++) {
-        base[k] = cm.llc[k] - cm.origin[k]; hw[k] = cm.horizontal[k] * a.inv_w; vh[k] = cm.vertical[k] * a.inv_h;
-        a.foot[k] = base[k]; a.foot[3 + k] = hw[k]; a.foot[6 + k] = vh[k];
-        lh += (double)hw[k] * hw[k]; lv += (double)vh[k] * vh[k];
-        dmax += std::fabs((double)cm.llc[k]) + std::fabs((double)cm.origin[k]) + std::fabs((double)cm.horizontal[k]) + std::fabs((double)cm.vertical[k]);
-      }
-      lh = std::sqrt(lh); lv = std::sqrt(lv);
-      // half a pixel each way (the jitter may round to the pixel's far edge), + the binary32 rounding of the camera's own arithmetic and of the centre ray
-      a.foot[9] = (float)((0.5 * (lh + lv)) * 1.001 + 1e-5 * dmax);
-      // ... and that rounding term alone, per component (the cache's choice of bins: pt_device.hpp, tri_pool_scan)
-      a.foot[10] = (float)(1e-5 * dmax);
-    }
-    const unsigned int slot = s->next_queue % kQueueRing;
-    if (s->ring_done[slot]) PT_HIP(hipStreamWaitEvent(st, s->ring_done[slot], 0));
-    else PT_HIP(hipEventCreateWithFlags(&s->ring_done[slot], hipEventDisableTiming));
-    s->next_queue++; // (only once nothing above can fail any more)
-    a.queue = s->queues.p + 2 * slot; // [0] ordinary queue, [1] wide-phase queue
-    PT_HIP(hipMemsetAsync(a.queue, 0, 2 * sizeof(unsigned int), st));
-    hipLaunchKernelGGL(v.kernel, grid, block, shmem, st, a);
-    PT_HIP(hipGetLastError());
-    s->last_kernels[a.cost ? 0 : 1] = v.tag;
-    PT_HIP(hipEventRecord(s->ring_done[slot], st));
-    return PT_OK;
-  };
-  // Heaviest-first tile order from a probe pass (see lpt_order_kernel); pointless for short renders.
+  if (window) { base.samples = w->done + p->samples; base.resume_rng = w->rng; base.resume_spp = w->done; base.keep_state = 1; }
+
+  // ---- the cost probe: heaviest-first tile order from a probe pass (see lpt_order_kernel); pointless for short renders ----
   int probe_spp = std::min(4, p->samples / 16);
   // Tiles are ordered by their ray count — or, where a wave holds a tile until its last pixel is done and pixels differ
   // widely (the sphere-field scenes the grid kernels run: a few glass / mirror pixels per tile), by 64 x their heaviest
@@ -2482,40 +2567,42 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
   if (cost_by_max) probe_spp = std::min(std::max(probe_spp, p->samples / 64), s->knobs.probe_spp_max);
   // (the triangle-pool kernels deal every wave a stratified sample of the frame's tiles — lane_acquire, scatter_p — which balances the
   // waves without knowing the costs: the probe only costs there, 1080p x 32 spp 3.12 -> 2.95 s without it; PT_LPT_SCATTER=1 keeps it)
-  const bool probe_pays = !(a.scatter_p > 0) || s->knobs.lpt_with_scatter;
+  const bool probe_pays = !scattered || s->knobs.lpt_with_scatter;
   bool probed = false; // the probe pass ran
+  KArgs frame = base;  // the frame pass (fast mode: the chunk pass): `base` + the tile order and the probe's samples, where there are any
   if (masked) {
-    a.order = w->active; // (n_split stays NULL: no wide phase)
+    frame.order = w->active; // (n_split stays NULL: no wide phase)
   } else if (probe_spp >= 1 && local_tiles >= 64 && !(p->flags & PT_FLAG_NO_LPT) && probe_pays) {
     if (int rc = reserve_tiles(s, local_tiles)) return rc; // first render at a new size only (or never: pt_scene_reserve)
     PT_HIP(hipMemsetAsync(s->ws_cost.p, 0, (size_t)local_tiles * sizeof(unsigned int), st));
-    KArgs main_args = a;
-    a.cost = s->ws_cost.p;
-    a.cost_max = (cost_by_max && !coop) ? 1 : 0;
-    a.samples = probe_spp;
-    a.keep_state = 0;
+    KArgs probe = base;
+    if (scattered) set_scatter(probe, s->knobs.scatter_log);
+    probe.cost = s->ws_cost.p;
+    probe.cost_max = (cost_by_max && !coop) ? 1 : 0;
+    probe.samples = probe_spp;
+    probe.keep_state = 0;
     // the probe's samples are kept (KArgs.resume_rng) — not in the opt-in fast mode, whose chunks are streams of their own
     const bool resume = !(p->flags & PT_FLAG_FAST_RNG) && !s->knobs.no_resume;
-    a.resume_rng = resume ? s->ws_rng.p : nullptr;
-    a.resume_spp = 0;
+    probe.resume_rng = resume ? s->ws_rng.p : nullptr;
+    probe.resume_spp = 0;
     // a sample window's probe renders the window's first samples from the accumulator's state, in place; with probe_resume = -1 it
     // only costs (from the pixels' seeds: it writes nothing) and the frame launch renders the whole window
-    if (window && resume) { a.samples = w->done + probe_spp; a.resume_rng = w->rng; a.resume_spp = w->done; }
+    if (window && resume) { probe.samples = w->done + probe_spp; probe.resume_rng = w->rng; probe.resume_spp = w->done; }
     int* const order_out = w ? w->order : s->ws_order.p;
     int* const nsplit_out = w ? w->nsplit : s->ws_nsplit.p;
-    int rc = launch(pv);
-    if (rc) return rc;
+    PassPlan probe_plan;
+    if (int rc = run_pass(s, p, pv, pv.chain_bound, pv.queued_walk, local_tiles, probe, st, &probe_plan)) return rc;
     probed = true;
     // rough per-iteration instruction counts: traversal (splittable) vs shading + camera + cooperative overhead (not)
     const int forced_logG = s->knobs.wide_logG; // 0: the model picks the group size of the wide phase
     const unsigned int* ranked = s->ws_cost.p;
-    if (a.cost_max && p->shard_count == 1 && !coop) { // tile_dilate_kernel (a shard's neighbours are other ranks' tiles: its own estimates)
-      hipLaunchKernelGGL(tile_dilate_kernel, dim3((unsigned int)((local_tiles + 255) / 256)), dim3(256), 0, st, s->ws_cost.p, a.tiles_x, (int)(a.n_tiles / a.tiles_x), s->ws_rank.p);
+    if (probe.cost_max && p->shard_count == 1 && !coop) { // tile_dilate_kernel (a shard's neighbours are other ranks' tiles: its own estimates)
+      hipLaunchKernelGGL(tile_dilate_kernel, dim3((unsigned int)((local_tiles + 255) / 256)), dim3(256), 0, st, s->ws_cost.p, base.tiles_x, (int)(base.n_tiles / base.tiles_x), s->ws_rank.p);
       PT_HIP(hipGetLastError());
       ranked = s->ws_rank.p;
     }
     // rough per-iteration instruction counts: traversal (splittable) vs shading + camera (not)
-    hipLaunchKernelGGL(lpt_order_kernel, dim3(1), dim3(1024), 0, st, ranked, local_tiles, order_out, n_waves_resident,
+    hipLaunchKernelGGL(lpt_order_kernel, dim3(1), dim3(1024), 0, st, ranked, local_tiles, order_out, probe_plan.n_waves_resident,
                        std::max(1.0f, s->traversal_cost), s->knobs.model_fixed, s->knobs.model_chain, forced_logG, coop ? nsplit_out : nullptr);
     PT_HIP(hipGetLastError());
     if (s->knobs.has_split_tiles) { // tuning knob: fixed number of split tiles (< 0: all)
@@ -2527,18 +2614,19 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
     }
     // (A second, ORDERED probe stage of samples / 8 that keeps counting also removes the slow launches tile_dilate_kernel is there for — 1080p x
     // 1024 spp 375 / 407 -> 380.8 +- 1.5 — at the price of the fast ones and of 4 % on chain-bound shards: not kept.)
-    a = main_args;
-    if (window) { if (resume) a.resume_spp = w->done + probe_spp; }
-    else if (resume) { a.resume_rng = s->ws_rng.p; a.resume_spp = probe_spp; }
-    a.order = order_out;
-    a.n_split = (coop && !(p->flags & PT_FLAG_NO_SPLIT)) ? nsplit_out : nullptr;
+    if (window) { if (resume) frame.resume_spp = w->done + probe_spp; }
+    else if (resume) { frame.resume_rng = s->ws_rng.p; frame.resume_spp = probe_spp; }
+    frame.order = order_out;
+    frame.n_split = (coop && !(p->flags & PT_FLAG_NO_SPLIT)) ? nsplit_out : nullptr;
     if (w) *w->has_order = true;
   } else if (w && *w->has_order) {
     // a window too short to probe: the order its accumulator kept from its last probed window (same scene, camera and frame: the tiles'
     // costs do not change between windows).  Never the scene's ws_order, which another render on the scene may have rewritten.
-    a.order = w->order;
-    a.n_split = (coop && !(p->flags & PT_FLAG_NO_SPLIT)) ? w->nsplit : nullptr;
+    frame.order = w->order;
+    frame.n_split = (coop && !(p->flags & PT_FLAG_NO_SPLIT)) ? w->nsplit : nullptr;
   }
+
+  // ---- the frame pass ----
   if (p->flags & PT_FLAG_FAST_RNG) {
     // OPT-IN decorrelated mode (include/pt_render.h): (tile, chunk) work units, per-chunk sums into a workspace, then
     // one ordered reduction.  No wide phase (a chunk is short by construction); the tile order of the probe still applies.
@@ -2548,22 +2636,21 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
     const size_t plane = (size_t)pt_framebuffer_floats(p), need = plane * (size_t)chunks;
     if (int rc = reserve_partial(s, need)) return rc; // first render at a new size only (or never: pt_scene_reserve)
     PT_HIP(hipMemsetAsync(s->ws_partial.p, 0, need * sizeof(float), st)); // pixels no lane owns add 0
-    a.fast_chunks = chunks;
-    a.fast_chunk0 = w ? w->done / PT_FAST_CHUNK_SPP : 0; // (a window starts on a chunk boundary: pt_render_accumulate)
-    a.samples = std::min(p->samples, (int)PT_FAST_CHUNK_SPP);
-    a.fast_stride = (long long)plane;
-    a.fb = s->ws_partial.p;
-    a.n_local_pixels = local_tiles * PT_TILE_PIXELS * chunks;
-    set_scatter();
-    a.n_split = nullptr;
-    launch_units = (long long)local_tiles * chunks;
+    frame.fast_chunks = chunks;
+    frame.fast_chunk0 = w ? w->done / PT_FAST_CHUNK_SPP : 0; // (a window starts on a chunk boundary: pt_render_accumulate)
+    frame.samples = std::min(p->samples, (int)PT_FAST_CHUNK_SPP);
+    frame.fast_stride = (long long)plane;
+    frame.fb = s->ws_partial.p;
+    frame.n_local_pixels = local_tiles * PT_TILE_PIXELS * chunks;
+    if (scattered) set_scatter(frame, s->knobs.scatter_log);
+    frame.n_split = nullptr;
     s->last_had_wide_phase = false;
-    Variant fv = choose_variant(s, p, local_tiles, true, a.n_local_pixels);
+    const Variant fv = choose_variant(s, p, local_tiles, true, frame.n_local_pixels);
     if (fv.rc) return fv.rc;
-    // (sticky: what the probe pass of this call ran stays set for its frame launch — the four-workgroup rule of `launch`, pt_debug_last_launch)
-    if (probed) { fv.chain_bound |= pv.chain_bound; fv.queued_walk |= pv.queued_walk; }
-    int rc = launch(fv);
-    if (rc) return rc;
+    // (what the probe pass of this call ran stays set for its chunk pass: run_pass)
+    if (int rc = run_pass(s, p, fv, fv.chain_bound || (probed && pv.chain_bound), fv.queued_walk || (probed && pv.queued_walk),
+                          (long long)local_tiles * chunks, frame, st))
+      return rc;
     if (w) { // a window: its chunks onto the accumulator's running sums, in chunk order, undivided
       hipLaunchKernelGGL(fast_accum_kernel, dim3((unsigned int)((plane + 255) / 256)), dim3(256), 0, st, s->ws_partial.p, fb, (long long)plane,
                          (long long)plane, chunks);
@@ -2575,17 +2662,17 @@ static int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderPa
     PT_HIP(hipGetLastError());
     return PT_OK;
   }
-  s->last_had_wide_phase = a.n_split != nullptr;
-  return launch(pv);
+  if (scattered) set_scatter(frame, s->knobs.scatter_log);
+  s->last_had_wide_phase = frame.n_split != nullptr;
+  return run_pass(s, p, pv, pv.chain_bound, pv.queued_walk, local_tiles, frame, st);
 }
 
 // ---- first-hit feature buffers: the AOV pass (aov_kernel) -------------------------------------------------------------------------
 // What pt_render_aov refuses, checked on the host before any device call (`depth` and the scheduling flags mean nothing to the pass).
-static int check_aov_params(const PtRenderParams* p) {
+int check_aov_params(const PtRenderParams* p) {
   if (!p) return fail(PT_ERR_INVALID_ARG, "render params are NULL");
   if (p->width <= 0 || p->height <= 0) return fail(PT_ERR_INVALID_ARG, "width and height must be > 0");
-  if (p->shard_count < 1 || p->shard_index < 0 || p->shard_index >= p->shard_count)
-    return fail(PT_ERR_INVALID_ARG, "need 0 <= shard_index < shard_count");
+  if (int rc = check_shard(p)) return rc;
   if (p->flags & (PT_FLAG_FAST_RNG | PT_FLAG_SINGLE_STREAM))
     return fail(PT_ERR_INVALID_ARG, "the AOV pass is defined on the reference's stream per pixel: no PT_FLAG_FAST_RNG, no PT_FLAG_SINGLE_STREAM");
   return PT_OK;
@@ -2594,22 +2681,15 @@ static int check_aov_params(const PtRenderParams* p) {
 // The launch: which aov_kernel (IMG: u,v tracked through the scan, as the scene's render kernels do; WALK: the sphere-grid walk the
 // launcher would pick for a frame of these parameters), one wave per tile of the planes.  Nothing is allocated and none of the scene's
 // launch workspaces is read or written.
-static int launch_aov(const PtScene* s, const PtCamera* cam, const PtRenderParams* p, const PtAovBuffers* b, hipStream_t st) {
+int launch_aov(const PtScene* s, const PtCamera* cam, const PtRenderParams* p, const PtAovBuffers* b, hipStream_t st) {
   int cur = -1;
   PT_HIP(hipGetDevice(&cur));
   if (cur != s->device) return fail(PT_ERR_INVALID_ARG, "pt_render_aov: the scene lives on another device (hipSetDevice to the scene's device first)");
   AovArgs a;
-  std::memcpy(&a.cam, cam, sizeof(Cam));
-  a.blob = s->blob.p; a.mats = s->mats; a.pool = s->pool.p; a.atlas = s->atlas.p;
+  set_frame(a, s, cam, p);
   a.albedo = b->albedo; a.normal = b->normal; a.direct = b->direct; a.depth = b->depth; a.coverage = b->coverage; a.id = b->id;
-  a.n_runs = s->n_runs;
-  a.width = p->width; a.height = p->height; a.samples = p->samples;
-  a.inv_w = 1.0f / (float)p->width; a.inv_h = 1.0f / (float)p->height; // host IEEE division: correctly rounded
-  a.pinhole = cam_is_pinhole(a.cam) ? 1 : 0;
   a.fast_ok = s->fast_ok ? 1 : 0;
-  a.shard_index = p->shard_index; a.shard_count = p->shard_count;
-  a.n_tiles = n_tiles_of(p, &a.tiles_x);
-  a.local_tiles = p->shard_count == 1 ? a.n_tiles : (a.n_tiles + p->shard_count - 1) / p->shard_count;
+  a.local_tiles = tiles_per_shard(a.n_tiles, p->shard_count);
   std::lock_guard<std::mutex> lock(s->sched); // (choose_variant caches its occupancy queries on the scene; last_aov)
   bool queued_walk = false;
   if (s->grid_spheres > 0) {
@@ -2627,10 +2707,14 @@ static int launch_aov(const PtScene* s, const PtCamera* cam, const PtRenderParam
   return PT_OK;
 }
 
+} // namespace
+
+extern "C" {
+
 int64_t pt_aov_plane_elems(const PtRenderParams* p, int32_t channels) {
   if (check_aov_params(p) || (channels != 1 && channels != 3)) return -1;
   if (p->shard_count == 1) return (int64_t)p->width * p->height * channels;
-  return (int64_t)((n_tiles_of(p, nullptr) + p->shard_count - 1) / p->shard_count) * PT_TILE_PIXELS * channels;
+  return (int64_t)tiles_per_shard(n_tiles_of(p, nullptr), p->shard_count) * PT_TILE_PIXELS * channels;
 }
 
 int pt_render_aov(const PtScene* scene, const PtCamera* cam, const PtRenderParams* p, const PtAovBuffers* buffers, void* stream) {
@@ -2707,7 +2791,7 @@ int pt_unshard_tiles(const float* gathered_device, const PtRenderParams* p, floa
   if (rc) return rc;
   int tiles_x;
   int n_tiles = n_tiles_of(p, &tiles_x);
-  int per = (n_tiles + p->shard_count - 1) / p->shard_count;
+  int per = tiles_per_shard(n_tiles, p->shard_count);
   dim3 block(256), grid((p->width + 255) / 256, p->height);
   hipLaunchKernelGGL(unshard_kernel, grid, block, 0, (hipStream_t)stream, gathered_device, fb_device, p->width, p->height,
                      tiles_x, p->shard_count, per);
@@ -3382,6 +3466,33 @@ int pt_debug_last_launch(const PtScene* scene, int32_t out[4]) {
   if (!scene || !out) return fail(PT_ERR_INVALID_ARG, "pt_debug_last_launch: NULL argument");
   std::lock_guard<std::mutex> lock(scene->sched);
   for (int k = 0; k < 4; k++) out[k] = scene->last_launch[k];
+  return PT_OK;
+}
+
+int pt_debug_plan_pass(const int64_t facts[20], int32_t out[14]) {
+  if (!facts || !out) return fail(PT_ERR_INVALID_ARG, "pt_debug_plan_pass: NULL argument");
+  for (int k = 0; k < 20; k++)
+    if (k != 11 && (facts[k] < INT32_MIN || facts[k] > INT32_MAX)) return fail(PT_ERR_INVALID_ARG, "pt_debug_plan_pass: a fact does not fit 32 bits");
+  if (facts[0] < 1 || facts[0] > 65536 || facts[1] < 1 || facts[1] > 64 || facts[2] < 64 || facts[2] % 64 != 0 || facts[2] > 1024 || facts[11] < 0 ||
+      facts[11] > (1ll << 40) || facts[12] < 0 || facts[13] < 1 || facts[18] < 0 || facts[19] < 0)
+    return fail(PT_ERR_INVALID_ARG, "pt_debug_plan_pass: need 1 <= CUs <= 65536, 1 <= workgroups per CU <= 64, block threads a multiple of 64 up to 1024, "
+                                    "samples >= 1, 0 <= launch units <= 2^40, counts >= 0");
+  PtTuning t;
+  tuning_defaults(t);
+  t.blocks_per_cu = (int32_t)facts[7]; t.lanes_cap = (int32_t)facts[8]; t.heavy_tiles = (int32_t)facts[9]; t.chain_priority = facts[10] ? -1 : 0;
+  const Knobs knobs(t); // (the PtTuning fields as a scene resolves them)
+  PassFacts f;
+  f.num_cus = (int)facts[0]; f.per_cu = (int)facts[1]; f.block_threads = (int)facts[2];
+  f.chain_bound = facts[3] != 0; f.use_grid = facts[4] != 0; f.queued_walk = facts[5] != 0;
+  f.flags = (uint32_t)facts[6];
+  f.blocks_per_cu = knobs.blocks_per_cu; f.lanes_cap = knobs.lanes_cap; f.heavy_tiles = knobs.heavy_tiles; f.no_chain_prio = knobs.no_chain_prio;
+  f.launch_units = facts[11]; f.n_local_pixels = (int)facts[12]; f.samples = (int)facts[13];
+  f.probe = facts[14] != 0; f.has_order = facts[15] != 0; f.has_split = facts[16] != 0;
+  f.tile_granular = facts[17] != 0; f.scatter_p = (int)facts[18]; f.fast_chunks = (int)facts[19];
+  const PassPlan pl = plan_pass(f);
+  const int words[14] = {pl.workgroups, pl.n_waves_resident, pl.lanes_cap, pl.tile_granular, pl.heavy_pixels, pl.heavy_lanes, pl.prio_onset,
+                         pl.prio_t1, pl.prio_t2, pl.prio_t3, pl.last_launch[0], pl.last_launch[1], pl.last_launch[2], pl.last_launch[3]};
+  for (int k = 0; k < 14; k++) out[k] = words[k];
   return PT_OK;
 }
 

@@ -1109,7 +1109,7 @@ def test_badouel_strategy_triangles(orc, lib):
 
 
 def test_heaviest_tiles_in_narrow_pieces_change_nothing(orc, torch_gpu):
-    """PtTuning.heavy_tiles (pt_render.hip: launch / lane_acquire): the head of the cost-sorted tile queue handed out 16 pixels at a time
+    """PtTuning.heavy_tiles (pt_render.hip: plan_pass / lane_acquire): the head of the cost-sorted tile queue handed out 16 pixels at a time
     — a quarter tile per wave, for launches bound by their heaviest tiles' chains — is another partition of the same pixels: the frame
     must equal the whole-tile frame bit for bit and the oracle's on sampled pixels, for head lengths below, at and beyond the tile count
     (and for a shard, where the launcher's own rule applies the mode)."""
@@ -1182,7 +1182,9 @@ def test_longest_remaining_chain_first_changes_no_value(orc, torch_gpu):
 
 
 def test_launcher_rules_for_chain_bound_launches(torch_gpu):
-    """What launch_render decides, read back through pt_debug_last_launch: the headline family keeps four workgroups per CU when a launch
+    """What plan_pass decides for launch_render's frame pass (choose_variant picked the kernel), read back through pt_debug_last_launch
+    (tests/test_launch_plan_cpu.py holds the same rules on the CPU, tests/test_gpu_launch_decisions.py a recorded matrix of launches):
+    the headline family keeps four workgroups per CU when a launch
     has fewer than 1.15 tiles per wave slot (a shard of 4 - 6 of the 1080p frame; 1.6 and shards of 3 on before the chain priorities of round 5)
     and its full occupancy otherwise; the 496-hittable scene's
     whole 1080p frame runs whole tiles through the queued walk, its shard 0/3 whole tiles with the narrow head, its shard 0/8 the
