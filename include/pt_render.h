@@ -613,6 +613,107 @@ int pt_denoise(const PtDenoiseParams* params, const float* color, const float* a
  * LDS-staged tile (the steps 1 and 2, unless PT_DENOISE_NO_LDS: profiles/denoise_bench.txt).  The bits do not depend on it.  For tests. */
 int pt_debug_last_denoise(int32_t out[8]);
 
+/* ---- variance-guided denoiser: the a-trous filter with a per-pixel colour tolerance taken from the adaptive half buffers ---------------
+ * Added without an ABI version change, like PtAccum: a caller detects the feature by the presence of these symbols.  pt_denoise and
+ * everything about it stay as they are.
+ *
+ * pt_denoise weighs colour differences against one sigma_color, which fits one noise level; an adaptive frame holds pixels from a few to a
+ * thousand samples.  This filter is the spatial half of SVGF (Schied et al., HPG 2017): the colour difference is measured in units of
+ * the pixel's own estimated standard deviation, the variance is smoothed by a 3 x 3 Gaussian before it is used, and it is propagated
+ * through the levels (the variance of a weighted mean), so that each level sees the noise the previous one left.
+ *
+ * VARIANCE ESTIMATE (pt_variance_estimate).  Writes a 3-channel plane in the frame buffer's layout — pt_framebuffer_floats() floats:
+ * [y][x][3] for whole frames, [local tile][64][3] for shards, padding pixels 0 — from an adaptive accumulator's sums S, half sums H and
+ * counts n, a.  Per pixel and channel, every value binary32 and every operation rounded once:
+ *   where a == 0 || a == n: +inf ("no estimate yet", the convention of pt_adaptive_error); otherwise, with b = n - a,
+ *   A = H / (float)a;  B = (S - H) / (float)b;  d = A - B;  f = ((float)a * (float)b) / ((float)n * (float)n);  var = (d * d) * f
+ * Why: the two halves are independent means of a and b samples of one distribution of variance s2, so Var(A - B) = s2 (1/a + 1/b) =
+ * s2 n / (a b), while the resolved pixel S / n has variance s2 / n: (A - B)^2 * a b / n^2 estimates the variance of the resolved pixel
+ * (with equal halves it is ((A - B) / 2)^2).  One squared difference is a noisy estimate — hence the filter's prefilter.
+ * Asynchronous on `stream`, allocates nothing.  Rejected (PT_ERR_INVALID_ARG): a NULL argument, a plain (non-adaptive) accumulator, a call
+ * before the accumulator's first window.
+ *
+ * THE FILTER (pt_variance_denoise).  Scope: pt_denoise's — whole frames only, no scene involved; color, variance, albedo, normal, out and
+ * variance_out are [height][width][3], depth is [height][width]; albedo, normal and depth are optional (NULL), variance_out is optional;
+ * `out` may be `color` and `variance_out` may be `variance` (the planes are read completely, by a prepass, before the first is written);
+ * asynchronous on `stream`; allocates nothing: the caller supplies `scratch`, pt_variance_denoise_scratch_floats(width, height) floats
+ * of device memory, 16-byte aligned.  `variance` is required: the variance of the pixel's MEAN per channel, from pt_variance_estimate or
+ * from anywhere else.
+ *
+ * DEFINITION.  Every value is IEEE binary32, every operation below is rounded once, nothing is fused, and the order of operations is the
+ * one written.  Terms not named here — K, h, x_n, x_d, x_a, k_n, sd2, k_a, pt_exp_neg, when a guide term is off — are pt_denoise's, verbatim.
+ *   m   = albedo + 1e-3f per channel with PT_VDENOISE_DEMODULATE, else 1
+ *   c_0 = color / m
+ *   v_0 = sanitised(variance) / (m * m): a variance value that is not (>= 0 && < +inf) — negative, NaN, inf — is taken as +0 first.  (The
+ *         filter then knows nothing about that pixel's noise beyond its neighbours' estimates, and is conservative there.)
+ * Iteration i = 0 ... iterations - 1 has step s = 2^i and makes c_(i+1), v_(i+1) from c_i, v_i; for pixel p = (x, y):
+ *   the prefilter, always at a distance of ONE pixel, whatever the step:
+ *     vs = (0, 0, 0), gs = 0
+ *     for dy = -1 ... 1 (outer), for dx = -1 ... 1 (inner): q = (x + dx, y + dy); a q outside the frame is skipped
+ *       g = G[dy + 1] * G[dx + 1],  G = {1/4, 1/2, 1/4}   (exact);   vs.ch = vs.ch + g * v_i(q).ch;   gs = gs + g
+ *     vbar.ch = vs.ch / gs
+ *   the colour scale, three divisions per pixel and none per tap:
+ *     iv.ch = 1.0f / (sv2 * vbar.ch + 1e-8f),  sv2 = sigma_variance * sigma_variance
+ *   sum = (0, 0, 0), vsum = (0, 0, 0), wsum = 0
+ *   for dy = -2 ... 2 (outer), for dx = -2 ... 2 (inner): tap q = (x + s dx, y + s dy); a tap outside the frame is skipped
+ *     x_c = ((dr * dr) * iv.r + (dg * dg) * iv.g) + (db * db) * iv.b      d. = c_i(p) - c_i(q) per channel
+ *     x   = ((x_c + x_n) + x_d) + x_a
+ *     if !(x < 80.0f) the tap is skipped (NaN included); otherwise w = h * pt_exp_neg(x),
+ *       sum.ch = sum.ch + w * c_i(q).ch;   vsum.ch = vsum.ch + (w * w) * v_i(q).ch;   wsum = wsum + w
+ *   c_(i+1)(p) = sum / wsum,  v_(i+1)(p) = vsum / (wsum * wsum)  per channel; where wsum == 0 both keep their value
+ * out = c_iterations * m;  variance_out (if not NULL) = v_iterations * (m * m) — the filtered frame's residual variance, under the
+ * filter's assumption that the taps are independent.
+ * The colour term is ON when sigma_variance > 0; when it is off x_c = 0, the prefilter is not needed, the filter is guide-only and the
+ * variance is only propagated.  The 1e-8f keeps iv finite where the estimate is 0 (a pixel whose halves agree, a sanitised value): such a
+ * pixel accepts only taps within ~1e-3 of its colour — it is left nearly alone rather than blurred on no evidence.
+ *
+ * Containment.  pt_denoise's: with the colour term on, a tap whose colour is NaN or inf has x = NaN or inf and is skipped, and a pixel whose
+ * own colour is not finite accepts no tap, its centre included, and keeps its value and its variance: a NaN or inf colour stays where it
+ * is and never spreads.  Every finite pixel accepts at least its centre tap (x = 0), so wsum is 0 or >= 9/64.  The same holds for a
+ * non-finite guide value whose term is on.  A non-finite VARIANCE of the caller's never enters: it is sanitised to 0.  The prefilter is not edge-aware
+ * (SVGF's is not either): no COLOUR is ever averaged across an edge the guides reject, but a pixel next to such an edge takes part of
+ * its tolerance from the variance on the other side.
+ *
+ * Rejected (PT_ERR_INVALID_ARG, on the host, before any device call): a NULL params, color, variance, out or scratch; a struct_size
+ * other than sizeof(PtVarianceDenoiseParams); width or height <= 0; iterations outside 1 ... PT_VDENOISE_MAX_ITERATIONS; a sigma that
+ * is not finite; sigma_variance > 0 whose sv2 or 1.0f / sv2 is not a finite binary32 number > 0; a guide sigma > 0 whose k (sigma_depth:
+ * sd2) is not one; PT_VDENOISE_DEMODULATE without an albedo plane; flags other than PT_VDENOISE_DEMODULATE and PT_VDENOISE_NO_LDS; `out`,
+ * `variance_out` or `scratch` overlapping a guide plane; `scratch` overlapping color, variance, out or variance_out, or not 16-byte
+ * aligned; `variance_out` overlapping `color` or `out`.  More than 2^30 pixels: PT_ERR_TOO_LARGE.                                      */
+#define PT_VDENOISE_DEMODULATE 1u
+#define PT_VDENOISE_NO_LDS 2u /* A/B switch, same bits: every iteration reads from global memory (default: the steps 1 and 2 read an LDS-staged tile) */
+#define PT_VDENOISE_MAX_ITERATIONS 8
+/* The defaults (pt_variance_denoise_params_init): pt_denoise's five levels, guide sigmas and demodulation; sigma_variance — the colour
+ * tolerance in standard deviations of the prefiltered estimate — is the value of {2, 3, 4} with the smallest worst-case MSE ratio over
+ * 8, 32 and 128 spp frames (tests/test_variance_denoise_cpu.py measures it; profiles/variance_denoise_bench.txt records the sweep). */
+#define PT_VDENOISE_DEFAULT_ITERATIONS 5
+#define PT_VDENOISE_DEFAULT_SIGMA_VARIANCE 2.0f
+#define PT_VDENOISE_DEFAULT_SIGMA_NORMAL 0.5f
+#define PT_VDENOISE_DEFAULT_SIGMA_DEPTH 0.2f
+#define PT_VDENOISE_DEFAULT_SIGMA_ALBEDO 0.0f
+#define PT_VDENOISE_DEFAULT_FLAGS PT_VDENOISE_DEMODULATE
+typedef struct PtVarianceDenoiseParams {
+  int32_t struct_size; /* sizeof(PtVarianceDenoiseParams) of the caller's header */
+  int32_t width, height;
+  int32_t iterations;  /* 1 ... PT_VDENOISE_MAX_ITERATIONS */
+  float sigma_variance, sigma_normal, sigma_depth, sigma_albedo; /* <= 0: term off */
+  uint32_t flags;      /* PT_VDENOISE_DEMODULATE, PT_VDENOISE_NO_LDS */
+  int32_t reserved;
+} PtVarianceDenoiseParams;
+/* The per-channel variance of each resolved pixel of an adaptive accumulator (the formula above); variance_device: pt_framebuffer_floats() floats. */
+int pt_variance_estimate(const PtAccum* acc, float* variance_device, void* stream);
+/* Host function, no GPU: struct_size + the defaults above for a frame of width x height. */
+void pt_variance_denoise_params_init(PtVarianceDenoiseParams* params, int32_t width, int32_t height);
+/* Host function, no GPU: floats of `scratch` for a frame of width x height, 20 per pixel — two working planes the iterations ping-pong
+ * between, each a 16-byte record (c.r, c.g, c.b, v.r) and an 8-byte record (v.g, v.b) per pixel, so that a tap's colour and variance are
+ * two loads, and pt_denoise's two 16-byte guide records per pixel, (normal, depth) and (albedo, 0); < 0 for invalid sizes. */
+int64_t pt_variance_denoise_scratch_floats(int32_t width, int32_t height);
+int pt_variance_denoise(const PtVarianceDenoiseParams* params, const float* color, const float* variance, const float* albedo,
+                        const float* normal, const float* depth, float* out, float* variance_out, float* scratch, void* stream);
+/* How the LAST pt_variance_denoise of this process read its taps, per iteration: out[i] = 0 iteration not run, 1 from global memory, 2 from
+ * an LDS-staged tile (the steps 1 and 2, unless PT_VDENOISE_NO_LDS).  The bits do not depend on it.  For tests. */
+int pt_debug_last_variance_denoise(int32_t out[8]);
+
 /* ---- function-level probes (parity tests call these; not used by render) ---- */
 
 /* One iteration of the bounce loop render.hpp:58-89 per record: hit_world,

@@ -18,6 +18,9 @@ With --denoise-out FILE the frame is also filtered by the edge-avoiding a-trous 
 --denoise-sigma-* options; the defaults are include/pt_render.h's) over feature buffers of --aov-spp camera rays per pixel — the ones
 --aov-dir writes, or a pass of its own — and FILE gets the filtered frame through the same output stage; out.png is byte-identical to
 the one written without the option.
+With --denoise-variance (needs --denoise-out and --noise-threshold) the filtered frame comes from the variance-guided filter instead
+(render.denoise_variance; --denoise-sigma-variance replaces --denoise-sigma-color): its colour tolerance is each pixel's own noise
+estimate, taken from the adaptive accumulator's half buffers, so one setting fits every sample count in the frame.
 """
 import argparse
 import os
@@ -72,8 +75,21 @@ def main() -> None:
     for term in ("color", "normal", "depth", "albedo"):
         ap.add_argument(f"--denoise-sigma-{term}", type=float, default=None, metavar="S",
                         help=f"denoiser: sigma of the {term} term, <= 0 turns it off (default: include/pt_render.h)")
+    ap.add_argument("--denoise-variance", action="store_true",
+                    help="denoiser: the variance-guided filter over the adaptive accumulator's noise estimate (needs --noise-threshold)")
+    ap.add_argument("--denoise-sigma-variance", type=float, default=None, metavar="S",
+                    help="variance-guided denoiser: colour tolerance in standard deviations, <= 0 turns it off (default: include/pt_render.h)")
     a = ap.parse_args()
+    if a.denoise_variance and a.noise_threshold is None:
+        ap.error("--denoise-variance needs --noise-threshold (the variance comes from the adaptive accumulator's half buffers)")
+    if a.denoise_variance and a.denoise_out is None:
+        ap.error("--denoise-variance needs --denoise-out")
+    if a.denoise_sigma_variance is not None and not a.denoise_variance:
+        ap.error("--denoise-sigma-variance needs --denoise-variance")
+    if a.denoise_variance and a.denoise_sigma_color is not None:
+        ap.error("--denoise-sigma-color does not apply to --denoise-variance (use --denoise-sigma-variance)")
     denoise_kw = {k: v for k, v in (("iterations", a.denoise_iterations), ("sigma_color", a.denoise_sigma_color),
+                                    ("sigma_variance", a.denoise_sigma_variance),
                                     ("sigma_normal", a.denoise_sigma_normal), ("sigma_depth", a.denoise_sigma_depth),
                                     ("sigma_albedo", a.denoise_sigma_albedo)) if v is not None}
     if denoise_kw and a.denoise_out is None:
@@ -115,8 +131,8 @@ def main() -> None:
     if adaptive:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        fb, counts = R.render_adaptive(a.width, a.height, packed, cam, a.depth, threshold=a.noise_threshold, min_spp=a.min_spp,
-                                       max_spp=a.spp, step=a.adaptive_step)
+        fb, counts, *variance = R.render_adaptive(a.width, a.height, packed, cam, a.depth, threshold=a.noise_threshold, min_spp=a.min_spp,
+                                                  max_spp=a.spp, step=a.adaptive_step, variance=a.denoise_variance)
         e1.record()
         rgb8 = R.tonemap_rgb8(fb)
         torch.cuda.synchronize()
@@ -150,7 +166,8 @@ def main() -> None:
     if a.aov_dir:
         write_aovs(a.aov_dir, planes)
     if a.denoise_out:
-        write_png(a.denoise_out, R.tonemap_rgb8(R.denoise(fb, **planes, **denoise_kw)).cpu().numpy())
+        filtered = R.denoise_variance(fb, variance[0], **planes, **denoise_kw) if a.denoise_variance else R.denoise(fb, **planes, **denoise_kw)
+        write_png(a.denoise_out, R.tonemap_rgb8(filtered).cpu().numpy())
     if mean_spp is not None:
         n = int(counts.sum())
         print(f"{a.scene}: {packed.n_hittables} hittables, {a.width}x{a.height}, adaptive {a.min_spp}..{a.spp} spp (threshold "

@@ -136,6 +136,14 @@ class PtDenoiseParams(C.Structure):
                 ("flags", C.c_uint32), ("reserved", C.c_int32)]
 
 
+class PtVarianceDenoiseParams(C.Structure):
+    """include/pt_render.h PtVarianceDenoiseParams: the variance-guided denoiser's parameters (pt_variance_denoise); a sigma <= 0
+    turns its term off."""
+    _fields_ = [("struct_size", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("iterations", C.c_int32),
+                ("sigma_variance", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("sigma_albedo", C.c_float),
+                ("flags", C.c_uint32), ("reserved", C.c_int32)]
+
+
 assert C.sizeof(PtHittable) == 64 and C.sizeof(PtMaterial) == 32 and C.sizeof(PtTexture) == 48
 assert C.sizeof(PtCamera) == 96 and C.sizeof(PtRenderParams) == 32
 
@@ -211,6 +219,12 @@ SIGNATURES = {
     "pt_denoise_scratch_floats": (C.c_int64, [C.c_int32, C.c_int32]),
     "pt_denoise": (C.c_int, [C.POINTER(PtDenoiseParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pt_debug_last_denoise": (C.c_int, [C.POINTER(C.c_int32)]),
+    # the variance-guided denoiser and the estimate that feeds it: likewise optional (VARIANCE_SYMBOLS)
+    "pt_variance_estimate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pt_variance_denoise_params_init": (None, [C.POINTER(PtVarianceDenoiseParams), C.c_int32, C.c_int32]),
+    "pt_variance_denoise_scratch_floats": (C.c_int64, [C.c_int32, C.c_int32]),
+    "pt_variance_denoise": (C.c_int, [C.POINTER(PtVarianceDenoiseParams)] + [C.c_void_p] * 9),
+    "pt_debug_last_variance_denoise": (C.c_int, [C.POINTER(C.c_int32)]),
     # the launcher's geometry rules for one pass, host-only: likewise optional (PLAN_SYMBOLS)
     "pt_debug_plan_pass": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
 }
@@ -243,6 +257,16 @@ PT_DENOISE_MAX_ITERATIONS = 8
 # the header's PT_DENOISE_DEFAULT_* (pt_denoise_params_init)
 PT_DENOISE_DEFAULT_ITERATIONS = 5
 PT_DENOISE_DEFAULT_SIGMA_COLOR, PT_DENOISE_DEFAULT_SIGMA_NORMAL, PT_DENOISE_DEFAULT_SIGMA_DEPTH, PT_DENOISE_DEFAULT_SIGMA_ALBEDO = 32.0, 0.5, 0.2, 0.0
+# the variance-guided denoiser (include/pt_render.h: pt_variance_estimate, pt_variance_denoise); has_variance_denoise() tells whether the
+# loaded library has it
+VARIANCE_SYMBOLS = frozenset({"pt_variance_estimate", "pt_variance_denoise_params_init", "pt_variance_denoise_scratch_floats",
+                              "pt_variance_denoise", "pt_debug_last_variance_denoise"})
+PT_VDENOISE_DEMODULATE = 1
+PT_VDENOISE_NO_LDS = 2  # A/B switch, same bits: every iteration reads from global memory
+PT_VDENOISE_MAX_ITERATIONS = 8
+# the header's PT_VDENOISE_DEFAULT_* (pt_variance_denoise_params_init)
+PT_VDENOISE_DEFAULT_ITERATIONS = 5
+PT_VDENOISE_DEFAULT_SIGMA_VARIANCE, PT_VDENOISE_DEFAULT_SIGMA_NORMAL, PT_VDENOISE_DEFAULT_SIGMA_DEPTH, PT_VDENOISE_DEFAULT_SIGMA_ALBEDO = 2.0, 0.5, 0.2, 0.0
 
 LIB_NAME = "libpt_render.so"
 _lib = None
@@ -287,7 +311,7 @@ def load_library() -> C.CDLL:
         pass  # torch-free hosts bind to /opt/rocm/lib through the library's RUNPATH
     lib = C.CDLL(str(path))
     for name, (res, args) in SIGNATURES.items():
-        if override_is_older_build(path, lib, name) or (name in ACCUM_SYMBOLS | ADAPTIVE_SYMBOLS | AOV_SYMBOLS | DENOISE_SYMBOLS | PLAN_SYMBOLS and not hasattr(lib, name)):
+        if override_is_older_build(path, lib, name) or (name in ACCUM_SYMBOLS | ADAPTIVE_SYMBOLS | AOV_SYMBOLS | DENOISE_SYMBOLS | PLAN_SYMBOLS | VARIANCE_SYMBOLS and not hasattr(lib, name)):
             continue
         fn = getattr(lib, name)  # AttributeError if the library does not export what the header declares
         fn.restype = res
@@ -321,6 +345,12 @@ def has_denoise(lib=None) -> bool:
     """Does the loaded library offer the a-trous denoiser (pt_denoise)?"""
     lib = lib or load_library()
     return all(hasattr(lib, n) for n in DENOISE_SYMBOLS)
+
+
+def has_variance_denoise(lib=None) -> bool:
+    """Does the loaded library offer the variance-guided denoiser (pt_variance_estimate, pt_variance_denoise)?"""
+    lib = lib or load_library()
+    return all(hasattr(lib, n) for n in VARIANCE_SYMBOLS)
 
 
 def check(code: int, where: str) -> None:

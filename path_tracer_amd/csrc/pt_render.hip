@@ -1460,6 +1460,226 @@ __global__ __launch_bounds__(256) void atrous_kernel(ATrousArgs a) {
   a.out[p * 3] = orr; a.out[p * 3 + 1] = og; a.out[p * 3 + 2] = ob;
 }
 
+// ---- variance-guided denoiser (include/pt_render.h: pt_variance_estimate, pt_variance_denoise) ----------------------------------------
+// The a-trous filter above with the colour tolerance taken per pixel from a variance plane, and the variance carried through the levels.
+// Same rules: the header states every operation, this is that text in HIP; -ffp-contract=off, correctly rounded division.
+
+// the variance of each resolved pixel from the two half buffers: (A - B)^2 a b / n^2 (the header says why); padding pixels of a shard: 0
+__global__ void variance_estimate_kernel(AFrame f, const float* __restrict__ sum, const float* __restrict__ half, const int* __restrict__ cnt,
+                                         const int* __restrict__ cnt_a, float* __restrict__ var) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= f.pixels) return;
+  int x, y;
+  float v0 = 0.0f, v1 = 0.0f, v2 = 0.0f;
+  if (aframe_xy(f, i, x, y)) {
+    const int n = cnt[i], a = cnt_a[i];
+    if (a == 0 || a == n) {
+      v0 = v1 = v2 = __builtin_inff();
+    } else {
+      const float fa = (float)a, fb = (float)(n - a), fn = (float)n;
+      const float fr = (fa * fb) / (fn * fn);
+      const float h0 = half[3 * i], h1 = half[3 * i + 1], h2 = half[3 * i + 2];
+      const float d0 = h0 / fa - (sum[3 * i] - h0) / fb, d1 = h1 / fa - (sum[3 * i + 1] - h1) / fb, d2 = h2 / fa - (sum[3 * i + 2] - h2) / fb;
+      v0 = (d0 * d0) * fr; v1 = (d1 * d1) * fr; v2 = (d2 * d2) * fr;
+    }
+  }
+  var[3 * i] = v0; var[3 * i + 1] = v1; var[3 * i + 2] = v2;
+}
+
+typedef float f2v __attribute__((ext_vector_type(2)));
+enum { VDN_LAST = 64 }; // beside DN_*: this launch is the last iteration and writes the caller's planes
+
+struct VdnArgs {
+  const f4* in_a;   // per pixel (c_i.r, c_i.g, c_i.b, v_i.r)
+  const f2v* in_b;  // per pixel (v_i.g, v_i.b)
+  f4* out_a;        // c_(i+1), v_(i+1) in the same records (every iteration but the last)
+  f2v* out_b;
+  float* out_color; // the last iteration: the caller's planes, [height][width][3]; out_var may be NULL
+  float* out_var;
+  const f4* g_nd;   // per pixel (normal, depth); read when ND
+  const f4* g_al;   // per pixel (albedo, 0); read when AL
+  int width, height, step;
+  unsigned terms;   // DN_COLOR ... DN_ALBEDO: which terms are on; DN_REMOD_OUT, VDN_LAST
+  float sv2, k_n, sd2, k_a;
+};
+
+// The prepass: c_0 and v_0 — the colour demodulated, the variance sanitised and demodulated — into the working records, and the guide
+// planes into atrous_pack_kernel's records.  It reads every plane of the caller's completely before the filter writes any: `out` may be
+// `color`, `variance_out` may be `variance`.
+__global__ __launch_bounds__(256) void vdn_pack_kernel(const float* __restrict__ color, const float* __restrict__ variance,
+                                                       const float* __restrict__ normal, const float* __restrict__ depth,
+                                                       const float* __restrict__ albedo, f4* __restrict__ rec_a, f2v* __restrict__ rec_b,
+                                                       f4* __restrict__ g_nd, f4* __restrict__ g_al, long long pixels, int demod) {
+  const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= pixels) return;
+  float cr = color[p * 3], cg = color[p * 3 + 1], cb = color[p * 3 + 2];
+  float vr = variance[p * 3], vg = variance[p * 3 + 1], vb = variance[p * 3 + 2];
+  vr = (vr >= 0.0f && vr < __builtin_inff()) ? vr : 0.0f;
+  vg = (vg >= 0.0f && vg < __builtin_inff()) ? vg : 0.0f;
+  vb = (vb >= 0.0f && vb < __builtin_inff()) ? vb : 0.0f;
+  if (demod) {
+    const float mr = albedo[p * 3] + 1e-3f, mg = albedo[p * 3 + 1] + 1e-3f, mb = albedo[p * 3 + 2] + 1e-3f;
+    cr = cr / mr; cg = cg / mg; cb = cb / mb;
+    vr = vr / (mr * mr); vg = vg / (mg * mg); vb = vb / (mb * mb);
+  }
+  const f4 ra = {cr, cg, cb, vr};
+  const f2v rb = {vg, vb};
+  rec_a[p] = ra;
+  rec_b[p] = rb;
+  if (g_nd) {
+    f4 r = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (normal) { r.x = normal[p * 3]; r.y = normal[p * 3 + 1]; r.z = normal[p * 3 + 2]; }
+    if (depth) r.w = depth[p];
+    g_nd[p] = r;
+  }
+  if (g_al) {
+    const f4 r = {albedo[p * 3], albedo[p * 3 + 1], albedo[p * 3 + 2], 0.0f};
+    g_al[p] = r;
+  }
+}
+
+// One iteration, atrous_kernel's shape: one thread per pixel, a 32 x 8 pixel workgroup, ND / AL as there.  STEP = 0: the prefilter's nine
+// variances and the 25 taps are read from global memory, at the step of the arguments.  STEP = 1, 2: the workgroup stages its tile with
+// the halo of 2 STEP pixels in LDS — 24 bytes of colour and variance and the guide records per pixel; the halo is >= 1, so the tile also
+// serves the 3 x 3 prefilter — and every read is an LDS read.  Same operations on the same values in the same order either way.
+template <int STEP>
+struct VdnTile {
+  static constexpr int R = 2 * STEP, TW = 32 + 2 * R, TH = 8 + 2 * R, N = TW * TH;
+};
+
+template <bool ND, bool AL, int STEP>
+__global__ __launch_bounds__(256) void vdn_kernel(VdnArgs a) {
+  using T = VdnTile<STEP>;
+  const int lx = threadIdx.x & 31, ly = threadIdx.x >> 5;
+  const int x = blockIdx.x * 32 + lx, y = blockIdx.y * 8 + ly;
+  const int step = STEP ? STEP : a.step;
+  __shared__ f4 s_a[STEP ? T::N : 1];
+  __shared__ f2v s_b[STEP ? T::N : 1];
+  __shared__ f4 s_nd[STEP && ND ? T::N : 1], s_al[STEP && AL ? T::N : 1];
+  if constexpr (STEP > 0) {
+    const int x0 = blockIdx.x * 32 - T::R, y0 = blockIdx.y * 8 - T::R;
+    for (int i = threadIdx.x; i < T::N; i += 256) {
+      const int gx = x0 + i % T::TW, gy = y0 + i / T::TW;
+      f4 ra = {0.0f, 0.0f, 0.0f, 0.0f}, nd = {0.0f, 0.0f, 0.0f, 0.0f}, al = {0.0f, 0.0f, 0.0f, 0.0f};
+      f2v rb = {0.0f, 0.0f};
+      if (gx >= 0 && gx < a.width && gy >= 0 && gy < a.height) { // (a slot outside the frame is never read: its tap is skipped)
+        const long long q = (long long)gy * a.width + gx;
+        ra = a.in_a[q]; rb = a.in_b[q];
+        if (ND) nd = a.g_nd[q];
+        if (AL) al = a.g_al[q];
+      }
+      s_a[i] = ra; s_b[i] = rb;
+      if (ND) s_nd[i] = nd;
+      if (AL) s_al[i] = al;
+    }
+    __syncthreads();
+  }
+  if (x >= a.width || y >= a.height) return;
+  const long long p = (long long)y * a.width + x;
+  const int lp = (ly + T::R) * T::TW + lx + T::R; // the pixel's slot in the tile (STEP > 0)
+  const bool t_c = a.terms & DN_COLOR, t_n = ND && (a.terms & DN_NORMAL), t_d = ND && (a.terms & DN_DEPTH), t_a = AL && (a.terms & DN_ALBEDO);
+  f4 ndp = {0.0f, 0.0f, 0.0f, 0.0f}, alp = {0.0f, 0.0f, 0.0f, 0.0f}, pa;
+  f2v pb;
+  if constexpr (STEP > 0) {
+    if (ND) ndp = s_nd[lp];
+    if (AL) alp = s_al[lp];
+    pa = s_a[lp]; pb = s_b[lp];
+  } else {
+    if (ND) ndp = a.g_nd[p];
+    if (AL) alp = a.g_al[p];
+    pa = a.in_a[p]; pb = a.in_b[p];
+  }
+  // the 3 x 3 prefilter of the variance, at a distance of one pixel whatever the step, and the colour scale it gives
+  float ivr = 0.0f, ivg = 0.0f, ivb = 0.0f;
+  if (t_c) {
+    float vr = 0.0f, vg = 0.0f, vb = 0.0f, gs = 0.0f;
+#pragma unroll
+    for (int dy = -1; dy <= 1; dy++) {
+      const int qy = y + dy;
+      if (qy < 0 || qy >= a.height) continue;
+#pragma unroll
+      for (int dx = -1; dx <= 1; dx++) {
+        const int qx = x + dx;
+        if (qx < 0 || qx >= a.width) continue;
+        constexpr float G[3] = {0.25f, 0.5f, 0.25f};
+        const float g = G[dy + 1] * G[dx + 1];
+        float qr;
+        f2v qb;
+        if constexpr (STEP > 0) {
+          const int lq = lp + dy * T::TW + dx; // inside the tile: R >= 1
+          qr = s_a[lq].w; qb = s_b[lq];
+        } else {
+          const long long q = (long long)qy * a.width + qx;
+          qr = a.in_a[q].w; qb = a.in_b[q];
+        }
+        vr = vr + g * qr; vg = vg + g * qb.x; vb = vb + g * qb.y;
+        gs = gs + g;
+      }
+    }
+    vr = vr / gs; vg = vg / gs; vb = vb / gs;
+    ivr = 1.0f / (a.sv2 * vr + 1e-8f); ivg = 1.0f / (a.sv2 * vg + 1e-8f); ivb = 1.0f / (a.sv2 * vb + 1e-8f);
+  }
+  const float den = a.sd2 * (ndp.w * ndp.w) + 1e-12f;
+  float sr = 0.0f, sg = 0.0f, sb = 0.0f, tr = 0.0f, tg = 0.0f, tb = 0.0f, ws = 0.0f;
+#pragma unroll
+  for (int dy = -2; dy <= 2; dy++) {
+    const int qy = y + dy * step;
+    if (qy < 0 || qy >= a.height) continue;
+#pragma unroll
+    for (int dx = -2; dx <= 2; dx++) {
+      const int qx = x + dx * step;
+      if (qx < 0 || qx >= a.width) continue;
+      constexpr float K[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
+      const float h = K[dy + 2] * K[dx + 2];
+      f4 qa, ndq = ndp, alq = alp;
+      f2v qb;
+      if constexpr (STEP > 0) {
+        const int lq = lp + dy * STEP * T::TW + dx * STEP; // inside the tile: |dy STEP|, |dx STEP| <= R
+        qa = s_a[lq]; qb = s_b[lq];
+        if (ND) ndq = s_nd[lq];
+        if (AL) alq = s_al[lq];
+      } else {
+        const long long q = (long long)qy * a.width + qx;
+        qa = a.in_a[q]; qb = a.in_b[q];
+        if (ND) ndq = a.g_nd[q];
+        if (AL) alq = a.g_al[q];
+      }
+      float xc = 0.0f, xn = 0.0f, xd = 0.0f, xa = 0.0f;
+      if (t_c) { const float dr = pa.x - qa.x, dg = pa.y - qa.y, db = pa.z - qa.z; xc = ((dr * dr) * ivr + (dg * dg) * ivg) + (db * db) * ivb; }
+      if (t_n) { const float dnx = ndp.x - ndq.x, dny = ndp.y - ndq.y, dnz = ndp.z - ndq.z; xn = ((dnx * dnx + dny * dny) + dnz * dnz) * a.k_n; }
+      if (t_d) { const float dz = ndp.w - ndq.w; xd = (dz * dz) / den; }
+      if (t_a) { const float dar = alp.x - alq.x, dag = alp.y - alq.y, dab = alp.z - alq.z; xa = ((dar * dar + dag * dag) + dab * dab) * a.k_a; }
+      const float xs = ((xc + xn) + xd) + xa;
+      if (!(xs < 80.0f)) continue;
+      const float w = h * exp_neg(xs);
+      const float w2 = w * w;
+      sr = sr + w * qa.x; sg = sg + w * qa.y; sb = sb + w * qa.z;
+      tr = tr + w2 * qa.w; tg = tg + w2 * qb.x; tb = tb + w2 * qb.y;
+      ws = ws + w;
+    }
+  }
+  float orr = pa.x, og = pa.y, ob = pa.z, vr = pa.w, vg = pb.x, vb = pb.y;
+  if (ws != 0.0f) {
+    const float ws2 = ws * ws;
+    orr = sr / ws; og = sg / ws; ob = sb / ws;
+    vr = tr / ws2; vg = tg / ws2; vb = tb / ws2;
+  }
+  if (a.terms & VDN_LAST) {
+    if (AL && (a.terms & DN_REMOD_OUT)) {
+      const float mr = alp.x + 1e-3f, mg = alp.y + 1e-3f, mb = alp.z + 1e-3f;
+      orr = orr * mr; og = og * mg; ob = ob * mb;
+      vr = vr * (mr * mr); vg = vg * (mg * mg); vb = vb * (mb * mb);
+    }
+    a.out_color[p * 3] = orr; a.out_color[p * 3 + 1] = og; a.out_color[p * 3 + 2] = ob;
+    if (a.out_var) { a.out_var[p * 3] = vr; a.out_var[p * 3 + 1] = vg; a.out_var[p * 3 + 2] = vb; }
+  } else {
+    const f4 ra = {orr, og, ob, vr};
+    const f2v rb = {vg, vb};
+    a.out_a[p] = ra;
+    a.out_b[p] = rb;
+  }
+}
+
 thread_local std::string g_last_error;
 
 // ---- tuning: include/pt_render.h PtTuning.  Resolved ONCE per scene (pt_scene_create / pt_debug_flatten), never on the launch path.
@@ -2944,6 +3164,130 @@ int pt_debug_last_denoise(int32_t out[8]) {
   return PT_OK;
 }
 
+// ---- variance-guided denoiser: pt_variance_denoise (vdn_pack_kernel, vdn_kernel) ------------------------------------------------------
+constexpr int kVdnLdsMaxStep = 2; // the largest step whose reads come from an LDS-staged tile (profiles/variance_denoise_bench.txt: the A/B)
+static std::mutex g_vdn_mutex;
+static int32_t g_last_vdn[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // the last pt_variance_denoise's read path per iteration
+
+void pt_variance_denoise_params_init(PtVarianceDenoiseParams* params, int32_t width, int32_t height) {
+  if (!params) return;
+  std::memset(params, 0, sizeof *params);
+  params->struct_size = (int32_t)sizeof(PtVarianceDenoiseParams);
+  params->width = width; params->height = height;
+  params->iterations = PT_VDENOISE_DEFAULT_ITERATIONS;
+  params->sigma_variance = PT_VDENOISE_DEFAULT_SIGMA_VARIANCE; params->sigma_normal = PT_VDENOISE_DEFAULT_SIGMA_NORMAL;
+  params->sigma_depth = PT_VDENOISE_DEFAULT_SIGMA_DEPTH; params->sigma_albedo = PT_VDENOISE_DEFAULT_SIGMA_ALBEDO;
+  params->flags = PT_VDENOISE_DEFAULT_FLAGS;
+}
+
+// per pixel: two working planes of a 16-byte and an 8-byte record (6 floats each) and two 16-byte guide records
+int64_t pt_variance_denoise_scratch_floats(int32_t width, int32_t height) {
+  if (width <= 0 || height <= 0 || (int64_t)width * height > ((int64_t)1 << 30)) return -1;
+  return 20 * ((int64_t)width * height);
+}
+
+int pt_variance_denoise(const PtVarianceDenoiseParams* params, const float* color, const float* variance, const float* albedo,
+                        const float* normal, const float* depth, float* out, float* variance_out, float* scratch, void* stream) {
+  const char* const who = "pt_variance_denoise: ";
+  auto bad = [&](const char* what) { return fail(PT_ERR_INVALID_ARG, std::string(who) + what); };
+  if (!params || !color || !variance || !out || !scratch) return bad("NULL params, color, variance, out or scratch");
+  if (params->struct_size != (int32_t)sizeof(PtVarianceDenoiseParams)) return bad("PtVarianceDenoiseParams.struct_size is not this library's");
+  if (params->width <= 0 || params->height <= 0) return bad("width and height must be > 0");
+  if (params->iterations < 1 || params->iterations > PT_VDENOISE_MAX_ITERATIONS) return bad("need 1 <= iterations <= 8");
+  const float sigmas[4] = {params->sigma_variance, params->sigma_normal, params->sigma_depth, params->sigma_albedo};
+  for (float s : sigmas)
+    if (!std::isfinite(s)) return bad("a sigma is not finite");
+  if (params->flags & ~(PT_VDENOISE_DEMODULATE | PT_VDENOISE_NO_LDS)) return bad("unknown flags");
+  const bool demod = params->flags & PT_VDENOISE_DEMODULATE;
+  if (demod && !albedo) return bad("PT_VDENOISE_DEMODULATE needs the albedo plane");
+  const int n_it = params->iterations;
+  unsigned terms = 0;
+  float sv2 = 0.0f, k_n = 0.0f, sd2 = 0.0f, k_a = 0.0f;
+  if (params->sigma_variance > 0.0f) {
+    terms |= DN_COLOR;
+    volatile float s2 = params->sigma_variance * params->sigma_variance;
+    sv2 = s2;
+    if (!denoise_k_ok(sv2) || !denoise_k_ok(denoise_k(params->sigma_variance))) return bad("sigma_variance^2 or its reciprocal leaves binary32");
+  }
+  if (params->sigma_normal > 0.0f && normal) {
+    terms |= DN_NORMAL;
+    k_n = denoise_k(params->sigma_normal);
+    if (!denoise_k_ok(k_n)) return bad("1 / sigma_normal^2 leaves binary32");
+  }
+  if (params->sigma_depth > 0.0f && depth) {
+    terms |= DN_DEPTH;
+    volatile float s2 = params->sigma_depth * params->sigma_depth;
+    sd2 = s2;
+    if (!denoise_k_ok(sd2)) return bad("sigma_depth^2 leaves binary32");
+  }
+  if (params->sigma_albedo > 0.0f && albedo) {
+    terms |= DN_ALBEDO;
+    k_a = denoise_k(params->sigma_albedo);
+    if (!denoise_k_ok(k_a)) return bad("1 / sigma_albedo^2 leaves binary32");
+  }
+  const int64_t pixels = (int64_t)params->width * params->height;
+  if (pixels > ((int64_t)1 << 30)) return fail(PT_ERR_TOO_LARGE, std::string(who) + "more than 2^30 pixels");
+  const int64_t scratch_floats = pt_variance_denoise_scratch_floats(params->width, params->height);
+  if ((uintptr_t)scratch % 16) return bad("scratch must be 16-byte aligned");
+  auto overlap = [](const void* a, int64_t a_floats, const void* b, int64_t b_floats) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a && b && a0 < b0 + (uintptr_t)b_floats * 4 && b0 < a0 + (uintptr_t)a_floats * 4;
+  };
+  const struct { const float* p; int64_t floats; } guides[3] = {{albedo, pixels * 3}, {normal, pixels * 3}, {depth, pixels}};
+  for (const auto& g : guides)
+    if (overlap(out, pixels * 3, g.p, g.floats) || overlap(variance_out, pixels * 3, g.p, g.floats) || overlap(scratch, scratch_floats, g.p, g.floats))
+      return bad("out, variance_out and scratch must not overlap a guide plane");
+  const float* const frames[4] = {color, variance, out, variance_out};
+  for (const float* f : frames)
+    if (overlap(scratch, scratch_floats, f, pixels * 3)) return bad("scratch must not overlap color, variance, out or variance_out");
+  if (overlap(variance_out, pixels * 3, color, pixels * 3) || overlap(variance_out, pixels * 3, out, pixels * 3))
+    return bad("variance_out must not overlap color or out");
+
+  hipStream_t st = (hipStream_t)stream;
+  // scratch: [A0 | A1 | g_nd | g_al] 16-byte records, then [B0 | B1] 8-byte records
+  f4* const rec_a[2] = {reinterpret_cast<f4*>(scratch), reinterpret_cast<f4*>(scratch) + pixels};
+  f4* const g_nd = rec_a[1] + pixels;
+  f4* const g_al = g_nd + pixels;
+  f2v* const rec_b[2] = {reinterpret_cast<f2v*>(g_al + pixels), reinterpret_cast<f2v*>(g_al + pixels) + pixels};
+  const bool nd = terms & (DN_NORMAL | DN_DEPTH), al = demod || (terms & DN_ALBEDO);
+  std::lock_guard<std::mutex> lock(g_vdn_mutex);
+  std::memset(g_last_vdn, 0, sizeof g_last_vdn);
+  hipLaunchKernelGGL(vdn_pack_kernel, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, st, color, variance, (terms & DN_NORMAL) ? normal : nullptr,
+                     (terms & DN_DEPTH) ? depth : nullptr, albedo, rec_a[0], rec_b[0], nd ? g_nd : nullptr, al ? g_al : nullptr, (long long)pixels,
+                     demod ? 1 : 0);
+  PT_HIP(hipGetLastError());
+  using Kernel = void (*)(VdnArgs);
+  static const Kernel kernels[3][2][2] = {
+      {{vdn_kernel<false, false, 0>, vdn_kernel<false, true, 0>}, {vdn_kernel<true, false, 0>, vdn_kernel<true, true, 0>}},
+      {{vdn_kernel<false, false, 1>, vdn_kernel<false, true, 1>}, {vdn_kernel<true, false, 1>, vdn_kernel<true, true, 1>}},
+      {{vdn_kernel<false, false, 2>, vdn_kernel<false, true, 2>}, {vdn_kernel<true, false, 2>, vdn_kernel<true, true, 2>}}};
+  const bool lds_ok = !(params->flags & PT_VDENOISE_NO_LDS);
+  const dim3 grid((unsigned)((params->width + 31) / 32), (unsigned)((params->height + 7) / 8));
+  for (int i = 0; i < n_it; i++) {
+    const bool last = i == n_it - 1;
+    VdnArgs a;
+    a.in_a = rec_a[i % 2]; a.in_b = rec_b[i % 2];
+    a.out_a = rec_a[(i + 1) % 2]; a.out_b = rec_b[(i + 1) % 2];
+    a.out_color = out; a.out_var = variance_out;
+    a.g_nd = g_nd; a.g_al = g_al;
+    a.width = params->width; a.height = params->height; a.step = 1 << i;
+    a.terms = terms | (last ? VDN_LAST : 0) | (demod && last ? DN_REMOD_OUT : 0);
+    a.sv2 = sv2; a.k_n = k_n; a.sd2 = sd2; a.k_a = k_a;
+    const int staged = lds_ok && a.step <= kVdnLdsMaxStep ? a.step : 0;
+    hipLaunchKernelGGL(kernels[staged][nd ? 1 : 0][al ? 1 : 0], grid, dim3(256), 0, st, a);
+    PT_HIP(hipGetLastError());
+    g_last_vdn[i] = staged ? 2 : 1;
+  }
+  return PT_OK;
+}
+
+int pt_debug_last_variance_denoise(int32_t out[8]) {
+  if (!out) return fail(PT_ERR_INVALID_ARG, "pt_debug_last_variance_denoise: NULL argument");
+  std::lock_guard<std::mutex> lock(g_vdn_mutex);
+  std::memcpy(out, g_last_vdn, sizeof g_last_vdn);
+  return PT_OK;
+}
+
 // ---- progressive rendering: sample windows into a PtAccum (include/pt_render.h) ------------------------------------------------
 } // extern "C"
 
@@ -3302,6 +3646,17 @@ int pt_adaptive_error(const PtAccum* acc, float* err_device, void* stream) {
   if (!err_device) return fail(PT_ERR_INVALID_ARG, "pt_adaptive_error: NULL argument");
   const AFrame f = frame_of(acc);
   hipLaunchKernelGGL(adaptive_error_kernel, dim3(blocks_of(f.pixels)), dim3(256), 0, (hipStream_t)stream, f, acc->sum.p, acc->half.p, acc->cnt.p, acc->cnt_a.p, err_device);
+  PT_HIP(hipGetLastError());
+  return PT_OK;
+}
+
+int pt_variance_estimate(const PtAccum* acc, float* variance_device, void* stream) {
+  if (int rc = adaptive_only(acc, "pt_variance_estimate")) return rc;
+  if (!variance_device) return fail(PT_ERR_INVALID_ARG, "pt_variance_estimate: NULL argument");
+  if (acc->max_n <= 0) return fail(PT_ERR_INVALID_ARG, "pt_variance_estimate: no samples rendered yet");
+  const AFrame f = frame_of(acc);
+  hipLaunchKernelGGL(variance_estimate_kernel, dim3(blocks_of(f.pixels)), dim3(256), 0, (hipStream_t)stream, f, acc->sum.p, acc->half.p, acc->cnt.p,
+                     acc->cnt_a.p, variance_device);
   PT_HIP(hipGetLastError());
   return PT_OK;
 }

@@ -411,6 +411,27 @@ inline void denoise(int width, int height, const float* color, const float* albe
   check(pt_denoise(&p, color, albedo, normal, depth, out, scratch, stream), "pt_denoise");
 }
 
+// The variance-guided denoiser (include/pt_render.h: pt_variance_denoise): denoise() with the colour tolerance taken per pixel from
+// `variance` ([height][width][3], the variance of each pixel's mean: accumulator::variance, or any other estimate), so that one setting
+// fits every sample count of an adaptive frame.  The buffers are DEVICE buffers the caller owns, as for denoise(); out may be color,
+// variance_out (optional: the filtered frame's residual variance) may be variance; scratch: variance_denoise_scratch_floats(width,
+// height) floats, 16-byte aligned.  The defaults are the header's (pt_variance_denoise_params_init).
+struct variance_denoise_params {
+  int iterations = PT_VDENOISE_DEFAULT_ITERATIONS;
+  float sigma_variance = PT_VDENOISE_DEFAULT_SIGMA_VARIANCE, sigma_normal = PT_VDENOISE_DEFAULT_SIGMA_NORMAL;
+  float sigma_depth = PT_VDENOISE_DEFAULT_SIGMA_DEPTH, sigma_albedo = PT_VDENOISE_DEFAULT_SIGMA_ALBEDO;
+  bool demodulate = true; // filter color / (albedo + 1e-3) and multiply the albedo back: needs the albedo plane
+};
+inline int64_t variance_denoise_scratch_floats(int width, int height) { return pt_variance_denoise_scratch_floats(width, height); }
+// asynchronous on `stream`
+inline void variance_denoise(int width, int height, const float* color, const float* variance, const float* albedo, const float* normal,
+                             const float* depth, float* out, float* variance_out, float* scratch, const variance_denoise_params& dp = {},
+                             void* stream = nullptr) {
+  const PtVarianceDenoiseParams p{(int32_t)sizeof(PtVarianceDenoiseParams), width, height, dp.iterations, dp.sigma_variance, dp.sigma_normal,
+                                  dp.sigma_depth, dp.sigma_albedo, dp.demodulate ? PT_VDENOISE_DEMODULATE : 0u, 0};
+  check(pt_variance_denoise(&p, color, variance, albedo, normal, depth, out, variance_out, scratch, stream), "pt_variance_denoise");
+}
+
 // Progressive rendering: one frame in sample windows; RAII over pt_accum_create / pt_accum_destroy (include/pt_render.h, PtAccum).
 // After windows totalling N samples, resolve() holds the bits render() gives at samples = N.  The scene must outlive the accumulator;
 // windows run on the default stream (or `stream`) and are ordered like renders of the scene.
@@ -445,6 +466,9 @@ class accumulator {
   }
   void counts(int32_t* counts_device, void* stream = nullptr) const { check(pt_adaptive_counts(a_, counts_device, stream), "pt_adaptive_counts"); }
   void error(float* err_device, void* stream = nullptr) const { check(pt_adaptive_error(a_, err_device, stream), "pt_adaptive_error"); }
+  // adaptive: the per-channel variance of each resolved pixel from the two half buffers (a DEVICE buffer of pt_framebuffer_floats()
+  // floats, laid out like the frame) — what variance_denoise() takes
+  void variance(float* variance_device, void* stream = nullptr) const { check(pt_variance_estimate(a_, variance_device, stream), "pt_variance_estimate"); }
   // the next window's mask; returns how many pixels are active (synchronises `stream`)
   int64_t select(float threshold, int min_spp, int max_spp, bool dilate, uint8_t* mask_device, void* stream = nullptr) const {
     int64_t n = 0;

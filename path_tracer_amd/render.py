@@ -203,6 +203,54 @@ def denoise(fb, *, albedo=None, normal=None, depth=None, iterations: int = abi.P
     return out
 
 
+def denoise_variance(fb, variance, *, albedo=None, normal=None, depth=None, iterations: int = abi.PT_VDENOISE_DEFAULT_ITERATIONS,
+                     sigma_variance: float = abi.PT_VDENOISE_DEFAULT_SIGMA_VARIANCE, sigma_normal: float = abi.PT_VDENOISE_DEFAULT_SIGMA_NORMAL,
+                     sigma_depth: float = abi.PT_VDENOISE_DEFAULT_SIGMA_DEPTH, sigma_albedo: float = abi.PT_VDENOISE_DEFAULT_SIGMA_ALBEDO,
+                     demodulate: bool = True, no_lds: bool = False, out=None, variance_out=None, **other_planes):
+    """The variance-guided a-trous filter (include/pt_render.h: pt_variance_denoise): denoise() with the colour tolerance taken per pixel
+    from `variance` — the variance of each pixel's mean, [H][W][3] float32 on the GPU, from Accumulator.variance() or anywhere else —
+    so one setting fits every sample count in an adaptive frame: denoise_variance(acc.resolve(), acc.variance(), **render_aov(...)).
+    The planes, their checks, `demodulate` and `no_lds` (PT_VDENOISE_NO_LDS) are denoise()'s; `sigma_variance` is the colour tolerance
+    in standard deviations (<= 0: guide-only).  `variance_out` (optional, may be `variance`) receives the filtered frame's residual
+    variance.  Asynchronous on torch's current stream; torch allocates the scratch.  Returns the filtered frame — `out` if given, which
+    may be `fb` itself."""
+    import torch
+
+    if not torch.cuda.is_available():
+        raise RuntimeError("path_tracer_amd.denoise_variance needs a HIP device: there is no CPU path in the product")
+    lib = abi.load_library()
+    if not abi.has_variance_denoise(lib):
+        raise ImportError(f"{abi.library_path()} predates the variance-guided denoiser (no pt_variance_denoise entry point)")
+    unknown = set(other_planes) - set(abi.AOV_PLANES)
+    if unknown:
+        raise TypeError(f"denoise_variance() got unexpected keyword arguments {sorted(unknown)}")
+
+    def plane(t, shape, what):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()):
+            raise ValueError(f"{what} must be a contiguous float32 CUDA tensor of shape {shape}")
+        return C.c_void_p(t.data_ptr()) if t is not None else None
+
+    if fb.dim() != 3 or fb.shape[2] != 3:
+        raise ValueError("fb must be a whole frame [H][W][3] (gather and unshard a multi-GPU frame first)")
+    if variance is None:
+        raise ValueError("variance must be a contiguous float32 CUDA tensor shaped like fb")
+    h, w, _ = (int(n) for n in fb.shape)
+    if out is None:
+        out = torch.empty((h, w, 3), dtype=torch.float32, device=fb.device)
+    n = lib.pt_variance_denoise_scratch_floats(w, h)
+    if n < 0:
+        abi.check(abi.PT_ERR_INVALID_ARG, "pt_variance_denoise_scratch_floats")
+    scratch = torch.empty(n, dtype=torch.float32, device=fb.device)
+    p = abi.PtVarianceDenoiseParams(C.sizeof(abi.PtVarianceDenoiseParams), w, h, int(iterations), float(sigma_variance), float(sigma_normal),
+                                    float(sigma_depth), float(sigma_albedo),
+                                    (abi.PT_VDENOISE_DEMODULATE if demodulate else 0) | (abi.PT_VDENOISE_NO_LDS if no_lds else 0), 0)
+    abi.check(lib.pt_variance_denoise(C.byref(p), plane(fb, (h, w, 3), "fb"), plane(variance, (h, w, 3), "variance"),
+                                      plane(albedo, (h, w, 3), "albedo"), plane(normal, (h, w, 3), "normal"), plane(depth, (h, w), "depth"),
+                                      plane(out, (h, w, 3), "out"), plane(variance_out, (h, w, 3), "variance_out"),
+                                      C.c_void_p(scratch.data_ptr()), _stream_ptr(torch)), "pt_variance_denoise")
+    return out
+
+
 def render_host(width: int, height: int, samples: int, scene, cam: camera, depth: int = 50, *, flags: int = 0,
                 shard_index: int = 0, shard_count: int = 1) -> np.ndarray:
     """Torch-free path: pt_render_host renders into a numpy array (allocates, copies back, syncs)."""
@@ -389,6 +437,29 @@ class Accumulator:
         guides = render_aov(self.width, self.height, aov_spp, self._ds, self.cam, planes=("albedo", "normal", "depth"))
         return denoise(self.resolve(), **guides, **kw)
 
+    def variance(self, out=None):
+        """The per-channel variance of each resolved pixel, estimated from the two half buffers (adaptive; include/pt_render.h:
+        pt_variance_estimate): float32, shaped like resolve(); +inf where a pixel has no estimate yet."""
+        import torch
+
+        if not abi.has_variance_denoise(self.lib):
+            raise ImportError(f"{abi.library_path()} predates the variance estimate (no pt_variance_estimate entry point)")
+        n = self.lib.pt_framebuffer_floats(C.byref(self._p))
+        if out is None:
+            out = torch.empty(self._shape(n), dtype=torch.float32, device="cuda")
+        elif out.numel() != n or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float32 CUDA tensor of pt_framebuffer_floats() elements")
+        abi.check(self.lib.pt_variance_estimate(self.handle, C.c_void_p(out.data_ptr()), _stream_ptr(torch)), "pt_variance_estimate")
+        return out
+
+    def denoise_variance(self, aov_spp: int = 16, **kw):
+        """resolve(), variance(), the feature buffers of the accumulator's own scene and bound camera (render_aov at `aov_spp` camera
+        rays per pixel) and denoise_variance() over them.  Adaptive accumulators, whole frames only."""
+        if self.shard_count != 1:
+            raise ValueError("Accumulator.denoise_variance: whole frames only (the filter reads neighbours: gather and unshard first)")
+        guides = render_aov(self.width, self.height, aov_spp, self._ds, self.cam, planes=("albedo", "normal", "depth"))
+        return denoise_variance(self.resolve(), self.variance(), **guides, **kw)
+
     def tonemap_rgb8(self):
         """resolve() + tonemap_rgb8() in one pass (whole frames): uint8 [H][W][3], row 0 = top."""
         import torch
@@ -493,7 +564,7 @@ def render_progressive(width: int, height: int, samples: int, scene, cam: camera
 
 
 def render_adaptive(width: int, height: int, scene, cam: camera, depth: int = 50, *, threshold: float, min_spp: int = 16,
-                    max_spp: int = 1024, step: int = 16, dilate: bool = True, flags: int = 0):
+                    max_spp: int = 1024, step: int = 16, dilate: bool = True, flags: int = 0, variance: bool = False):
     """Adaptive sampling (include/pt_render.h: pt_adaptive_*): a window of min_spp samples of every pixel, then windows of `step`
     samples of the pixels pt_adaptive_select keeps active (noise estimate above `threshold`, or below min_spp; with `dilate`, next to
     such a pixel) until none is.  Returns (framebuffer, counts): each pixel holds the bits render() gives at its own count, which lies
@@ -503,7 +574,10 @@ def render_adaptive(width: int, height: int, scene, cam: camera, depth: int = 50
     Each select synchronises the stream (its count decides the next window).  With a negative threshold every pixel below max_spp is
     noisy, so the selection follows from the counts alone: while every window has been unmasked, every pixel is active until the
     counts reach max_spp, and the loop skips the select (and its synchronisation) — the same windows, asynchronous like
-    render_progressive."""
+    render_progressive.
+
+    `variance=True` also returns the per-pixel variance estimate of the finished frame (Accumulator.variance(), what
+    denoise_variance() takes): (framebuffer, counts, variance)."""
     if min_spp <= 0 or step <= 0 or max_spp < min_spp or (max_spp - min_spp) % step != 0:
         raise ValueError("need 0 < min_spp <= max_spp, step > 0 and (max_spp - min_spp) % step == 0")
     acc = Accumulator(width, height, scene, cam, depth, flags=flags, adaptive=True)
@@ -520,6 +594,8 @@ def render_adaptive(width: int, height: int, scene, cam: camera, depth: int = 50
                 break
             uniform = uniform and n_active == pixels
             acc.add(step, None if n_active == pixels else mask)
+        if variance:
+            return acc.resolve(), acc.counts(), acc.variance()
         return acc.resolve(), acc.counts()
     finally:
         acc.close()
