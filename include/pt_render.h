@@ -714,6 +714,113 @@ int pt_variance_denoise(const PtVarianceDenoiseParams* params, const float* colo
  * an LDS-staged tile (the steps 1 and 2, unless PT_VDENOISE_NO_LDS).  The bits do not depend on it.  For tests. */
 int pt_debug_last_variance_denoise(int32_t out[8]);
 
+/* ---- temporal reprojection: a frame's history carried across camera moves ------------------------------------------------------------
+ * Added without an ABI version change, like PtAccum: a caller detects the feature by the presence of these symbols.  Nothing above changes.
+ *
+ * The temporal half of SVGF (Schied et al., HPG 2017), whose spatial half is pt_variance_denoise: each frame of a sequence is blended
+ * into the history of the frames before it, fetched for every pixel through the PREVIOUS camera and rejected where the guides say the
+ * surface is another one.  Two pieces are needed, and both are here: the reprojection (PtTemporal), and frames that do not repeat their
+ * random numbers (pt_adaptive_next_frame) — pt_render and pt_accum_reset seed a pixel's generator with its linear id, so two frames from
+ * the same or a nearby camera carry the SAME noise and no image-space accumulator could average them.
+ *
+ * NEXT FRAME (pt_adaptive_next_frame).  Adaptive accumulators only (PT_ERR_INVALID_ARG for NULL or a plain accumulator).  Starts a new
+ * image that CONTINUES every pixel's stream: S, H, n, a and the unmasked sample count are zeroed, the camera binding and the kept tile
+ * order are released exactly as pt_accum_reset releases them, and the per-pixel generator states are KEPT.  Asynchronous on `stream`,
+ * allocates nothing, launches no kernel (an adaptive accumulator's windows always resume from the stored state).
+ * CONTRACT, to the bit: let s_p be pixel p's generator state at the call.  After any sequence of windows, masked or not, totalling n_p
+ * samples under the newly bound camera, S_p is the binary32 sum from +0, in sample order, of the n_p sample colours the reference's loop
+ * (render.hpp:95-101) produces when its generator starts at s_p; the pixel resolves to S_p / (float)n_p; and the pixel's state is where
+ * that loop left it.  Such a frame is the reference's estimator on a LATER PART of the pixel's stream: it equals pt_render's image at no
+ * sample count.  pt_adaptive_export / pt_adaptive_import work unchanged afterwards.
+ * (Declared `extern`, which changes nothing for a C or C++ caller: the eight entry points adaptive sampling was introduced with are
+ * told from later ones by their plain one-word declarations.)
+ *
+ * THE HISTORY (PtTemporal).  Scope: pt_denoise's — whole frames only, no scene involved; planes [height][width](x3), y = 0 the bottom row;
+ * pt_temporal_push is asynchronous on `stream` and allocates nothing (pt_temporal_create is the only allocation: pt_temporal_state_bytes
+ * of device memory, two histories of 48 bytes per pixel — a push reads one and writes the other).  depth, normal and id are
+ * pt_render_aov's planes for the same camera: the mean t along the UN-NORMALISED camera ray, 0 where missed; the mean normal; the
+ * hittable of sample 0.  normal, id, variance_in, out_variance and out_history are optional (NULL).  out_color may be color and
+ * out_variance may be variance_in.  Pushes of one PtTemporal are stream-ordered like renders of one PtScene.
+ *
+ * State.  Per pixel: c, the accumulated colour (also the first moment); m2, the accumulated second moment; N, the history length as a
+ * float (0: unusable); z, n, k: the depth, normal and id pushed with the frame (0 for a NULL plane) — stored as three 16-byte records,
+ * (c.rgb, N), (m2.rgb, z), (n.xyz, bits of k), so that a tap is three 16-byte loads.  The history also keeps the camera of the last push.
+ *
+ * Host-side constants, from the previous camera (primed):  g = lower_left_corner' - origin' per component;
+ *   fo = -((g.x w'.x + g.y w'.y) + g.z w'.z);   hh = (h'.x h'.x + h'.y h'.y) + h'.z h'.z  (h' = horizontal');   vv likewise from vertical'.
+ * A camera whose fo, hh or vv is not a finite number > 0 is refused (when it is pushed: a stored camera is always sound).
+ *
+ * DEFINITION.  Every value is IEEE binary32, every operation below is rounded once, nothing is fused, and the order of operations is the
+ * one written.  For pixel p = (x, y) of a W x H frame, with C = color(p), z = depth(p), n = normal(p), k = id(p):
+ *   finite(C) = every channel has |C.ch| < inf.
+ *   !finite(C):  out_color = C, out_variance = +inf, out_history = 0; stored record: c = m2 = 0, N = 0.  (A NaN or inf stays where it is and
+ *                never enters a history.)
+ *   No usable history (the first push, or the first after pt_temporal_reset):  N = 1, alpha_p = 1, c = C, m2 = C * C.
+ *   Otherwise:
+ *     sc = ((float)x + 0.5f) / (float)W;   tc = ((float)y + 0.5f) / (float)H
+ *     dir = ((lower_left_corner + sc * horizontal) + tc * vertical) - origin           per component, the camera of this push
+ *     hit = z > 0                                                                      (NaN: false)
+ *     d   = hit ? ((origin + z * dir) - origin') : dir      (a missed pixel reprojects as a direction: the sky is at infinity)
+ *     cp  = -((d.x w'.x + d.y w'.y) + d.z w'.z);   r = fo / cp;   te = cp / fo
+ *     s'  = (((d.x h'.x + d.y h'.y) + d.z h'.z) * r) / hh + 0.5f;   t' likewise with vertical', vv
+ *     fx  = s' * (float)W - 0.5f;   fy = t' * (float)H - 0.5f
+ *     usable = cp > 0 && fx >= -1 && fx < W && fy >= -1 && fy < H                      (NaN fails)
+ *     x0 = floorf(fx), y0 = floorf(fy), ax = fx - x0, ay = fy - y0
+ *     hc = hm = (0, 0, 0), hN = 0, bs = 0
+ *     for j = 0, 1 (outer), i = 0, 1 (inner): q = (x0 + i, y0 + j); a q outside the frame is skipped
+ *       b = (i ? ax : 1.0f - ax) * (j ? ay : 1.0f - ay)
+ *       consistent(q) = N'(q) >= 1
+ *                    && (hit ? (z'(q) > 0 && fabsf(z'(q) - te) <= tol_depth * te) : !(z'(q) > 0))
+ *                    && (id == NULL     || k'(q) == k)
+ *                    && (normal == NULL || ((dn.x dn.x + dn.y dn.y) + dn.z dn.z) <= tol_normal * tol_normal),   dn = n - n'(q)
+ *       if consistent: hc.ch = hc.ch + b * c'(q).ch;  hm.ch = hm.ch + b * m2'(q).ch;  hN = hN + b * N'(q);  bs = bs + b
+ *     if !(usable && bs > 0.01f): as "no usable history".
+ *     Else:
+ *       hcn = hc / bs;  hmn = hm / bs;  N = fminf(hN / bs + 1.0f, 65536.0f);  alpha_p = fmaxf(1.0f / N, alpha)
+ *       c = hcn + alpha_p * (C - hcn);   m2 = hmn + alpha_p * (C * C - hmn)
+ *   Then, for every pixel with finite(C):
+ *     out_color = c;  out_history = N
+ *     out_variance = N >= 4 ? fmaxf(m2 - c * c, 0) * alpha_p : (variance_in ? variance_in(p) : +inf)
+ * te is the depth the pixel's surface would have had in the previous frame, in that frame's units, so the depth test compares like with
+ * like.  The variance is that of the accumulated mean: s^2 / N while alpha_p = 1 / N, and within a factor 2 (on the safe side) once the
+ * exponential floor `alpha` holds.  The +inf is pt_variance_estimate's "no estimate" value, which pt_variance_denoise sanitises; a young
+ * history (N < 4) passes the caller's own estimate through.  A camera that turned away (cp <= 0), a disoccluded surface (every tap
+ * inconsistent) and a pixel that reprojects outside the previous frame all start a new history of length 1.
+ * Cameras with a lens (lens_radius > 0) reproject through the lens centre; the consistency tests reject what that gets wrong.
+ *
+ * Rejected (PT_ERR_INVALID_ARG, on the host, before any device call): a NULL state, params, cam, color, depth or out_color; a struct_size
+ * other than sizeof(PtTemporalParams); alpha outside (0, 1]; a tolerance that is not finite and > 0; flags (none is defined); a degenerate
+ * camera (above); an out plane overlapping a guide plane (depth, normal, id) or another out plane.  pt_temporal_create: width or height <= 0;
+ * more than 2^30 pixels: PT_ERR_TOO_LARGE.
+ *
+ * Out of scope: shards (gather first, as for the denoisers); checkpointing the history; SVGF's 3 x 3 fallback search; moving geometry
+ * other than what the guides already reject.  profiles/temporal_bench.txt holds the measured cost.                                   */
+#define PT_TEMPORAL_DEFAULT_ALPHA 0.1f
+#define PT_TEMPORAL_DEFAULT_TOL_DEPTH 0.1f
+#define PT_TEMPORAL_DEFAULT_TOL_NORMAL 0.5f
+extern int pt_adaptive_next_frame(PtAccum* acc, void* stream);
+typedef struct PtTemporal PtTemporal; /* device-resident history of one image sequence; 2 x 48 bytes per pixel */
+typedef struct PtTemporalParams {
+  int32_t struct_size; /* sizeof(PtTemporalParams) of the caller's header */
+  float alpha, tol_depth, tol_normal;
+  uint32_t flags;      /* none defined: 0 */
+  int32_t reserved[3];
+} PtTemporalParams;
+/* Host function, no GPU: struct_size + the defaults above (alpha 0.1, tol_depth 0.1, tol_normal 0.5). */
+void pt_temporal_params_init(PtTemporalParams* params);
+/* Host function, no GPU: device bytes of the state of a width x height sequence; < 0 for invalid sizes. */
+int64_t pt_temporal_state_bytes(int32_t width, int32_t height);
+/* Allocates the state on the current device (the only allocation); no history yet. */
+int pt_temporal_create(int32_t width, int32_t height, PtTemporal** out);
+void pt_temporal_destroy(PtTemporal* state);
+/* Forget the history: the next push starts one. */
+int pt_temporal_reset(PtTemporal* state, void* stream);
+/* Pushes since create / reset (host-side count; -1 for NULL). */
+int32_t pt_temporal_frames(const PtTemporal* state);
+int pt_temporal_push(PtTemporal* state, const PtTemporalParams* params, const PtCamera* cam, const float* color, const float* depth,
+                     const float* normal, const int32_t* id, const float* variance_in, float* out_color, float* out_variance,
+                     float* out_history, void* stream);
+
 /* ---- function-level probes (parity tests call these; not used by render) ---- */
 
 /* One iteration of the bounce loop render.hpp:58-89 per record: hit_world,

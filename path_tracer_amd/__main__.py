@@ -21,6 +21,12 @@ the one written without the option.
 With --denoise-variance (needs --denoise-out and --noise-threshold) the filtered frame comes from the variance-guided filter instead
 (render.denoise_variance; --denoise-sigma-variance replaces --denoise-sigma-color): its colour tolerance is each pixel's own noise
 estimate, taken from the adaptive accumulator's half buffers, so one setting fits every sample count in the frame.
+With --frames N --frames-dir DIR a camera path is rendered as well: frame f looks from look_from + f x --move (dx,dy,dz) and goes to
+DIR/frame_<f>.png through the same output stage, --spp samples each.  With --temporal the frames come from render.render_temporal — one
+adaptive accumulator continued from frame to frame (no frame repeats another's random numbers) and the history reprojected across the
+camera moves (render.TemporalAccumulator) — and frame_<f>.png is the accumulated frame; with --temporal --denoise-variance it is that
+frame filtered by the variance-guided filter, fed the temporal variance.  out.png is byte-identical to the one written without the
+options.
 """
 import argparse
 import os
@@ -43,6 +49,21 @@ def write_aovs(aov_dir, planes) -> None:
         rgb8 = (fb.clamp(0.0, 0.999) * 256.0).to(torch.uint8).flip(0).contiguous()
         write_png(os.path.join(aov_dir, f"{name}.png"), rgb8.cpu().numpy())
     np.savez(os.path.join(aov_dir, "aov.npz"), **{k: v.cpu().numpy() for k, v in planes.items()})
+
+
+def write_frames(a, packed, cam_args, move, denoise_kw) -> None:
+    """The camera path of --frames: DIR/frame_<f>.png, frame f looking from look_from + f x move.  Plain: render() per frame.  --temporal:
+    render_temporal's accumulated frame, or with --denoise-variance that frame through the variance-guided filter."""
+    os.makedirs(a.frames_dir, exist_ok=True)
+    cams = [scenes.make_camera(dict(cam_args, look_from=tuple(float(p) + f * d for p, d in zip(cam_args["look_from"], move))), a.width, a.height)
+            for f in range(a.frames)]
+    if not a.temporal:
+        for f, c in enumerate(cams):
+            write_png(os.path.join(a.frames_dir, f"frame_{f}.png"), R.tonemap_rgb8(R.render(a.width, a.height, a.spp, packed, c, a.depth)).cpu().numpy())
+        return
+    for f, frame in enumerate(R.render_temporal(a.width, a.height, a.spp, packed, cams, a.depth, aov_spp=a.aov_spp, denoise=a.denoise_variance,
+                                                denoise_kw=denoise_kw)):
+        write_png(os.path.join(a.frames_dir, f"frame_{f}.png"), R.tonemap_rgb8(frame["filtered" if a.denoise_variance else "temporal"]).cpu().numpy())
 
 
 def main() -> None:
@@ -79,10 +100,35 @@ def main() -> None:
                     help="denoiser: the variance-guided filter over the adaptive accumulator's noise estimate (needs --noise-threshold)")
     ap.add_argument("--denoise-sigma-variance", type=float, default=None, metavar="S",
                     help="variance-guided denoiser: colour tolerance in standard deviations, <= 0 turns it off (default: include/pt_render.h)")
+    ap.add_argument("--frames", type=int, default=None, metavar="N", help="also render a camera path of N frames into --frames-dir")
+    ap.add_argument("--move", default=None, metavar="DX,DY,DZ", help="camera path: look_from moves by this per frame (default 0,0,0)")
+    ap.add_argument("--frames-dir", default=None, metavar="DIR", help="camera path: where frame_<f>.png goes")
+    ap.add_argument("--temporal", action="store_true",
+                    help="camera path: carry each frame's history across the camera moves (temporal reprojection)")
     a = ap.parse_args()
-    if a.denoise_variance and a.noise_threshold is None:
+    if a.frames is None and (a.move is not None or a.frames_dir is not None or a.temporal):
+        ap.error("--move, --frames-dir and --temporal need --frames")
+    move = (0.0, 0.0, 0.0)
+    if a.frames is not None:
+        if a.frames < 1:
+            ap.error("--frames must be >= 1")
+        if a.frames_dir is None:
+            ap.error("--frames needs --frames-dir")
+        if a.move is not None:
+            try:
+                move = tuple(float(v) for v in a.move.split(","))
+            except ValueError:
+                move = ()
+            if len(move) != 3 or any(v != v or v in (float("inf"), float("-inf")) for v in move):
+                ap.error("--move must be three finite numbers dx,dy,dz")
+        if a.spp < 1:
+            ap.error("--frames needs --spp >= 1")
+    temporal_filter = a.temporal and a.denoise_variance
+    if temporal_filter and a.denoise_out is not None and a.noise_threshold is None:
+        ap.error("--denoise-out with --denoise-variance needs --noise-threshold (without --denoise-out, --temporal --denoise-variance filters the frames only)")
+    if a.denoise_variance and a.noise_threshold is None and not a.temporal:
         ap.error("--denoise-variance needs --noise-threshold (the variance comes from the adaptive accumulator's half buffers)")
-    if a.denoise_variance and a.denoise_out is None:
+    if a.denoise_variance and a.denoise_out is None and not a.temporal:
         ap.error("--denoise-variance needs --denoise-out")
     if a.denoise_sigma_variance is not None and not a.denoise_variance:
         ap.error("--denoise-sigma-variance needs --denoise-variance")
@@ -92,13 +138,13 @@ def main() -> None:
                                     ("sigma_variance", a.denoise_sigma_variance),
                                     ("sigma_normal", a.denoise_sigma_normal), ("sigma_depth", a.denoise_sigma_depth),
                                     ("sigma_albedo", a.denoise_sigma_albedo)) if v is not None}
-    if denoise_kw and a.denoise_out is None:
+    if denoise_kw and a.denoise_out is None and not temporal_filter:
         ap.error("--denoise-iterations and --denoise-sigma-* need --denoise-out")
     if a.denoise_iterations is not None and not 1 <= a.denoise_iterations <= 8:
         ap.error("--denoise-iterations must be in 1 .. 8")
     if any(v != v or v in (float("inf"), float("-inf")) for k, v in denoise_kw.items() if k != "iterations"):
         ap.error("--denoise-sigma-* must be finite")
-    if a.aov_spp is not None and a.aov_dir is None and a.denoise_out is None:
+    if a.aov_spp is not None and a.aov_dir is None and a.denoise_out is None and not a.temporal:
         ap.error("--aov-spp needs --aov-dir")
     a.aov_spp = 16 if a.aov_spp is None else a.aov_spp
     if not 1 <= a.aov_spp <= 1 << 24:
@@ -168,6 +214,8 @@ def main() -> None:
     if a.denoise_out:
         filtered = R.denoise_variance(fb, variance[0], **planes, **denoise_kw) if a.denoise_variance else R.denoise(fb, **planes, **denoise_kw)
         write_png(a.denoise_out, R.tonemap_rgb8(filtered).cpu().numpy())
+    if a.frames is not None:
+        write_frames(a, packed, cam_args, move, denoise_kw)
     if mean_spp is not None:
         n = int(counts.sum())
         print(f"{a.scene}: {packed.n_hittables} hittables, {a.width}x{a.height}, adaptive {a.min_spp}..{a.spp} spp (threshold "

@@ -144,6 +144,12 @@ class PtVarianceDenoiseParams(C.Structure):
                 ("flags", C.c_uint32), ("reserved", C.c_int32)]
 
 
+class PtTemporalParams(C.Structure):
+    """include/pt_render.h PtTemporalParams: the temporal reprojection's parameters (pt_temporal_push)."""
+    _fields_ = [("struct_size", C.c_int32), ("alpha", C.c_float), ("tol_depth", C.c_float), ("tol_normal", C.c_float),
+                ("flags", C.c_uint32), ("reserved", C.c_int32 * 3)]
+
+
 assert C.sizeof(PtHittable) == 64 and C.sizeof(PtMaterial) == 32 and C.sizeof(PtTexture) == 48
 assert C.sizeof(PtCamera) == 96 and C.sizeof(PtRenderParams) == 32
 
@@ -225,6 +231,15 @@ SIGNATURES = {
     "pt_variance_denoise_scratch_floats": (C.c_int64, [C.c_int32, C.c_int32]),
     "pt_variance_denoise": (C.c_int, [C.POINTER(PtVarianceDenoiseParams)] + [C.c_void_p] * 9),
     "pt_debug_last_variance_denoise": (C.c_int, [C.POINTER(C.c_int32)]),
+    # temporal reprojection and the frame that continues every pixel's stream: likewise optional (TEMPORAL_SYMBOLS)
+    "pt_adaptive_next_frame": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pt_temporal_params_init": (None, [C.POINTER(PtTemporalParams)]),
+    "pt_temporal_state_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "pt_temporal_create": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "pt_temporal_destroy": (None, [C.c_void_p]),
+    "pt_temporal_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pt_temporal_frames": (C.c_int32, [C.c_void_p]),
+    "pt_temporal_push": (C.c_int, [C.c_void_p, C.POINTER(PtTemporalParams), C.POINTER(PtCamera)] + [C.c_void_p] * 9),
     # the launcher's geometry rules for one pass, host-only: likewise optional (PLAN_SYMBOLS)
     "pt_debug_plan_pass": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
 }
@@ -236,7 +251,8 @@ PT_ACCUM_MAGIC = 0x43415450
 PT_ACCUM_FORMAT = 1
 PT_ACCUM_HEADER_BYTES = 160
 # adaptive sampling (include/pt_render.h: pt_adaptive_*); has_adaptive() tells whether the loaded library has them
-ADAPTIVE_SYMBOLS = frozenset(n for n in SIGNATURES if n.startswith("pt_adaptive_"))
+# (pt_adaptive_next_frame came later and is detected with temporal reprojection: TEMPORAL_SYMBOLS)
+ADAPTIVE_SYMBOLS = frozenset(n for n in SIGNATURES if n.startswith("pt_adaptive_") and n != "pt_adaptive_next_frame")
 PT_ADAPTIVE_FORMAT = 2
 PT_ADAPTIVE_DILATE = 1
 # first-hit feature buffers (include/pt_render.h: pt_render_aov); has_aov() tells whether the loaded library has them
@@ -267,6 +283,12 @@ PT_VDENOISE_MAX_ITERATIONS = 8
 # the header's PT_VDENOISE_DEFAULT_* (pt_variance_denoise_params_init)
 PT_VDENOISE_DEFAULT_ITERATIONS = 5
 PT_VDENOISE_DEFAULT_SIGMA_VARIANCE, PT_VDENOISE_DEFAULT_SIGMA_NORMAL, PT_VDENOISE_DEFAULT_SIGMA_DEPTH, PT_VDENOISE_DEFAULT_SIGMA_ALBEDO = 2.0, 0.5, 0.2, 0.0
+
+# temporal reprojection (include/pt_render.h: pt_adaptive_next_frame, pt_temporal_*); has_temporal() tells whether the loaded library has it
+TEMPORAL_SYMBOLS = frozenset({"pt_adaptive_next_frame", "pt_temporal_params_init", "pt_temporal_state_bytes", "pt_temporal_create",
+                              "pt_temporal_destroy", "pt_temporal_reset", "pt_temporal_frames", "pt_temporal_push"})
+# the header's PT_TEMPORAL_DEFAULT_* (pt_temporal_params_init)
+PT_TEMPORAL_DEFAULT_ALPHA, PT_TEMPORAL_DEFAULT_TOL_DEPTH, PT_TEMPORAL_DEFAULT_TOL_NORMAL = 0.1, 0.1, 0.5
 
 LIB_NAME = "libpt_render.so"
 _lib = None
@@ -311,7 +333,7 @@ def load_library() -> C.CDLL:
         pass  # torch-free hosts bind to /opt/rocm/lib through the library's RUNPATH
     lib = C.CDLL(str(path))
     for name, (res, args) in SIGNATURES.items():
-        if override_is_older_build(path, lib, name) or (name in ACCUM_SYMBOLS | ADAPTIVE_SYMBOLS | AOV_SYMBOLS | DENOISE_SYMBOLS | PLAN_SYMBOLS | VARIANCE_SYMBOLS and not hasattr(lib, name)):
+        if override_is_older_build(path, lib, name) or (name in ACCUM_SYMBOLS | ADAPTIVE_SYMBOLS | AOV_SYMBOLS | DENOISE_SYMBOLS | PLAN_SYMBOLS | VARIANCE_SYMBOLS | TEMPORAL_SYMBOLS and not hasattr(lib, name)):
             continue
         fn = getattr(lib, name)  # AttributeError if the library does not export what the header declares
         fn.restype = res
@@ -351,6 +373,12 @@ def has_variance_denoise(lib=None) -> bool:
     """Does the loaded library offer the variance-guided denoiser (pt_variance_estimate, pt_variance_denoise)?"""
     lib = lib or load_library()
     return all(hasattr(lib, n) for n in VARIANCE_SYMBOLS)
+
+
+def has_temporal(lib=None) -> bool:
+    """Does the loaded library offer temporal reprojection (pt_adaptive_next_frame, pt_temporal_push)?"""
+    lib = lib or load_library()
+    return has_adaptive(lib) and all(hasattr(lib, n) for n in TEMPORAL_SYMBOLS)
 
 
 def check(code: int, where: str) -> None:

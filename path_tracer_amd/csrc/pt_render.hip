@@ -1680,6 +1680,117 @@ __global__ __launch_bounds__(256) void vdn_kernel(VdnArgs a) {
   }
 }
 
+// ---- temporal reprojection (include/pt_render.h: PtTemporal, pt_temporal_push) ----------------------------------------------------------
+// The temporal half of SVGF: a frame is blended into the history of the frames before it, fetched through the previous camera.  Same rules
+// as the filters above: the header states every operation, this is that text in HIP; -ffp-contract=off, correctly rounded division.
+struct TemporalArgs {
+  const float* color;   // [height][width][3]
+  const float* depth;   // [height][width]
+  const float* normal;  // [height][width][3] or NULL
+  const int* id;        // [height][width] or NULL
+  const float* var_in;  // [height][width][3] or NULL
+  float* out_color;     // may be color
+  float* out_var;       // may be var_in; or NULL
+  float* out_hist;      // or NULL
+  const f4* prev;       // the history read: three planes of `pixels` records — (c.rgb, N), (m2.rgb, z), (n.xyz, bits of k)
+  f4* next;             // the history written: the other buffer, same layout
+  long long pixels;
+  int width, height;
+  int has_history;      // 0: the first push (or the first after a reset): `prev` is not read
+  float o[3], llc[3], hor[3], ver[3];  // the camera of this frame
+  float po[3], pw[3], ph[3], pv[3];    // the previous push's: origin', w', horizontal', vertical'
+  float fo, hh, vv;                    // ... and the host's constants of it
+  float alpha, tol_depth, tn2;         // tn2 = tol_normal * tol_normal
+};
+
+// One thread per pixel, a 32 x 8 pixel workgroup: neighbouring pixels reproject to neighbouring history pixels, so the four taps of a
+// workgroup fall into a few shared cache lines.  A tap is three 16-byte loads.  Every pixel writes its three history records.
+__global__ __launch_bounds__(256) void temporal_push_kernel(TemporalArgs a) {
+  const int lx = threadIdx.x & 31, ly = threadIdx.x >> 5;
+  const int x = blockIdx.x * 32 + lx, y = blockIdx.y * 8 + ly;
+  if (x >= a.width || y >= a.height) return;
+  const long long p = (long long)y * a.width + x;
+  const float inf = __builtin_inff();
+  const float cr = a.color[p * 3], cg = a.color[p * 3 + 1], cb = a.color[p * 3 + 2];
+  const float z = a.depth[p];
+  float nx = 0.0f, ny = 0.0f, nz = 0.0f;
+  if (a.normal) { nx = a.normal[p * 3]; ny = a.normal[p * 3 + 1]; nz = a.normal[p * 3 + 2]; }
+  const int k = a.id ? a.id[p] : 0;
+  const bool fin = fabsf(cr) < inf && fabsf(cg) < inf && fabsf(cb) < inf;
+  // no usable history: the frame starts one
+  float N = 1.0f, ap = 1.0f;
+  float c0 = cr, c1 = cg, c2 = cb, m0 = cr * cr, m1 = cg * cg, m2 = cb * cb;
+  if (a.has_history && fin) {
+    const float sc = ((float)x + 0.5f) / (float)a.width, tc = ((float)y + 0.5f) / (float)a.height;
+    const float rx = ((a.llc[0] + sc * a.hor[0]) + tc * a.ver[0]) - a.o[0];
+    const float ry = ((a.llc[1] + sc * a.hor[1]) + tc * a.ver[1]) - a.o[1];
+    const float rz = ((a.llc[2] + sc * a.hor[2]) + tc * a.ver[2]) - a.o[2];
+    const bool hit = z > 0.0f;
+    float dx = rx, dy = ry, dz = rz; // a missed pixel reprojects as a direction
+    if (hit) { dx = (a.o[0] + z * rx) - a.po[0]; dy = (a.o[1] + z * ry) - a.po[1]; dz = (a.o[2] + z * rz) - a.po[2]; }
+    const float cp = -((dx * a.pw[0] + dy * a.pw[1]) + dz * a.pw[2]);
+    const float r = a.fo / cp, te = cp / a.fo;
+    const float s1 = (((dx * a.ph[0] + dy * a.ph[1]) + dz * a.ph[2]) * r) / a.hh + 0.5f;
+    const float t1 = (((dx * a.pv[0] + dy * a.pv[1]) + dz * a.pv[2]) * r) / a.vv + 0.5f;
+    const float fx = s1 * (float)a.width - 0.5f, fy = t1 * (float)a.height - 0.5f;
+    if (cp > 0.0f && fx >= -1.0f && fx < (float)a.width && fy >= -1.0f && fy < (float)a.height) { // (NaN fails)
+      const float fx0 = floorf(fx), fy0 = floorf(fy);
+      const float ax = fx - fx0, ay = fy - fy0;
+      const int x0 = (int)fx0, y0 = (int)fy0; // -1 ... width - 1, -1 ... height - 1
+      const float tol_te = a.tol_depth * te;
+      float h0 = 0.0f, h1 = 0.0f, h2 = 0.0f, g0 = 0.0f, g1 = 0.0f, g2 = 0.0f, hN = 0.0f, bs = 0.0f;
+#pragma unroll
+      for (int j = 0; j < 2; j++) {
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+          const int qx = x0 + i, qy = y0 + j;
+          if (qx < 0 || qx >= a.width || qy < 0 || qy >= a.height) continue;
+          const float b = (i ? ax : 1.0f - ax) * (j ? ay : 1.0f - ay);
+          const long long q = (long long)qy * a.width + qx;
+          const f4 qa = a.prev[q], qb = a.prev[a.pixels + q], qc = a.prev[2 * a.pixels + q];
+          bool ok = qa.w >= 1.0f;
+          ok = ok && (hit ? (qb.w > 0.0f && fabsf(qb.w - te) <= tol_te) : !(qb.w > 0.0f));
+          if (a.id) ok = ok && __float_as_int(qc.w) == k;
+          if (a.normal) {
+            const float ex = nx - qc.x, ey = ny - qc.y, ez = nz - qc.z;
+            ok = ok && ((ex * ex + ey * ey) + ez * ez) <= a.tn2;
+          }
+          if (ok) {
+            h0 = h0 + b * qa.x; h1 = h1 + b * qa.y; h2 = h2 + b * qa.z;
+            g0 = g0 + b * qb.x; g1 = g1 + b * qb.y; g2 = g2 + b * qb.z;
+            hN = hN + b * qa.w;
+            bs = bs + b;
+          }
+        }
+      }
+      if (bs > 0.01f) {
+        h0 = h0 / bs; h1 = h1 / bs; h2 = h2 / bs;
+        g0 = g0 / bs; g1 = g1 / bs; g2 = g2 / bs;
+        N = fminf(hN / bs + 1.0f, 65536.0f);
+        ap = fmaxf(1.0f / N, a.alpha);
+        c0 = h0 + ap * (cr - h0); c1 = h1 + ap * (cg - h1); c2 = h2 + ap * (cb - h2);
+        m0 = g0 + ap * (cr * cr - g0); m1 = g1 + ap * (cg * cg - g1); m2 = g2 + ap * (cb * cb - g2);
+      }
+    }
+  }
+  float o0 = cr, o1 = cg, o2 = cb, v0 = inf, v1 = inf, v2 = inf, oh = 0.0f;
+  if (fin) {
+    o0 = c0; o1 = c1; o2 = c2; oh = N;
+    if (N >= 4.0f) {
+      v0 = fmaxf(m0 - c0 * c0, 0.0f) * ap; v1 = fmaxf(m1 - c1 * c1, 0.0f) * ap; v2 = fmaxf(m2 - c2 * c2, 0.0f) * ap;
+    } else if (a.var_in) {
+      v0 = a.var_in[p * 3]; v1 = a.var_in[p * 3 + 1]; v2 = a.var_in[p * 3 + 2];
+    }
+  } else { // a colour that is not finite stays where it is and never enters a history
+    c0 = c1 = c2 = m0 = m1 = m2 = 0.0f; N = 0.0f;
+  }
+  a.out_color[p * 3] = o0; a.out_color[p * 3 + 1] = o1; a.out_color[p * 3 + 2] = o2;
+  if (a.out_var) { a.out_var[p * 3] = v0; a.out_var[p * 3 + 1] = v1; a.out_var[p * 3 + 2] = v2; }
+  if (a.out_hist) a.out_hist[p] = oh;
+  const f4 ra = {c0, c1, c2, N}, rb = {m0, m1, m2, z}, rc = {nx, ny, nz, __int_as_float(k)};
+  a.next[p] = ra; a.next[a.pixels + p] = rb; a.next[2 * a.pixels + p] = rc;
+}
+
 thread_local std::string g_last_error;
 
 // ---- tuning: include/pt_render.h PtTuning.  Resolved ONCE per scene (pt_scene_create / pt_debug_flatten), never on the launch path.
@@ -3288,6 +3399,134 @@ int pt_debug_last_variance_denoise(int32_t out[8]) {
   return PT_OK;
 }
 
+// ---- temporal reprojection: PtTemporal, pt_temporal_push (temporal_push_kernel) -------------------------------------------------------
+} // extern "C"
+
+struct PtTemporal {
+  int32_t width = 0, height = 0;
+  long long pixels = 0;
+  DevBuf<f4> rec;     // two histories of three planes of `pixels` 16-byte records: a push reads one and writes the other
+  int cur = 0;        // the history the next push reads
+  int32_t frames = 0; // pushes since create / reset (0: no history)
+  PtCamera cam{};     // the camera of the last push
+};
+
+namespace {
+// fo, hh, vv of a camera (include/pt_render.h): each product and each sum rounded to binary32
+struct TemporalConsts { float fo, hh, vv; bool ok; };
+TemporalConsts temporal_consts(const PtCamera& c) {
+  volatile float g[3], t[3], s;
+  for (int i = 0; i < 3; i++) g[i] = c.lower_left_corner[i] - c.origin[i];
+  auto dot = [&](const float* a, const float* b) {
+    for (int i = 0; i < 3; i++) t[i] = a[i] * b[i];
+    s = t[0] + t[1];
+    s = s + t[2];
+    return (float)s;
+  };
+  const float gg[3] = {g[0], g[1], g[2]};
+  TemporalConsts k;
+  k.fo = -dot(gg, c.w);
+  k.hh = dot(c.horizontal, c.horizontal);
+  k.vv = dot(c.vertical, c.vertical);
+  auto good = [](float v) { return std::isfinite(v) && v > 0.0f; };
+  k.ok = good(k.fo) && good(k.hh) && good(k.vv);
+  return k;
+}
+} // namespace
+
+extern "C" {
+
+void pt_temporal_params_init(PtTemporalParams* params) {
+  if (!params) return;
+  std::memset(params, 0, sizeof *params);
+  params->struct_size = (int32_t)sizeof(PtTemporalParams);
+  params->alpha = PT_TEMPORAL_DEFAULT_ALPHA;
+  params->tol_depth = PT_TEMPORAL_DEFAULT_TOL_DEPTH;
+  params->tol_normal = PT_TEMPORAL_DEFAULT_TOL_NORMAL;
+}
+
+// two histories of three 16-byte records per pixel
+int64_t pt_temporal_state_bytes(int32_t width, int32_t height) {
+  if (width <= 0 || height <= 0 || (int64_t)width * height > ((int64_t)1 << 30)) return -1;
+  return 96 * ((int64_t)width * height);
+}
+
+int pt_temporal_create(int32_t width, int32_t height, PtTemporal** out) {
+  if (!out) return fail(PT_ERR_INVALID_ARG, "pt_temporal_create: out is NULL");
+  *out = nullptr;
+  if (width <= 0 || height <= 0) return fail(PT_ERR_INVALID_ARG, "pt_temporal_create: width and height must be > 0");
+  if ((int64_t)width * height > ((int64_t)1 << 30)) return fail(PT_ERR_TOO_LARGE, "pt_temporal_create: more than 2^30 pixels");
+  std::unique_ptr<PtTemporal> t(new PtTemporal());
+  t->width = width; t->height = height; t->pixels = (long long)width * height;
+  const hipError_t e = t->rec.alloc((size_t)t->pixels * 6);
+  if (e != hipSuccess) return fail(PT_ERR_HIP, std::string("pt_temporal_create: hipMalloc: ") + hipGetErrorString(e));
+  *out = t.release();
+  return PT_OK;
+}
+
+void pt_temporal_destroy(PtTemporal* t) { delete t; }
+
+// (nothing to do on the device: a push without history does not read the records)
+int pt_temporal_reset(PtTemporal* t, void* stream) {
+  if (!t) return fail(PT_ERR_INVALID_ARG, "pt_temporal_reset: NULL state");
+  t->frames = 0;
+  return PT_OK;
+}
+
+int32_t pt_temporal_frames(const PtTemporal* t) { return t ? t->frames : -1; }
+
+int pt_temporal_push(PtTemporal* t, const PtTemporalParams* params, const PtCamera* cam, const float* color, const float* depth,
+                     const float* normal, const int32_t* id, const float* variance_in, float* out_color, float* out_variance,
+                     float* out_history, void* stream) {
+  auto bad = [&](const char* what) { return fail(PT_ERR_INVALID_ARG, std::string("pt_temporal_push: ") + what); };
+  // (the arguments that can be judged without the state first: the state is read only once they are sound)
+  if (!t || !params || !cam || !color || !depth || !out_color) return bad("NULL state, params, cam, color, depth or out_color");
+  if (params->struct_size != (int32_t)sizeof(PtTemporalParams)) return bad("PtTemporalParams.struct_size is not this library's");
+  if (!(params->alpha > 0.0f && params->alpha <= 1.0f)) return bad("need 0 < alpha <= 1");
+  if (!(std::isfinite(params->tol_depth) && params->tol_depth > 0.0f) || !(std::isfinite(params->tol_normal) && params->tol_normal > 0.0f))
+    return bad("a tolerance is not a finite number > 0");
+  if (params->flags) return bad("unknown flags");
+  if (!temporal_consts(*cam).ok) return bad("a degenerate camera (fo, hh or vv is not a finite number > 0)");
+  const long long pixels = t->pixels;
+  auto overlap = [](const void* a, int64_t a_floats, const void* b, int64_t b_floats) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a && b && a0 < b0 + (uintptr_t)b_floats * 4 && b0 < a0 + (uintptr_t)a_floats * 4;
+  };
+  const struct { const void* p; int64_t floats; } outs[3] = {{out_color, pixels * 3}, {out_variance, pixels * 3}, {out_history, pixels}},
+                                                  guides[3] = {{depth, pixels}, {normal, pixels * 3}, {id, pixels}};
+  for (const auto& o : outs)
+    for (const auto& g : guides)
+      if (overlap(o.p, o.floats, g.p, g.floats)) return bad("an out plane overlaps a guide plane");
+  for (int i = 0; i < 3; i++)
+    for (int j = i + 1; j < 3; j++)
+      if (overlap(outs[i].p, outs[i].floats, outs[j].p, outs[j].floats)) return bad("the out planes overlap one another");
+
+  TemporalArgs a;
+  a.color = color; a.depth = depth; a.normal = normal; a.id = id; a.var_in = variance_in;
+  a.out_color = out_color; a.out_var = out_variance; a.out_hist = out_history;
+  a.prev = t->rec.p + (size_t)t->cur * 3 * (size_t)pixels;
+  a.next = t->rec.p + (size_t)(1 - t->cur) * 3 * (size_t)pixels;
+  a.pixels = pixels; a.width = t->width; a.height = t->height;
+  a.has_history = t->frames > 0 ? 1 : 0;
+  const PtCamera& pc = a.has_history ? t->cam : *cam;
+  const TemporalConsts k = temporal_consts(pc); // (sound: every stored camera passed the check above)
+  for (int i = 0; i < 3; i++) {
+    a.o[i] = cam->origin[i]; a.llc[i] = cam->lower_left_corner[i]; a.hor[i] = cam->horizontal[i]; a.ver[i] = cam->vertical[i];
+    a.po[i] = pc.origin[i]; a.pw[i] = pc.w[i]; a.ph[i] = pc.horizontal[i]; a.pv[i] = pc.vertical[i];
+  }
+  a.fo = k.fo; a.hh = k.hh; a.vv = k.vv;
+  a.alpha = params->alpha; a.tol_depth = params->tol_depth;
+  volatile float tn2 = params->tol_normal * params->tol_normal;
+  a.tn2 = tn2;
+  const dim3 grid((unsigned)((t->width + 31) / 32), (unsigned)((t->height + 7) / 8));
+  hipLaunchKernelGGL(temporal_push_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
+  PT_HIP(hipGetLastError());
+  t->cur = 1 - t->cur;
+  t->cam = *cam;
+  if (t->frames < INT32_MAX) t->frames++;
+  return PT_OK;
+}
+
 // ---- progressive rendering: sample windows into a PtAccum (include/pt_render.h) ------------------------------------------------
 } // extern "C"
 
@@ -3631,6 +3870,24 @@ int pt_adaptive_window(PtAccum* acc, const PtCamera* cam, int32_t samples, const
   if (!mask_device) acc->done += samples;
   acc->max_n += samples;
   if (!acc->cam_bound) { acc->cam = *cam; acc->cam_bound = true; }
+  return PT_OK;
+}
+
+// A new image that continues every pixel's stream: pt_accum_reset without the re-seeding.  Every window of an adaptive accumulator
+// resumes from the stored state, so this is memsets and host bookkeeping: no kernel.
+int pt_adaptive_next_frame(PtAccum* acc, void* stream) {
+  if (int rc = adaptive_only(acc, "pt_adaptive_next_frame")) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  PT_HIP(hipMemsetAsync(acc->sum.p, 0, acc->fb_floats * sizeof(float), st));
+  PT_HIP(hipMemsetAsync(acc->half.p, 0, acc->fb_floats * sizeof(float), st));
+  PT_HIP(hipMemsetAsync(acc->prev.p, 0, acc->fb_floats * sizeof(float), st));
+  acc->prev_synced = true;
+  PT_HIP(hipMemsetAsync(acc->cnt.p, 0, std::max<size_t>(acc->pixels, 1) * sizeof(int), st));
+  PT_HIP(hipMemsetAsync(acc->cnt_a.p, 0, std::max<size_t>(acc->pixels, 1) * sizeof(int), st));
+  acc->max_n = 0;
+  acc->done = 0;
+  acc->cam_bound = false;
+  acc->has_order = false;
   return PT_OK;
 }
 

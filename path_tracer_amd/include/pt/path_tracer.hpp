@@ -432,6 +432,35 @@ inline void variance_denoise(int width, int height, const float* color, const fl
   check(pt_variance_denoise(&p, color, variance, albedo, normal, depth, out, variance_out, scratch, stream), "pt_variance_denoise");
 }
 
+// Temporal reprojection (include/pt_render.h: PtTemporal): the history of one image sequence, RAII over pt_temporal_create /
+// pt_temporal_destroy.  push() blends a frame into the history fetched through the previous push's camera and rejected by the guides
+// (depth: required; normal, id: optional) — render_aov's planes for the frame's camera.  The planes are DEVICE buffers the caller owns,
+// [height][width](x3); out_color may be color, out_variance may be variance_in; variance_in, out_variance and out_history are optional.
+// The defaults are the header's (pt_temporal_params_init).
+struct temporal_params {
+  float alpha = PT_TEMPORAL_DEFAULT_ALPHA, tol_depth = PT_TEMPORAL_DEFAULT_TOL_DEPTH, tol_normal = PT_TEMPORAL_DEFAULT_TOL_NORMAL;
+};
+class temporal {
+ public:
+  temporal(int width, int height) { check(pt_temporal_create(width, height, &t_), "pt_temporal_create"); }
+  ~temporal() { pt_temporal_destroy(t_); }
+  temporal(const temporal&) = delete;
+  temporal& operator=(const temporal&) = delete;
+  // asynchronous on `stream`
+  void push(const camera& cam, const float* color, const float* depth, const float* normal, const int32_t* id, const float* variance_in,
+            float* out_color, float* out_variance = nullptr, float* out_history = nullptr, const temporal_params& tp = {},
+            void* stream = nullptr) {
+    const PtTemporalParams p{(int32_t)sizeof(PtTemporalParams), tp.alpha, tp.tol_depth, tp.tol_normal, 0u, {0, 0, 0}};
+    check(pt_temporal_push(t_, &p, &cam.c, color, depth, normal, id, variance_in, out_color, out_variance, out_history, stream), "pt_temporal_push");
+  }
+  void reset(void* stream = nullptr) { check(pt_temporal_reset(t_, stream), "pt_temporal_reset"); }
+  int frames() const { return pt_temporal_frames(t_); }
+  PtTemporal* handle() const { return t_; }
+
+ private:
+  PtTemporal* t_ = nullptr;
+};
+
 // Progressive rendering: one frame in sample windows; RAII over pt_accum_create / pt_accum_destroy (include/pt_render.h, PtAccum).
 // After windows totalling N samples, resolve() holds the bits render() gives at samples = N.  The scene must outlive the accumulator;
 // windows run on the default stream (or `stream`) and are ordered like renders of the scene.
@@ -486,6 +515,13 @@ class accumulator {
   }
   int samples() const { return pt_accum_samples(a_); }
   void reset(void* stream = nullptr) { check(pt_accum_reset(a_, stream), "pt_accum_reset"); }
+  // adaptive: a new image that CONTINUES every pixel's random stream (pt_adaptive_next_frame) — the frames of a sequence then carry
+  // independent noise, which is what pt::temporal averages; the next window binds `cam` (or the camera used so far)
+  void next_frame(void* stream = nullptr) { check(pt_adaptive_next_frame(a_, stream), "pt_adaptive_next_frame"); }
+  void next_frame(const camera& cam, void* stream = nullptr) {
+    next_frame(stream);
+    cam_ = cam.c;
+  }
 
   // the mean so far, in render()'s layout (host memory: from the exported sums, divided here with the same correctly rounded IEEE
   // division as the device's resolve — the host build has no fast-math, no contraction)

@@ -474,6 +474,19 @@ class Accumulator:
 
         abi.check(self.lib.pt_accum_reset(self.handle, _stream_ptr(torch)), "pt_accum_reset")
 
+    def next_frame(self, cam: "camera | None" = None) -> "Accumulator":
+        """A new image that CONTINUES every pixel's random stream (adaptive; include/pt_render.h: pt_adaptive_next_frame): sums and
+        counts back to 0, the camera binding released, the generator states kept — so the frames of a sequence carry independent noise
+        (reset() re-seeds: its frames repeat theirs).  The next window binds `cam` if given, else the camera used so far."""
+        import torch
+
+        if not abi.has_temporal(self.lib):
+            raise ImportError(f"{abi.library_path()} predates temporal reprojection (no pt_adaptive_next_frame entry point)")
+        abi.check(self.lib.pt_adaptive_next_frame(self.handle, _stream_ptr(torch)), "pt_adaptive_next_frame")
+        if cam is not None:
+            self.cam = cam
+        return self
+
     def state(self) -> np.ndarray:
         """The exported state (pt_accum_export: header, sums, generator states; adaptive: pt_adaptive_export's format 2, which adds
         H and the counts n and a) as bytes in a uint8 array."""
@@ -543,6 +556,118 @@ class _BoundCamera:
 
     def __init__(self, c: "abi.PtCamera"):
         self.c = c
+
+
+class TemporalAccumulator:
+    """Temporal reprojection (include/pt_render.h: PtTemporal): the history of one image sequence, carried across camera moves.
+
+    push() blends a frame into the history of the frames before it, fetched through the previous push's camera and rejected where the
+    guides (render_aov's depth, normal, id for the frame's camera) say the surface is another one.  Whole frames only; asynchronous on
+    torch's current stream; pushes of one TemporalAccumulator must be stream-ordered."""
+
+    def __init__(self, width: int, height: int):
+        import torch
+
+        if not torch.cuda.is_available():
+            raise RuntimeError("path_tracer_amd.render.TemporalAccumulator needs a HIP device: there is no CPU path in the product")
+        self.lib = abi.load_library()
+        if not abi.has_temporal(self.lib):
+            raise ImportError(f"{abi.library_path()} predates temporal reprojection (no pt_temporal_* entry points)")
+        self.width, self.height = int(width), int(height)
+        self.handle = C.c_void_p()
+        abi.check(self.lib.pt_temporal_create(self.width, self.height, C.byref(self.handle)), "pt_temporal_create")
+
+    @property
+    def frames(self) -> int:
+        """Pushes since the constructor or the last reset()."""
+        return int(self.lib.pt_temporal_frames(self.handle))
+
+    def push(self, fb, cam: camera, *, depth, normal=None, id=None, variance=None, out=None, alpha: float = abi.PT_TEMPORAL_DEFAULT_ALPHA,
+             tol_depth: float = abi.PT_TEMPORAL_DEFAULT_TOL_DEPTH, tol_normal: float = abi.PT_TEMPORAL_DEFAULT_TOL_NORMAL, **other_planes):
+        """One frame: `fb` [H][W][3] float32 on the GPU (render()'s or Accumulator.resolve()'s), `cam` its camera, depth [H][W] (required),
+        normal [H][W][3], id [H][W] int32 (optional) its feature buffers — push(fb, cam, **render_aov(...)) works: the planes the pass
+        does not take are ignored — and `variance` [H][W][3] (optional) the frame's own variance estimate, passed through where the
+        history is younger than 4 frames.  Returns (color, variance, history): the accumulated frame (`out` if given, which may be
+        `fb`), the variance of the accumulated mean (+inf where there is no estimate) and the history length [H][W]."""
+        import torch
+
+        unknown = set(other_planes) - set(abi.AOV_PLANES)
+        if unknown:
+            raise TypeError(f"push() got unexpected keyword arguments {sorted(unknown)}")
+        h, w = self.height, self.width
+
+        def plane(t, shape, what, dtype=torch.float32):
+            if t is not None and (tuple(t.shape) != shape or t.dtype != dtype or not t.is_cuda or not t.is_contiguous()):
+                raise ValueError(f"{what} must be a contiguous {dtype} CUDA tensor of shape {shape}")
+            return C.c_void_p(t.data_ptr()) if t is not None else None
+
+        if fb is None or depth is None:
+            raise ValueError("push() needs the frame and its depth plane")
+        if out is None:
+            out = torch.empty((h, w, 3), dtype=torch.float32, device=fb.device)
+        var_out = torch.empty((h, w, 3), dtype=torch.float32, device=fb.device)
+        hist = torch.empty((h, w), dtype=torch.float32, device=fb.device)
+        p = abi.PtTemporalParams(C.sizeof(abi.PtTemporalParams), float(alpha), float(tol_depth), float(tol_normal), 0)
+        abi.check(self.lib.pt_temporal_push(self.handle, C.byref(p), C.byref(cam.c), plane(fb, (h, w, 3), "fb"), plane(depth, (h, w), "depth"),
+                                            plane(normal, (h, w, 3), "normal"), plane(id, (h, w), "id", torch.int32),
+                                            plane(variance, (h, w, 3), "variance"), plane(out, (h, w, 3), "out"),
+                                            C.c_void_p(var_out.data_ptr()), C.c_void_p(hist.data_ptr()), _stream_ptr(torch)), "pt_temporal_push")
+        return out, var_out, hist
+
+    def reset(self) -> None:
+        """Forget the history: the next push starts one."""
+        import torch
+
+        abi.check(self.lib.pt_temporal_reset(self.handle, _stream_ptr(torch)), "pt_temporal_reset")
+
+    def close(self) -> None:
+        if self.handle:
+            self.lib.pt_temporal_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+
+def render_temporal(width: int, height: int, spp: int, scene, cams, depth: int = 50, *, aov_spp: int = 4, denoise: bool = True,
+                    denoise_kw: "dict | None" = None, **params):
+    """A camera path rendered at `spp` samples per frame with its history carried along: for each camera of `cams` yields a dict with
+    `noisy` (the frame alone), `temporal`, `variance`, `history` (TemporalAccumulator.push's results) and, with `denoise`, `filtered` —
+    denoise_variance() over the temporal colour and variance with that frame's guides (render_aov at `aov_spp` camera rays per pixel).
+    One adaptive accumulator renders every frame, with next_frame() between them: no frame repeats another's random numbers.  A frame
+    of 2 samples or more is rendered in two windows, so that its own variance estimate (Accumulator.variance(), from the two halves)
+    exists and is what `variance` holds where the history is younger than 4 frames.
+    `params`: push()'s alpha, tol_depth, tol_normal; `denoise_kw`: denoise_variance()'s parameters."""
+    import torch
+
+    if spp <= 0:
+        raise ValueError("spp must be > 0")
+    ds = _as_device_scene(scene, cache_key=("cuda", torch.cuda.current_device(), torch.cuda.current_stream().cuda_stream))
+    acc, hist = None, TemporalAccumulator(width, height)
+    try:
+        for cam in cams:
+            if acc is None:
+                acc = Accumulator(width, height, ds, cam, depth, adaptive=True)
+            else:
+                acc.next_frame(cam)
+            acc.add(spp - spp // 2)
+            if spp >= 2:
+                acc.add(spp // 2)
+            noisy, var = acc.resolve(), acc.variance()
+            guides = render_aov(width, height, aov_spp, ds, cam, planes=("albedo", "normal", "depth", "id"))
+            color, variance, history = hist.push(noisy, cam, variance=var, **guides, **params)
+            frame = dict(noisy=noisy, temporal=color, variance=variance, history=history)
+            if denoise:
+                frame["filtered"] = denoise_variance(color, variance, albedo=guides["albedo"], normal=guides["normal"], depth=guides["depth"],
+                                                     **(denoise_kw or {}))
+            yield frame
+    finally:
+        if acc is not None:
+            acc.close()
+        hist.close()
 
 
 def render_progressive(width: int, height: int, samples: int, scene, cam: camera, depth: int = 50, *, step: int, flags: int = 0,
