@@ -918,6 +918,20 @@ int pt_debug_plan_pass(const int64_t facts[20], int32_t out[14]);
  * tag from one constant (csrc/pt_render.hip: picked_of), so the tag is the kernel that ran.  For tests (tests/kernel_variant_cases.py). */
 int pt_debug_last_kernels(const PtScene* scene, int32_t out[24]);
 
+/* The pool plan the LAST frame pass of this scene was given (csrc/pt_device.hpp: PoolPlan): out[0] = 1 if the pass's kernel took the
+ * scene's ONE slab pool from its kernel arguments instead of walking the run list (a rect / box-only scene whose first run heads a pool
+ * with an octant table that spans every run, rendered by an LDS-resident kernel compiled for such scenes, rays allowed to be regular),
+ * out[1] = the pool's entries, out[2] / out[3] = the 16-byte-record offsets in the blob of its exact entries and of its octant table's
+ * first record.  out[1..3] say what the scene's blob holds whether or not out[0] claims it.  For tests (tests/test_gpu_pool_plan.py).   */
+int pt_debug_last_pool_plan(const PtScene* scene, int32_t out[4]);
+
+/* The same derivation host-only — no device call — for the frame pass of a render of `desc` with `params` (tuning NULL = defaults +
+ * environment): out[0..3] as above; out[4] = offset of the pool's slab entries, out[5] = the bits of its largest |coordinate|,
+ * out[6..8] = the first run's header (device kind, first record, count); out[9] = 1 if the SCENE allows the plan (whatever kernel and
+ * flags), out[10] / out[11] = the LDS and MATS template arguments of the kernel the launcher would pick (0 where another kernel family
+ * runs).  Scenes that are not rects and boxes under lambertian / light materials never read a plan: out[0] = 0 without asking further. */
+int pt_debug_pool_plan(const PtSceneDesc* desc, const PtTuning* tuning, const PtRenderParams* params, int32_t out[12]);
+
 /* Which aov_kernel the LAST pt_render_aov of this scene launched: out[0] = its sphere-grid walk (1 wave-synchronous, 2 through the LDS pair
  * queue; scenes without a sphere grid: 1), out[1] = 1 if u,v are tracked through the scan; both 0 before the first pass.  For tests.  */
 int pt_debug_last_aov(const PtScene* scene, int32_t out[2]);

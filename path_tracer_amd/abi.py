@@ -242,6 +242,9 @@ SIGNATURES = {
     "pt_temporal_push": (C.c_int, [C.c_void_p, C.POINTER(PtTemporalParams), C.POINTER(PtCamera)] + [C.c_void_p] * 9),
     # the launcher's geometry rules for one pass, host-only: likewise optional (PLAN_SYMBOLS)
     "pt_debug_plan_pass": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    # the one-pool plan of rect / box-only scenes, as the last frame pass got it and as derived without a device: likewise optional (POOL_PLAN_SYMBOLS)
+    "pt_debug_last_pool_plan": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "pt_debug_pool_plan": (C.c_int, [C.POINTER(PtSceneDesc), C.POINTER(PtTuning), C.POINTER(PtRenderParams), C.POINTER(C.c_int32)]),
 }
 
 # Entry points a library may lack and still load for everything else (include/pt_render.h: the feature is detected by their presence);
@@ -263,6 +266,9 @@ AOV_CHANNELS = {"albedo": 3, "normal": 3, "direct": 3, "depth": 1, "coverage": 1
 DENOISE_SYMBOLS = frozenset({"pt_denoise_params_init", "pt_denoise_scratch_floats", "pt_denoise", "pt_debug_last_denoise"})
 # the launcher's planner as an entry point (include/pt_render.h: pt_debug_plan_pass): the order of its facts and of its output words
 PLAN_SYMBOLS = frozenset({"pt_debug_plan_pass"})
+# the one-pool plan's read-backs (include/pt_render.h: pt_debug_last_pool_plan, pt_debug_pool_plan) and the order of the latter's words
+POOL_PLAN_SYMBOLS = frozenset({"pt_debug_last_pool_plan", "pt_debug_pool_plan"})
+POOL_PLAN_WORDS = ("one", "n", "x_off", "oct_off", "pool_off", "bmax_bits", "kind", "off", "count", "scene_allows", "lds", "mats")
 PLAN_FACTS = ("num_cus", "per_cu", "block_threads", "chain_bound", "use_grid", "queued_walk", "flags", "blocks_per_cu", "lanes_cap", "heavy_tiles",
               "no_chain_prio", "launch_units", "n_local_pixels", "samples", "probe", "has_order", "has_split", "tile_granular", "scatter_p", "fast_chunks")
 PLAN_WORDS = ("workgroups", "n_waves_resident", "lanes_cap", "tile_granular", "heavy_pixels", "heavy_lanes", "prio_onset", "prio_t1", "prio_t2",
@@ -333,7 +339,7 @@ def load_library() -> C.CDLL:
         pass  # torch-free hosts bind to /opt/rocm/lib through the library's RUNPATH
     lib = C.CDLL(str(path))
     for name, (res, args) in SIGNATURES.items():
-        if override_is_older_build(path, lib, name) or (name in ACCUM_SYMBOLS | ADAPTIVE_SYMBOLS | AOV_SYMBOLS | DENOISE_SYMBOLS | PLAN_SYMBOLS | VARIANCE_SYMBOLS | TEMPORAL_SYMBOLS and not hasattr(lib, name)):
+        if override_is_older_build(path, lib, name) or (name in ACCUM_SYMBOLS | ADAPTIVE_SYMBOLS | AOV_SYMBOLS | DENOISE_SYMBOLS | PLAN_SYMBOLS | POOL_PLAN_SYMBOLS | VARIANCE_SYMBOLS | TEMPORAL_SYMBOLS and not hasattr(lib, name)):
             continue
         fn = getattr(lib, name)  # AttributeError if the library does not export what the header declares
         fn.restype = res

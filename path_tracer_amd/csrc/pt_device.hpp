@@ -1378,8 +1378,29 @@ __device__ __forceinline__ unsigned long long slab_chunk_pass(P xrecs, P slrecs,
 // The kernels of rect / box-only scenes (the headline family): 2.  The kernels that carry every hittable kind: 1 — except the queued sphere-grid
 // walk's (GRID = 2), which keep the scalar form: they hold five more values across a scan, and the bounds in vector registers push their
 // scratch from 20 to 28 bytes at the 96-register budget (tests/test_kernel_resources_cpu.py holds 24).  One form per kernel, never two.
+// x_off / oct_off: where the exact entries and the octant table start (f4 offsets into the blob).  Both follow from (pool_off, n) —
+// pool_tables — and a scene whose whole list is ONE pool has them ready in its kernel arguments (PoolPlan).
+__host__ __device__ __forceinline__ void pool_tables(int pool_off, int n, int& x_off, int& oct_off) {
+  x_off = pool_off + 2 * (n + (n & 1));
+  oct_off = x_off + 2 * n;
+}
+// The one pool of a scene whose whole list it covers, for the LDS-resident kernels of rect / box-only scenes: what the run header and the
+// pool's aux record would say, as launch constants (pt_render.hip: KArgs.plan, scene_pool_plan, pass_pool_plan).  `one` = 0: every bounce walks the list.
+struct PoolPlan {
+  // the four words the kernel reads, in ONE s_load_dwordx4:
+  int one = 0;       // the first run heads a pool with an octant table that spans every run, and the launch's kernel may use that
+  int n = 0;         // the pool's entries
+  float bmax = 0.0f; // the largest |coordinate| of the pool (aux.x)
+  int x_off = 0;     // f4 offset into the blob of the exact entries; the octant table's first record follows them: x_off + 2 n
+  // what else the plan stands for (never read by the kernel; pt_debug_last_pool_plan / pt_debug_pool_plan show it)
+  int oct_off = 0;   // f4 offset of the octant table's first record
+  int pool_off = 0;  // f4 offset of the slab entries
+  int kind = 0, off = 0, count = 0; // the first run's header
+};
+static_assert(offsetof(PoolPlan, x_off) == 12, "the kernel's four words lead");
+
 template <int LDS_FORM, typename P>
-__device__ __forceinline__ void slab_pool(P blob, cst_f4p cblob, int pool_off, int n, float bmax, const RayCtx& c, HitState& h) {
+__device__ __forceinline__ void slab_pool(P blob, cst_f4p cblob, int pool_off, int x_off, int oct_off, int n, float bmax, const RayCtx& c, HitState& h) {
   constexpr int FORM = __is_same(P, lds_f4p) ? LDS_FORM : 0;
   constexpr bool OCT = FORM > 0;
   const float kP = 0x1.2p-21f;           // 9u
@@ -1397,7 +1418,7 @@ __device__ __forceinline__ void slab_pool(P blob, cst_f4p cblob, int pool_off, i
     op = (c.r.o - ps) * ny;
     // the lane's octant record: q = sx | sy << 1 | sz << 2, two f4 per octant
     const unsigned int q2 = (((unsigned int)as_i(c.yx) >> 30) & 2u) | (((unsigned int)as_i(c.yy) >> 29) & 4u) | (((unsigned int)as_i(c.yz) >> 28) & 8u);
-    otab = blob + pool_off + 2 * (n + (n & 1)) + 2 * n + (int)q2;
+    otab = blob + oct_off + (int)q2;
   } else {
     om = (mk(0.0f, 0.0f, 0.0f) - (c.r.o + pp)) * yv;
     op = (mk(0.0f, 0.0f, 0.0f) - (c.r.o - pp)) * yv;
@@ -1407,7 +1428,7 @@ __device__ __forceinline__ void slab_pool(P blob, cst_f4p cblob, int pool_off, i
 #endif
   for (int base = 0; base < n; base += 16) {
     const int cn = n - base < 16 ? n - base : 16;
-    const P xrecs = blob + pool_off + 2 * (n + (n & 1)) + 2 * base;
+    const P xrecs = blob + x_off + 2 * base;
     const cst_f4p srecs = cblob + pool_off + 2 * base; // the slab entries through the scalar cache (wave-uniform reads) ...
     const P slrecs = blob + pool_off + 2 * base;       // ... and where the lanes read them individually
     const P ochunk = otab + 16 * base;                 // sign-resolved form: the lane's octant record of the chunk's first entry
@@ -2313,7 +2334,31 @@ __device__ __forceinline__ int record_size(int kind) {
 // its direction-map part as a request in *dfr (tri_pool_scan<true>).
 template <bool IMG, bool BADOUEL = false, int GRID = 1, bool TRIPOOL = false, bool RECTBOX = false, bool DEFER = false, typename P>
 __device__ __forceinline__ void hit_world_range(P blob, cst_f4p cblob, int ri0, int ri1, const RayCtx& c, bool fast, uint32_t& rng, HitState& h, const f4* pool = nullptr,
-                                                TriDefer* dfr = nullptr, const TriPrimCtx* pc = nullptr) {
+                                                TriDefer* dfr = nullptr, const TriPrimCtx* pc = nullptr, const PoolPlan* plan = nullptr) {
+  // PLANNED — the kernels of rect / box-only scenes that read the LDS image: a pool is reached through the PLAN alone.  Every run of such a
+  // scene is a rect or a box run, so the flattener's one maximal stretch is the whole list: a pool, where there is one, is headed by run 0,
+  // spans every run and (an LDS kernel was chosen) has its octant table — exactly what scene_pool_plan (pt_render.hip) checks before it
+  // sets `one`.  With it, and every live ray of the wave regular, the bounce IS the pool, from launch constants: no run header, no aux
+  // record — two dependent scalar loads with a full wait each — no table addresses rebuilt from (pool offset, n), no run's scan with no
+  // records behind it.  Without it the walk below scans every run record by record, which is what it did before for these kernels
+  // whenever it met no pool head (`fast` false: an irregular ray; a scene whose boxes do not pay for a pool): its runs' aux records are
+  // not even read.  (A pool the plan does not claim would be scanned, not culled: the same image, slower; the flattener lays out none.)
+  constexpr bool PLANNED = RECTBOX && __is_same(P, lds_f4p);
+  if constexpr (PLANNED) {
+    int planned = (fast && ri0 == 0) ? plan->one : 0;
+    int n = plan->n, x_off = plan->x_off;
+    float bmax = plan->bmax;
+#ifdef __HIP_DEVICE_COMPILE__
+    // (every word of the plan is taken HERE, where the flag is needed anyway: read behind the branch, the compiler splits the plan's load and
+    // sinks the other words' part behind it — a scalar-cache round trip in front of the pool again)
+    asm volatile("" : "+s"(planned), "+s"(n), "+s"(x_off), "+s"(bmax));
+    // ((closest, hit) as they come in — hit_begin's constants — are written ONCE, here: left to itself the compiler writes them again on every
+    // path behind the branch, the pool's two early exits included)
+    asm volatile("" : "+v"(h.closest), "+v"(h.hit));
+#endif
+    ri1 = planned != 0 ? ri0 : ri1; // the pool covers every run: the walk below has none left (decided ahead of the pool, not behind it)
+    if (planned != 0) slab_pool<2>(blob, cblob, 0 /* the slab entries: the sign-resolved form reads the octant table instead */, x_off, x_off + 2 * n, n, bmax, c, h);
+  }
   for (int ri = ri0; ri < ri1; ++ri) {
 #ifdef PT_STAMPS_RUNS /* diagnostic build: cycles per run of the list (wave leader's clock), g_runs[min(ri, 15)] */
     const unsigned long long run_t0 = __builtin_amdgcn_s_memtime();
@@ -2327,7 +2372,10 @@ __device__ __forceinline__ void hit_world_range(P blob, cst_f4p cblob, int ri0, 
 #ifdef PT_ABLATE_TAIL /* measurement-only build (a WRONG image): what would the runs behind the first cost if they were free? */
     if (ri > 0) continue;
 #endif
-    if constexpr (RECTBOX) {
+    if constexpr (PLANNED) {
+      static_assert(!IMG, "scenes of rects and boxes only have no image texture that tracks u, v");
+      hit_records_rectbox(blob + off, kind, as_i(runf.z), off, c, fast, h);
+    } else if constexpr (RECTBOX) {
       // every run is a rect or a box run and carries the pool's aux record; the pool and the run's own scan one after the other, each
       // under its own guard (hit_records_rectbox says why), the scan with no records where the pool has covered the run
       static_assert(!IMG, "scenes of rects and boxes only have no image texture that tracks u, v");
@@ -2337,7 +2385,9 @@ __device__ __forceinline__ void hit_world_range(P blob, cst_f4p cblob, int ri0, 
       asm volatile("" : "+s"(span));
 #endif
       if (span != 0) { // head of a slab pool: the pool covers this run and the next span - 1
-        slab_pool<2>(blob, cblob, as_i(aux.z), as_i(aux.w), aux.x, c, h);
+        int x_off, oct_off;
+        pool_tables(as_i(aux.z), as_i(aux.w), x_off, oct_off);
+        slab_pool<2>(blob, cblob, as_i(aux.z), x_off, oct_off, as_i(aux.w), aux.x, c, h);
         ri += span - 1;
       }
       hit_records_rectbox(blob + off, kind, span != 0 ? 0 : as_i(runf.z), off, c, fast, h);
@@ -2346,7 +2396,9 @@ __device__ __forceinline__ void hit_world_range(P blob, cst_f4p cblob, int ri0, 
       if (fast && (kind == DK_RECT || kind == DK_BOX)) { // head of a slab pool: the pool covers this run and the next span - 1
         const f4 aux = cblob[off - 1];                   // (largest |coordinate|, span, pool offset, entries)
         if (as_i(aux.y) != 0) {
-          slab_pool<GRID == 2 ? 0 : 1>(blob, cblob, as_i(aux.z), as_i(aux.w), aux.x, c, h);
+          int x_off, oct_off;
+          pool_tables(as_i(aux.z), as_i(aux.w), x_off, oct_off);
+          slab_pool<GRID == 2 ? 0 : 1>(blob, cblob, as_i(aux.z), x_off, oct_off, as_i(aux.w), aux.x, c, h);
           ri += as_i(aux.y) - 1;
           continue;
         }
@@ -2359,9 +2411,9 @@ __device__ __forceinline__ void hit_world_range(P blob, cst_f4p cblob, int ri0, 
 }
 template <bool IMG, bool BADOUEL = false, int GRID = 1, bool TRIPOOL = false, bool RECTBOX = false, typename P>
 __device__ __forceinline__ void hit_world(P blob, cst_f4p cblob, int n_runs, const RayCtx& c, bool fast, uint32_t& rng, HitState& h, const f4* pool = nullptr,
-                                          const TriPrimCtx* pc = nullptr) {
+                                          const TriPrimCtx* pc = nullptr, const PoolPlan* plan = nullptr) {
   hit_begin(h);
-  hit_world_range<IMG, BADOUEL, GRID, TRIPOOL, RECTBOX, false>(blob, cblob, 0, n_runs, c, fast, rng, h, pool, nullptr, pc);
+  hit_world_range<IMG, BADOUEL, GRID, TRIPOOL, RECTBOX, false>(blob, cblob, 0, n_runs, c, fast, rng, h, pool, nullptr, pc, plan);
 }
 
 // Wave-uniform switch: the straight-line rect/box path is used only when every live lane's ray is regular.

@@ -96,6 +96,9 @@ constexpr unsigned kQueueRing = 256;        // launches in flight on one scene m
 // The kernels' only argument.  Every member starts "off": a launcher writes only what its launch uses.
 struct KArgs {
   Cam cam = {};
+  // Behind the camera, and read like it — from the kernarg segment, once per bounce, where the bounce has latency to hide (render_kernel):
+  // the one slab pool of a rect / box-only scene as launch constants (pt_device.hpp: PoolPlan; scene_pool_plan, pass_pool_plan).  one = 0: no such scene.
+  PoolPlan plan = {};
   const f4* blob = nullptr;
   const f4* mats = nullptr;
   const f4* pool = nullptr;    // tables of the triangle pools (pt_flatten.hpp: put_tri_pool); NULL when the scene has none
@@ -640,11 +643,29 @@ void render_kernel(KArgs a) {
         const CoopScene cs{a.n_runs, a.coop_prefix};
         hit_world_lds<IMG>((lds_f4p)smem, (cst_f4p)a.blob, cs, L.ray, L.rng, L.live, true, a.fast_ok != 0, L.wide, h);
       } else {
+        // (rect / box-only scenes) the pool plan: ONE load from the kernarg segment per bounce, requested ahead of the ray context's
+        // reciprocals, which hide it; through an opaque pointer, like the camera in lane_regenerate and for its reason — eight more
+        // SGPRs held across the whole loop are what the allocator parks in VGPR lanes
+        PoolPlan plan;
+        if constexpr ((MATS & MATS_RECTBOX_ONLY) != 0) {
+          static_assert(offsetof(KArgs, plan) == sizeof(Cam), "the pool plan rides behind the camera");
+#ifdef __HIP_DEVICE_COMPILE__
+          unsigned long long kp = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
+          asm volatile("" : "+s"(kp));
+          // (as ONE vector of the four words the pool needs: member by member it is three loads; all eight, and the allocator reuses the
+          // registers of the words nobody reads while the load is in flight — a full wait a few instructions behind it)
+          typedef int i4v __attribute__((ext_vector_type(4)));
+          const i4v w = *(const __attribute__((address_space(4))) i4v*)(kp + offsetof(KArgs, plan));
+          plan.one = w[0]; plan.n = w[1]; plan.bmax = __int_as_float(w[2]); plan.x_off = w[3];
+#else
+          plan = a.plan;
+#endif
+        }
         RayCtx c = make_ctx(L.ray, a.fast_ok != 0);
         c.live = L.live;
         const bool fast = wave_all_regular(c, L.live);
         regular = fast;
-        hit_world<IMG, BADOUEL, GRID, false, (MATS & MATS_RECTBOX_ONLY) != 0>((lds_f4p)smem, (cst_f4p)a.blob, a.n_runs, c, fast, L.rng, h);
+        hit_world<IMG, BADOUEL, GRID, false, (MATS & MATS_RECTBOX_ONLY) != 0>((lds_f4p)smem, (cst_f4p)a.blob, a.n_runs, c, fast, L.rng, h, nullptr, nullptr, &plan);
       }
 #ifdef PT_STAMPS
       asm volatile("" ::"v"(h.closest), "v"(h.hit));
@@ -1997,6 +2018,8 @@ struct PtScene {
   bool pools_need_scalar = false; // the scene has slab pools WITHOUT octant tables (ptf::flatten): only the scalar-cache kernels scan such pools
   bool rectbox_only = false;   // every hittable is a rect or a box (kernels compiled with MATS_RECTBOX_ONLY: resolve_hit)
   bool mats_simple = false;    // every material is lambertian or lightsource over a solid texture (kernels compiled with MATS_LAMB_LIGHT_SOLID)
+  PoolPlan pool_plan;          // what the flattened scene allows (scene_pool_plan); a pass's kernel gets pass_pool_plan's view of it
+  mutable PoolPlan last_pool_plan; // ... and what the last frame pass was given (pt_debug_last_pool_plan)
   size_t blob_bytes = 0, atlas_bytes = 0;
   int num_cus = 256;
   size_t lds_per_block = 64 * 1024; // hipDeviceProp_t::sharedMemPerBlock (gfx950: 160 KB; the Makefile's ARCH=gfx942: 64 KB)
@@ -2206,6 +2229,79 @@ Variant choose_variant(const PtScene* s, const PtRenderParams* p, int local_tile
   }
 }
 
+// ---- the pool plan (pt_device.hpp: PoolPlan; hit_world_range, PLANNED) ----------------------------------------------------
+// What a flattened scene allows, read from its blob the way the kernel's walk reads it: run 0's header, the aux record in front of its
+// first record, and from (pool offset, n) the tables' places as slab_pool's callers compute them.  `one` is set where run 0 heads a pool
+// that spans EVERY run of the list and carries an octant table; a list with a run outside the pool, with more than one pool, or whose
+// pools have no tables (the blob beyond the LDS image) leaves it clear.  Which kernel runs, and under which flags, is pass_pool_plan's.
+PoolPlan scene_pool_plan(const ptf::Flat& flat) {
+  PoolPlan pl;
+  if (flat.n_runs < 1 || flat.blob.size() <= (size_t)flat.n_runs) return pl;
+  auto word = [](float f) { int32_t v; std::memcpy(&v, &f, 4); return v; };
+  const ptf::F4& run = flat.blob[0];
+  pl.kind = word(run.x); pl.off = word(run.y); pl.count = word(run.z);
+  if ((pl.kind != DK_RECT && pl.kind != DK_BOX) || pl.off < 1 || (size_t)pl.off > flat.blob.size()) return pl;
+  const ptf::F4& aux = flat.blob[(size_t)pl.off - 1]; // (largest |coordinate|, span, pool offset, entries)
+  const int span = word(aux.y);
+  pl.bmax = aux.x; pl.pool_off = word(aux.z); pl.n = word(aux.w);
+  pool_tables(pl.pool_off, pl.n, pl.x_off, pl.oct_off);
+  pl.one = (span == flat.n_runs && pl.n > 0 && flat.pool_octants && flat.fast_ok) ? 1 : 0;
+  return pl;
+}
+
+// The plan one pass's kernel is given: the scene's, claimed only for a kernel that reads it — render_kernel over the LDS image, compiled
+// for rect / box-only scenes (hit_world_range: PLANNED) — and only where rays may be regular at all (PT_FLAG_NO_FASTDIV: none is, every
+// wave walks the list).  Every other kernel walks as it always did and never looks at the plan.
+PoolPlan pass_pool_plan(const PtScene* s, const PtRenderParams* p, const Variant& v) {
+  PoolPlan pl = s->pool_plan;
+  const bool reads_plan = v.tag.w[0] == KFAM_RENDER && v.tag.w[2] /* lds */ && (v.tag.w[10] & MATS_RECTBOX_ONLY) != 0;
+  if (!reads_plan || !s->fast_ok || (p->flags & PT_FLAG_NO_FASTDIV)) pl.one = 0;
+  return pl;
+}
+
+// What a scene's launches decide from — plain facts of the description and of its flattened form, no device: pt_scene_create_tuned
+// fills the PtScene it uploads with them, pt_debug_pool_plan a PtScene that never sees a device.
+void set_scene_facts(PtScene* s, const PtSceneDesc* desc, const PtTuning& tun, const ptf::Flat& flat) {
+  s->knobs = Knobs(tun);
+  s->n_runs = flat.n_runs;
+  s->blob_f4 = (int)flat.blob.size();
+  s->has_image = flat.has_image;
+  s->fast_ok = flat.fast_ok;
+  s->coop_ok = flat.coop_ok && !flat.has_badouel; // the cooperative scans do not carry the Badouel loop
+  s->has_badouel = flat.has_badouel;
+  s->track_uv = flat.has_image && !flat.coop_ok;
+  s->coop_prefix = flat.coop_prefix;
+  s->n_hittables = desc->n_hittables;
+  for (int i = 0; i < desc->n_hittables; i++) {
+    switch (desc->hittables[i].kind) {
+      case PT_HIT_SPHERE: s->traversal_cost += 22.0f; break;
+      case PT_HIT_TRIANGLE: s->traversal_cost += 35.0f; break;
+      case PT_HIT_BOX: s->traversal_cost += 120.0f; break;
+      case PT_HIT_CONSTANT_MEDIUM: s->traversal_cost += 300.0f; break;
+      default: s->traversal_cost += 20.0f; break;
+    }
+  }
+  s->grid_spheres = flat.grid_spheres;
+  s->pools_need_scalar = flat.pooled > 0 && !flat.pool_octants;
+  s->rectbox_only = desc->n_hittables > 0 && !s->knobs.generic_materials;
+#ifdef PT_NO_RECTBOX /* A/B build */
+  s->rectbox_only = false;
+#endif
+  for (int i = 0; i < desc->n_hittables && s->rectbox_only; i++) {
+    const int k = desc->hittables[i].kind;
+    if (k != PT_HIT_XY_RECT && k != PT_HIT_XZ_RECT && k != PT_HIT_YZ_RECT && k != PT_HIT_BOX) s->rectbox_only = false;
+  }
+  s->mats_simple = desc->n_materials > 0 && !s->knobs.generic_materials; // PtTuning.generic_materials: A/B knob (generic shading)
+  for (int i = 0; i < desc->n_materials && s->mats_simple; i++) {
+    const PtMaterial& m = desc->materials[i];
+    if ((m.kind != PT_MAT_LAMBERTIAN && m.kind != PT_MAT_LIGHTSOURCE) || desc->textures[m.texture].kind != PT_TEX_SOLID) s->mats_simple = false;
+  }
+  s->tri_pooled = flat.has_badouel ? 0 : flat.tri_pooled; // (scenes with Badouel-strategy triangles keep the round-2 kernels)
+  s->blob_bytes = flat.blob.size() * 16;
+  s->mats_f4 = (int)flat.mats.size();
+  s->pool_plan = scene_pool_plan(flat);
+}
+
 } // namespace
 
 extern "C" {
@@ -2346,7 +2442,6 @@ int pt_scene_create_tuned(const PtSceneDesc* desc, const PtTuning* tuning, PtSce
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(PT_ERR_NO_DEVICE, "no HIP device visible");
   std::unique_ptr<PtScene> owner(new PtScene()); // (an early return frees what was allocated so far: every buffer is a DevBuf)
   PtScene* const s = owner.get();
-  s->knobs = Knobs(tun);
   PT_HIP(hipGetDevice(&s->device));
   {
     hipDeviceProp_t prop;
@@ -2354,40 +2449,7 @@ int pt_scene_create_tuned(const PtSceneDesc* desc, const PtTuning* tuning, PtSce
     s->num_cus = prop.multiProcessorCount;
     s->lds_per_block = prop.sharedMemPerBlock;
   }
-  s->n_runs = flat.n_runs;
-  s->blob_f4 = (int)flat.blob.size();
-  s->has_image = flat.has_image;
-  s->fast_ok = flat.fast_ok;
-  s->coop_ok = flat.coop_ok && !flat.has_badouel; // the cooperative scans do not carry the Badouel loop
-  s->has_badouel = flat.has_badouel;
-  s->track_uv = flat.has_image && !flat.coop_ok;
-  s->coop_prefix = flat.coop_prefix;
-  s->n_hittables = desc->n_hittables;
-  for (int i = 0; i < desc->n_hittables; i++) {
-    switch (desc->hittables[i].kind) {
-      case PT_HIT_SPHERE: s->traversal_cost += 22.0f; break;
-      case PT_HIT_TRIANGLE: s->traversal_cost += 35.0f; break;
-      case PT_HIT_BOX: s->traversal_cost += 120.0f; break;
-      case PT_HIT_CONSTANT_MEDIUM: s->traversal_cost += 300.0f; break;
-      default: s->traversal_cost += 20.0f; break;
-    }
-  }
-  s->grid_spheres = flat.grid_spheres;
-  s->pools_need_scalar = flat.pooled > 0 && !flat.pool_octants;
-  s->rectbox_only = desc->n_hittables > 0 && !s->knobs.generic_materials;
-#ifdef PT_NO_RECTBOX /* A/B build */
-  s->rectbox_only = false;
-#endif
-  for (int i = 0; i < desc->n_hittables && s->rectbox_only; i++) {
-    const int k = desc->hittables[i].kind;
-    if (k != PT_HIT_XY_RECT && k != PT_HIT_XZ_RECT && k != PT_HIT_YZ_RECT && k != PT_HIT_BOX) s->rectbox_only = false;
-  }
-  s->mats_simple = desc->n_materials > 0 && !s->knobs.generic_materials; // PtTuning.generic_materials: A/B knob (generic shading)
-  for (int i = 0; i < desc->n_materials && s->mats_simple; i++) {
-    const PtMaterial& m = desc->materials[i];
-    if ((m.kind != PT_MAT_LAMBERTIAN && m.kind != PT_MAT_LIGHTSOURCE) || desc->textures[m.texture].kind != PT_TEX_SOLID) s->mats_simple = false;
-  }
-  s->tri_pooled = flat.has_badouel ? 0 : flat.tri_pooled; // (scenes with Badouel-strategy triangles keep the round-2 kernels)
+  set_scene_facts(s, desc, tun, flat);
   // The binned renderer serves scenes with ONE pooled run whose stale u, v need no tracking (pt_binned.hpp); PtTuning.tri_binned = 1 (measured: it does not pay yet — docs/EXPERIMENTS.md — so it is opt-in).
   if (s->tri_pooled > 0 && flat.tri_pool_runs == 1 && !s->track_uv && tun.tri_binned > 0) {
     s->binned = true;
@@ -2398,8 +2460,6 @@ int pt_scene_create_tuned(const PtSceneDesc* desc, const PtTuning* tuning, PtSce
     s->bin_keys = (int)keys;
     s->bin_base1 = flat.tri_maps > 0 ? 3 * flat.tri_map_res[0] * flat.tri_map_res[0] : 0;
   }
-  s->blob_bytes = flat.blob.size() * 16;
-  s->mats_f4 = (int)flat.mats.size();
   // one buffer: [blob records][material table] so a kernel can stage both with one contiguous copy
   const size_t blob_bytes = flat.blob.size() * 16, mats_bytes = flat.mats.size() * 16;
   PT_HIP(s->blob.alloc(flat.blob.size() + flat.mats.size()));
@@ -2845,6 +2905,7 @@ int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderParams* p
                                         std::to_string(cur) + " (hipSetDevice to the scene's device first)");
   std::lock_guard<std::mutex> lock(s->sched);
   s->last_kernels[0] = s->last_kernels[1] = KTag{}; // (a pass that does not run leaves family 0)
+  s->last_pool_plan = PoolPlan{};
   KArgs base;
   set_frame(base, s, cam, p);
   base.fb = fb;
@@ -2876,6 +2937,7 @@ int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderParams* p
   if (pv.rc) return pv.rc;
   const bool tri_pool = pv.tri_pool, use_grid = pv.use_grid, coop = pv.coop; // (the same in every pass)
   base.coop_prefix = pv.coop_prefix;
+  base.plan = pass_pool_plan(s, p, pv); // (the probe pass and the frame pass run pv's kernel; the fast mode's chunk pass sets its own)
   base.samples_total = p->samples;
   if (const char* e = std::getenv("PT_TILE_GROUP")) { const int g = std::atoi(e); if (g == 16 || g == 32) base.tile_group = g; } // (experiment)
   // default: whole tiles for the resident kernels (coherent primary rays), single pixels for the lock-step
@@ -2978,6 +3040,8 @@ int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderParams* p
     s->last_had_wide_phase = false;
     const Variant fv = choose_variant(s, p, local_tiles, true, frame.n_local_pixels);
     if (fv.rc) return fv.rc;
+    frame.plan = pass_pool_plan(s, p, fv);
+    s->last_pool_plan = frame.plan;
     // (what the probe pass of this call ran stays set for its chunk pass: run_pass)
     if (int rc = run_pass(s, p, fv, fv.chain_bound || (probed && pv.chain_bound), fv.queued_walk || (probed && pv.queued_walk),
                           (long long)local_tiles * chunks, frame, st))
@@ -2995,6 +3059,7 @@ int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderParams* p
   }
   if (scattered) set_scatter(frame, s->knobs.scatter_log);
   s->last_had_wide_phase = frame.n_split != nullptr;
+  s->last_pool_plan = frame.plan;
   return run_pass(s, p, pv, pv.chain_bound, pv.queued_walk, local_tiles, frame, st);
 }
 
@@ -4113,6 +4178,44 @@ int pt_debug_last_kernels(const PtScene* scene, int32_t out[24]) {
   std::lock_guard<std::mutex> lock(scene->sched);
   for (int pass = 0; pass < 2; pass++)
     for (int k = 0; k < 12; k++) out[12 * pass + k] = scene->last_kernels[pass].w[k];
+  return PT_OK;
+}
+
+static void pool_plan_words(const PoolPlan& pl, int32_t out[4]) { out[0] = pl.one; out[1] = pl.n; out[2] = pl.x_off; out[3] = pl.oct_off; }
+
+int pt_debug_last_pool_plan(const PtScene* scene, int32_t out[4]) {
+  if (!scene || !out) return fail(PT_ERR_INVALID_ARG, "pt_debug_last_pool_plan: NULL argument");
+  std::lock_guard<std::mutex> lock(scene->sched);
+  pool_plan_words(scene->last_pool_plan, out);
+  return PT_OK;
+}
+
+int pt_debug_pool_plan(const PtSceneDesc* desc, const PtTuning* tuning, const PtRenderParams* params, int32_t out[12]) {
+  if (!desc || !params || !out) return fail(PT_ERR_INVALID_ARG, "pt_debug_pool_plan: NULL argument");
+  if (int rc = check_params(params)) return rc;
+  PtTuning tun;
+  std::string err;
+  if (int rc = resolve_tuning(tuning, tun, err)) return fail(rc, err);
+  ptf::Flat flat;
+  if (int rc = flatten_tuned(desc, tun, flat, err)) return fail(rc, err);
+  PtScene s; // (never meets a device: facts only)
+  set_scene_facts(&s, desc, tun, flat);
+  PoolPlan pl = s.pool_plan;
+  pl.one = 0;
+  int32_t mats = 0, lds = 0;
+  // Only the headline family reads the plan, and choosing among its kernels asks the device nothing (no sphere grid: no occupancy query)
+  if (s.rectbox_only && s.mats_simple && s.grid_spheres == 0 && s.tri_pooled == 0 && !(params->flags & PT_FLAG_SINGLE_STREAM)) {
+    const int local_tiles = local_tiles_of(params);
+    const Variant v = choose_variant(&s, params, local_tiles, (params->flags & PT_FLAG_FAST_RNG) != 0, local_tiles * PT_TILE_PIXELS);
+    if (v.rc) return v.rc;
+    pl = pass_pool_plan(&s, params, v);
+    lds = v.tag.w[0] == KFAM_RENDER ? v.tag.w[2] : 0;
+    mats = v.tag.w[0] == KFAM_RENDER ? v.tag.w[10] : 0;
+  }
+  pool_plan_words(pl, out);
+  out[4] = pl.pool_off; std::memcpy(&out[5], &pl.bmax, 4);
+  out[6] = pl.kind; out[7] = pl.off; out[8] = pl.count;
+  out[9] = s.pool_plan.one; out[10] = lds; out[11] = mats;
   return PT_OK;
 }
 
