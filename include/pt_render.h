@@ -821,6 +821,119 @@ int pt_temporal_push(PtTemporal* state, const PtTemporalParams* params, const Pt
                      const float* normal, const int32_t* id, const float* variance_in, float* out_color, float* out_variance,
                      float* out_history, void* stream);
 
+/* ---- display stage: histogram auto-exposure and filmic tone curves ---------------------------------------------------------------------
+ * Added without an ABI version change, like PtAccum: a caller detects the feature by the presence of these symbols.  Nothing above changes:
+ * pt_tonemap_rgb8 and pt_accum_tonemap_rgb8 stay the reference's output stage.
+ *
+ * The end of the interactive chain render -> guides -> temporal -> filter -> DISPLAY: the frame is metered with a luminance histogram on the
+ * device, an exposure is solved from it (with eye adaptation across the frames of a sequence), and exposure, a tone curve and the existing
+ * quantiser are applied — without a round trip to the host between metering and applying.
+ *
+ * Scope.  pt_denoise's — whole frames only, no scene involved: color and linear_out are [height][width][3], y = 0 the bottom row (the layout
+ * pt_render writes with shard_count = 1); rgb8_out is [height][width][3] bytes, row 0 = top (pt_tonemap_rgb8's).  pt_display_meter,
+ * pt_display_set_exposure, pt_display_reset and pt_display_apply are asynchronous on `stream` and allocate nothing (pt_display_create is the
+ * only allocation); calls on one PtDisplay are stream-ordered like renders of one PtScene.
+ *
+ * DEFINITION.  Every float value is IEEE binary32 unless binary64 is named, every operation below is rounded once, nothing is fused, the
+ * order of operations is the one written, and divisions are the correctly rounded ones.
+ *
+ * Luminance (Rec. 709).  Y = (0.2126f * R + 0.7152f * G) + 0.0722f * B.
+ *
+ * Metering histogram.  256 uint32 bins, 8 per octave over the 32 octaves [2^-16, 2^16), keyed on the bit pattern of Y (no logarithm):
+ *   a pixel whose Y is NaN, +-inf, negative or +-0 is not binned: it is counted in `rejected`;
+ *   otherwise bin = clamp((int)(bits(Y) >> 20) - ((127 - 16) << 3), 0, 255)  (denormals and Y < 2^-16: bin 0; Y >= 2^16: bin 255).
+ * Only the pixels of the metering rectangle [x0, x1) x [y0, y1) are read (frame coordinates: y = 0 the bottom row); PtDisplayParams' rect of
+ * four zeros means the whole frame.  Counts are integers: the histogram does not depend on the order the hardware adds them in.
+ *
+ * Solve (integers and one binary64 division).  N = the sum of the bins; lo_n = (uint64)N * lo_permille / 1000, hi_n likewise from
+ * hi_permille.  Walking the bins in ascending order, bin b holds the ranks [r_b, r_b + count_b), r_b = the sum of the bins below it, and
+ * contributes c_b = the number of its ranks inside [lo_n, hi_n).  Its value, in 1/65536 octave, is the log2 of the geometric centre of
+ * the bin:  value_b = 65536 * ((b >> 3) - 16) + LOGC[b & 7],  LOGC[j] = round(65536 * log2(1 + (2j + 1) / 16)) = PT_DISPLAY_LOGC below.
+ *   S = sum of c_b * value_b (int64; |S| < 2^53 since N <= 2^31),  C = sum of c_b
+ *   C == 0 (nothing binned, or an empty band): the exposure stays as it is.  Otherwise
+ *   t   = (float)(((double)S / (double)C) * 0x1p-16)                     the mean log2 luminance of the band
+ *   e_t = fminf(fmaxf((PT_DISPLAY_LOG2_KEY - t) + ev_bias, ev_min), ev_max)   the target exposure in stops
+ *
+ * Adaptation.  The first metering since create or reset that solves (C > 0) sets e = e_t.  Later ones set e = e + (e_t - e) * a, with
+ * a = adapt_up when e_t > e, else adapt_down (1 = instant).  pt_display_set_exposure sets e = fminf(fmaxf(ev, -32), 32) and counts as a
+ * first metering: the next one adapts from it.  e lives in device memory; nothing on the way to pt_display_apply reads it on the host.
+ *
+ * Scale.  k = ceilf(e);  scale = ldexpf(pt_exp_neg((k - e) * 0x1.62e430p-1f), (int)k)  — 2^e: k - e is exact and lies in [0, 1), inside
+ * pt_exp_neg's domain (pt_denoise's function, verbatim); an integer e gives exactly 2^e and e == 0 exactly 1.
+ *
+ * Curve, per channel.  x = c * scale;  if !(x >= 0): x = +0 (NaN and negative values);  if x > 0x1p20f: x = 0x1p20f;  then
+ *   PT_TONE_REFERENCE  y = x
+ *   PT_TONE_REINHARD   y = (x * (1.0f + x * iw2)) / (1.0f + x),  iw2 = 1.0f / (white * white) computed once on the host (extended
+ *                      Reinhard: `white` is the input that maps to 1)
+ *   PT_TONE_ACES       y = (x * (2.51f * x + 0.03f)) / (x * (2.43f * x + 0.59f) + 0.14f)       (Narkowicz's fit of the ACES film curve)
+ *
+ * Output.  rgb8_out = pt_tonemap_rgb8's quantiser of y (sqrt, clamp to [0, 0.999], * 256, truncate, int(NaN) = 0) with its vertical flip;
+ * linear_out = y, not flipped, in the frame buffer's layout.  The transfer stays the reference's gamma 2.  PT_TONE_REFERENCE at e = 0 gives
+ * pt_tonemap_rgb8's bytes exactly, for every input.  With state == NULL pt_display_apply takes e = fminf(fmaxf(ev_bias, -32), 32): the
+ * manual, stateless use.
+ *
+ * Rejected (PT_ERR_INVALID_ARG, on the host, before any device call and before the state is read): a NULL params, color or (pt_display_meter,
+ * pt_display_set_exposure, pt_display_reset, pt_display_exposure, pt_display_histogram) state; both outputs NULL; a struct_size other than
+ * sizeof(PtDisplayParams); width or height <= 0 or more than 2^31 pixels; an unknown tone; flags (none is defined);
+ * lo_permille >= hi_permille or either outside [0, 1000]; an adaptation rate outside (0, 1]; ev_min > ev_max or either outside [-32, 32];
+ * an ev_bias that is not finite, an ev that is NaN; a `white` whose iw2 is not a finite binary32 number > 0; a rectangle that is not all zeros and is
+ * empty or leaves the frame; rgb8_out overlapping color or linear_out; linear_out overlapping color without being color.                  */
+#define PT_TONE_REFERENCE 0
+#define PT_TONE_REINHARD 1
+#define PT_TONE_ACES 2
+#define PT_DISPLAY_LOG2_KEY (-0x1.3ca9c6p+1f) /* log2(0.18): the band's geometric mean is exposed to middle grey */
+#define PT_DISPLAY_LOGC {5732, 16248, 25711, 34312, 42196, 49472, 56229, 62534}
+/* The defaults (pt_display_params_init); DESIGN.md gives the reason for each: the ACES curve; no bias; the full +-16 stop range; the band
+ * from the 40th to the 95th percentile (shadows do not drive the exposure, the brightest 5 % — emitters — do not either); instant
+ * adaptation (a still image has no history); white 4 (Reinhard only). */
+#define PT_DISPLAY_DEFAULT_TONE PT_TONE_ACES
+#define PT_DISPLAY_DEFAULT_EV_BIAS 0.0f
+#define PT_DISPLAY_DEFAULT_EV_MIN -16.0f
+#define PT_DISPLAY_DEFAULT_EV_MAX 16.0f
+#define PT_DISPLAY_DEFAULT_LO_PERMILLE 400
+#define PT_DISPLAY_DEFAULT_HI_PERMILLE 950
+#define PT_DISPLAY_DEFAULT_ADAPT_UP 1.0f
+#define PT_DISPLAY_DEFAULT_ADAPT_DOWN 1.0f
+#define PT_DISPLAY_DEFAULT_WHITE 4.0f
+typedef struct PtDisplay PtDisplay; /* device-resident metering state: the histogram, `rejected`, e, scale */
+typedef struct PtDisplayParams {
+  int32_t struct_size; /* sizeof(PtDisplayParams) of the caller's header */
+  int32_t tone;        /* PT_TONE_* */
+  uint32_t flags;      /* none defined: 0 */
+  float ev_bias, ev_min, ev_max;
+  int32_t lo_permille, hi_permille;
+  float adapt_up, adapt_down;
+  float white;
+  int32_t rect_x0, rect_y0, rect_x1, rect_y1; /* the metering rectangle; four zeros: the whole frame */
+  int32_t reserved;
+} PtDisplayParams;
+/* Host function, no GPU: struct_size + the defaults above. */
+void pt_display_params_init(PtDisplayParams* params);
+/* Allocates the state on the current device (the only allocation): no exposure yet (e = 0, scale = 1), empty histogram. */
+int pt_display_create(PtDisplay** out);
+void pt_display_destroy(PtDisplay* state);
+/* Back to the state after create: the next metering is instant. */
+int pt_display_reset(PtDisplay* state, void* stream);
+/* Meterings since create / reset (host-side count; -1 for NULL). */
+int32_t pt_display_frames(const PtDisplay* state);
+/* Histogram, solve and adaptation, all on `stream`. */
+int pt_display_meter(PtDisplay* state, const PtDisplayParams* params, const float* color, int32_t width, int32_t height, void* stream);
+/* A manual exposure, in stops. */
+int pt_display_set_exposure(PtDisplay* state, float ev, void* stream);
+/* Exposure, curve and quantiser in one pass; either output may be NULL, state may be NULL (e = ev_bias), linear_out may be color. */
+int pt_display_apply(const PtDisplay* state, const PtDisplayParams* params, const float* color, int32_t width, int32_t height,
+                     uint8_t* rgb8_out, float* linear_out, void* stream);
+/* For inspection and tests; both SYNCHRONISE `stream`: the exposure e, and the last metering's 256 bins followed by `rejected`. */
+int pt_display_exposure(const PtDisplay* state, float* ev_host, void* stream);
+int pt_display_histogram(const PtDisplay* state, uint32_t host[257], void* stream);
+/* The launch geometry of the LAST pt_display_meter and pt_display_apply of this process: out[0] = the metering kernel's workgroups,
+ * out[1] = its threads per workgroup, out[2] = the trips a thread makes through its metering loop, out[3] = the pixels it takes per trip
+ * (4, as three 16-byte loads, where the metered pixels are one contiguous 16-byte aligned range — a whole frame, a rectangle as wide as
+ * the frame —, else 1: a frame of more than out[0] * out[1] * out[3] pixels takes the loop more than once), out[4] / out[5] = the apply
+ * kernel's grid (x, y), out[6] = the values a thread of it takes per row (4 where the width is a multiple of 4 and the planes are 16-byte
+ * aligned, rgb8_out 4-byte; else 1), out[7] = its tone + 1; zeros before the first call.  The bits do not depend on any of it.  For tests. */
+int pt_debug_last_display(int32_t out[8]);
+
 /* ---- function-level probes (parity tests call these; not used by render) ---- */
 
 /* One iteration of the bounce loop render.hpp:58-89 per record: hit_world,

@@ -27,6 +27,12 @@ adaptive accumulator continued from frame to frame (no frame repeats another's r
 camera moves (render.TemporalAccumulator) — and frame_<f>.png is the accumulated frame; with --temporal --denoise-variance it is that
 frame filtered by the variance-guided filter, fed the temporal variance.  out.png is byte-identical to the one written without the
 options.
+With --display-out FILE the frame also goes through the display stage (render.Display; include/pt_render.h: PtDisplay) into FILE: --tone
+picks the curve (reference, reinhard, aces; default aces), --exposure EV is a manual exposure in stops, and with --auto-exposure the
+exposure is solved on the device from the frame's luminance histogram (--exposure is then a bias on it).  With --frames-dir and any of
+these options the frame PNGs go through the display stage as well, metered in order: with --auto-exposure the exposure adapts from frame to
+frame at the rates --adapt-up and --adapt-down (1 = instant, the default).  out.png is byte-identical to the one written without the
+options.
 """
 import argparse
 import os
@@ -51,19 +57,33 @@ def write_aovs(aov_dir, planes) -> None:
     np.savez(os.path.join(aov_dir, "aov.npz"), **{k: v.cpu().numpy() for k, v in planes.items()})
 
 
+def make_shower(a):
+    """The output stage of a frame -> uint8 image: the reference's (render.tonemap_rgb8) without display options; with them the display
+    stage — a manual exposure, or with --auto-exposure one Display whose exposure adapts over the frames it is shown in order."""
+    if not a.display:
+        return R.tonemap_rgb8
+    ev = 0.0 if a.exposure is None else a.exposure
+    if not a.auto_exposure:
+        return lambda fb: R.display(fb, a.tone, ev)
+    disp = R.Display(a.tone, ev_bias=ev, adapt_up=1.0 if a.adapt_up is None else a.adapt_up, adapt_down=1.0 if a.adapt_down is None else a.adapt_down)
+    return lambda fb: disp.meter(fb).apply(fb)
+
+
 def write_frames(a, packed, cam_args, move, denoise_kw) -> None:
     """The camera path of --frames: DIR/frame_<f>.png, frame f looking from look_from + f x move.  Plain: render() per frame.  --temporal:
-    render_temporal's accumulated frame, or with --denoise-variance that frame through the variance-guided filter."""
+    render_temporal's accumulated frame, or with --denoise-variance that frame through the variance-guided filter.  Each frame leaves
+    through make_shower's output stage, in order."""
+    show = make_shower(a)
     os.makedirs(a.frames_dir, exist_ok=True)
     cams = [scenes.make_camera(dict(cam_args, look_from=tuple(float(p) + f * d for p, d in zip(cam_args["look_from"], move))), a.width, a.height)
             for f in range(a.frames)]
     if not a.temporal:
         for f, c in enumerate(cams):
-            write_png(os.path.join(a.frames_dir, f"frame_{f}.png"), R.tonemap_rgb8(R.render(a.width, a.height, a.spp, packed, c, a.depth)).cpu().numpy())
+            write_png(os.path.join(a.frames_dir, f"frame_{f}.png"), show(R.render(a.width, a.height, a.spp, packed, c, a.depth)).cpu().numpy())
         return
     for f, frame in enumerate(R.render_temporal(a.width, a.height, a.spp, packed, cams, a.depth, aov_spp=a.aov_spp, denoise=a.denoise_variance,
                                                 denoise_kw=denoise_kw)):
-        write_png(os.path.join(a.frames_dir, f"frame_{f}.png"), R.tonemap_rgb8(frame["filtered" if a.denoise_variance else "temporal"]).cpu().numpy())
+        write_png(os.path.join(a.frames_dir, f"frame_{f}.png"), show(frame["filtered" if a.denoise_variance else "temporal"]).cpu().numpy())
 
 
 def main() -> None:
@@ -105,7 +125,25 @@ def main() -> None:
     ap.add_argument("--frames-dir", default=None, metavar="DIR", help="camera path: where frame_<f>.png goes")
     ap.add_argument("--temporal", action="store_true",
                     help="camera path: carry each frame's history across the camera moves (temporal reprojection)")
+    ap.add_argument("--tone", default=None, choices=["reference", "reinhard", "aces"], help="display stage: the tone curve (default aces)")
+    ap.add_argument("--exposure", type=float, default=None, metavar="EV",
+                    help="display stage: exposure in stops (manual; with --auto-exposure a bias on the metered exposure)")
+    ap.add_argument("--auto-exposure", action="store_true", help="display stage: solve the exposure from the frame's luminance histogram")
+    ap.add_argument("--adapt-up", type=float, default=None, metavar="A", help="auto-exposure over --frames: rate towards a higher exposure, in (0, 1]")
+    ap.add_argument("--adapt-down", type=float, default=None, metavar="A", help="auto-exposure over --frames: rate towards a lower exposure, in (0, 1]")
+    ap.add_argument("--display-out", default=None, metavar="FILE", help="also write the frame through the display stage (exposure + tone curve)")
     a = ap.parse_args()
+    a.display = a.tone is not None or a.exposure is not None or a.auto_exposure or a.adapt_up is not None or a.adapt_down is not None
+    if a.display and a.display_out is None and a.frames_dir is None:
+        ap.error("--tone, --exposure, --auto-exposure, --adapt-up and --adapt-down need --display-out or --frames-dir")
+    a.display = a.display or a.display_out is not None
+    a.tone = "aces" if a.tone is None else a.tone
+    if (a.adapt_up is not None or a.adapt_down is not None) and not a.auto_exposure:
+        ap.error("--adapt-up and --adapt-down need --auto-exposure")
+    if any(v is not None and not 0.0 < v <= 1.0 for v in (a.adapt_up, a.adapt_down)):
+        ap.error("--adapt-up and --adapt-down must be in (0, 1]")
+    if a.exposure is not None and not -32.0 <= a.exposure <= 32.0:
+        ap.error("--exposure must be in -32 .. 32")
     if a.frames is None and (a.move is not None or a.frames_dir is not None or a.temporal):
         ap.error("--move, --frames-dir and --temporal need --frames")
     move = (0.0, 0.0, 0.0)
@@ -201,7 +239,7 @@ def main() -> None:
             torch.cuda.synchronize()
             ms += e0.elapsed_time(e1)
             write_png(os.path.join(a.preview_dir, f"preview_{acc.samples}.png"), rgb8.cpu().numpy())
-        fb = acc.resolve() if a.denoise_out else None
+        fb = acc.resolve() if a.denoise_out or a.display_out else None
         acc.close()
     else:
         fb, ms = R.render(a.width, a.height, a.spp, packed, cam, a.depth, timed=True)
@@ -214,6 +252,8 @@ def main() -> None:
     if a.denoise_out:
         filtered = R.denoise_variance(fb, variance[0], **planes, **denoise_kw) if a.denoise_variance else R.denoise(fb, **planes, **denoise_kw)
         write_png(a.denoise_out, R.tonemap_rgb8(filtered).cpu().numpy())
+    if a.display_out:
+        write_png(a.display_out, make_shower(a)(fb).cpu().numpy())
     if a.frames is not None:
         write_frames(a, packed, cam_args, move, denoise_kw)
     if mean_spp is not None:

@@ -150,6 +150,14 @@ class PtTemporalParams(C.Structure):
                 ("flags", C.c_uint32), ("reserved", C.c_int32 * 3)]
 
 
+class PtDisplayParams(C.Structure):
+    """include/pt_render.h PtDisplayParams: the display stage's parameters (pt_display_meter, pt_display_apply)."""
+    _fields_ = [("struct_size", C.c_int32), ("tone", C.c_int32), ("flags", C.c_uint32), ("ev_bias", C.c_float), ("ev_min", C.c_float),
+                ("ev_max", C.c_float), ("lo_permille", C.c_int32), ("hi_permille", C.c_int32), ("adapt_up", C.c_float),
+                ("adapt_down", C.c_float), ("white", C.c_float), ("rect_x0", C.c_int32), ("rect_y0", C.c_int32), ("rect_x1", C.c_int32),
+                ("rect_y1", C.c_int32), ("reserved", C.c_int32)]
+
+
 assert C.sizeof(PtHittable) == 64 and C.sizeof(PtMaterial) == 32 and C.sizeof(PtTexture) == 48
 assert C.sizeof(PtCamera) == 96 and C.sizeof(PtRenderParams) == 32
 
@@ -240,6 +248,18 @@ SIGNATURES = {
     "pt_temporal_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
     "pt_temporal_frames": (C.c_int32, [C.c_void_p]),
     "pt_temporal_push": (C.c_int, [C.c_void_p, C.POINTER(PtTemporalParams), C.POINTER(PtCamera)] + [C.c_void_p] * 9),
+    # the display stage (histogram auto-exposure, tone curves): likewise optional (DISPLAY_SYMBOLS)
+    "pt_display_params_init": (None, [C.POINTER(PtDisplayParams)]),
+    "pt_display_create": (C.c_int, [C.POINTER(C.c_void_p)]),
+    "pt_display_destroy": (None, [C.c_void_p]),
+    "pt_display_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pt_display_frames": (C.c_int32, [C.c_void_p]),
+    "pt_display_meter": (C.c_int, [C.c_void_p, C.POINTER(PtDisplayParams), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "pt_display_set_exposure": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p]),
+    "pt_display_apply": (C.c_int, [C.c_void_p, C.POINTER(PtDisplayParams), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pt_display_exposure": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_void_p]),
+    "pt_display_histogram": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]),
+    "pt_debug_last_display": (C.c_int, [C.POINTER(C.c_int32)]),
     # the launcher's geometry rules for one pass, host-only: likewise optional (PLAN_SYMBOLS)
     "pt_debug_plan_pass": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     # the one-pool plan of rect / box-only scenes, as the last frame pass got it and as derived without a device: likewise optional (POOL_PLAN_SYMBOLS)
@@ -296,6 +316,18 @@ TEMPORAL_SYMBOLS = frozenset({"pt_adaptive_next_frame", "pt_temporal_params_init
 # the header's PT_TEMPORAL_DEFAULT_* (pt_temporal_params_init)
 PT_TEMPORAL_DEFAULT_ALPHA, PT_TEMPORAL_DEFAULT_TOL_DEPTH, PT_TEMPORAL_DEFAULT_TOL_NORMAL = 0.1, 0.1, 0.5
 
+# the display stage (include/pt_render.h: pt_display_*); has_display() tells whether the loaded library has it
+DISPLAY_SYMBOLS = frozenset({"pt_display_params_init", "pt_display_create", "pt_display_destroy", "pt_display_reset", "pt_display_frames",
+                             "pt_display_meter", "pt_display_set_exposure", "pt_display_apply", "pt_display_exposure", "pt_display_histogram",
+                             "pt_debug_last_display"})
+PT_TONE_REFERENCE, PT_TONE_REINHARD, PT_TONE_ACES = 0, 1, 2
+TONES = {"reference": PT_TONE_REFERENCE, "reinhard": PT_TONE_REINHARD, "aces": PT_TONE_ACES}
+# the header's PT_DISPLAY_DEFAULT_* (pt_display_params_init)
+PT_DISPLAY_DEFAULT_TONE = PT_TONE_ACES
+PT_DISPLAY_DEFAULT_EV_BIAS, PT_DISPLAY_DEFAULT_EV_MIN, PT_DISPLAY_DEFAULT_EV_MAX = 0.0, -16.0, 16.0
+PT_DISPLAY_DEFAULT_LO_PERMILLE, PT_DISPLAY_DEFAULT_HI_PERMILLE = 400, 950
+PT_DISPLAY_DEFAULT_ADAPT_UP, PT_DISPLAY_DEFAULT_ADAPT_DOWN, PT_DISPLAY_DEFAULT_WHITE = 1.0, 1.0, 4.0
+
 LIB_NAME = "libpt_render.so"
 _lib = None
 
@@ -339,7 +371,7 @@ def load_library() -> C.CDLL:
         pass  # torch-free hosts bind to /opt/rocm/lib through the library's RUNPATH
     lib = C.CDLL(str(path))
     for name, (res, args) in SIGNATURES.items():
-        if override_is_older_build(path, lib, name) or (name in ACCUM_SYMBOLS | ADAPTIVE_SYMBOLS | AOV_SYMBOLS | DENOISE_SYMBOLS | PLAN_SYMBOLS | POOL_PLAN_SYMBOLS | VARIANCE_SYMBOLS | TEMPORAL_SYMBOLS and not hasattr(lib, name)):
+        if override_is_older_build(path, lib, name) or (name in ACCUM_SYMBOLS | ADAPTIVE_SYMBOLS | AOV_SYMBOLS | DENOISE_SYMBOLS | PLAN_SYMBOLS | POOL_PLAN_SYMBOLS | VARIANCE_SYMBOLS | TEMPORAL_SYMBOLS | DISPLAY_SYMBOLS and not hasattr(lib, name)):
             continue
         fn = getattr(lib, name)  # AttributeError if the library does not export what the header declares
         fn.restype = res
@@ -385,6 +417,12 @@ def has_temporal(lib=None) -> bool:
     """Does the loaded library offer temporal reprojection (pt_adaptive_next_frame, pt_temporal_push)?"""
     lib = lib or load_library()
     return has_adaptive(lib) and all(hasattr(lib, n) for n in TEMPORAL_SYMBOLS)
+
+
+def has_display(lib=None) -> bool:
+    """Does the loaded library offer the display stage (pt_display_meter, pt_display_apply)?"""
+    lib = lib or load_library()
+    return all(hasattr(lib, n) for n in DISPLAY_SYMBOLS)
 
 
 def check(code: int, where: str) -> None:

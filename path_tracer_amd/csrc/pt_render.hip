@@ -1812,6 +1812,188 @@ __global__ __launch_bounds__(256) void temporal_push_kernel(TemporalArgs a) {
   a.next[p] = ra; a.next[a.pixels + p] = rb; a.next[2 * a.pixels + p] = rc;
 }
 
+// ---- display stage (include/pt_render.h: PtDisplay, pt_display_meter, pt_display_apply) ---------------------------------------------------
+// The end of the image-space chain: a luminance histogram, an exposure solved from it on the device, and exposure + tone curve + quantise()
+// in one pass.  Same rules as the filters above: the header states every operation, this is that text in HIP.
+//
+// The state, in device memory (uint32 words): the working histogram — 256 bins, then `rejected` as a 257th — which is all zeros between
+// meterings; the last metering's copy of it (pt_display_histogram); e, scale and `primed` (0: the next metering that solves is instant).
+enum { DISP_BINS = 257, DISP_WORK = 0, DISP_LAST = 257, DISP_E = 514, DISP_SCALE = 515, DISP_PRIMED = 516, DISP_WORDS = 517 };
+enum { DISP_METER_THREADS = 256, DISP_METER_MAX_BLOCKS = 256 }; // the fastest grid measured, one workgroup per CU (profiles/display_bench.txt): the rest of a frame is the metering loop
+
+// bin of one pixel: 0 ... 255, or 256 = rejected (NaN, +-inf, negative, +-0)
+__device__ __forceinline__ int display_bin(float r, float g, float b) {
+  const float y = (0.2126f * r + 0.7152f * g) + 0.0722f * b;
+  const unsigned bits = __float_as_uint(y);
+  if (!(y > 0.0f) || bits >= 0x7f800000u) return 256;
+  const int k = (int)(bits >> 20) - ((127 - 16) << 3);
+  return k < 0 ? 0 : k > 255 ? 255 : k;
+}
+
+// 2^e for |e| <= 32 (include/pt_render.h: Scale)
+__device__ __forceinline__ float display_scale(float e) {
+  const float k = ceilf(e);
+  return ldexpf(exp_neg((k - e) * 0x1.62e430p-1f), (int)k);
+}
+
+// One LDS histogram per workgroup, one LDS integer atomic per pixel, and the workgroup's non-zero bins to the global histogram with one
+// atomic each.  What costs is the number of workgroups — each one zeroes, synchronises and flushes up to 257 atomics onto the same 257
+// words — not the LDS atomics: a constant frame, whose adds all hit one address, meters no slower than a frame that spreads over every bin,
+// so per-wave histograms and a ballot that adds a wave's equal bins once were measured and dropped (profiles/display_bench.txt;
+// tools/ubench/display_stage.hip keeps the forms).  Hence the small grid and the grid-stride loop.
+//   VEC   the pixels are ONE contiguous range (a whole frame, or a rectangle as wide as the frame) that starts on a 16-byte boundary:
+//         a thread takes four consecutive pixels as three 16-byte loads; the last n % 4 pixels are taken one by one
+//   !VEC  any rectangle: one pixel per thread and trip, its position from the rectangle's width
+template <bool VEC>
+__global__ __launch_bounds__(DISP_METER_THREADS) void display_meter_kernel(const float* __restrict__ color, unsigned* __restrict__ hist, int width,
+                                                                           int x0, int y0, int rw, unsigned n) {
+  __shared__ unsigned lds[DISP_BINS];
+  for (int i = threadIdx.x; i < DISP_BINS; i += DISP_METER_THREADS) lds[i] = 0u;
+  __syncthreads();
+  const unsigned stride = gridDim.x * DISP_METER_THREADS;
+  if (VEC) {
+    const float* const first = color + ((long long)y0 * width + x0) * 3;
+    const unsigned groups = n >> 2;
+    for (unsigned g = blockIdx.x * DISP_METER_THREADS + threadIdx.x; g < groups; g += stride) {
+      const f4* const q = reinterpret_cast<const f4*>(first) + (size_t)g * 3;
+      const f4 a = q[0], b = q[1], c = q[2];
+      atomicAdd(&lds[display_bin(a.x, a.y, a.z)], 1u);
+      atomicAdd(&lds[display_bin(a.w, b.x, b.y)], 1u);
+      atomicAdd(&lds[display_bin(b.z, b.w, c.x)], 1u);
+      atomicAdd(&lds[display_bin(c.y, c.z, c.w)], 1u);
+    }
+    const unsigned i = (groups << 2) + threadIdx.x;
+    if (blockIdx.x == 0 && i < n) atomicAdd(&lds[display_bin(first[(size_t)i * 3], first[(size_t)i * 3 + 1], first[(size_t)i * 3 + 2])], 1u);
+  } else {
+    for (unsigned i = blockIdx.x * DISP_METER_THREADS + threadIdx.x; i < n; i += stride) {
+      const unsigned ry = i / (unsigned)rw, rx = i - ry * (unsigned)rw;
+      const long long p = ((long long)(y0 + (int)ry) * width + (x0 + (int)rx)) * 3;
+      atomicAdd(&lds[display_bin(color[p], color[p + 1], color[p + 2])], 1u);
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < DISP_BINS; i += DISP_METER_THREADS)
+    if (lds[i]) atomicAdd(&hist[i], lds[i]);
+}
+
+struct DisplaySolveArgs {
+  unsigned* state; // DISP_WORDS words
+  int lo_permille, hi_permille;
+  float ev_bias, ev_min, ev_max, adapt_up, adapt_down;
+};
+
+// One wave: lane l owns the bins 4 l ... 4 l + 3.  An inclusive wave scan of the lanes' counts gives every bin its first rank; the band's
+// S and C are integer sums, reduced across the wave (any order: the same bits); lane 0 divides, adapts and stores e and scale.  Every lane
+// copies its bins to the last-metering histogram and zeroes them for the next one.
+__global__ __launch_bounds__(64) void display_solve_kernel(DisplaySolveArgs a) {
+  constexpr int LOGC[8] = PT_DISPLAY_LOGC;
+  const int lane = threadIdx.x;
+  unsigned* const work = a.state + DISP_WORK;
+  unsigned* const last = a.state + DISP_LAST;
+  unsigned c[4], mine = 0u;
+  for (int j = 0; j < 4; j++) { c[j] = work[4 * lane + j]; mine += c[j]; }
+  unsigned incl = mine; // <= 2^31: the frame's pixels
+  for (int d = 1; d < 64; d <<= 1) {
+    const unsigned up = __shfl_up(incl, d, 64);
+    if (lane >= d) incl += up;
+  }
+  const unsigned long long N = __shfl(incl, 63, 64);
+  const unsigned long long lo_n = N * (unsigned long long)a.lo_permille / 1000ull, hi_n = N * (unsigned long long)a.hi_permille / 1000ull;
+  unsigned long long rank = incl - mine;
+  long long S = 0;
+  unsigned long long C = 0;
+  for (int j = 0; j < 4; j++) {
+    const int b = 4 * lane + j;
+    const unsigned long long end = rank + c[j];
+    const unsigned long long from = rank > lo_n ? rank : lo_n, to = end < hi_n ? end : hi_n;
+    if (to > from) {
+      const long long value = 65536ll * ((b >> 3) - 16) + LOGC[b & 7];
+      S += (long long)(to - from) * value;
+      C += to - from;
+    }
+    rank = end;
+  }
+  for (int d = 32; d >= 1; d >>= 1) {
+    S += __shfl_xor(S, d, 64);
+    C += __shfl_xor(C, d, 64);
+  }
+  for (int j = 0; j < 4; j++) { last[4 * lane + j] = c[j]; work[4 * lane + j] = 0u; }
+  if (lane == 0) {
+    last[256] = work[256];
+    work[256] = 0u;
+    if (C != 0) {
+      const float t = (float)(((double)S / (double)C) * 0x1p-16);
+      const float et = fminf(fmaxf((PT_DISPLAY_LOG2_KEY - t) + a.ev_bias, a.ev_min), a.ev_max);
+      float e = et;
+      if (a.state[DISP_PRIMED]) {
+        const float e0 = __uint_as_float(a.state[DISP_E]);
+        e = e0 + (et - e0) * (et > e0 ? a.adapt_up : a.adapt_down);
+      }
+      a.state[DISP_E] = __float_as_uint(e);
+      a.state[DISP_SCALE] = __float_as_uint(display_scale(e));
+      a.state[DISP_PRIMED] = 1u;
+    }
+  }
+}
+
+// pt_display_reset (reset != 0: the state after create) and pt_display_set_exposure (e = ev, primed)
+__global__ __launch_bounds__(64) void display_set_kernel(unsigned* state, int reset, float ev) {
+  if (reset)
+    for (int i = threadIdx.x; i < 2 * DISP_BINS; i += 64) state[i] = 0u;
+  if (threadIdx.x == 0) {
+    state[DISP_E] = __float_as_uint(reset ? 0.0f : ev);
+    state[DISP_SCALE] = __float_as_uint(reset ? 1.0f : display_scale(ev));
+    state[DISP_PRIMED] = reset ? 0u : 1u;
+  }
+}
+
+template <int TONE>
+__device__ __forceinline__ float display_curve(float x, float iw2) {
+  if (TONE == PT_TONE_REINHARD) return (x * (1.0f + x * iw2)) / (1.0f + x);
+  if (TONE == PT_TONE_ACES) return (x * (2.51f * x + 0.03f)) / (x * (2.43f * x + 0.59f) + 0.14f);
+  return x;
+}
+
+// One pass over the rows' values (the curve is per channel, so a row is 3 * width independent values: the loads, the byte stores and the
+// float stores are all contiguous across a wave).  blockIdx.y walks the rows; row 0 of rgb8 is the top.  `scale` is read once: the state's
+// (written by display_solve_kernel / display_set_kernel earlier on the stream), or 2^ev for the stateless call.  linear may be color: a
+// thread reads its values before it writes them.
+//   VEC   3 * width is a multiple of 4 and the planes are 16-byte aligned (rgb8: 4-byte): a thread takes four values — one 16-byte load, one
+//         4-byte store of the bytes, one 16-byte store of the floats
+//   !VEC  one value per thread
+__device__ __forceinline__ float display_clamp(float x) {
+  if (!(x >= 0.0f)) x = 0.0f;
+  return x > 0x1p20f ? 0x1p20f : x;
+}
+
+template <int TONE, bool VEC>
+__global__ __launch_bounds__(256) void display_apply_kernel(const float* color, const unsigned* __restrict__ state, float ev, float iw2,
+                                                            uint8_t* __restrict__ rgb8, float* linear, int width, int height) {
+  const long long row_items = VEC ? 3ll * width / 4 : 3ll * width;
+  const long long f = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (f >= row_items) return;
+  const float scale = state ? __uint_as_float(state[DISP_SCALE]) : display_scale(ev);
+  for (int row = blockIdx.y; row < height; row += gridDim.y) { // row 0 = top
+    const long long src = (long long)(height - 1 - row) * row_items + f, dst = (long long)row * row_items + f;
+    if (VEC) {
+      const f4 v = reinterpret_cast<const f4*>(color)[src];
+      f4 y;
+      y.x = display_curve<TONE>(display_clamp(v.x * scale), iw2); y.y = display_curve<TONE>(display_clamp(v.y * scale), iw2);
+      y.z = display_curve<TONE>(display_clamp(v.z * scale), iw2); y.w = display_curve<TONE>(display_clamp(v.w * scale), iw2);
+      if (rgb8) {
+        uchar4 o;
+        o.x = quantise(y.x); o.y = quantise(y.y); o.z = quantise(y.z); o.w = quantise(y.w);
+        reinterpret_cast<uchar4*>(rgb8)[dst] = o;
+      }
+      if (linear) reinterpret_cast<f4*>(linear)[src] = y;
+    } else {
+      const float y = display_curve<TONE>(display_clamp(color[src] * scale), iw2);
+      if (rgb8) rgb8[dst] = quantise(y);
+      if (linear) linear[src] = y;
+    }
+  }
+}
+
 thread_local std::string g_last_error;
 
 // ---- tuning: include/pt_render.h PtTuning.  Resolved ONCE per scene (pt_scene_create / pt_debug_flatten), never on the launch path.
@@ -3589,6 +3771,177 @@ int pt_temporal_push(PtTemporal* t, const PtTemporalParams* params, const PtCame
   t->cur = 1 - t->cur;
   t->cam = *cam;
   if (t->frames < INT32_MAX) t->frames++;
+  return PT_OK;
+}
+
+// ---- display stage: PtDisplay, pt_display_meter (display_meter_kernel, display_solve_kernel), pt_display_apply (display_apply_kernel) ----
+} // extern "C"
+
+struct PtDisplay {
+  DevBuf<unsigned> words; // DISP_WORDS: the working histogram, the last metering's, e, scale, primed
+  int32_t frames = 0;     // meterings since create / reset
+};
+
+namespace {
+std::mutex g_display_mutex;
+int32_t g_last_display[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // pt_debug_last_display
+
+// What can be judged of a call without a live object: the params, the frame, the rectangle.  iw2 = 1.0f / (white * white), rounded twice.
+int display_check(const char* call, const PtDisplayParams* p, const float* color, int32_t width, int32_t height, float* iw2_out) {
+  auto bad = [&](const char* what) { return fail(PT_ERR_INVALID_ARG, std::string(call) + ": " + what); };
+  if (!p || !color) return bad("NULL params or color");
+  if (p->struct_size != (int32_t)sizeof(PtDisplayParams)) return bad("PtDisplayParams.struct_size is not this library's");
+  if (width <= 0 || height <= 0) return bad("width and height must be > 0");
+  if ((int64_t)width * height > ((int64_t)1 << 31)) return bad("more than 2^31 pixels");
+  if (p->tone != PT_TONE_REFERENCE && p->tone != PT_TONE_REINHARD && p->tone != PT_TONE_ACES) return bad("unknown tone");
+  if (p->flags) return bad("unknown flags");
+  if (p->lo_permille < 0 || p->hi_permille > 1000 || p->lo_permille >= p->hi_permille) return bad("need 0 <= lo_permille < hi_permille <= 1000");
+  if (!(p->adapt_up > 0.0f && p->adapt_up <= 1.0f) || !(p->adapt_down > 0.0f && p->adapt_down <= 1.0f)) return bad("an adaptation rate is outside (0, 1]");
+  if (!(p->ev_min >= -32.0f && p->ev_max <= 32.0f && p->ev_min <= p->ev_max)) return bad("need -32 <= ev_min <= ev_max <= 32");
+  if (!std::isfinite(p->ev_bias)) return bad("ev_bias is not finite");
+  volatile float w2 = p->white * p->white;
+  volatile float iw2 = 1.0f / w2;
+  if (!(std::isfinite(iw2) && iw2 > 0.0f)) return bad("white: 1 / (white * white) is not a finite binary32 number > 0");
+  if (p->rect_x0 || p->rect_y0 || p->rect_x1 || p->rect_y1) {
+    if (p->rect_x0 < 0 || p->rect_y0 < 0 || p->rect_x1 > width || p->rect_y1 > height || p->rect_x0 >= p->rect_x1 || p->rect_y0 >= p->rect_y1)
+      return bad("the metering rectangle is empty or leaves the frame");
+  }
+  if (iw2_out) *iw2_out = iw2;
+  return PT_OK;
+}
+} // namespace
+
+extern "C" {
+
+void pt_display_params_init(PtDisplayParams* params) {
+  if (!params) return;
+  std::memset(params, 0, sizeof *params);
+  params->struct_size = (int32_t)sizeof(PtDisplayParams);
+  params->tone = PT_DISPLAY_DEFAULT_TONE;
+  params->ev_bias = PT_DISPLAY_DEFAULT_EV_BIAS; params->ev_min = PT_DISPLAY_DEFAULT_EV_MIN; params->ev_max = PT_DISPLAY_DEFAULT_EV_MAX;
+  params->lo_permille = PT_DISPLAY_DEFAULT_LO_PERMILLE; params->hi_permille = PT_DISPLAY_DEFAULT_HI_PERMILLE;
+  params->adapt_up = PT_DISPLAY_DEFAULT_ADAPT_UP; params->adapt_down = PT_DISPLAY_DEFAULT_ADAPT_DOWN;
+  params->white = PT_DISPLAY_DEFAULT_WHITE;
+}
+
+int pt_display_create(PtDisplay** out) {
+  if (!out) return fail(PT_ERR_INVALID_ARG, "pt_display_create: out is NULL");
+  *out = nullptr;
+  std::unique_ptr<PtDisplay> d(new PtDisplay());
+  const hipError_t e = d->words.alloc(DISP_WORDS);
+  if (e != hipSuccess) return fail(PT_ERR_HIP, std::string("pt_display_create: hipMalloc: ") + hipGetErrorString(e));
+  std::vector<unsigned> init(DISP_WORDS, 0u);
+  const float one = 1.0f;
+  std::memcpy(&init[DISP_SCALE], &one, sizeof one);
+  PT_HIP(hipMemcpy(d->words.p, init.data(), DISP_WORDS * sizeof(unsigned), hipMemcpyHostToDevice));
+  *out = d.release();
+  return PT_OK;
+}
+
+void pt_display_destroy(PtDisplay* d) { delete d; }
+
+int pt_display_reset(PtDisplay* d, void* stream) {
+  if (!d) return fail(PT_ERR_INVALID_ARG, "pt_display_reset: NULL state");
+  hipLaunchKernelGGL(display_set_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, d->words.p, 1, 0.0f);
+  PT_HIP(hipGetLastError());
+  d->frames = 0;
+  return PT_OK;
+}
+
+int32_t pt_display_frames(const PtDisplay* d) { return d ? d->frames : -1; }
+
+int pt_display_set_exposure(PtDisplay* d, float ev, void* stream) {
+  if (!d) return fail(PT_ERR_INVALID_ARG, "pt_display_set_exposure: NULL state");
+  if (ev != ev) return fail(PT_ERR_INVALID_ARG, "pt_display_set_exposure: ev is NaN");
+  hipLaunchKernelGGL(display_set_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, d->words.p, 0, std::fmin(std::fmax(ev, -32.0f), 32.0f));
+  PT_HIP(hipGetLastError());
+  return PT_OK;
+}
+
+int pt_display_meter(PtDisplay* d, const PtDisplayParams* p, const float* color, int32_t width, int32_t height, void* stream) {
+  if (const int rc = display_check("pt_display_meter", p, color, width, height, nullptr)) return rc;
+  if (!d) return fail(PT_ERR_INVALID_ARG, "pt_display_meter: NULL state");
+  const bool whole = !(p->rect_x0 || p->rect_y0 || p->rect_x1 || p->rect_y1);
+  const int x0 = whole ? 0 : p->rect_x0, y0 = whole ? 0 : p->rect_y0, x1 = whole ? width : p->rect_x1, y1 = whole ? height : p->rect_y1;
+  const int64_t n = (int64_t)(x1 - x0) * (y1 - y0); // 1 ... 2^31
+  // four pixels per thread where the rectangle is one contiguous, 16-byte aligned range of the frame
+  const bool vec = x1 - x0 == width && ((uintptr_t)(color + ((int64_t)y0 * width + x0) * 3) & 15) == 0;
+  const int64_t items = vec ? (n + 3) / 4 : n;
+  const unsigned blocks = (unsigned)std::min<int64_t>((items + DISP_METER_THREADS - 1) / DISP_METER_THREADS, DISP_METER_MAX_BLOCKS);
+  unsigned* const work = d->words.p + DISP_WORK;
+  const dim3 grid(blocks), block(DISP_METER_THREADS);
+  if (vec)
+    hipLaunchKernelGGL(display_meter_kernel<true>, grid, block, 0, (hipStream_t)stream, color, work, (int)width, x0, y0, x1 - x0, (unsigned)n);
+  else
+    hipLaunchKernelGGL(display_meter_kernel<false>, grid, block, 0, (hipStream_t)stream, color, work, (int)width, x0, y0, x1 - x0, (unsigned)n);
+  PT_HIP(hipGetLastError());
+  DisplaySolveArgs a;
+  a.state = d->words.p;
+  a.lo_permille = p->lo_permille; a.hi_permille = p->hi_permille;
+  a.ev_bias = p->ev_bias; a.ev_min = p->ev_min; a.ev_max = p->ev_max; a.adapt_up = p->adapt_up; a.adapt_down = p->adapt_down;
+  hipLaunchKernelGGL(display_solve_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a);
+  PT_HIP(hipGetLastError());
+  if (d->frames < INT32_MAX) d->frames++;
+  {
+    std::lock_guard<std::mutex> lock(g_display_mutex);
+    g_last_display[0] = (int32_t)blocks; g_last_display[1] = DISP_METER_THREADS;
+    g_last_display[2] = (int32_t)((items + (int64_t)blocks * DISP_METER_THREADS - 1) / ((int64_t)blocks * DISP_METER_THREADS));
+    g_last_display[3] = vec ? 4 : 1;
+  }
+  return PT_OK;
+}
+
+int pt_display_apply(const PtDisplay* d, const PtDisplayParams* p, const float* color, int32_t width, int32_t height, uint8_t* rgb8_out,
+                     float* linear_out, void* stream) {
+  float iw2 = 0.0f;
+  if (const int rc = display_check("pt_display_apply", p, color, width, height, &iw2)) return rc;
+  auto bad = [&](const char* what) { return fail(PT_ERR_INVALID_ARG, std::string("pt_display_apply: ") + what); };
+  if (!rgb8_out && !linear_out) return bad("rgb8_out and linear_out are both NULL");
+  const uintptr_t values = (uintptr_t)width * (uintptr_t)height * 3;
+  auto overlap = [](const void* a, uintptr_t a_bytes, const void* b, uintptr_t b_bytes) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a && b && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+  };
+  if (overlap(rgb8_out, values, color, values * 4) || overlap(rgb8_out, values, linear_out, values * 4)) return bad("rgb8_out overlaps color or linear_out");
+  if (linear_out != color && overlap(linear_out, values * 4, color, values * 4)) return bad("linear_out overlaps color without being color");
+  const float ev = std::fmin(std::fmax(p->ev_bias, -32.0f), 32.0f);
+  const unsigned* state = d ? d->words.p : nullptr;
+  // four values per thread where the rows and the planes allow 16-byte loads and stores
+  const bool vec = width % 4 == 0 && ((uintptr_t)color & 15) == 0 && ((uintptr_t)linear_out & 15) == 0 && ((uintptr_t)rgb8_out & 3) == 0;
+  const long long row_items = vec ? 3ll * width / 4 : 3ll * width;
+  const dim3 grid((unsigned)((row_items + 255) / 256), (unsigned)std::min<int32_t>(height, 65535)), block(256);
+#define PT_DISPLAY_APPLY(TONE, VEC) \
+  hipLaunchKernelGGL((display_apply_kernel<TONE, VEC>), grid, block, 0, (hipStream_t)stream, color, state, ev, iw2, rgb8_out, linear_out, (int)width, (int)height)
+  if (p->tone == PT_TONE_REINHARD) { if (vec) PT_DISPLAY_APPLY(PT_TONE_REINHARD, true); else PT_DISPLAY_APPLY(PT_TONE_REINHARD, false); }
+  else if (p->tone == PT_TONE_ACES) { if (vec) PT_DISPLAY_APPLY(PT_TONE_ACES, true); else PT_DISPLAY_APPLY(PT_TONE_ACES, false); }
+  else { if (vec) PT_DISPLAY_APPLY(PT_TONE_REFERENCE, true); else PT_DISPLAY_APPLY(PT_TONE_REFERENCE, false); }
+#undef PT_DISPLAY_APPLY
+  PT_HIP(hipGetLastError());
+  {
+    std::lock_guard<std::mutex> lock(g_display_mutex);
+    g_last_display[4] = (int32_t)grid.x; g_last_display[5] = (int32_t)grid.y; g_last_display[6] = vec ? 4 : 1; g_last_display[7] = p->tone + 1;
+  }
+  return PT_OK;
+}
+
+int pt_display_exposure(const PtDisplay* d, float* ev_host, void* stream) {
+  if (!d || !ev_host) return fail(PT_ERR_INVALID_ARG, "pt_display_exposure: NULL argument");
+  PT_HIP(hipMemcpyAsync(ev_host, d->words.p + DISP_E, sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  PT_HIP(hipStreamSynchronize((hipStream_t)stream));
+  return PT_OK;
+}
+
+int pt_display_histogram(const PtDisplay* d, uint32_t host[257], void* stream) {
+  if (!d || !host) return fail(PT_ERR_INVALID_ARG, "pt_display_histogram: NULL argument");
+  PT_HIP(hipMemcpyAsync(host, d->words.p + DISP_LAST, DISP_BINS * sizeof(uint32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  PT_HIP(hipStreamSynchronize((hipStream_t)stream));
+  return PT_OK;
+}
+
+int pt_debug_last_display(int32_t out[8]) {
+  if (!out) return fail(PT_ERR_INVALID_ARG, "pt_debug_last_display: NULL argument");
+  std::lock_guard<std::mutex> lock(g_display_mutex);
+  std::memcpy(out, g_last_display, sizeof g_last_display);
   return PT_OK;
 }
 

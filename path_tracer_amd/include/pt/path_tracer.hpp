@@ -461,6 +461,65 @@ class temporal {
   PtTemporal* t_ = nullptr;
 };
 
+// The display stage (include/pt_render.h: PtDisplay): a luminance histogram metered on the device, an exposure solved from it with eye
+// adaptation across the frames of a sequence, and exposure + tone curve + the output stage's quantiser in one pass; RAII over
+// pt_display_create / pt_display_destroy.  color and linear_out are DEVICE buffers [height][width][3] (the frame buffer's layout), rgb8_out
+// is [height][width][3] bytes with row 0 = top; either output may be null, linear_out may be color.  The defaults are the header's
+// (pt_display_params_init).  display_apply() is the stateless form: the exposure is dp.ev_bias.
+struct display_params {
+  int tone = PT_DISPLAY_DEFAULT_TONE; // PT_TONE_REFERENCE, PT_TONE_REINHARD, PT_TONE_ACES
+  float ev_bias = PT_DISPLAY_DEFAULT_EV_BIAS, ev_min = PT_DISPLAY_DEFAULT_EV_MIN, ev_max = PT_DISPLAY_DEFAULT_EV_MAX;
+  int lo_permille = PT_DISPLAY_DEFAULT_LO_PERMILLE, hi_permille = PT_DISPLAY_DEFAULT_HI_PERMILLE;
+  float adapt_up = PT_DISPLAY_DEFAULT_ADAPT_UP, adapt_down = PT_DISPLAY_DEFAULT_ADAPT_DOWN;
+  float white = PT_DISPLAY_DEFAULT_WHITE;
+  int rect[4] = {0, 0, 0, 0}; // x0, y0, x1, y1 of the metering rectangle; four zeros: the whole frame
+  PtDisplayParams c() const {
+    return PtDisplayParams{(int32_t)sizeof(PtDisplayParams), tone, 0u, ev_bias, ev_min, ev_max, lo_permille, hi_permille, adapt_up, adapt_down,
+                           white, rect[0], rect[1], rect[2], rect[3], 0};
+  }
+};
+inline void display_apply(int width, int height, const float* color, uint8_t* rgb8_out, float* linear_out = nullptr,
+                          const display_params& dp = {}, void* stream = nullptr) {
+  const PtDisplayParams p = dp.c();
+  check(pt_display_apply(nullptr, &p, color, width, height, rgb8_out, linear_out, stream), "pt_display_apply");
+}
+class display {
+ public:
+  explicit display(const display_params& dp = {}) : params(dp) { check(pt_display_create(&d_), "pt_display_create"); }
+  ~display() { pt_display_destroy(d_); }
+  display(const display&) = delete;
+  display& operator=(const display&) = delete;
+  // asynchronous on `stream`: histogram, solve and adaptation
+  void meter(int width, int height, const float* color, void* stream = nullptr) {
+    const PtDisplayParams p = params.c();
+    check(pt_display_meter(d_, &p, color, width, height, stream), "pt_display_meter");
+  }
+  // asynchronous on `stream`: the exposure is the state's
+  void apply(int width, int height, const float* color, uint8_t* rgb8_out, float* linear_out = nullptr, void* stream = nullptr) const {
+    const PtDisplayParams p = params.c();
+    check(pt_display_apply(d_, &p, color, width, height, rgb8_out, linear_out, stream), "pt_display_apply");
+  }
+  void set_exposure(float ev, void* stream = nullptr) { check(pt_display_set_exposure(d_, ev, stream), "pt_display_set_exposure"); }
+  void reset(void* stream = nullptr) { check(pt_display_reset(d_, stream), "pt_display_reset"); }
+  int frames() const { return pt_display_frames(d_); }
+  // these two synchronise `stream`
+  float exposure(void* stream = nullptr) const {
+    float ev = 0.0f;
+    check(pt_display_exposure(d_, &ev, stream), "pt_display_exposure");
+    return ev;
+  }
+  std::array<uint32_t, 257> histogram(void* stream = nullptr) const {
+    std::array<uint32_t, 257> h{};
+    check(pt_display_histogram(d_, h.data(), stream), "pt_display_histogram");
+    return h;
+  }
+  PtDisplay* handle() const { return d_; }
+  display_params params;
+
+ private:
+  PtDisplay* d_ = nullptr;
+};
+
 // Progressive rendering: one frame in sample windows; RAII over pt_accum_create / pt_accum_destroy (include/pt_render.h, PtAccum).
 // After windows totalling N samples, resolve() holds the bits render() gives at samples = N.  The scene must outlive the accumulator;
 // windows run on the default stream (or `stream`) and are ordered like renders of the scene.

@@ -330,6 +330,141 @@ def tonemap_rgb8(fb):
     return out
 
 
+def _display_params(tone, ev_bias, ev_min, ev_max, lo_permille, hi_permille, adapt_up, adapt_down, white, rect) -> abi.PtDisplayParams:
+    if isinstance(tone, str):
+        if tone not in abi.TONES:
+            raise ValueError(f"tone must be one of {sorted(abi.TONES)}")
+        tone = abi.TONES[tone]
+    x0, y0, x1, y1 = (0, 0, 0, 0) if rect is None else rect
+    return abi.PtDisplayParams(C.sizeof(abi.PtDisplayParams), int(tone), 0, float(ev_bias), float(ev_min), float(ev_max), int(lo_permille),
+                               int(hi_permille), float(adapt_up), float(adapt_down), float(white), int(x0), int(y0), int(x1), int(y1), 0)
+
+
+def _frame_ptr(fb, what="fb"):
+    import torch
+
+    if fb is None or fb.dim() != 3 or fb.shape[2] != 3 or fb.dtype != torch.float32 or not fb.is_cuda or not fb.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous float32 CUDA tensor of shape [H][W][3]")
+    return C.c_void_p(fb.data_ptr())
+
+
+def _display_apply(lib, handle, p, fb, out, linear):
+    """pt_display_apply -> the uint8 image [H][W][3] (row 0 = top), or (image, linear plane) with `linear`: True allocates the plane, a tensor
+    is written (it may be `fb`)."""
+    import torch
+
+    h, w, _ = fb.shape
+    src = _frame_ptr(fb)
+    if out is None:
+        out = torch.empty((h, w, 3), dtype=torch.uint8, device=fb.device)
+    elif tuple(out.shape) != (h, w, 3) or out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous():
+        raise ValueError("out must be a contiguous uint8 CUDA tensor of shape [H][W][3]")
+    lin = None
+    if linear is True:
+        lin = torch.empty((h, w, 3), dtype=torch.float32, device=fb.device)
+    elif linear is not None and linear is not False:
+        lin = linear
+        if tuple(lin.shape) != (h, w, 3):
+            raise ValueError("linear must have the frame's shape")
+        _frame_ptr(lin, "linear")
+    abi.check(lib.pt_display_apply(handle, C.byref(p), src, w, h, C.c_void_p(out.data_ptr()), C.c_void_p(lin.data_ptr()) if lin is not None else None,
+                                   _stream_ptr(torch)), "pt_display_apply")
+    return out if lin is None else (out, lin)
+
+
+class Display:
+    """The display stage (include/pt_render.h: PtDisplay): meter() builds the frame's luminance histogram on the device, solves an exposure
+    from it and adapts towards it (the first metering is instant); apply() scales by 2^exposure, applies the tone curve and the output
+    stage's quantiser.  Nothing between the two comes back to the host.  Whole frames [H][W][3] float32 on the GPU; asynchronous on
+    torch's current stream; the calls on one Display must be stream-ordered.
+    tone: "reference", "reinhard" or "aces"; rect: the metering rectangle (x0, y0, x1, y1), y = 0 the bottom row (None: the whole frame);
+    the other parameters and their defaults are the header's (PtDisplayParams)."""
+
+    def __init__(self, tone="aces", *, ev_bias: float = abi.PT_DISPLAY_DEFAULT_EV_BIAS, ev_min: float = abi.PT_DISPLAY_DEFAULT_EV_MIN,
+                 ev_max: float = abi.PT_DISPLAY_DEFAULT_EV_MAX, lo_permille: int = abi.PT_DISPLAY_DEFAULT_LO_PERMILLE,
+                 hi_permille: int = abi.PT_DISPLAY_DEFAULT_HI_PERMILLE, adapt_up: float = abi.PT_DISPLAY_DEFAULT_ADAPT_UP,
+                 adapt_down: float = abi.PT_DISPLAY_DEFAULT_ADAPT_DOWN, white: float = abi.PT_DISPLAY_DEFAULT_WHITE, rect=None):
+        import torch
+
+        if not torch.cuda.is_available():
+            raise RuntimeError("path_tracer_amd.render.Display needs a HIP device: there is no CPU path in the product")
+        self.lib = abi.load_library()
+        if not abi.has_display(self.lib):
+            raise ImportError(f"{abi.library_path()} predates the display stage (no pt_display_* entry points)")
+        self.params = _display_params(tone, ev_bias, ev_min, ev_max, lo_permille, hi_permille, adapt_up, adapt_down, white, rect)
+        self.handle = C.c_void_p()
+        abi.check(self.lib.pt_display_create(C.byref(self.handle)), "pt_display_create")
+
+    @property
+    def frames(self) -> int:
+        """Meterings since the constructor or the last reset()."""
+        return int(self.lib.pt_display_frames(self.handle))
+
+    def meter(self, fb) -> "Display":
+        """Histogram, solve and adaptation over the frame `fb`."""
+        import torch
+
+        h, w, _ = fb.shape
+        abi.check(self.lib.pt_display_meter(self.handle, C.byref(self.params), _frame_ptr(fb), w, h, _stream_ptr(torch)), "pt_display_meter")
+        return self
+
+    def apply(self, fb, out=None, linear=False):
+        """The frame at the state's exposure through the tone curve: the uint8 image [H][W][3], row 0 = top (`out` if given); with `linear`
+        (True, or a float32 tensor to write, which may be `fb`) also the curve's output before the quantiser: (image, plane)."""
+        return _display_apply(self.lib, self.handle, self.params, fb, out, linear)
+
+    def exposure(self) -> float:
+        """The exposure in stops (synchronises the stream: for inspection)."""
+        import torch
+
+        ev = C.c_float()
+        abi.check(self.lib.pt_display_exposure(self.handle, C.byref(ev), _stream_ptr(torch)), "pt_display_exposure")
+        return float(ev.value)
+
+    def histogram(self) -> np.ndarray:
+        """The last metering's 256 bins followed by the rejected count, uint32[257] (synchronises the stream: for inspection)."""
+        import torch
+
+        host = np.zeros(257, dtype=np.uint32)
+        abi.check(self.lib.pt_display_histogram(self.handle, host.ctypes.data_as(C.POINTER(C.c_uint32)), _stream_ptr(torch)), "pt_display_histogram")
+        return host
+
+    def set_exposure(self, ev: float) -> "Display":
+        """A manual exposure in stops (clamped to +-32); a later meter() adapts from it."""
+        import torch
+
+        abi.check(self.lib.pt_display_set_exposure(self.handle, float(ev), _stream_ptr(torch)), "pt_display_set_exposure")
+        return self
+
+    def reset(self) -> None:
+        """Forget the exposure: the next meter() is instant."""
+        import torch
+
+        abi.check(self.lib.pt_display_reset(self.handle, _stream_ptr(torch)), "pt_display_reset")
+
+    def close(self) -> None:
+        if self.handle:
+            self.lib.pt_display_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+
+def display(fb, tone="aces", ev: float = 0.0, *, white: float = abi.PT_DISPLAY_DEFAULT_WHITE, out=None, linear=False):
+    """The stateless display stage: `fb` at a manual exposure of `ev` stops through the tone curve -> uint8 [H][W][3], row 0 = top (with
+    `linear`: (image, plane), as Display.apply).  display(fb, "reference", 0.0) is tonemap_rgb8(fb)."""
+    lib = abi.load_library()
+    if not abi.has_display(lib):
+        raise ImportError(f"{abi.library_path()} predates the display stage (no pt_display_* entry points)")
+    p = _display_params(tone, ev, abi.PT_DISPLAY_DEFAULT_EV_MIN, abi.PT_DISPLAY_DEFAULT_EV_MAX, abi.PT_DISPLAY_DEFAULT_LO_PERMILLE,
+                        abi.PT_DISPLAY_DEFAULT_HI_PERMILLE, 1.0, 1.0, white, None)
+    return _display_apply(lib, None, p, fb, out, linear)
+
+
 class Accumulator:
     """Progressive rendering (include/pt_render.h PtAccum): one frame rendered in sample windows.
 
@@ -467,6 +602,14 @@ class Accumulator:
         out = torch.empty((self.height, self.width, 3), dtype=torch.uint8, device="cuda")
         abi.check(self.lib.pt_accum_tonemap_rgb8(self.handle, C.c_void_p(out.data_ptr()), _stream_ptr(torch)), "pt_accum_tonemap_rgb8")
         return out
+
+    def display(self, disp: "Display", out=None):
+        """resolve(), then disp.meter() and disp.apply() over it: the uint8 image [H][W][3], row 0 = top, at the exposure the Display
+        adapted to (whole frames)."""
+        if self.shard_count != 1:
+            raise ValueError("Accumulator.display: whole frames only (gather and unshard first)")
+        fb = self.resolve()
+        return disp.meter(fb).apply(fb, out=out)
 
     def reset(self) -> None:
         """Back to 0 samples (the next window binds its camera: set .cam first to render another view)."""
@@ -633,13 +776,15 @@ class TemporalAccumulator:
 
 
 def render_temporal(width: int, height: int, spp: int, scene, cams, depth: int = 50, *, aov_spp: int = 4, denoise: bool = True,
-                    denoise_kw: "dict | None" = None, **params):
+                    denoise_kw: "dict | None" = None, display: "Display | None" = None, **params):
     """A camera path rendered at `spp` samples per frame with its history carried along: for each camera of `cams` yields a dict with
     `noisy` (the frame alone), `temporal`, `variance`, `history` (TemporalAccumulator.push's results) and, with `denoise`, `filtered` —
     denoise_variance() over the temporal colour and variance with that frame's guides (render_aov at `aov_spp` camera rays per pixel).
     One adaptive accumulator renders every frame, with next_frame() between them: no frame repeats another's random numbers.  A frame
     of 2 samples or more is rendered in two windows, so that its own variance estimate (Accumulator.variance(), from the two halves)
     exists and is what `variance` holds where the history is younger than 4 frames.
+    With `display` (a Display) each frame also has `rgb8`: the end of the chain — `filtered` (or `temporal` without `denoise`) metered and
+    shown by it, its exposure adapting from frame to frame.
     `params`: push()'s alpha, tol_depth, tol_normal; `denoise_kw`: denoise_variance()'s parameters."""
     import torch
 
@@ -663,6 +808,9 @@ def render_temporal(width: int, height: int, spp: int, scene, cams, depth: int =
             if denoise:
                 frame["filtered"] = denoise_variance(color, variance, albedo=guides["albedo"], normal=guides["normal"], depth=guides["depth"],
                                                      **(denoise_kw or {}))
+            if display is not None:
+                shown = frame["filtered" if denoise else "temporal"]
+                frame["rgb8"] = display.meter(shown).apply(shown)
             yield frame
     finally:
         if acc is not None:
