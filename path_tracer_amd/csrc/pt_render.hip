@@ -1355,18 +1355,61 @@ __device__ __forceinline__ float exp_neg(float x) { // pt_exp_neg: 0 <= x < 80
 
 enum { DN_COLOR = 1, DN_NORMAL = 2, DN_DEPTH = 4, DN_ALBEDO = 8, DN_DEMOD_IN = 16, DN_REMOD_OUT = 32 };
 
-struct ATrousArgs {
-  const float* in;  // c_i: [height][width][3] (iteration 0: the caller's colour, or its copy in scratch)
-  float* out;       // c_(i+1)
+// The filter core: what atrous_kernel and vdn_kernel (below) share.  One iteration of either is one thread per pixel in a 32 x 8 pixel
+// workgroup (a wave is two rows of 32, so a tap's 64 reads from global memory are two runs of contiguous records).  ND / AL: the launch
+// reads the (normal, depth) / (albedo) records at all.  STEP = 0: every tap is read from global memory, at the step of the arguments.
+// STEP = 1, 2: the step is STEP and the workgroup first stages its tile with the halo of 2 STEP pixels in LDS, and the taps read LDS.  Same
+// operations on the same values in the same order either way: the bits do not depend on the path.  The core is the tile's geometry, the
+// arguments both launches carry, the guide records fetched from either place and a tap's exponent from the guide terms; each kernel adds
+// its payload: its colour records and their staging, its colour term, its sums and its write-out.  (The staging loop and the 5 x 5 walk
+// stay written out in both kernels: behind shared functions they compile to other registers and instructions —
+// profiles/atrous_core_refactor.txt.)
+struct FilterArgs { // the tail of both kernels' arguments
   const f4* g_nd;   // per pixel (normal, depth); read when ND
   const f4* g_al;   // per pixel (albedo, 0); read when AL
   int width, height, step;
-  unsigned terms;   // DN_*: which terms are on, and whether this launch demodulates what it reads / remodulates what it writes
-  float k_c, k_n, sd2, k_a;
+  unsigned terms;   // DN_* (and VDN_LAST): which terms are on, and what this launch does to what it reads and writes
+  float k_color;    // the filter's colour scale: atrous_kernel's k_c, vdn_kernel's sv2
+  float k_n, sd2, k_a;
+};
+
+template <int STEP>
+struct FilterTile {
+  static constexpr int R = 2 * STEP, TW = 32 + 2 * R, TH = 8 + 2 * R, N = TW * TH;
+};
+
+struct Guides { f4 nd, al; }; // a pixel's guide records
+constexpr Guides kNoGuides = {{0.0f, 0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f, 0.0f}};
+
+// the records at index i of the packed planes (i: a pixel) or of the staged tile (i: a slot); one the launch does not read stays as in g
+template <bool ND, bool AL, class I>
+__device__ __forceinline__ Guides guides_at(const f4* nd, const f4* al, I i, Guides g) {
+  if (ND) g.nd = nd[i];
+  if (AL) g.al = al[i];
+  return g;
+}
+
+// a tap's exponent: the payload's colour term xc and the three guide terms between the centre p and the tap q, summed in the header's order
+template <bool ND, bool AL>
+__device__ __forceinline__ float filter_exponent(const FilterArgs& f, float xc, const Guides& p, const Guides& q, float den) {
+  const bool t_n = ND && (f.terms & DN_NORMAL), t_d = ND && (f.terms & DN_DEPTH), t_a = AL && (f.terms & DN_ALBEDO);
+  float xn = 0.0f, xd = 0.0f, xa = 0.0f;
+  if (t_n) { const float dnx = p.nd.x - q.nd.x, dny = p.nd.y - q.nd.y, dnz = p.nd.z - q.nd.z; xn = ((dnx * dnx + dny * dny) + dnz * dnz) * f.k_n; }
+  if (t_d) { const float dz = p.nd.w - q.nd.w; xd = (dz * dz) / den; }
+  if (t_a) { const float dar = p.al.x - q.al.x, dag = p.al.y - q.al.y, dab = p.al.z - q.al.z; xa = ((dar * dar + dag * dag) + dab * dab) * f.k_a; }
+  return ((xc + xn) + xd) + xa;
+}
+
+// ---- the a-trous filter's kernels ----
+struct ATrousArgs {
+  const float* in;  // c_i: [height][width][3] (iteration 0: the caller's colour, or its copy in scratch)
+  float* out;       // c_(i+1)
+  FilterArgs f;     // k_color: k_c of this iteration; terms: DN_DEMOD_IN / DN_REMOD_OUT say whether this launch de- / remodulates
 };
 
 // The prepass: the guide planes the caller handed over, packed into one or two 16-byte records per pixel, so that a tap reads its guides
 // with one or two global_load_dwordx4 instead of up to seven scalar-sized loads from three planes.  A NULL plane packs as 0.
+// (vdn_pack_kernel ends with the same text: behind a shared function it compiles to other registers — profiles/atrous_core_refactor.txt.)
 __global__ __launch_bounds__(256) void atrous_pack_kernel(const float* __restrict__ normal, const float* __restrict__ depth,
                                                           const float* __restrict__ albedo, f4* __restrict__ g_nd, f4* __restrict__ g_al, long long pixels) {
   const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1383,23 +1426,15 @@ __global__ __launch_bounds__(256) void atrous_pack_kernel(const float* __restric
   }
 }
 
-// One iteration, one thread per pixel, a 32 x 8 pixel workgroup (a wave is two rows of 32, so a tap's 64 colour reads from global memory
-// are two runs of 384 contiguous bytes).  ND / AL: the launch reads the (normal, depth) / (albedo) records at all.  STEP = 0: every tap
-// is read from global memory, at the step of the arguments.  STEP = 1, 2: the step is STEP and the workgroup first stages its tile with
-// the halo of 2 STEP pixels in LDS — colour (demodulated once per staged pixel instead of once per tap) and the guide records — and the
-// taps read LDS.  Same operations on the same values in the same order either way: the bits do not depend on the path.
-template <int STEP>
-struct ATrousTile {
-  static constexpr int R = 2 * STEP, TW = 32 + 2 * R, TH = 8 + 2 * R, N = TW * TH;
-};
-
+// The payload: three floats of colour per pixel, demodulated as they are read — in the staged tile once per slot instead of once per tap —
+// a colour term with one scale k_c, and the weighted colour sum.
 template <bool ND, bool AL, int STEP>
 __global__ __launch_bounds__(256) void atrous_kernel(ATrousArgs a) {
-  using T = ATrousTile<STEP>;
+  using T = FilterTile<STEP>;
   const int lx = threadIdx.x & 31, ly = threadIdx.x >> 5;
   const int x = blockIdx.x * 32 + lx, y = blockIdx.y * 8 + ly;
-  const bool demod = AL && (a.terms & DN_DEMOD_IN);
-  const int step = STEP ? STEP : a.step;
+  const bool demod = AL && (a.f.terms & DN_DEMOD_IN);
+  const int step = STEP ? STEP : a.f.step;
   __shared__ float s_r[STEP ? T::N : 1], s_g[STEP ? T::N : 1], s_b[STEP ? T::N : 1];
   __shared__ f4 s_nd[STEP && ND ? T::N : 1], s_al[STEP && AL ? T::N : 1];
   if constexpr (STEP > 0) {
@@ -1407,68 +1442,60 @@ __global__ __launch_bounds__(256) void atrous_kernel(ATrousArgs a) {
     for (int i = threadIdx.x; i < T::N; i += 256) {
       const int gx = x0 + i % T::TW, gy = y0 + i / T::TW;
       float cr = 0.0f, cg = 0.0f, cb = 0.0f;
-      f4 nd = {0.0f, 0.0f, 0.0f, 0.0f}, al = {0.0f, 0.0f, 0.0f, 0.0f};
-      if (gx >= 0 && gx < a.width && gy >= 0 && gy < a.height) { // (a slot outside the frame is never read: its tap is skipped)
-        const long long q = (long long)gy * a.width + gx;
+      Guides g = kNoGuides;
+      if (gx >= 0 && gx < a.f.width && gy >= 0 && gy < a.f.height) { // (a slot outside the frame is never read: its tap is skipped)
+        const long long q = (long long)gy * a.f.width + gx;
         cr = a.in[q * 3]; cg = a.in[q * 3 + 1]; cb = a.in[q * 3 + 2];
-        if (ND) nd = a.g_nd[q];
-        if (AL) al = a.g_al[q];
-        if (demod) { cr = cr / (al.x + 1e-3f); cg = cg / (al.y + 1e-3f); cb = cb / (al.z + 1e-3f); }
+        g = guides_at<ND, AL>(a.f.g_nd, a.f.g_al, q, g);
+        if (demod) { cr = cr / (g.al.x + 1e-3f); cg = cg / (g.al.y + 1e-3f); cb = cb / (g.al.z + 1e-3f); }
       }
       s_r[i] = cr; s_g[i] = cg; s_b[i] = cb;
-      if (ND) s_nd[i] = nd;
-      if (AL) s_al[i] = al;
+      if (ND) s_nd[i] = g.nd;
+      if (AL) s_al[i] = g.al;
     }
     __syncthreads();
   }
-  if (x >= a.width || y >= a.height) return;
-  const long long p = (long long)y * a.width + x;
+  if (x >= a.f.width || y >= a.f.height) return;
+  const long long p = (long long)y * a.f.width + x;
   const int lp = (ly + T::R) * T::TW + lx + T::R; // the pixel's slot in the tile (STEP > 0)
-  const bool t_c = a.terms & DN_COLOR, t_n = ND && (a.terms & DN_NORMAL), t_d = ND && (a.terms & DN_DEPTH), t_a = AL && (a.terms & DN_ALBEDO);
-  f4 ndp = {0.0f, 0.0f, 0.0f, 0.0f}, alp = {0.0f, 0.0f, 0.0f, 0.0f};
+  const bool t_c = a.f.terms & DN_COLOR;
+  Guides gp = kNoGuides;
   float pr, pg, pb;
   if constexpr (STEP > 0) {
-    if (ND) ndp = s_nd[lp];
-    if (AL) alp = s_al[lp];
+    gp = guides_at<ND, AL>(s_nd, s_al, lp, gp);
     pr = s_r[lp]; pg = s_g[lp]; pb = s_b[lp];
   } else {
-    if (ND) ndp = a.g_nd[p];
-    if (AL) alp = a.g_al[p];
+    gp = guides_at<ND, AL>(a.f.g_nd, a.f.g_al, p, gp);
     pr = a.in[p * 3]; pg = a.in[p * 3 + 1]; pb = a.in[p * 3 + 2];
-    if (demod) { pr = pr / (alp.x + 1e-3f); pg = pg / (alp.y + 1e-3f); pb = pb / (alp.z + 1e-3f); }
+    if (demod) { pr = pr / (gp.al.x + 1e-3f); pg = pg / (gp.al.y + 1e-3f); pb = pb / (gp.al.z + 1e-3f); }
   }
-  const float den = a.sd2 * (ndp.w * ndp.w) + 1e-12f;
+  const float den = a.f.sd2 * (gp.nd.w * gp.nd.w) + 1e-12f;
   float sr = 0.0f, sg = 0.0f, sb = 0.0f, ws = 0.0f;
 #pragma unroll
   for (int dy = -2; dy <= 2; dy++) {
     const int qy = y + dy * step;
-    if (qy < 0 || qy >= a.height) continue;
+    if (qy < 0 || qy >= a.f.height) continue;
 #pragma unroll
     for (int dx = -2; dx <= 2; dx++) {
       const int qx = x + dx * step;
-      if (qx < 0 || qx >= a.width) continue;
+      if (qx < 0 || qx >= a.f.width) continue;
       constexpr float K[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
       const float h = K[dy + 2] * K[dx + 2];
       float cr, cg, cb;
-      f4 ndq = ndp, alq = alp;
+      Guides gq;
       if constexpr (STEP > 0) {
         const int lq = lp + dy * STEP * T::TW + dx * STEP; // inside the tile: |dy STEP|, |dx STEP| <= R
         cr = s_r[lq]; cg = s_g[lq]; cb = s_b[lq];
-        if (ND) ndq = s_nd[lq];
-        if (AL) alq = s_al[lq];
+        gq = guides_at<ND, AL>(s_nd, s_al, lq, gp);
       } else {
-        const long long q = (long long)qy * a.width + qx;
+        const long long q = (long long)qy * a.f.width + qx;
         cr = a.in[q * 3]; cg = a.in[q * 3 + 1]; cb = a.in[q * 3 + 2];
-        if (ND) ndq = a.g_nd[q];
-        if (AL) alq = a.g_al[q];
-        if (demod) { cr = cr / (alq.x + 1e-3f); cg = cg / (alq.y + 1e-3f); cb = cb / (alq.z + 1e-3f); }
+        gq = guides_at<ND, AL>(a.f.g_nd, a.f.g_al, q, gp);
+        if (demod) { cr = cr / (gq.al.x + 1e-3f); cg = cg / (gq.al.y + 1e-3f); cb = cb / (gq.al.z + 1e-3f); }
       }
-      float xc = 0.0f, xn = 0.0f, xd = 0.0f, xa = 0.0f;
-      if (t_c) { const float dr = pr - cr, dg = pg - cg, db = pb - cb; xc = ((dr * dr + dg * dg) + db * db) * a.k_c; }
-      if (t_n) { const float dnx = ndp.x - ndq.x, dny = ndp.y - ndq.y, dnz = ndp.z - ndq.z; xn = ((dnx * dnx + dny * dny) + dnz * dnz) * a.k_n; }
-      if (t_d) { const float dz = ndp.w - ndq.w; xd = (dz * dz) / den; }
-      if (t_a) { const float dar = alp.x - alq.x, dag = alp.y - alq.y, dab = alp.z - alq.z; xa = ((dar * dar + dag * dag) + dab * dab) * a.k_a; }
-      const float xs = ((xc + xn) + xd) + xa;
+      float xc = 0.0f;
+      if (t_c) { const float dr = pr - cr, dg = pg - cg, db = pb - cb; xc = ((dr * dr + dg * dg) + db * db) * a.f.k_color; }
+      const float xs = filter_exponent<ND, AL>(a.f, xc, gp, gq, den);
       if (!(xs < 80.0f)) continue;
       const float w = h * exp_neg(xs);
       sr = sr + w * cr; sg = sg + w * cg; sb = sb + w * cb;
@@ -1477,7 +1504,7 @@ __global__ __launch_bounds__(256) void atrous_kernel(ATrousArgs a) {
   }
   float orr = pr, og = pg, ob = pb;
   if (ws != 0.0f) { orr = sr / ws; og = sg / ws; ob = sb / ws; }
-  if (AL && (a.terms & DN_REMOD_OUT)) { orr = orr * (alp.x + 1e-3f); og = og * (alp.y + 1e-3f); ob = ob * (alp.z + 1e-3f); }
+  if (AL && (a.f.terms & DN_REMOD_OUT)) { orr = orr * (gp.al.x + 1e-3f); og = og * (gp.al.y + 1e-3f); ob = ob * (gp.al.z + 1e-3f); }
   a.out[p * 3] = orr; a.out[p * 3 + 1] = og; a.out[p * 3 + 2] = ob;
 }
 
@@ -1517,11 +1544,7 @@ struct VdnArgs {
   f2v* out_b;
   float* out_color; // the last iteration: the caller's planes, [height][width][3]; out_var may be NULL
   float* out_var;
-  const f4* g_nd;   // per pixel (normal, depth); read when ND
-  const f4* g_al;   // per pixel (albedo, 0); read when AL
-  int width, height, step;
-  unsigned terms;   // DN_COLOR ... DN_ALBEDO: which terms are on; DN_REMOD_OUT, VDN_LAST
-  float sv2, k_n, sd2, k_a;
+  FilterArgs f;     // k_color: sv2; terms: DN_COLOR ... DN_ALBEDO, DN_REMOD_OUT, VDN_LAST
 };
 
 // The prepass: c_0 and v_0 — the colour demodulated, the variance sanitised and demodulated — into the working records, and the guide
@@ -1559,21 +1582,15 @@ __global__ __launch_bounds__(256) void vdn_pack_kernel(const float* __restrict__
   }
 }
 
-// One iteration, atrous_kernel's shape: one thread per pixel, a 32 x 8 pixel workgroup, ND / AL as there.  STEP = 0: the prefilter's nine
-// variances and the 25 taps are read from global memory, at the step of the arguments.  STEP = 1, 2: the workgroup stages its tile with
-// the halo of 2 STEP pixels in LDS — 24 bytes of colour and variance and the guide records per pixel; the halo is >= 1, so the tile also
-// serves the 3 x 3 prefilter — and every read is an LDS read.  Same operations on the same values in the same order either way.
-template <int STEP>
-struct VdnTile {
-  static constexpr int R = 2 * STEP, TW = 32 + 2 * R, TH = 8 + 2 * R, N = TW * TH;
-};
-
+// The payload: per pixel a 16-byte record (colour, variance.r) and an 8-byte record (variance.g, variance.b), staged as they are; the
+// tile's halo is >= 1, so it also serves the 3 x 3 prefilter of the variance, whose nine reads are global at STEP = 0 like the 25 taps'; a
+// colour term scaled per channel by the prefiltered variance; the weighted colour sum and the variance sum weighted by w^2.
 template <bool ND, bool AL, int STEP>
 __global__ __launch_bounds__(256) void vdn_kernel(VdnArgs a) {
-  using T = VdnTile<STEP>;
+  using T = FilterTile<STEP>;
   const int lx = threadIdx.x & 31, ly = threadIdx.x >> 5;
   const int x = blockIdx.x * 32 + lx, y = blockIdx.y * 8 + ly;
-  const int step = STEP ? STEP : a.step;
+  const int step = STEP ? STEP : a.f.step;
   __shared__ f4 s_a[STEP ? T::N : 1];
   __shared__ f2v s_b[STEP ? T::N : 1];
   __shared__ f4 s_nd[STEP && ND ? T::N : 1], s_al[STEP && AL ? T::N : 1];
@@ -1581,33 +1598,32 @@ __global__ __launch_bounds__(256) void vdn_kernel(VdnArgs a) {
     const int x0 = blockIdx.x * 32 - T::R, y0 = blockIdx.y * 8 - T::R;
     for (int i = threadIdx.x; i < T::N; i += 256) {
       const int gx = x0 + i % T::TW, gy = y0 + i / T::TW;
-      f4 ra = {0.0f, 0.0f, 0.0f, 0.0f}, nd = {0.0f, 0.0f, 0.0f, 0.0f}, al = {0.0f, 0.0f, 0.0f, 0.0f};
+      f4 ra = {0.0f, 0.0f, 0.0f, 0.0f};
       f2v rb = {0.0f, 0.0f};
-      if (gx >= 0 && gx < a.width && gy >= 0 && gy < a.height) { // (a slot outside the frame is never read: its tap is skipped)
-        const long long q = (long long)gy * a.width + gx;
+      Guides g = kNoGuides;
+      if (gx >= 0 && gx < a.f.width && gy >= 0 && gy < a.f.height) { // (a slot outside the frame is never read: its tap is skipped)
+        const long long q = (long long)gy * a.f.width + gx;
         ra = a.in_a[q]; rb = a.in_b[q];
-        if (ND) nd = a.g_nd[q];
-        if (AL) al = a.g_al[q];
+        g = guides_at<ND, AL>(a.f.g_nd, a.f.g_al, q, g);
       }
       s_a[i] = ra; s_b[i] = rb;
-      if (ND) s_nd[i] = nd;
-      if (AL) s_al[i] = al;
+      if (ND) s_nd[i] = g.nd;
+      if (AL) s_al[i] = g.al;
     }
     __syncthreads();
   }
-  if (x >= a.width || y >= a.height) return;
-  const long long p = (long long)y * a.width + x;
+  if (x >= a.f.width || y >= a.f.height) return;
+  const long long p = (long long)y * a.f.width + x;
   const int lp = (ly + T::R) * T::TW + lx + T::R; // the pixel's slot in the tile (STEP > 0)
-  const bool t_c = a.terms & DN_COLOR, t_n = ND && (a.terms & DN_NORMAL), t_d = ND && (a.terms & DN_DEPTH), t_a = AL && (a.terms & DN_ALBEDO);
-  f4 ndp = {0.0f, 0.0f, 0.0f, 0.0f}, alp = {0.0f, 0.0f, 0.0f, 0.0f}, pa;
+  const bool t_c = a.f.terms & DN_COLOR;
+  Guides gp = kNoGuides;
+  f4 pa;
   f2v pb;
   if constexpr (STEP > 0) {
-    if (ND) ndp = s_nd[lp];
-    if (AL) alp = s_al[lp];
+    gp = guides_at<ND, AL>(s_nd, s_al, lp, gp);
     pa = s_a[lp]; pb = s_b[lp];
   } else {
-    if (ND) ndp = a.g_nd[p];
-    if (AL) alp = a.g_al[p];
+    gp = guides_at<ND, AL>(a.f.g_nd, a.f.g_al, p, gp);
     pa = a.in_a[p]; pb = a.in_b[p];
   }
   // the 3 x 3 prefilter of the variance, at a distance of one pixel whatever the step, and the colour scale it gives
@@ -1617,11 +1633,11 @@ __global__ __launch_bounds__(256) void vdn_kernel(VdnArgs a) {
 #pragma unroll
     for (int dy = -1; dy <= 1; dy++) {
       const int qy = y + dy;
-      if (qy < 0 || qy >= a.height) continue;
+      if (qy < 0 || qy >= a.f.height) continue;
 #pragma unroll
       for (int dx = -1; dx <= 1; dx++) {
         const int qx = x + dx;
-        if (qx < 0 || qx >= a.width) continue;
+        if (qx < 0 || qx >= a.f.width) continue;
         constexpr float G[3] = {0.25f, 0.5f, 0.25f};
         const float g = G[dy + 1] * G[dx + 1];
         float qr;
@@ -1630,7 +1646,7 @@ __global__ __launch_bounds__(256) void vdn_kernel(VdnArgs a) {
           const int lq = lp + dy * T::TW + dx; // inside the tile: R >= 1
           qr = s_a[lq].w; qb = s_b[lq];
         } else {
-          const long long q = (long long)qy * a.width + qx;
+          const long long q = (long long)qy * a.f.width + qx;
           qr = a.in_a[q].w; qb = a.in_b[q];
         }
         vr = vr + g * qr; vg = vg + g * qb.x; vb = vb + g * qb.y;
@@ -1638,39 +1654,35 @@ __global__ __launch_bounds__(256) void vdn_kernel(VdnArgs a) {
       }
     }
     vr = vr / gs; vg = vg / gs; vb = vb / gs;
-    ivr = 1.0f / (a.sv2 * vr + 1e-8f); ivg = 1.0f / (a.sv2 * vg + 1e-8f); ivb = 1.0f / (a.sv2 * vb + 1e-8f);
+    ivr = 1.0f / (a.f.k_color * vr + 1e-8f); ivg = 1.0f / (a.f.k_color * vg + 1e-8f); ivb = 1.0f / (a.f.k_color * vb + 1e-8f);
   }
-  const float den = a.sd2 * (ndp.w * ndp.w) + 1e-12f;
+  const float den = a.f.sd2 * (gp.nd.w * gp.nd.w) + 1e-12f;
   float sr = 0.0f, sg = 0.0f, sb = 0.0f, tr = 0.0f, tg = 0.0f, tb = 0.0f, ws = 0.0f;
 #pragma unroll
   for (int dy = -2; dy <= 2; dy++) {
     const int qy = y + dy * step;
-    if (qy < 0 || qy >= a.height) continue;
+    if (qy < 0 || qy >= a.f.height) continue;
 #pragma unroll
     for (int dx = -2; dx <= 2; dx++) {
       const int qx = x + dx * step;
-      if (qx < 0 || qx >= a.width) continue;
+      if (qx < 0 || qx >= a.f.width) continue;
       constexpr float K[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
       const float h = K[dy + 2] * K[dx + 2];
-      f4 qa, ndq = ndp, alq = alp;
+      f4 qa;
+      Guides gq;
       f2v qb;
       if constexpr (STEP > 0) {
         const int lq = lp + dy * STEP * T::TW + dx * STEP; // inside the tile: |dy STEP|, |dx STEP| <= R
         qa = s_a[lq]; qb = s_b[lq];
-        if (ND) ndq = s_nd[lq];
-        if (AL) alq = s_al[lq];
+        gq = guides_at<ND, AL>(s_nd, s_al, lq, gp);
       } else {
-        const long long q = (long long)qy * a.width + qx;
+        const long long q = (long long)qy * a.f.width + qx;
         qa = a.in_a[q]; qb = a.in_b[q];
-        if (ND) ndq = a.g_nd[q];
-        if (AL) alq = a.g_al[q];
+        gq = guides_at<ND, AL>(a.f.g_nd, a.f.g_al, q, gp);
       }
-      float xc = 0.0f, xn = 0.0f, xd = 0.0f, xa = 0.0f;
+      float xc = 0.0f;
       if (t_c) { const float dr = pa.x - qa.x, dg = pa.y - qa.y, db = pa.z - qa.z; xc = ((dr * dr) * ivr + (dg * dg) * ivg) + (db * db) * ivb; }
-      if (t_n) { const float dnx = ndp.x - ndq.x, dny = ndp.y - ndq.y, dnz = ndp.z - ndq.z; xn = ((dnx * dnx + dny * dny) + dnz * dnz) * a.k_n; }
-      if (t_d) { const float dz = ndp.w - ndq.w; xd = (dz * dz) / den; }
-      if (t_a) { const float dar = alp.x - alq.x, dag = alp.y - alq.y, dab = alp.z - alq.z; xa = ((dar * dar + dag * dag) + dab * dab) * a.k_a; }
-      const float xs = ((xc + xn) + xd) + xa;
+      const float xs = filter_exponent<ND, AL>(a.f, xc, gp, gq, den);
       if (!(xs < 80.0f)) continue;
       const float w = h * exp_neg(xs);
       const float w2 = w * w;
@@ -1685,9 +1697,9 @@ __global__ __launch_bounds__(256) void vdn_kernel(VdnArgs a) {
     orr = sr / ws; og = sg / ws; ob = sb / ws;
     vr = tr / ws2; vg = tg / ws2; vb = tb / ws2;
   }
-  if (a.terms & VDN_LAST) {
-    if (AL && (a.terms & DN_REMOD_OUT)) {
-      const float mr = alp.x + 1e-3f, mg = alp.y + 1e-3f, mb = alp.z + 1e-3f;
+  if (a.f.terms & VDN_LAST) {
+    if (AL && (a.f.terms & DN_REMOD_OUT)) {
+      const float mr = gp.al.x + 1e-3f, mg = gp.al.y + 1e-3f, mb = gp.al.z + 1e-3f;
       orr = orr * mr; og = og * mg; ob = ob * mb;
       vr = vr * (mr * mr); vg = vg * (mg * mg); vb = vb * (mb * mb);
     }
@@ -3385,10 +3397,143 @@ int pt_tonemap_rgb8(const float* fb_device, int32_t width, int32_t height, uint8
   return PT_OK;
 }
 
-// ---- denoiser: pt_denoise (atrous_pack_kernel, atrous_kernel) ---------------------------------------------------------------------
-constexpr int kDenoiseLdsMaxStep = 2; // the largest step whose taps are read from an LDS-staged tile (profiles/denoise_bench.txt: the A/B)
-static std::mutex g_denoise_mutex;
-static int32_t g_last_denoise[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // the last pt_denoise's read path per iteration (pt_debug_last_denoise)
+// ---- the denoisers' host side, once: what pt_denoise and pt_variance_denoise check, decide and launch alike ---------------------------------
+} // extern "C"
+
+namespace {
+// do the bytes [a, a + a_bytes) and [b, b + b_bytes) meet?  A NULL plane meets nothing.
+bool overlaps(const void* a, uintptr_t a_bytes, const void* b, uintptr_t b_bytes) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a && b && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+// the largest step whose reads come from an LDS-staged tile (profiles/denoise_bench.txt, profiles/variance_denoise_bench.txt: the A/Bs)
+constexpr int kFilterLdsMaxStep = 2;
+static_assert(PT_DENOISE_DEMODULATE == PT_VDENOISE_DEMODULATE && PT_DENOISE_NO_LDS == PT_VDENOISE_NO_LDS &&
+              PT_DENOISE_MAX_ITERATIONS == 8 && PT_VDENOISE_MAX_ITERATIONS == 8, "filter_plan reads either filter's flags and iterations");
+
+// an entry point's read path per iteration of its last call (0: not run, 1: global memory, 2: an LDS tile), for its pt_debug_last_* getter
+struct LastPath {
+  std::mutex mutex;
+  int32_t path[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  std::unique_lock<std::mutex> begin() { // a call starts: held while it launches
+    std::unique_lock<std::mutex> lock(mutex);
+    std::memset(path, 0, sizeof path);
+    return lock;
+  }
+  int copy_out(const char* who, int32_t out[8]) {
+    if (!out) return fail(PT_ERR_INVALID_ARG, std::string(who) + ": NULL argument");
+    std::lock_guard<std::mutex> lock(mutex);
+    std::memcpy(out, path, sizeof path);
+    return PT_OK;
+  }
+} g_last_denoise, g_last_vdn;
+
+// k = 1.0f / (sigma * sigma) in binary32, as the header defines it (host arithmetic: IEEE, no excess precision on this target)
+float denoise_k(float sigma) {
+  volatile float s2 = sigma * sigma;
+  volatile float k = 1.0f / s2;
+  return k;
+}
+bool denoise_k_ok(float k) { return std::isfinite(k) && k > 0.0f; }
+
+struct FilterCall { // a call of either entry point: the fields its parameter struct shares with the other's, and the planes both take
+  const char *who, *macro; // "pt_denoise", "PT_DENOISE": for messages
+  int32_t width, height, iterations;
+  float sigma_color, sigma_normal, sigma_depth, sigma_albedo; // sigma_color: the filter's own colour sigma, here only to be finite
+  uint32_t flags;
+  const float *albedo, *normal, *depth;
+  const float* written[2]; // out and the filter's second output plane, or NULL
+  const char* written_names;
+  const float* scratch;
+  int64_t scratch_floats;
+};
+
+struct FilterPlan {
+  unsigned terms = 0; // DN_COLOR ... DN_ALBEDO
+  float k_n = 0.0f, sd2 = 0.0f, k_a = 0.0f;
+  bool demod = false, nd = false, al = false; // nd, al: the launches read the (normal, depth) / (albedo) records
+  int32_t width = 0, height = 0, iterations = 0;
+  int64_t pixels = 0;
+  dim3 grid;
+  int staged[8] = {}; // per iteration: the STEP of its kernel (0: taps from global memory)
+};
+
+// The checks in the order both entry points report them, after their own NULL and struct_size checks; color_k() converts the filter's
+// colour sigma (> 0) where that conversion's error is due and returns what is wrong with it, or NULL.
+template <class ColorK>
+int filter_plan(const FilterCall& c, ColorK&& color_k, FilterPlan& p) {
+  auto bad = [&](const std::string& what) { return fail(PT_ERR_INVALID_ARG, std::string(c.who) + ": " + what); };
+  if (c.width <= 0 || c.height <= 0) return bad("width and height must be > 0");
+  if (c.iterations < 1 || c.iterations > PT_DENOISE_MAX_ITERATIONS) return bad("need 1 <= iterations <= 8");
+  for (float s : {c.sigma_color, c.sigma_normal, c.sigma_depth, c.sigma_albedo})
+    if (!std::isfinite(s)) return bad("a sigma is not finite");
+  if (c.flags & ~(PT_DENOISE_DEMODULATE | PT_DENOISE_NO_LDS)) return bad("unknown flags");
+  p = FilterPlan{};
+  p.demod = c.flags & PT_DENOISE_DEMODULATE;
+  if (p.demod && !c.albedo) return bad(std::string(c.macro) + "_DEMODULATE needs the albedo plane");
+  p.width = c.width; p.height = c.height; p.iterations = c.iterations;
+  if (c.sigma_color > 0.0f) {
+    p.terms |= DN_COLOR;
+    if (const char* what = color_k()) return bad(what);
+  }
+  if (c.sigma_normal > 0.0f && c.normal) {
+    p.terms |= DN_NORMAL;
+    p.k_n = denoise_k(c.sigma_normal);
+    if (!denoise_k_ok(p.k_n)) return bad("1 / sigma_normal^2 leaves binary32");
+  }
+  if (c.sigma_depth > 0.0f && c.depth) {
+    p.terms |= DN_DEPTH;
+    volatile float s2 = c.sigma_depth * c.sigma_depth;
+    p.sd2 = s2;
+    if (!denoise_k_ok(p.sd2)) return bad("sigma_depth^2 leaves binary32");
+  }
+  if (c.sigma_albedo > 0.0f && c.albedo) {
+    p.terms |= DN_ALBEDO;
+    p.k_a = denoise_k(c.sigma_albedo);
+    if (!denoise_k_ok(p.k_a)) return bad("1 / sigma_albedo^2 leaves binary32");
+  }
+  p.pixels = (int64_t)c.width * c.height;
+  if (p.pixels > ((int64_t)1 << 30)) return fail(PT_ERR_TOO_LARGE, std::string(c.who) + ": more than 2^30 pixels");
+  if ((uintptr_t)c.scratch % 16) return bad("scratch must be 16-byte aligned");
+  const uintptr_t frame = (uintptr_t)p.pixels * 12;
+  const struct { const float* p; uintptr_t bytes; } guides[3] = {{c.albedo, frame}, {c.normal, frame}, {c.depth, frame / 3}};
+  for (const auto& g : guides)
+    if (overlaps(c.written[0], frame, g.p, g.bytes) || overlaps(c.written[1], frame, g.p, g.bytes) ||
+        overlaps(c.scratch, (uintptr_t)c.scratch_floats * 4, g.p, g.bytes))
+      return bad(std::string(c.written_names) + " and scratch must not overlap a guide plane");
+  p.nd = p.terms & (DN_NORMAL | DN_DEPTH); p.al = p.demod || (p.terms & DN_ALBEDO);
+  p.grid = dim3((unsigned)((c.width + 31) / 32), (unsigned)((c.height + 7) / 8));
+  // the kernel of an iteration: reads from an LDS-staged tile at the steps 1 and 2 (unless PT_*_NO_LDS), from global memory beyond
+  for (int i = 0; i < c.iterations; i++) p.staged[i] = !(c.flags & PT_DENOISE_NO_LDS) && (1 << i) <= kFilterLdsMaxStep ? 1 << i : 0;
+  return PT_OK;
+}
+
+// a filter kernel's instantiations as [STEP][ND][AL]
+#define PT_FILTER_KERNELS(K)                                                                                   \
+  {{{K<false, false, 0>, K<false, true, 0>}, {K<true, false, 0>, K<true, true, 0>}},                           \
+   {{K<false, false, 1>, K<false, true, 1>}, {K<true, false, 1>, K<true, true, 1>}},                           \
+   {{K<false, false, 2>, K<false, true, 2>}, {K<true, false, 2>, K<true, true, 2>}}}
+
+// The iterations: fill(a, i) completes iteration i's arguments — its planes, a.f.g_nd / g_al, a.f.k_color and its own bits of a.f.terms.
+template <class Args, class Fill>
+int filter_launch(const FilterPlan& p, void (*const (&kernels)[3][2][2])(Args), LastPath& last, hipStream_t st, Fill&& fill) {
+  for (int i = 0; i < p.iterations; i++) {
+    Args a;
+    a.f.width = p.width; a.f.height = p.height; a.f.step = 1 << i;
+    a.f.terms = p.terms; a.f.k_n = p.k_n; a.f.sd2 = p.sd2; a.f.k_a = p.k_a;
+    fill(a, i);
+    hipLaunchKernelGGL(kernels[p.staged[i]][p.nd ? 1 : 0][p.al ? 1 : 0], p.grid, dim3(256), 0, st, a);
+    PT_HIP(hipGetLastError());
+    last.path[i] = p.staged[i] ? 2 : 1;
+  }
+  return PT_OK;
+}
+} // namespace
+
+extern "C" {
+
+// ---- denoiser: pt_denoise (atrous_pack_kernel, atrous_kernel): its colour ladder k_c(i), its scratch of one colour plane ---------------------
 
 void pt_denoise_params_init(PtDenoiseParams* params, int32_t width, int32_t height) {
   if (!params) return;
@@ -3410,122 +3555,61 @@ int64_t pt_denoise_scratch_floats(int32_t width, int32_t height) {
   return denoise_color_floats(pixels) + 8 * pixels;
 }
 
-// k = 1.0f / (sigma * sigma) in binary32, as the header defines it (host arithmetic: IEEE, no excess precision on this target)
-static float denoise_k(float sigma) {
-  volatile float s2 = sigma * sigma;
-  volatile float k = 1.0f / s2;
-  return k;
-}
-static bool denoise_k_ok(float k) { return std::isfinite(k) && k > 0.0f; }
-
 int pt_denoise(const PtDenoiseParams* params, const float* color, const float* albedo, const float* normal, const float* depth,
                float* out, float* scratch, void* stream) {
   if (!params || !color || !out || !scratch) return fail(PT_ERR_INVALID_ARG, "pt_denoise: NULL params, color, out or scratch");
   if (params->struct_size != (int32_t)sizeof(PtDenoiseParams)) return fail(PT_ERR_INVALID_ARG, "pt_denoise: PtDenoiseParams.struct_size is not this library's");
-  if (params->width <= 0 || params->height <= 0) return fail(PT_ERR_INVALID_ARG, "pt_denoise: width and height must be > 0");
-  if (params->iterations < 1 || params->iterations > PT_DENOISE_MAX_ITERATIONS) return fail(PT_ERR_INVALID_ARG, "pt_denoise: need 1 <= iterations <= 8");
-  const float sigmas[4] = {params->sigma_color, params->sigma_normal, params->sigma_depth, params->sigma_albedo};
-  for (float s : sigmas)
-    if (!std::isfinite(s)) return fail(PT_ERR_INVALID_ARG, "pt_denoise: a sigma is not finite");
-  if (params->flags & ~(PT_DENOISE_DEMODULATE | PT_DENOISE_NO_LDS)) return fail(PT_ERR_INVALID_ARG, "pt_denoise: unknown flags");
-  const bool demod = params->flags & PT_DENOISE_DEMODULATE;
-  if (demod && !albedo) return fail(PT_ERR_INVALID_ARG, "pt_denoise: PT_DENOISE_DEMODULATE needs the albedo plane");
   const int n_it = params->iterations;
-  unsigned terms = 0;
-  float k_c[PT_DENOISE_MAX_ITERATIONS] = {}, k_n = 0.0f, sd2 = 0.0f, k_a = 0.0f;
-  if (params->sigma_color > 0.0f) {
-    terms |= DN_COLOR;
-    for (int i = 0; i < n_it; i++) {
-      k_c[i] = denoise_k(std::ldexp(params->sigma_color, -i)); // sigma_color * 2^-i: exact (or rounded once into the denormals, whose k is refused)
-      if (!denoise_k_ok(k_c[i])) return fail(PT_ERR_INVALID_ARG, "pt_denoise: 1 / sigma_color^2 leaves binary32 at one of the iterations");
-    }
-  }
-  if (params->sigma_normal > 0.0f && normal) {
-    terms |= DN_NORMAL;
-    k_n = denoise_k(params->sigma_normal);
-    if (!denoise_k_ok(k_n)) return fail(PT_ERR_INVALID_ARG, "pt_denoise: 1 / sigma_normal^2 leaves binary32");
-  }
-  if (params->sigma_depth > 0.0f && depth) {
-    terms |= DN_DEPTH;
-    volatile float s2 = params->sigma_depth * params->sigma_depth;
-    sd2 = s2;
-    if (!denoise_k_ok(sd2)) return fail(PT_ERR_INVALID_ARG, "pt_denoise: sigma_depth^2 leaves binary32");
-  }
-  if (params->sigma_albedo > 0.0f && albedo) {
-    terms |= DN_ALBEDO;
-    k_a = denoise_k(params->sigma_albedo);
-    if (!denoise_k_ok(k_a)) return fail(PT_ERR_INVALID_ARG, "pt_denoise: 1 / sigma_albedo^2 leaves binary32");
-  }
-  const int64_t pixels = (int64_t)params->width * params->height;
-  if (pixels > ((int64_t)1 << 30)) return fail(PT_ERR_TOO_LARGE, "pt_denoise: more than 2^30 pixels");
   const int64_t scratch_floats = pt_denoise_scratch_floats(params->width, params->height);
-  if ((uintptr_t)scratch % 16) return fail(PT_ERR_INVALID_ARG, "pt_denoise: scratch must be 16-byte aligned");
-  auto overlap = [](const void* a, int64_t a_floats, const void* b, int64_t b_floats) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a && b && a0 < b0 + (uintptr_t)b_floats * 4 && b0 < a0 + (uintptr_t)a_floats * 4;
-  };
-  const struct { const float* p; int64_t floats; } guides[3] = {{albedo, pixels * 3}, {normal, pixels * 3}, {depth, pixels}};
-  for (const auto& g : guides)
-    if (overlap(out, pixels * 3, g.p, g.floats) || overlap(scratch, scratch_floats, g.p, g.floats))
-      return fail(PT_ERR_INVALID_ARG, "pt_denoise: out and scratch must not overlap a guide plane");
-  if (overlap(scratch, scratch_floats, color, pixels * 3) || overlap(scratch, scratch_floats, out, pixels * 3))
+  float k_c[PT_DENOISE_MAX_ITERATIONS] = {};
+  FilterPlan plan;
+  const int rc = filter_plan({"pt_denoise", "PT_DENOISE", params->width, params->height, n_it, params->sigma_color, params->sigma_normal,
+                              params->sigma_depth, params->sigma_albedo, params->flags, albedo, normal, depth, {out, nullptr}, "out", scratch,
+                              scratch_floats},
+                             [&]() -> const char* {
+                               for (int i = 0; i < n_it; i++) {
+                                 k_c[i] = denoise_k(std::ldexp(params->sigma_color, -i)); // sigma_color * 2^-i: exact (or rounded once into the denormals, whose k is refused)
+                                 if (!denoise_k_ok(k_c[i])) return "1 / sigma_color^2 leaves binary32 at one of the iterations";
+                               }
+                               return nullptr;
+                             }, plan);
+  if (rc) return rc;
+  const int64_t pixels = plan.pixels;
+  const uintptr_t frame = (uintptr_t)pixels * 12;
+  if (overlaps(scratch, (uintptr_t)scratch_floats * 4, color, frame) || overlaps(scratch, (uintptr_t)scratch_floats * 4, out, frame))
     return fail(PT_ERR_INVALID_ARG, "pt_denoise: scratch must not overlap color or out");
 
   hipStream_t st = (hipStream_t)stream;
   float* const plane = scratch; // the colour plane the iterations ping-pong with `out`
   f4* const g_nd = reinterpret_cast<f4*>(scratch + denoise_color_floats(pixels));
   f4* const g_al = g_nd + pixels;
-  const bool nd = terms & (DN_NORMAL | DN_DEPTH), al = demod || (terms & DN_ALBEDO);
-  std::lock_guard<std::mutex> lock(g_denoise_mutex);
-  std::memset(g_last_denoise, 0, sizeof g_last_denoise);
-  if (nd || al) {
-    hipLaunchKernelGGL(atrous_pack_kernel, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, st, (terms & DN_NORMAL) ? normal : nullptr,
-                       (terms & DN_DEPTH) ? depth : nullptr, albedo, nd ? g_nd : nullptr, al ? g_al : nullptr, (long long)pixels);
+  const auto lock = g_last_denoise.begin();
+  if (plan.nd || plan.al) {
+    hipLaunchKernelGGL(atrous_pack_kernel, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, st, (plan.terms & DN_NORMAL) ? normal : nullptr,
+                       (plan.terms & DN_DEPTH) ? depth : nullptr, albedo, plan.nd ? g_nd : nullptr, plan.al ? g_al : nullptr, (long long)pixels);
     PT_HIP(hipGetLastError());
   }
   // Iteration i writes `out` when an even number of iterations follows it and the scratch plane otherwise, so the last one writes `out`.
   // With an odd count the first would read `color` while writing `out`: where the two overlap it reads a copy in the scratch plane.
   const float* src = color;
-  if (n_it % 2 == 1 && overlap(out, pixels * 3, color, pixels * 3)) {
+  if (n_it % 2 == 1 && overlaps(out, frame, color, frame)) {
     PT_HIP(hipMemcpyAsync(plane, color, (size_t)pixels * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
     src = plane;
   }
-  // the kernel of an iteration: taps from an LDS-staged tile at the steps 1 and 2 (unless PT_DENOISE_NO_LDS), from global memory beyond
-  using Kernel = void (*)(ATrousArgs);
-  static const Kernel kernels[3][2][2] = {
-      {{atrous_kernel<false, false, 0>, atrous_kernel<false, true, 0>}, {atrous_kernel<true, false, 0>, atrous_kernel<true, true, 0>}},
-      {{atrous_kernel<false, false, 1>, atrous_kernel<false, true, 1>}, {atrous_kernel<true, false, 1>, atrous_kernel<true, true, 1>}},
-      {{atrous_kernel<false, false, 2>, atrous_kernel<false, true, 2>}, {atrous_kernel<true, false, 2>, atrous_kernel<true, true, 2>}}};
-  const bool lds_ok = !(params->flags & PT_DENOISE_NO_LDS);
-  const dim3 grid((unsigned)((params->width + 31) / 32), (unsigned)((params->height + 7) / 8));
-  for (int i = 0; i < n_it; i++) {
-    ATrousArgs a;
+  static void (*const kernels[3][2][2])(ATrousArgs) = PT_FILTER_KERNELS(atrous_kernel);
+  return filter_launch(plan, kernels, g_last_denoise, st, [&](ATrousArgs& a, int i) {
     a.in = src;
     a.out = (n_it - 1 - i) % 2 == 0 ? out : plane;
-    a.g_nd = g_nd; a.g_al = g_al;
-    a.width = params->width; a.height = params->height; a.step = 1 << i;
-    a.terms = terms | (demod && i == 0 ? DN_DEMOD_IN : 0) | (demod && i == n_it - 1 ? DN_REMOD_OUT : 0);
-    a.k_c = k_c[i]; a.k_n = k_n; a.sd2 = sd2; a.k_a = k_a;
-    const int staged = lds_ok && a.step <= kDenoiseLdsMaxStep ? a.step : 0;
-    hipLaunchKernelGGL(kernels[staged][nd ? 1 : 0][al ? 1 : 0], grid, dim3(256), 0, st, a);
-    PT_HIP(hipGetLastError());
-    g_last_denoise[i] = staged ? 2 : 1;
+    a.f.g_nd = g_nd; a.f.g_al = g_al;
+    a.f.terms |= (plan.demod && i == 0 ? DN_DEMOD_IN : 0) | (plan.demod && i == n_it - 1 ? DN_REMOD_OUT : 0);
+    a.f.k_color = k_c[i];
     src = a.out;
-  }
-  return PT_OK;
+  });
 }
 
-int pt_debug_last_denoise(int32_t out[8]) {
-  if (!out) return fail(PT_ERR_INVALID_ARG, "pt_debug_last_denoise: NULL argument");
-  std::lock_guard<std::mutex> lock(g_denoise_mutex);
-  std::memcpy(out, g_last_denoise, sizeof g_last_denoise);
-  return PT_OK;
-}
+int pt_debug_last_denoise(int32_t out[8]) { return g_last_denoise.copy_out("pt_debug_last_denoise", out); }
 
-// ---- variance-guided denoiser: pt_variance_denoise (vdn_pack_kernel, vdn_kernel) ------------------------------------------------------
-constexpr int kVdnLdsMaxStep = 2; // the largest step whose reads come from an LDS-staged tile (profiles/variance_denoise_bench.txt: the A/B)
-static std::mutex g_vdn_mutex;
-static int32_t g_last_vdn[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // the last pt_variance_denoise's read path per iteration
+// ---- variance-guided denoiser: pt_variance_denoise (vdn_pack_kernel, vdn_kernel): its sv2, its variance planes, its scratch of records ------
 
 void pt_variance_denoise_params_init(PtVarianceDenoiseParams* params, int32_t width, int32_t height) {
   if (!params) return;
@@ -3546,60 +3630,27 @@ int64_t pt_variance_denoise_scratch_floats(int32_t width, int32_t height) {
 
 int pt_variance_denoise(const PtVarianceDenoiseParams* params, const float* color, const float* variance, const float* albedo,
                         const float* normal, const float* depth, float* out, float* variance_out, float* scratch, void* stream) {
-  const char* const who = "pt_variance_denoise: ";
-  auto bad = [&](const char* what) { return fail(PT_ERR_INVALID_ARG, std::string(who) + what); };
+  auto bad = [&](const char* what) { return fail(PT_ERR_INVALID_ARG, std::string("pt_variance_denoise: ") + what); };
   if (!params || !color || !variance || !out || !scratch) return bad("NULL params, color, variance, out or scratch");
   if (params->struct_size != (int32_t)sizeof(PtVarianceDenoiseParams)) return bad("PtVarianceDenoiseParams.struct_size is not this library's");
-  if (params->width <= 0 || params->height <= 0) return bad("width and height must be > 0");
-  if (params->iterations < 1 || params->iterations > PT_VDENOISE_MAX_ITERATIONS) return bad("need 1 <= iterations <= 8");
-  const float sigmas[4] = {params->sigma_variance, params->sigma_normal, params->sigma_depth, params->sigma_albedo};
-  for (float s : sigmas)
-    if (!std::isfinite(s)) return bad("a sigma is not finite");
-  if (params->flags & ~(PT_VDENOISE_DEMODULATE | PT_VDENOISE_NO_LDS)) return bad("unknown flags");
-  const bool demod = params->flags & PT_VDENOISE_DEMODULATE;
-  if (demod && !albedo) return bad("PT_VDENOISE_DEMODULATE needs the albedo plane");
-  const int n_it = params->iterations;
-  unsigned terms = 0;
-  float sv2 = 0.0f, k_n = 0.0f, sd2 = 0.0f, k_a = 0.0f;
-  if (params->sigma_variance > 0.0f) {
-    terms |= DN_COLOR;
-    volatile float s2 = params->sigma_variance * params->sigma_variance;
-    sv2 = s2;
-    if (!denoise_k_ok(sv2) || !denoise_k_ok(denoise_k(params->sigma_variance))) return bad("sigma_variance^2 or its reciprocal leaves binary32");
-  }
-  if (params->sigma_normal > 0.0f && normal) {
-    terms |= DN_NORMAL;
-    k_n = denoise_k(params->sigma_normal);
-    if (!denoise_k_ok(k_n)) return bad("1 / sigma_normal^2 leaves binary32");
-  }
-  if (params->sigma_depth > 0.0f && depth) {
-    terms |= DN_DEPTH;
-    volatile float s2 = params->sigma_depth * params->sigma_depth;
-    sd2 = s2;
-    if (!denoise_k_ok(sd2)) return bad("sigma_depth^2 leaves binary32");
-  }
-  if (params->sigma_albedo > 0.0f && albedo) {
-    terms |= DN_ALBEDO;
-    k_a = denoise_k(params->sigma_albedo);
-    if (!denoise_k_ok(k_a)) return bad("1 / sigma_albedo^2 leaves binary32");
-  }
-  const int64_t pixels = (int64_t)params->width * params->height;
-  if (pixels > ((int64_t)1 << 30)) return fail(PT_ERR_TOO_LARGE, std::string(who) + "more than 2^30 pixels");
   const int64_t scratch_floats = pt_variance_denoise_scratch_floats(params->width, params->height);
-  if ((uintptr_t)scratch % 16) return bad("scratch must be 16-byte aligned");
-  auto overlap = [](const void* a, int64_t a_floats, const void* b, int64_t b_floats) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a && b && a0 < b0 + (uintptr_t)b_floats * 4 && b0 < a0 + (uintptr_t)a_floats * 4;
-  };
-  const struct { const float* p; int64_t floats; } guides[3] = {{albedo, pixels * 3}, {normal, pixels * 3}, {depth, pixels}};
-  for (const auto& g : guides)
-    if (overlap(out, pixels * 3, g.p, g.floats) || overlap(variance_out, pixels * 3, g.p, g.floats) || overlap(scratch, scratch_floats, g.p, g.floats))
-      return bad("out, variance_out and scratch must not overlap a guide plane");
-  const float* const frames[4] = {color, variance, out, variance_out};
-  for (const float* f : frames)
-    if (overlap(scratch, scratch_floats, f, pixels * 3)) return bad("scratch must not overlap color, variance, out or variance_out");
-  if (overlap(variance_out, pixels * 3, color, pixels * 3) || overlap(variance_out, pixels * 3, out, pixels * 3))
-    return bad("variance_out must not overlap color or out");
+  float sv2 = 0.0f;
+  FilterPlan plan;
+  const int rc = filter_plan({"pt_variance_denoise", "PT_VDENOISE", params->width, params->height, params->iterations, params->sigma_variance,
+                              params->sigma_normal, params->sigma_depth, params->sigma_albedo, params->flags, albedo, normal, depth,
+                              {out, variance_out}, "out, variance_out", scratch, scratch_floats},
+                             [&]() -> const char* {
+                               volatile float s2 = params->sigma_variance * params->sigma_variance;
+                               sv2 = s2;
+                               const bool ok = denoise_k_ok(sv2) && denoise_k_ok(denoise_k(params->sigma_variance));
+                               return ok ? nullptr : "sigma_variance^2 or its reciprocal leaves binary32";
+                             }, plan);
+  if (rc) return rc;
+  const int64_t pixels = plan.pixels;
+  const uintptr_t frame = (uintptr_t)pixels * 12;
+  for (const float* f : {color, variance, (const float*)out, (const float*)variance_out})
+    if (overlaps(scratch, (uintptr_t)scratch_floats * 4, f, frame)) return bad("scratch must not overlap color, variance, out or variance_out");
+  if (overlaps(variance_out, frame, color, frame) || overlaps(variance_out, frame, out, frame)) return bad("variance_out must not overlap color or out");
 
   hipStream_t st = (hipStream_t)stream;
   // scratch: [A0 | A1 | g_nd | g_al] 16-byte records, then [B0 | B1] 8-byte records
@@ -3607,44 +3658,24 @@ int pt_variance_denoise(const PtVarianceDenoiseParams* params, const float* colo
   f4* const g_nd = rec_a[1] + pixels;
   f4* const g_al = g_nd + pixels;
   f2v* const rec_b[2] = {reinterpret_cast<f2v*>(g_al + pixels), reinterpret_cast<f2v*>(g_al + pixels) + pixels};
-  const bool nd = terms & (DN_NORMAL | DN_DEPTH), al = demod || (terms & DN_ALBEDO);
-  std::lock_guard<std::mutex> lock(g_vdn_mutex);
-  std::memset(g_last_vdn, 0, sizeof g_last_vdn);
-  hipLaunchKernelGGL(vdn_pack_kernel, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, st, color, variance, (terms & DN_NORMAL) ? normal : nullptr,
-                     (terms & DN_DEPTH) ? depth : nullptr, albedo, rec_a[0], rec_b[0], nd ? g_nd : nullptr, al ? g_al : nullptr, (long long)pixels,
-                     demod ? 1 : 0);
+  const auto lock = g_last_vdn.begin();
+  hipLaunchKernelGGL(vdn_pack_kernel, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, st, color, variance, (plan.terms & DN_NORMAL) ? normal : nullptr,
+                     (plan.terms & DN_DEPTH) ? depth : nullptr, albedo, rec_a[0], rec_b[0], plan.nd ? g_nd : nullptr, plan.al ? g_al : nullptr,
+                     (long long)pixels, plan.demod ? 1 : 0);
   PT_HIP(hipGetLastError());
-  using Kernel = void (*)(VdnArgs);
-  static const Kernel kernels[3][2][2] = {
-      {{vdn_kernel<false, false, 0>, vdn_kernel<false, true, 0>}, {vdn_kernel<true, false, 0>, vdn_kernel<true, true, 0>}},
-      {{vdn_kernel<false, false, 1>, vdn_kernel<false, true, 1>}, {vdn_kernel<true, false, 1>, vdn_kernel<true, true, 1>}},
-      {{vdn_kernel<false, false, 2>, vdn_kernel<false, true, 2>}, {vdn_kernel<true, false, 2>, vdn_kernel<true, true, 2>}}};
-  const bool lds_ok = !(params->flags & PT_VDENOISE_NO_LDS);
-  const dim3 grid((unsigned)((params->width + 31) / 32), (unsigned)((params->height + 7) / 8));
-  for (int i = 0; i < n_it; i++) {
-    const bool last = i == n_it - 1;
-    VdnArgs a;
+  static void (*const kernels[3][2][2])(VdnArgs) = PT_FILTER_KERNELS(vdn_kernel);
+  return filter_launch(plan, kernels, g_last_vdn, st, [&](VdnArgs& a, int i) {
+    const bool last = i == plan.iterations - 1;
     a.in_a = rec_a[i % 2]; a.in_b = rec_b[i % 2];
     a.out_a = rec_a[(i + 1) % 2]; a.out_b = rec_b[(i + 1) % 2];
     a.out_color = out; a.out_var = variance_out;
-    a.g_nd = g_nd; a.g_al = g_al;
-    a.width = params->width; a.height = params->height; a.step = 1 << i;
-    a.terms = terms | (last ? VDN_LAST : 0) | (demod && last ? DN_REMOD_OUT : 0);
-    a.sv2 = sv2; a.k_n = k_n; a.sd2 = sd2; a.k_a = k_a;
-    const int staged = lds_ok && a.step <= kVdnLdsMaxStep ? a.step : 0;
-    hipLaunchKernelGGL(kernels[staged][nd ? 1 : 0][al ? 1 : 0], grid, dim3(256), 0, st, a);
-    PT_HIP(hipGetLastError());
-    g_last_vdn[i] = staged ? 2 : 1;
-  }
-  return PT_OK;
+    a.f.g_nd = g_nd; a.f.g_al = g_al;
+    a.f.terms |= (last ? VDN_LAST : 0) | (plan.demod && last ? DN_REMOD_OUT : 0);
+    a.f.k_color = sv2;
+  });
 }
 
-int pt_debug_last_variance_denoise(int32_t out[8]) {
-  if (!out) return fail(PT_ERR_INVALID_ARG, "pt_debug_last_variance_denoise: NULL argument");
-  std::lock_guard<std::mutex> lock(g_vdn_mutex);
-  std::memcpy(out, g_last_vdn, sizeof g_last_vdn);
-  return PT_OK;
-}
+int pt_debug_last_variance_denoise(int32_t out[8]) { return g_last_vdn.copy_out("pt_debug_last_variance_denoise", out); }
 
 // ---- temporal reprojection: PtTemporal, pt_temporal_push (temporal_push_kernel) -------------------------------------------------------
 } // extern "C"
@@ -3735,18 +3766,15 @@ int pt_temporal_push(PtTemporal* t, const PtTemporalParams* params, const PtCame
   if (params->flags) return bad("unknown flags");
   if (!temporal_consts(*cam).ok) return bad("a degenerate camera (fo, hh or vv is not a finite number > 0)");
   const long long pixels = t->pixels;
-  auto overlap = [](const void* a, int64_t a_floats, const void* b, int64_t b_floats) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a && b && a0 < b0 + (uintptr_t)b_floats * 4 && b0 < a0 + (uintptr_t)a_floats * 4;
-  };
-  const struct { const void* p; int64_t floats; } outs[3] = {{out_color, pixels * 3}, {out_variance, pixels * 3}, {out_history, pixels}},
-                                                  guides[3] = {{depth, pixels}, {normal, pixels * 3}, {id, pixels}};
+  const uintptr_t plane = (uintptr_t)pixels * 4;
+  const struct { const void* p; uintptr_t bytes; } outs[3] = {{out_color, plane * 3}, {out_variance, plane * 3}, {out_history, plane}},
+                                                   guides[3] = {{depth, plane}, {normal, plane * 3}, {id, plane}};
   for (const auto& o : outs)
     for (const auto& g : guides)
-      if (overlap(o.p, o.floats, g.p, g.floats)) return bad("an out plane overlaps a guide plane");
+      if (overlaps(o.p, o.bytes, g.p, g.bytes)) return bad("an out plane overlaps a guide plane");
   for (int i = 0; i < 3; i++)
     for (int j = i + 1; j < 3; j++)
-      if (overlap(outs[i].p, outs[i].floats, outs[j].p, outs[j].floats)) return bad("the out planes overlap one another");
+      if (overlaps(outs[i].p, outs[i].bytes, outs[j].p, outs[j].bytes)) return bad("the out planes overlap one another");
 
   TemporalArgs a;
   a.color = color; a.depth = depth; a.normal = normal; a.id = id; a.var_in = variance_in;
@@ -3898,12 +3926,8 @@ int pt_display_apply(const PtDisplay* d, const PtDisplayParams* p, const float* 
   auto bad = [&](const char* what) { return fail(PT_ERR_INVALID_ARG, std::string("pt_display_apply: ") + what); };
   if (!rgb8_out && !linear_out) return bad("rgb8_out and linear_out are both NULL");
   const uintptr_t values = (uintptr_t)width * (uintptr_t)height * 3;
-  auto overlap = [](const void* a, uintptr_t a_bytes, const void* b, uintptr_t b_bytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a && b && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-  };
-  if (overlap(rgb8_out, values, color, values * 4) || overlap(rgb8_out, values, linear_out, values * 4)) return bad("rgb8_out overlaps color or linear_out");
-  if (linear_out != color && overlap(linear_out, values * 4, color, values * 4)) return bad("linear_out overlaps color without being color");
+  if (overlaps(rgb8_out, values, color, values * 4) || overlaps(rgb8_out, values, linear_out, values * 4)) return bad("rgb8_out overlaps color or linear_out");
+  if (linear_out != color && overlaps(linear_out, values * 4, color, values * 4)) return bad("linear_out overlaps color without being color");
   const float ev = std::fmin(std::fmax(p->ev_bias, -32.0f), 32.0f);
   const unsigned* state = d ? d->words.p : nullptr;
   // four values per thread where the rows and the planes allow 16-byte loads and stores

@@ -159,6 +159,40 @@ def render_aov(width: int, height: int, samples: int, scene, cam: camera, *, pla
     return out
 
 
+def _filter_call(me, entry, has, stage, fb, out, other_planes, **needed):
+    """What denoise() and denoise_variance() (`me`) do before they call `entry`: the device and entry-point checks, the unknown keywords,
+    the frame's shape, the planes in `needed` that must not be None, `out` and the scratch.  Returns the library, the plane checker
+    (tensor or None -> pointer or None), H, W, out, the scratch tensor (the caller keeps it alive across the call) and the stream."""
+    import torch
+
+    if not torch.cuda.is_available():
+        raise RuntimeError(f"path_tracer_amd.{me} needs a HIP device: there is no CPU path in the product")
+    lib = abi.load_library()
+    if not has(lib):
+        raise ImportError(f"{abi.library_path()} predates the {stage} (no {entry} entry point)")
+    unknown = set(other_planes) - set(abi.AOV_PLANES)
+    if unknown:
+        raise TypeError(f"{me}() got unexpected keyword arguments {sorted(unknown)}")
+
+    def plane(t, shape, what):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()):
+            raise ValueError(f"{what} must be a contiguous float32 CUDA tensor of shape {shape}")
+        return C.c_void_p(t.data_ptr()) if t is not None else None
+
+    if fb.dim() != 3 or fb.shape[2] != 3:
+        raise ValueError("fb must be a whole frame [H][W][3] (gather and unshard a multi-GPU frame first)")
+    for what, t in needed.items():
+        if t is None:
+            raise ValueError(f"{what} must be a contiguous float32 CUDA tensor shaped like fb")
+    h, w, _ = (int(n) for n in fb.shape)
+    if out is None:
+        out = torch.empty((h, w, 3), dtype=torch.float32, device=fb.device)
+    n = getattr(lib, entry + "_scratch_floats")(w, h)
+    if n < 0:
+        abi.check(abi.PT_ERR_INVALID_ARG, entry + "_scratch_floats")
+    return lib, plane, h, w, out, torch.empty(n, dtype=torch.float32, device=fb.device), _stream_ptr(torch)
+
+
 def denoise(fb, *, albedo=None, normal=None, depth=None, iterations: int = abi.PT_DENOISE_DEFAULT_ITERATIONS,
             sigma_color: float = abi.PT_DENOISE_DEFAULT_SIGMA_COLOR, sigma_normal: float = abi.PT_DENOISE_DEFAULT_SIGMA_NORMAL,
             sigma_depth: float = abi.PT_DENOISE_DEFAULT_SIGMA_DEPTH, sigma_albedo: float = abi.PT_DENOISE_DEFAULT_SIGMA_ALBEDO,
@@ -170,36 +204,11 @@ def denoise(fb, *, albedo=None, normal=None, depth=None, iterations: int = abi.P
     `no_lds`: the A/B switch PT_DENOISE_NO_LDS (every tap from global memory; the same bits).
     Asynchronous on torch's current stream; torch allocates the scratch.  Returns the filtered frame — `out` if given, which may be
     `fb` itself."""
-    import torch
-
-    if not torch.cuda.is_available():
-        raise RuntimeError("path_tracer_amd.denoise needs a HIP device: there is no CPU path in the product")
-    lib = abi.load_library()
-    if not abi.has_denoise(lib):
-        raise ImportError(f"{abi.library_path()} predates the denoiser (no pt_denoise entry point)")
-    unknown = set(other_planes) - set(abi.AOV_PLANES)
-    if unknown:
-        raise TypeError(f"denoise() got unexpected keyword arguments {sorted(unknown)}")
-
-    def plane(t, shape, what):
-        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()):
-            raise ValueError(f"{what} must be a contiguous float32 CUDA tensor of shape {shape}")
-        return C.c_void_p(t.data_ptr()) if t is not None else None
-
-    if fb.dim() != 3 or fb.shape[2] != 3:
-        raise ValueError("fb must be a whole frame [H][W][3] (gather and unshard a multi-GPU frame first)")
-    h, w, _ = (int(n) for n in fb.shape)
-    if out is None:
-        out = torch.empty((h, w, 3), dtype=torch.float32, device=fb.device)
-    n = lib.pt_denoise_scratch_floats(w, h)
-    if n < 0:
-        abi.check(abi.PT_ERR_INVALID_ARG, "pt_denoise_scratch_floats")
-    scratch = torch.empty(n, dtype=torch.float32, device=fb.device)
+    lib, plane, h, w, out, scratch, stream = _filter_call("denoise", "pt_denoise", abi.has_denoise, "denoiser", fb, out, other_planes)
     p = abi.PtDenoiseParams(C.sizeof(abi.PtDenoiseParams), w, h, int(iterations), float(sigma_color), float(sigma_normal), float(sigma_depth),
                             float(sigma_albedo), (abi.PT_DENOISE_DEMODULATE if demodulate else 0) | (abi.PT_DENOISE_NO_LDS if no_lds else 0), 0)
     abi.check(lib.pt_denoise(C.byref(p), plane(fb, (h, w, 3), "fb"), plane(albedo, (h, w, 3), "albedo"), plane(normal, (h, w, 3), "normal"),
-                             plane(depth, (h, w), "depth"), plane(out, (h, w, 3), "out"), C.c_void_p(scratch.data_ptr()), _stream_ptr(torch)),
-              "pt_denoise")
+                             plane(depth, (h, w), "depth"), plane(out, (h, w, 3), "out"), C.c_void_p(scratch.data_ptr()), stream), "pt_denoise")
     return out
 
 
@@ -214,40 +223,15 @@ def denoise_variance(fb, variance, *, albedo=None, normal=None, depth=None, iter
     in standard deviations (<= 0: guide-only).  `variance_out` (optional, may be `variance`) receives the filtered frame's residual
     variance.  Asynchronous on torch's current stream; torch allocates the scratch.  Returns the filtered frame — `out` if given, which
     may be `fb` itself."""
-    import torch
-
-    if not torch.cuda.is_available():
-        raise RuntimeError("path_tracer_amd.denoise_variance needs a HIP device: there is no CPU path in the product")
-    lib = abi.load_library()
-    if not abi.has_variance_denoise(lib):
-        raise ImportError(f"{abi.library_path()} predates the variance-guided denoiser (no pt_variance_denoise entry point)")
-    unknown = set(other_planes) - set(abi.AOV_PLANES)
-    if unknown:
-        raise TypeError(f"denoise_variance() got unexpected keyword arguments {sorted(unknown)}")
-
-    def plane(t, shape, what):
-        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()):
-            raise ValueError(f"{what} must be a contiguous float32 CUDA tensor of shape {shape}")
-        return C.c_void_p(t.data_ptr()) if t is not None else None
-
-    if fb.dim() != 3 or fb.shape[2] != 3:
-        raise ValueError("fb must be a whole frame [H][W][3] (gather and unshard a multi-GPU frame first)")
-    if variance is None:
-        raise ValueError("variance must be a contiguous float32 CUDA tensor shaped like fb")
-    h, w, _ = (int(n) for n in fb.shape)
-    if out is None:
-        out = torch.empty((h, w, 3), dtype=torch.float32, device=fb.device)
-    n = lib.pt_variance_denoise_scratch_floats(w, h)
-    if n < 0:
-        abi.check(abi.PT_ERR_INVALID_ARG, "pt_variance_denoise_scratch_floats")
-    scratch = torch.empty(n, dtype=torch.float32, device=fb.device)
+    lib, plane, h, w, out, scratch, stream = _filter_call("denoise_variance", "pt_variance_denoise", abi.has_variance_denoise,
+                                                          "variance-guided denoiser", fb, out, other_planes, variance=variance)
     p = abi.PtVarianceDenoiseParams(C.sizeof(abi.PtVarianceDenoiseParams), w, h, int(iterations), float(sigma_variance), float(sigma_normal),
                                     float(sigma_depth), float(sigma_albedo),
                                     (abi.PT_VDENOISE_DEMODULATE if demodulate else 0) | (abi.PT_VDENOISE_NO_LDS if no_lds else 0), 0)
     abi.check(lib.pt_variance_denoise(C.byref(p), plane(fb, (h, w, 3), "fb"), plane(variance, (h, w, 3), "variance"),
                                       plane(albedo, (h, w, 3), "albedo"), plane(normal, (h, w, 3), "normal"), plane(depth, (h, w), "depth"),
                                       plane(out, (h, w, 3), "out"), plane(variance_out, (h, w, 3), "variance_out"),
-                                      C.c_void_p(scratch.data_ptr()), _stream_ptr(torch)), "pt_variance_denoise")
+                                      C.c_void_p(scratch.data_ptr()), stream), "pt_variance_denoise")
     return out
 
 

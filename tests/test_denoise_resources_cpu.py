@@ -3,39 +3,16 @@ cross-compiles gfx950 without a GPU): every atrous_kernel instantiation — (nor
 not x taps from global memory / from an LDS tile at step 1 / at step 2 — and the guide-packing prepass run without scratch memory, and the
 LDS tiles are the sizes the kernel's layout says."""
 import re
-import subprocess
-from pathlib import Path
 
 import pytest
 
-ROOT = Path(__file__).resolve().parent.parent
-CSRC = ROOT / "path_tracer_amd" / "csrc"
-
-
-def _flags():
-    mk = (CSRC / "Makefile").read_text()
-    m = re.search(r"^FLAGS\s*=\s*(.*?)(?<!\\)\n", mk, re.S | re.M)
-    flags = m.group(1).replace("\\\n", " ").replace("$(ARCH)", "gfx950").split()
-    return [f for f in flags if f not in ("-fPIC",) and not f.startswith("-W")]
+import kernel_resource_usage
+from kernel_resource_usage import flags as _flags
 
 
 @pytest.fixture(scope="module")
 def usage():
-    cmd = ["/opt/rocm/bin/hipcc", *_flags(), "--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage", "-o", "/dev/null",
-           str(CSRC / "pt_render.hip")]
-    p = subprocess.run(cmd, capture_output=True, text=True, cwd=CSRC, timeout=600)
-    assert p.returncode == 0, p.stderr[-2000:]
-    out, name = {}, None
-    for line in p.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            out[name] = {}
-        for key in ("VGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "LDS Size [bytes/block]"):
-            m = re.search(re.escape(key) + r": (\d+)", line)
-            if m and name:
-                out[name][key] = int(m.group(1))
-    return out
+    return kernel_resource_usage.usage()
 
 
 def test_flags_keep_the_numerics_contract():

@@ -2,42 +2,17 @@
 kernels for scenes without image textures must fit 7 waves per SIMD (<= 72 VGPRs) WITHOUT scratch — a spill there sits
 around every list scan and cost 4 % of the headline number when a wider triangle loop once pushed them over."""
 import re
-import subprocess
-from pathlib import Path
 
 import pytest
 
+import kernel_resource_usage
 import kernel_variant_cases as K
-
-ROOT = Path(__file__).resolve().parent.parent
-CSRC = ROOT / "path_tracer_amd" / "csrc"
-
-
-def _flags():
-    mk = (CSRC / "Makefile").read_text()
-    m = re.search(r"^FLAGS\s*=\s*(.*?)(?<!\\)\n", mk, re.S | re.M)
-    flags = m.group(1).replace("\\\n", " ").replace("$(ARCH)", "gfx950").split()
-    return [f for f in flags if f not in ("-fPIC",) and not f.startswith("-W")]
+from kernel_resource_usage import flags as _flags  # noqa: F401 (the ISA tests import the Makefile's FLAGS from here)
 
 
 @pytest.fixture(scope="module")
 def usage():
-    cmd = ["/opt/rocm/bin/hipcc", *_flags(), "--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage", "-o", "/dev/null",
-           str(CSRC / "pt_render.hip")]
-    p = subprocess.run(cmd, capture_output=True, text=True, cwd=CSRC, timeout=600)
-    assert p.returncode == 0, p.stderr[-2000:]
-    out = {}
-    name = None
-    for line in p.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            out[name] = {}
-        for key in ("VGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]"):
-            m = re.search(re.escape(key) + r": (\d+)", line)
-            if m and name:
-                out[name][key] = int(m.group(1))
-    return out
+    return kernel_resource_usage.usage()
 
 
 def test_headline_kernels_fit_seven_waves_without_scratch(usage):

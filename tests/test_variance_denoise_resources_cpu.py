@@ -3,39 +3,15 @@ a-trous kernels (hipcc cross-compiles gfx950 without a GPU): every vdn_kernel in
 records read or not x reads from global memory / from an LDS tile at step 1 / at step 2 — the packing prepass and the variance estimate
 run without scratch memory at an occupancy of 4 waves per SIMD or more, and the LDS tiles are the sizes the kernel's layout says."""
 import re
-import subprocess
-from pathlib import Path
 
 import pytest
 
-ROOT = Path(__file__).resolve().parent.parent
-CSRC = ROOT / "path_tracer_amd" / "csrc"
-
-
-def _flags():
-    mk = (CSRC / "Makefile").read_text()
-    m = re.search(r"^FLAGS\s*=\s*(.*?)(?<!\\)\n", mk, re.S | re.M)
-    flags = m.group(1).replace("\\\n", " ").replace("$(ARCH)", "gfx950").split()
-    return [f for f in flags if f not in ("-fPIC",) and not f.startswith("-W")]
+import kernel_resource_usage
 
 
 @pytest.fixture(scope="module")
 def usage():
-    cmd = ["/opt/rocm/bin/hipcc", *_flags(), "--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage", "-o", "/dev/null",
-           str(CSRC / "pt_render.hip")]
-    p = subprocess.run(cmd, capture_output=True, text=True, cwd=CSRC, timeout=600)
-    assert p.returncode == 0, p.stderr[-2000:]
-    out, name = {}, None
-    for line in p.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            out[name] = {}
-        for key in ("VGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "LDS Size [bytes/block]"):
-            m = re.search(re.escape(key) + r": (\d+)", line)
-            if m and name:
-                out[name][key] = int(m.group(1))
-    return out
+    return kernel_resource_usage.usage()
 
 
 def test_vdn_kernels_have_no_scratch(usage):
