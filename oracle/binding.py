@@ -48,7 +48,11 @@ def load() -> C.CDLL:
         return _lib
     if not LIB.exists():
         build()
-    lib = C.CDLL(str(LIB))
+    _lib = _declare(C.CDLL(str(LIB)))
+    return _lib
+
+
+def _declare(lib: C.CDLL) -> C.CDLL:
     lib.orc_set_math.argtypes = [C.c_int]
     lib.orc_get_math.restype = C.c_int
     lib.orc_xorshift32.restype = C.c_uint32
@@ -76,8 +80,31 @@ def load() -> C.CDLL:
     lib.orc_max_threads.restype = C.c_int
     lib.orc_set_threads.restype = None
     lib.orc_set_threads.argtypes = [C.c_int]
-    _lib = lib
     return lib
+
+
+class Bound:
+    """A second build of pt_oracle.c loaded from `path`, beside the global one and without touching it: the function-level
+    probes only (tests/test_physics_model_cpu.py loads deliberately wrong builds this way)."""
+
+    def __init__(self, path):
+        self.lib = _declare(C.CDLL(str(path)))
+
+    def set_math(self, portable: bool) -> None:
+        self.lib.orc_set_math(1 if portable else 0)
+
+    def bounce(self, packed, recs_in):
+        return bounce(packed, recs_in, self.lib)
+
+    def camera_init(self, *args, **kw):
+        return camera_init(*args, **kw, lib=self.lib)
+
+    def camera_rays(self, cam, width, height, xy, rng_in):
+        return camera_rays(cam, width, height, xy, rng_in, self.lib)
+
+
+def bind(path) -> Bound:
+    return Bound(path)
 
 
 def set_math(portable: bool) -> None:
@@ -92,10 +119,10 @@ def params(width, height, samples, depth=50, shard_index=0, shard_count=1, flags
     return abi.PtRenderParams(width, height, samples, depth, shard_index, shard_count, flags, 0)
 
 
-def camera_init(look_from, look_at, vup, vfov, aspect, aperture, focus_dist, t0=0.0, t1=0.0) -> abi.PtCamera:
+def camera_init(look_from, look_at, vup, vfov, aspect, aperture, focus_dist, t0=0.0, t1=0.0, lib=None) -> abi.PtCamera:
     cam = abi.PtCamera()
     a3 = lambda v: (C.c_float * 3)(*[float(np.float32(x)) for x in v])  # noqa: E731
-    load().orc_camera_init(C.byref(cam), a3(look_from), a3(look_at), a3(vup), np.float32(vfov), np.float32(aspect),
+    (lib or load()).orc_camera_init(C.byref(cam), a3(look_from), a3(look_at), a3(vup), np.float32(vfov), np.float32(aspect),
                            np.float32(aperture), np.float32(focus_dist), np.float32(t0), np.float32(t1))
     return cam
 
@@ -156,8 +183,8 @@ def render_pixels_rays(packed, cam: abi.PtCamera, width, height, samples, xy: np
     return out, rays
 
 
-def bounce(packed, recs_in):
-    lib = load()
+def bounce(packed, recs_in, lib=None):
+    lib = lib or load()
     n = len(recs_in)
     out = (abi.PtBounceOut * max(1, n))()
     rc = lib.orc_bounce(C.byref(packed.desc), recs_in, out, n, 0)
@@ -166,8 +193,8 @@ def bounce(packed, recs_in):
     return out
 
 
-def camera_rays(cam: abi.PtCamera, width, height, xy: np.ndarray, rng_in: np.ndarray):
-    lib = load()
+def camera_rays(cam: abi.PtCamera, width, height, xy: np.ndarray, rng_in: np.ndarray, lib=None):
+    lib = lib or load()
     n = len(rng_in)
     xy = np.ascontiguousarray(xy, dtype=np.int32)
     rng_in = np.ascontiguousarray(rng_in, dtype=np.uint32)

@@ -20,6 +20,7 @@ from conftest import assert_bit_identical, bits, psnr_8bit
 from dist_util import unshard_reference
 from path_tracer_amd import abi, scenes
 from path_tracer_amd import render as R
+from physics_cases import random_bounce_inputs
 
 pytestmark = pytest.mark.gpu
 GOLDEN = Path(__file__).parent / "golden"
@@ -312,25 +313,6 @@ def test_pinhole_camera_shortcut_is_exact(lib, orc):
         c = scenes.make_camera(dict(cams[0], look_from=frm), 64, 36)
         orc.set_math(True)
         assert_bit_identical(R.render_host(64, 36, 8, ps, c), orc.render(ps, c.c, 64, 36, 8), f"pinhole from {frm}")
-
-
-def random_bounce_inputs(rng, n, center, extent):
-    recs = (abi.PtBounceIn * n)()
-    o = (rng.random((n, 3), dtype=np.float32) - 0.5) * 2 * extent + center
-    target = (rng.random((n, 3), dtype=np.float32) - 0.5) * extent + center
-    d = (target - o).astype(np.float32)
-    d[::7] *= np.float32(0.01)   # short directions: t far beyond 1
-    d[::11] *= np.float32(50.0)
-    tm = rng.random(n, dtype=np.float32)
-    st = rng.integers(1, 2 ** 32, n, dtype=np.uint64).astype(np.uint32)
-    att = rng.random((n, 3), dtype=np.float32)
-    for k in range(n):
-        recs[k].origin[:] = o[k].tolist()
-        recs[k].dir[:] = d[k].tolist()
-        recs[k].time = float(tm[k])
-        recs[k].rng_state = int(st[k])
-        recs[k].attenuation[:] = att[k].tolist()
-    return recs
 
 
 BOUNCE_FIELDS = [n for n, _ in abi.PtBounceOut._fields_]
