@@ -348,7 +348,7 @@ int pt_render(const PtScene* scene, const PtCamera* cam, const PtRenderParams* p
               float* fb_device, void* stream);
 
 /* Same, timed: brackets the kernel launch with HIP events recorded on `stream`
- * and returns the kernel's duration (blocks until done).                        */
+ * and returns the kernel's duration (synchronises `stream`: blocks until done). */
 int pt_render_timed(const PtScene* scene, const PtCamera* cam, const PtRenderParams* p,
                     float* fb_device, void* stream, float* kernel_ms);
 
@@ -357,12 +357,14 @@ int pt_render_host(const PtScene* scene, const PtCamera* cam, const PtRenderPara
                    float* fb_host);
 
 /* Root-side un-interleave after the RCCL gather: gathered is
- * [shard_count][pt_shard_tiles][64][3] device floats -> fb [height][width][3].  */
+ * [shard_count][pt_shard_tiles][64][3] device floats -> fb [height][width][3].
+ * Asynchronous on `stream`, allocates nothing.                                  */
 int pt_unshard_tiles(const float* gathered_device, const PtRenderParams* p,
                      float* fb_device, void* stream);
 
 /* Output stage of main.cpp:33-59: sqrt gamma, clamp [0,0.999], *256 -> u8,
- * vertical flip; rgb8_device is [height][width][3], row 0 = top.               */
+ * vertical flip; rgb8_device is [height][width][3], row 0 = top.  Asynchronous
+ * on `stream`, allocates nothing.                                             */
 int pt_tonemap_rgb8(const float* fb_device, int32_t width, int32_t height,
                     uint8_t* rgb8_device, void* stream);
 
@@ -410,14 +412,16 @@ typedef struct PtAccum PtAccum; /* device-resident per-pixel state of a frame re
 int pt_accum_create(const PtScene* scene, const PtRenderParams* p, PtAccum** out);
 void pt_accum_destroy(PtAccum* acc);
 /* Back to 0 samples: same scene and frame parameters; the camera binding and the kept tile order are released (a camera that moved
- * starts a new image: the next window binds its camera). */
+ * starts a new image: the next window binds its camera).  Asynchronous on `stream`. */
 int pt_accum_reset(PtAccum* acc, void* stream);
 int32_t pt_accum_samples(const PtAccum* acc); /* samples rendered so far (host-side count; -1 for NULL) */
 /* Render samples [done, done + samples) of every pixel; asynchronous on `stream` like pt_render. */
 int pt_render_accumulate(PtAccum* acc, const PtCamera* cam, int32_t samples, void* stream);
-/* fb = sum / done (correctly rounded, as render.hpp:102), pt_render's layout and bits; fb_device: pt_framebuffer_floats() floats. */
+/* fb = sum / done (correctly rounded, as render.hpp:102), pt_render's layout and bits; fb_device: pt_framebuffer_floats() floats.
+ * Asynchronous on `stream`, allocates nothing. */
 int pt_accum_resolve(const PtAccum* acc, float* fb_device, void* stream);
-/* resolve + the output stage of pt_tonemap_rgb8 in one pass (whole frames): rgb8_device is [height][width][3], row 0 = top. */
+/* resolve + the output stage of pt_tonemap_rgb8 in one pass (whole frames): rgb8_device is [height][width][3], row 0 = top.
+ * Asynchronous on `stream`, allocates nothing. */
 int pt_accum_tonemap_rgb8(const PtAccum* acc, uint8_t* rgb8_device, void* stream);
 /* Host function, no GPU: bytes of an exported state for these frame parameters (samples ignored); < 0 for invalid ones. */
 int64_t pt_accum_state_bytes(const PtRenderParams* p);
@@ -472,11 +476,12 @@ int pt_accum_import(PtAccum* acc, const void* host, int64_t bytes, void* stream)
 #define PT_ADAPTIVE_DILATE 1u
 /* Validates the parameters (before any device call) and allocates the state on the current device; destroyed with pt_accum_destroy. */
 int pt_adaptive_create(const PtScene* scene, const PtRenderParams* p, PtAccum** out);
-/* `samples` more samples of each pixel whose mask byte is nonzero (NULL: every pixel); a mask synchronises `stream` once. */
+/* `samples` more samples of each pixel whose mask byte is nonzero (NULL: every pixel: asynchronous on `stream` like
+ * pt_render_accumulate); a mask synchronises `stream` once. */
 int pt_adaptive_window(PtAccum* acc, const PtCamera* cam, int32_t samples, const uint8_t* mask_device, void* stream);
-/* Per-pixel sample counts n (P i32). */
+/* Per-pixel sample counts n (P i32).  Asynchronous on `stream`, allocates nothing. */
 int pt_adaptive_counts(const PtAccum* acc, int32_t* counts_device, void* stream);
-/* Per-pixel error estimate (P f32; the formula above). */
+/* Per-pixel error estimate (P f32; the formula above).  Asynchronous on `stream`, allocates nothing. */
 int pt_adaptive_error(const PtAccum* acc, float* err_device, void* stream);
 /* The next window's mask (P u8: 1 active, 0 not) by the rule above; synchronises `stream`: n_active is a host value. */
 int pt_adaptive_select(const PtAccum* acc, float threshold, int32_t min_spp, int32_t max_spp, uint32_t flags,
@@ -529,6 +534,7 @@ typedef struct PtAovBuffers { /* device pointers; NULL = plane not wanted */
 } PtAovBuffers;
 /* Host function, no GPU: elements of a plane of `channels` (1 or 3) channels for these parameters (samples ignored); < 0 for invalid ones. */
 int64_t pt_aov_plane_elems(const PtRenderParams* p, int32_t channels);
+/* The pass defined above; asynchronous on `stream`, allocates nothing. */
 int pt_render_aov(const PtScene* scene, const PtCamera* cam, const PtRenderParams* p, const PtAovBuffers* buffers, void* stream);
 
 /* ---- denoiser: the edge-avoiding a-trous wavelet filter, guided by the feature buffers ---------------------------------------------
@@ -607,6 +613,7 @@ void pt_denoise_params_init(PtDenoiseParams* params, int32_t width, int32_t heig
 /* Host function, no GPU: floats of `scratch` for a frame of width x height — one colour plane (the iterations ping-pong between it and
  * `out`) and two 16-byte guide records per pixel, (normal, depth) and (albedo, 0), packed by a prepass; < 0 for invalid sizes. */
 int64_t pt_denoise_scratch_floats(int32_t width, int32_t height);
+/* The filter defined above; asynchronous on `stream`, allocates nothing. */
 int pt_denoise(const PtDenoiseParams* params, const float* color, const float* albedo, const float* normal, const float* depth,
                float* out, float* scratch, void* stream);
 /* How the LAST pt_denoise of this process read its taps, per iteration: out[i] = 0 iteration not run, 1 from global memory, 2 from an
@@ -700,7 +707,8 @@ typedef struct PtVarianceDenoiseParams {
   uint32_t flags;      /* PT_VDENOISE_DEMODULATE, PT_VDENOISE_NO_LDS */
   int32_t reserved;
 } PtVarianceDenoiseParams;
-/* The per-channel variance of each resolved pixel of an adaptive accumulator (the formula above); variance_device: pt_framebuffer_floats() floats. */
+/* The per-channel variance of each resolved pixel of an adaptive accumulator (the formula above); variance_device: pt_framebuffer_floats() floats.
+ * Asynchronous on `stream`, allocates nothing. */
 int pt_variance_estimate(const PtAccum* acc, float* variance_device, void* stream);
 /* Host function, no GPU: struct_size + the defaults above for a frame of width x height. */
 void pt_variance_denoise_params_init(PtVarianceDenoiseParams* params, int32_t width, int32_t height);
@@ -708,6 +716,7 @@ void pt_variance_denoise_params_init(PtVarianceDenoiseParams* params, int32_t wi
  * between, each a 16-byte record (c.r, c.g, c.b, v.r) and an 8-byte record (v.g, v.b) per pixel, so that a tap's colour and variance are
  * two loads, and pt_denoise's two 16-byte guide records per pixel, (normal, depth) and (albedo, 0); < 0 for invalid sizes. */
 int64_t pt_variance_denoise_scratch_floats(int32_t width, int32_t height);
+/* The filter defined above; asynchronous on `stream`, allocates nothing. */
 int pt_variance_denoise(const PtVarianceDenoiseParams* params, const float* color, const float* variance, const float* albedo,
                         const float* normal, const float* depth, float* out, float* variance_out, float* scratch, void* stream);
 /* How the LAST pt_variance_denoise of this process read its taps, per iteration: out[i] = 0 iteration not run, 1 from global memory, 2 from
@@ -798,6 +807,7 @@ int pt_debug_last_variance_denoise(int32_t out[8]);
 #define PT_TEMPORAL_DEFAULT_ALPHA 0.1f
 #define PT_TEMPORAL_DEFAULT_TOL_DEPTH 0.1f
 #define PT_TEMPORAL_DEFAULT_TOL_NORMAL 0.5f
+/* NEXT FRAME above; asynchronous on `stream`, allocates nothing, launches no kernel. */
 extern int pt_adaptive_next_frame(PtAccum* acc, void* stream);
 typedef struct PtTemporal PtTemporal; /* device-resident history of one image sequence; 2 x 48 bytes per pixel */
 typedef struct PtTemporalParams {
@@ -813,7 +823,7 @@ int64_t pt_temporal_state_bytes(int32_t width, int32_t height);
 /* Allocates the state on the current device (the only allocation); no history yet. */
 int pt_temporal_create(int32_t width, int32_t height, PtTemporal** out);
 void pt_temporal_destroy(PtTemporal* state);
-/* Forget the history: the next push starts one. */
+/* Forget the history: the next push starts one.  Asynchronous on `stream` (host bookkeeping only). */
 int pt_temporal_reset(PtTemporal* state, void* stream);
 /* Pushes since create / reset (host-side count; -1 for NULL). */
 int32_t pt_temporal_frames(const PtTemporal* state);
@@ -916,7 +926,7 @@ void pt_display_destroy(PtDisplay* state);
 int pt_display_reset(PtDisplay* state, void* stream);
 /* Meterings since create / reset (host-side count; -1 for NULL). */
 int32_t pt_display_frames(const PtDisplay* state);
-/* Histogram, solve and adaptation, all on `stream`. */
+/* Histogram, solve and adaptation; asynchronous on `stream`: nothing comes back to the host. */
 int pt_display_meter(PtDisplay* state, const PtDisplayParams* params, const float* color, int32_t width, int32_t height, void* stream);
 /* A manual exposure, in stops. */
 int pt_display_set_exposure(PtDisplay* state, float ev, void* stream);

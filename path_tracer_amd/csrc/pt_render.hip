@@ -4162,8 +4162,10 @@ int accum_create(const PtScene* scene, const PtRenderParams* p, PtAccum** out, b
       if (r != hipSuccess) e = r;
     if (e != hipSuccess) return bad(e, "hipMalloc");
     if (int rc = adaptive_clear(acc, nullptr)) return rc;
-    if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) return bad(e, "hipStreamSynchronize");
   }
+  // The clears above run on the null stream, and neither hipMemset nor hipMemsetAsync has finished when it returns: the first window may
+  // be queued on a non-blocking stream, which does not wait for the null stream — a clear still pending there would land on its sums.
+  if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) return bad(e, "hipStreamSynchronize");
   {
     // the scene's launch workspaces a window uses (probe costs, tile ranks; the candidate cache): sized now, not by a window
     std::lock_guard<std::mutex> lock(scene->sched);
