@@ -33,6 +33,11 @@ exposure is solved on the device from the frame's luminance histogram (--exposur
 these options the frame PNGs go through the display stage as well, metered in order: with --auto-exposure the exposure adapts from frame to
 frame at the rates --adapt-up and --adapt-down (1 = instant, the default).  out.png is byte-identical to the one written without the
 options.
+With --firefly-clamp [K] the firefly stage (render.firefly; include/pt_post.h) runs on the frame before --denoise-out, --display-out and the
+--frames-dir frames consume it: a pixel brighter than K times (default 1) its brightest neighbour — with --firefly-rank 2 its second
+brightest — is scaled down to that, and a pixel that is not finite becomes the mean of its finite neighbours.  The clamp is biased (it
+removes energy), so it is never on unless asked; the numbers of clamped and repaired pixels are printed.  out.png is byte-identical to the
+one written without the options.
 """
 import argparse
 import os
@@ -69,20 +74,39 @@ def make_shower(a):
     return lambda fb: disp.meter(fb).apply(fb)
 
 
+def clamp_fireflies(a, fb, what, variance=None):
+    """--firefly-clamp: the frame (and its variance) through the firefly stage, the counts printed; without the option, as they came."""
+    if a.firefly_kw is None:
+        return (fb, variance) if variance is not None else fb
+    *res, n = R.firefly(fb, variance, counts=True, **a.firefly_kw)
+    print_firefly_counts(a, what, n)
+    return tuple(res) if variance is not None else res[0]
+
+
+def print_firefly_counts(a, what, n) -> None:
+    clamped, repaired = (int(v) for v in n.cpu().numpy())
+    print(f"{what}: firefly clamp (rank {a.firefly_kw['rank']}, k {a.firefly_kw['k']:g}): {clamped} pixels clamped, {repaired} repaired")
+
+
 def write_frames(a, packed, cam_args, move, denoise_kw) -> None:
     """The camera path of --frames: DIR/frame_<f>.png, frame f looking from look_from + f x move.  Plain: render() per frame.  --temporal:
     render_temporal's accumulated frame, or with --denoise-variance that frame through the variance-guided filter.  Each frame leaves
-    through make_shower's output stage, in order."""
+    through make_shower's output stage, in order.  --firefly-clamp: each frame goes through the firefly stage first (--temporal: before its
+    history takes it in)."""
     show = make_shower(a)
     os.makedirs(a.frames_dir, exist_ok=True)
     cams = [scenes.make_camera(dict(cam_args, look_from=tuple(float(p) + f * d for p, d in zip(cam_args["look_from"], move))), a.width, a.height)
             for f in range(a.frames)]
     if not a.temporal:
         for f, c in enumerate(cams):
-            write_png(os.path.join(a.frames_dir, f"frame_{f}.png"), show(R.render(a.width, a.height, a.spp, packed, c, a.depth)).cpu().numpy())
+            fb = clamp_fireflies(a, R.render(a.width, a.height, a.spp, packed, c, a.depth), f"frame {f}")
+            write_png(os.path.join(a.frames_dir, f"frame_{f}.png"), show(fb).cpu().numpy())
         return
+    extra = {} if a.firefly_kw is None else {"firefly": a.firefly_kw}  # (absent: render_temporal issues exactly the calls it always did)
     for f, frame in enumerate(R.render_temporal(a.width, a.height, a.spp, packed, cams, a.depth, aov_spp=a.aov_spp, denoise=a.denoise_variance,
-                                                denoise_kw=denoise_kw)):
+                                                denoise_kw=denoise_kw, **extra)):
+        if a.firefly_kw is not None:
+            print_firefly_counts(a, f"frame {f}", frame["firefly_counts"])
         write_png(os.path.join(a.frames_dir, f"frame_{f}.png"), show(frame["filtered" if a.denoise_variance else "temporal"]).cpu().numpy())
 
 
@@ -132,7 +156,20 @@ def main() -> None:
     ap.add_argument("--adapt-up", type=float, default=None, metavar="A", help="auto-exposure over --frames: rate towards a higher exposure, in (0, 1]")
     ap.add_argument("--adapt-down", type=float, default=None, metavar="A", help="auto-exposure over --frames: rate towards a lower exposure, in (0, 1]")
     ap.add_argument("--display-out", default=None, metavar="FILE", help="also write the frame through the display stage (exposure + tone curve)")
+    ap.add_argument("--firefly-clamp", type=float, nargs="?", const=1.0, default=None, metavar="K",
+                    help="firefly stage: scale a pixel brighter than K x (default 1) its brightest neighbour down to that, repair NaN / inf; "
+                         "acts on what --denoise-out, --display-out and --frames-dir consume (biased: off unless given)")
+    ap.add_argument("--firefly-rank", type=int, default=None, metavar="R", help="firefly stage: 1 = the brightest neighbour (default), 2 = the second brightest")
     a = ap.parse_args()
+    if a.firefly_rank is not None and a.firefly_clamp is None:
+        ap.error("--firefly-rank needs --firefly-clamp")
+    if a.firefly_clamp is not None and a.denoise_out is None and a.display_out is None and a.frames_dir is None:
+        ap.error("--firefly-clamp needs --denoise-out, --display-out or --frames-dir")
+    if a.firefly_clamp is not None and not (0.0 < a.firefly_clamp < float("inf")):
+        ap.error("--firefly-clamp must be finite and > 0")
+    if a.firefly_rank is not None and a.firefly_rank not in (1, 2):
+        ap.error("--firefly-rank must be 1 or 2")
+    a.firefly_kw = None if a.firefly_clamp is None else dict(rank=1 if a.firefly_rank is None else a.firefly_rank, k=a.firefly_clamp)
     a.display = a.tone is not None or a.exposure is not None or a.auto_exposure or a.adapt_up is not None or a.adapt_down is not None
     if a.display and a.display_out is None and a.frames_dir is None:
         ap.error("--tone, --exposure, --auto-exposure, --adapt-up and --adapt-down need --display-out or --frames-dir")
@@ -249,6 +286,11 @@ def main() -> None:
     planes = R.render_aov(a.width, a.height, a.aov_spp, packed, cam) if a.aov_dir or a.denoise_out else None
     if a.aov_dir:
         write_aovs(a.aov_dir, planes)
+    if a.denoise_out or a.display_out:
+        if a.denoise_out and a.denoise_variance:
+            fb, variance[0] = clamp_fireflies(a, fb, "frame", variance[0])
+        else:
+            fb = clamp_fireflies(a, fb, "frame")
     if a.denoise_out:
         filtered = R.denoise_variance(fb, variance[0], **planes, **denoise_kw) if a.denoise_variance else R.denoise(fb, **planes, **denoise_kw)
         write_png(a.denoise_out, R.tonemap_rgb8(filtered).cpu().numpy())

@@ -1,4 +1,4 @@
-"""ctypes mirror of include/pt_render.h — the C-ABI drop-in boundary of render().
+"""ctypes mirror of include/pt_render.h — the C-ABI drop-in boundary of render() — and of include/pt_post.h (POST_SIGNATURES).
 
 The structs are declared field-for-field as in the header; `load_library()` opens the
 in-tree `libpt_render.so` built by `__graft_entry__.build()` (hipcc, gfx950) and fails
@@ -158,6 +158,12 @@ class PtDisplayParams(C.Structure):
                 ("rect_y1", C.c_int32), ("reserved", C.c_int32)]
 
 
+class PtFireflyParams(C.Structure):
+    """include/pt_post.h PtFireflyParams: the firefly stage's parameters (pt_firefly)."""
+    _fields_ = [("struct_size", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("rank", C.c_int32), ("k", C.c_float),
+                ("flags", C.c_uint32), ("reserved", C.c_int32 * 2)]
+
+
 assert C.sizeof(PtHittable) == 64 and C.sizeof(PtMaterial) == 32 and C.sizeof(PtTexture) == 48
 assert C.sizeof(PtCamera) == 96 and C.sizeof(PtRenderParams) == 32
 
@@ -266,6 +272,21 @@ SIGNATURES = {
     "pt_debug_last_pool_plan": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "pt_debug_pool_plan": (C.c_int, [C.POINTER(PtSceneDesc), C.POINTER(PtTuning), C.POINTER(PtRenderParams), C.POINTER(C.c_int32)]),
 }
+
+# name -> (restype, argtypes): every entry point include/pt_post.h declares — the image-space stages added since pt_render.h's table was
+# closed.  A table of its own: SIGNATURES stays exactly what pt_render.h declares.  Optional, like DISPLAY_SYMBOLS: load_library() applies a
+# row where the library exports the symbol; has_firefly() tells whether the loaded one has the stage.
+POST_SIGNATURES = {
+    "pt_firefly_params_init": (None, [C.POINTER(PtFireflyParams), C.c_int32, C.c_int32]),
+    "pt_firefly": (C.c_int, [C.POINTER(PtFireflyParams)] + [C.c_void_p] * 6),
+    "pt_debug_last_firefly": (C.c_int, [C.POINTER(C.c_int32)]),
+}
+FIREFLY_SYMBOLS = frozenset({"pt_firefly_params_init", "pt_firefly", "pt_debug_last_firefly"})
+PT_FIREFLY_REPAIR = 1
+PT_FIREFLY_NO_LDS = 2  # A/B switch, same bits: every neighbour from global memory
+PT_FIREFLY_TILE_W, PT_FIREFLY_TILE_H = 32, 8
+# the header's PT_FIREFLY_DEFAULT_* (pt_firefly_params_init)
+PT_FIREFLY_DEFAULT_RANK, PT_FIREFLY_DEFAULT_K, PT_FIREFLY_DEFAULT_FLAGS = 1, 1.0, PT_FIREFLY_REPAIR
 
 # Entry points a library may lack and still load for everything else (include/pt_render.h: the feature is detected by their presence);
 # has_accumulator() tells whether the loaded one has them.
@@ -376,6 +397,11 @@ def load_library() -> C.CDLL:
         fn = getattr(lib, name)  # AttributeError if the library does not export what the header declares
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in POST_SIGNATURES.items():  # include/pt_post.h: applied where the library has the symbol
+        if hasattr(lib, name):
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
     older_ok = bool(os.environ.get("PT_RENDER_LIB")) and os.environ.get("PT_RENDER_LIB_ALLOW_OLDER") == "1"  # (A/B tooling: an older build beside this tree)
     if lib.pt_abi_version() != PT_ABI_VERSION and not (older_ok and lib.pt_abi_version() == 1):
         raise ImportError(f"{path}: ABI version {lib.pt_abi_version()} != {PT_ABI_VERSION}")
@@ -423,6 +449,12 @@ def has_display(lib=None) -> bool:
     """Does the loaded library offer the display stage (pt_display_meter, pt_display_apply)?"""
     lib = lib or load_library()
     return all(hasattr(lib, n) for n in DISPLAY_SYMBOLS)
+
+
+def has_firefly(lib=None) -> bool:
+    """Does the loaded library offer the firefly stage (include/pt_post.h: pt_firefly)?"""
+    lib = lib or load_library()
+    return all(hasattr(lib, n) for n in FIREFLY_SYMBOLS)
 
 
 def check(code: int, where: str) -> None:

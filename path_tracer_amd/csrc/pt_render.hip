@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/pt_render.h"
+#include "../../include/pt_post.h"
 #include "pt_device.hpp"
 #include "pt_flatten.hpp"
 
@@ -2006,6 +2007,8 @@ __global__ __launch_bounds__(256) void display_apply_kernel(const float* color, 
   }
 }
 
+#include "pt_firefly.hpp"
+
 thread_local std::string g_last_error;
 
 // ---- tuning: include/pt_render.h PtTuning.  Resolved ONCE per scene (pt_scene_create / pt_debug_flatten), never on the launch path.
@@ -3966,6 +3969,69 @@ int pt_debug_last_display(int32_t out[8]) {
   if (!out) return fail(PT_ERR_INVALID_ARG, "pt_debug_last_display: NULL argument");
   std::lock_guard<std::mutex> lock(g_display_mutex);
   std::memcpy(out, g_last_display, sizeof g_last_display);
+  return PT_OK;
+}
+
+// ---- firefly stage (include/pt_post.h): pt_firefly (firefly_kernel) ------------------------------------------------------------------------
+static std::mutex g_firefly_mutex;
+static int32_t g_last_firefly[4] = {0, 0, 0, 0}; // pt_debug_last_firefly
+
+void pt_firefly_params_init(PtFireflyParams* params, int32_t width, int32_t height) {
+  if (!params) return;
+  std::memset(params, 0, sizeof *params);
+  params->struct_size = (int32_t)sizeof(PtFireflyParams);
+  params->width = width; params->height = height;
+  params->rank = PT_FIREFLY_DEFAULT_RANK;
+  params->k = PT_FIREFLY_DEFAULT_K;
+  params->flags = PT_FIREFLY_DEFAULT_FLAGS;
+}
+
+int pt_firefly(const PtFireflyParams* params, const float* color, const float* variance, float* out, float* variance_out, uint32_t* counts,
+               void* stream) {
+  auto bad = [&](const char* what) { return fail(PT_ERR_INVALID_ARG, std::string("pt_firefly: ") + what); };
+  if (!params || !color || !out) return bad("NULL params, color or out");
+  if (params->struct_size != (int32_t)sizeof(PtFireflyParams)) return bad("PtFireflyParams.struct_size is not this library's");
+  if (params->width <= 0 || params->height <= 0) return bad("width and height must be > 0");
+  if (params->rank != 1 && params->rank != 2) return bad("rank must be 1 or 2");
+  if (!(std::isfinite(params->k) && params->k > 0.0f)) return bad("k must be finite and > 0");
+  if (params->flags & ~(PT_FIREFLY_REPAIR | PT_FIREFLY_NO_LDS)) return bad("unknown flags");
+  if (variance_out && !variance) return bad("variance_out needs variance");
+  const int64_t pixels = (int64_t)params->width * params->height;
+  if (pixels > ((int64_t)1 << 30)) return fail(PT_ERR_TOO_LARGE, "pt_firefly: more than 2^30 pixels");
+  if ((uintptr_t)counts % 8) return bad("counts must be 8-byte aligned");
+  const uintptr_t frame = (uintptr_t)pixels * 12;
+  const void* const var_written = variance_out == variance ? nullptr : variance_out; // variance_out may BE variance
+  if (overlaps(out, frame, color, frame) || overlaps(out, frame, variance, frame) || overlaps(var_written, frame, color, frame) ||
+      overlaps(var_written, frame, variance, frame) || overlaps(counts, 8, color, frame) || overlaps(counts, 8, variance, frame))
+    return bad("out, variance_out and counts must not overlap color or variance (variance_out may be variance itself)");
+  if (overlaps(out, frame, variance_out, frame) || overlaps(counts, 8, out, frame) || overlaps(counts, 8, variance_out, frame))
+    return bad("out, variance_out and counts must not overlap one another");
+
+  hipStream_t st = (hipStream_t)stream;
+  const bool lds = !(params->flags & PT_FIREFLY_NO_LDS);
+  FireflyArgs a;
+  a.color = color; a.variance = variance; a.out = out; a.variance_out = variance_out;
+  a.counts = reinterpret_cast<unsigned long long*>(counts);
+  a.width = params->width; a.height = params->height;
+  a.tiles_x = (params->width + PT_FIREFLY_TILE_W - 1) / PT_FIREFLY_TILE_W;
+  a.rank = params->rank; a.repair = params->flags & PT_FIREFLY_REPAIR; a.k = params->k;
+  const int64_t tiles_y = (params->height + PT_FIREFLY_TILE_H - 1) / PT_FIREFLY_TILE_H;
+  a.tiles = (int)(a.tiles_x * tiles_y); // (at most 2^30: a frame one pixel wide and 2^30 rows high has 2^27)
+  const dim3 grid((unsigned)std::min(a.tiles, (int)PT_FIREFLY_MAX_BLOCKS)); // one dimension; each workgroup walks the tiles grid.x apart
+  std::lock_guard<std::mutex> lock(g_firefly_mutex);
+  std::memset(g_last_firefly, 0, sizeof g_last_firefly);
+  if (counts) PT_HIP(hipMemsetAsync(counts, 0, 8, st));
+  if (lds) hipLaunchKernelGGL(firefly_kernel<true>, grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(firefly_kernel<false>, grid, dim3(256), 0, st, a);
+  PT_HIP(hipGetLastError());
+  g_last_firefly[0] = lds ? 2 : 1; g_last_firefly[1] = a.tiles_x; g_last_firefly[2] = (int32_t)tiles_y; g_last_firefly[3] = variance_out ? 2 : 1;
+  return PT_OK;
+}
+
+int pt_debug_last_firefly(int32_t out[4]) {
+  if (!out) return fail(PT_ERR_INVALID_ARG, "pt_debug_last_firefly: NULL argument");
+  std::lock_guard<std::mutex> lock(g_firefly_mutex);
+  std::memcpy(out, g_last_firefly, sizeof g_last_firefly);
   return PT_OK;
 }
 

@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "../../../include/pt_render.h"
+#include "../../../include/pt_post.h"
 #include "image_io.hpp"
 
 namespace pt {
@@ -519,6 +520,23 @@ class display {
  private:
   PtDisplay* d_ = nullptr;
 };
+
+// The firefly stage (include/pt_post.h: pt_firefly), before the filters: a pixel whose luminance exceeds k times the largest (rank 1) or
+// second largest (rank 2) luminance among its up to eight neighbours is scaled down to that; with `repair` a pixel that is not finite
+// becomes the mean of its finite neighbours.  The clamp is BIASED (it only removes energy): nothing applies it unless asked.  color, out
+// and the optional variance, variance_out ([height][width][3]) and counts (uint32[2]: clamped, repaired) are DEVICE buffers the caller
+// owns; out must not overlap color, variance_out may be variance.  The defaults are the header's (pt_firefly_params_init).
+struct firefly_params {
+  int rank = PT_FIREFLY_DEFAULT_RANK;
+  float k = PT_FIREFLY_DEFAULT_K;
+  bool repair = true;
+};
+// asynchronous on `stream`
+inline void firefly(int width, int height, const float* color, const float* variance, float* out, float* variance_out = nullptr,
+                    uint32_t* counts = nullptr, const firefly_params& fp = {}, void* stream = nullptr) {
+  const PtFireflyParams p{(int32_t)sizeof(PtFireflyParams), width, height, fp.rank, fp.k, fp.repair ? PT_FIREFLY_REPAIR : 0u, {0, 0}};
+  check(pt_firefly(&p, color, variance, out, variance_out, counts, stream), "pt_firefly");
+}
 
 // Progressive rendering: one frame in sample windows; RAII over pt_accum_create / pt_accum_destroy (include/pt_render.h, PtAccum).
 // After windows totalling N samples, resolve() holds the bits render() gives at samples = N.  The scene must outlive the accumulator;

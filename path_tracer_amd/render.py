@@ -235,6 +235,67 @@ def denoise_variance(fb, variance, *, albedo=None, normal=None, depth=None, iter
     return out
 
 
+def firefly(fb, variance=None, *, rank: int = abi.PT_FIREFLY_DEFAULT_RANK, k: float = abi.PT_FIREFLY_DEFAULT_K, repair: bool = True,
+            no_lds: bool = False, out=None, variance_out=None, counts=False):
+    """The firefly stage (include/pt_post.h: pt_firefly), before the filters: a pixel whose luminance exceeds `k` times the largest
+    (`rank` 1) or second largest (`rank` 2) luminance among its up to eight neighbours is scaled down to that; with `repair` a pixel that
+    is not finite becomes the mean of its finite neighbours.  The clamp is BIASED — it only removes energy — so nothing applies it unless
+    asked.  `fb`: [H][W][3] float32 on the GPU, a whole frame; `variance` (optional): the variance of each pixel's mean, shaped like fb —
+    scaled by s^2 where a pixel was scaled by s, +inf where it was repaired.  `out` must not be `fb`; `variance_out` may be `variance`.
+    `no_lds`: the A/B switch PT_FIREFLY_NO_LDS (the same bits).  Asynchronous on torch's current stream.
+    Returns the frame; with `variance`, (frame, variance_out); with `counts` (True, or a 2-element uint32 / int32 device tensor to write),
+    the uint32 device tensor {clamped, repaired} appended — nothing is read back: .cpu() it when the numbers are wanted."""
+    import torch
+
+    if not torch.cuda.is_available():
+        raise RuntimeError("path_tracer_amd.firefly needs a HIP device: there is no CPU path in the product")
+    lib = abi.load_library()
+    if not abi.has_firefly(lib):
+        raise ImportError(f"{abi.library_path()} predates the firefly stage (no pt_firefly entry point)")
+    if fb is None or fb.dim() != 3 or fb.shape[2] != 3:
+        raise ValueError("fb must be a whole frame [H][W][3] (gather and unshard a multi-GPU frame first)")
+    h, w, _ = (int(n) for n in fb.shape)
+    if variance is None and variance_out is not None:
+        raise ValueError("variance_out needs variance")
+    if out is None:
+        out = torch.empty((h, w, 3), dtype=torch.float32, device=fb.device)
+    if variance is not None and variance_out is None:
+        variance_out = torch.empty((h, w, 3), dtype=torch.float32, device=fb.device)
+    for what, t in (("fb", fb), ("variance", variance), ("out", out), ("variance_out", variance_out)):
+        if t is not None:
+            if tuple(t.shape) != (h, w, 3):
+                raise ValueError(f"{what} must have the frame's shape")
+            _frame_ptr(t, what)
+    n = None
+    if counts is True:
+        n = torch.empty(2, dtype=torch.uint32, device=fb.device)
+    elif counts is not None and counts is not False:
+        n = counts
+        if n.numel() != 2 or n.dtype not in (torch.uint32, torch.int32) or not n.is_cuda or not n.is_contiguous():
+            raise ValueError("counts must be a contiguous uint32 (or int32) CUDA tensor of 2 elements")
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    p = abi.PtFireflyParams(C.sizeof(abi.PtFireflyParams), w, h, int(rank), float(k),
+                            (abi.PT_FIREFLY_REPAIR if repair else 0) | (abi.PT_FIREFLY_NO_LDS if no_lds else 0))
+    abi.check(lib.pt_firefly(C.byref(p), ptr(fb), ptr(variance), ptr(out), ptr(variance_out), ptr(n), _stream_ptr(torch)), "pt_firefly")
+    res = (out,) + ((variance_out,) if variance is not None else ()) + ((n.view(torch.uint32),) if n is not None else ())
+    return res[0] if len(res) == 1 else res
+
+
+_firefly = firefly  # (the hosts below take a keyword named `firefly`)
+
+
+def _firefly_kw(firefly_arg, who):
+    """The `firefly=` keyword of the hosts that take it: None / False -> None (the stage is not run), True -> {} (the defaults), a dict ->
+    firefly()'s keyword arguments."""
+    if firefly_arg is None or firefly_arg is False:
+        return None
+    if firefly_arg is True:
+        return {}
+    if isinstance(firefly_arg, dict) and not set(firefly_arg) - {"rank", "k", "repair", "no_lds"}:
+        return dict(firefly_arg)
+    raise TypeError(f"{who}: firefly must be True or a dict of rank, k, repair, no_lds")
+
+
 def render_host(width: int, height: int, samples: int, scene, cam: camera, depth: int = 50, *, flags: int = 0,
                 shard_index: int = 0, shard_count: int = 1) -> np.ndarray:
     """Torch-free path: pt_render_host renders into a numpy array (allocates, copies back, syncs)."""
@@ -548,13 +609,17 @@ class Accumulator:
         abi.check(self.lib.pt_accum_resolve(self.handle, C.c_void_p(out.data_ptr()), _stream_ptr(torch)), "pt_accum_resolve")
         return out
 
-    def denoise(self, aov_spp: int = 16, **kw):
+    def denoise(self, aov_spp: int = 16, *, firefly=None, **kw):
         """resolve(), the feature buffers of the accumulator's own scene and bound camera (render_aov at `aov_spp` camera rays per
-        pixel) and denoise() over them: denoise(resolve(), **render_aov(...), **kw).  Whole frames only."""
+        pixel) and denoise() over them: denoise(resolve(), **render_aov(...), **kw).  Whole frames only.  `firefly` (True, or a dict of
+        firefly()'s rank, k, repair): the firefly stage runs on the resolved frame before the filter."""
         if self.shard_count != 1:
             raise ValueError("Accumulator.denoise: whole frames only (the filter reads neighbours: gather and unshard first)")
+        fkw = _firefly_kw(firefly, "Accumulator.denoise")
         guides = render_aov(self.width, self.height, aov_spp, self._ds, self.cam, planes=("albedo", "normal", "depth"))
-        return denoise(self.resolve(), **guides, **kw)
+        if fkw is None:
+            return denoise(self.resolve(), **guides, **kw)
+        return denoise(_firefly(self.resolve(), **fkw), **guides, **kw)
 
     def variance(self, out=None):
         """The per-channel variance of each resolved pixel, estimated from the two half buffers (adaptive; include/pt_render.h:
@@ -571,13 +636,19 @@ class Accumulator:
         abi.check(self.lib.pt_variance_estimate(self.handle, C.c_void_p(out.data_ptr()), _stream_ptr(torch)), "pt_variance_estimate")
         return out
 
-    def denoise_variance(self, aov_spp: int = 16, **kw):
+    def denoise_variance(self, aov_spp: int = 16, *, firefly=None, **kw):
         """resolve(), variance(), the feature buffers of the accumulator's own scene and bound camera (render_aov at `aov_spp` camera
-        rays per pixel) and denoise_variance() over them.  Adaptive accumulators, whole frames only."""
+        rays per pixel) and denoise_variance() over them.  Adaptive accumulators, whole frames only.  `firefly` (True, or a dict of
+        firefly()'s rank, k, repair): the firefly stage runs on the resolved frame and its variance before the filter."""
         if self.shard_count != 1:
             raise ValueError("Accumulator.denoise_variance: whole frames only (the filter reads neighbours: gather and unshard first)")
+        fkw = _firefly_kw(firefly, "Accumulator.denoise_variance")
         guides = render_aov(self.width, self.height, aov_spp, self._ds, self.cam, planes=("albedo", "normal", "depth"))
-        return denoise_variance(self.resolve(), self.variance(), **guides, **kw)
+        if fkw is None:
+            return denoise_variance(self.resolve(), self.variance(), **guides, **kw)
+        var = self.variance()
+        color, var = _firefly(self.resolve(), var, variance_out=var, **fkw)
+        return denoise_variance(color, var, **guides, **kw)
 
     def tonemap_rgb8(self):
         """resolve() + tonemap_rgb8() in one pass (whole frames): uint8 [H][W][3], row 0 = top."""
@@ -760,7 +831,7 @@ class TemporalAccumulator:
 
 
 def render_temporal(width: int, height: int, spp: int, scene, cams, depth: int = 50, *, aov_spp: int = 4, denoise: bool = True,
-                    denoise_kw: "dict | None" = None, display: "Display | None" = None, **params):
+                    denoise_kw: "dict | None" = None, display: "Display | None" = None, firefly=None, **params):
     """A camera path rendered at `spp` samples per frame with its history carried along: for each camera of `cams` yields a dict with
     `noisy` (the frame alone), `temporal`, `variance`, `history` (TemporalAccumulator.push's results) and, with `denoise`, `filtered` —
     denoise_variance() over the temporal colour and variance with that frame's guides (render_aov at `aov_spp` camera rays per pixel).
@@ -769,11 +840,15 @@ def render_temporal(width: int, height: int, spp: int, scene, cams, depth: int =
     exists and is what `variance` holds where the history is younger than 4 frames.
     With `display` (a Display) each frame also has `rgb8`: the end of the chain — `filtered` (or `temporal` without `denoise`) metered and
     shown by it, its exposure adapting from frame to frame.
+    With `firefly` (True, or a dict of firefly()'s rank, k, repair) the firefly stage runs on `noisy` and its variance before the push, and
+    each frame also has `clamped`: the frame the history took in (`noisy` stays the frame alone), and `firefly_counts`: the stage's
+    {clamped, repaired} as a uint32 device tensor.
     `params`: push()'s alpha, tol_depth, tol_normal; `denoise_kw`: denoise_variance()'s parameters."""
     import torch
 
     if spp <= 0:
         raise ValueError("spp must be > 0")
+    fkw = _firefly_kw(firefly, "render_temporal")
     ds = _as_device_scene(scene, cache_key=("cuda", torch.cuda.current_device(), torch.cuda.current_stream().cuda_stream))
     acc, hist = None, TemporalAccumulator(width, height)
     try:
@@ -787,8 +862,13 @@ def render_temporal(width: int, height: int, spp: int, scene, cams, depth: int =
                 acc.add(spp // 2)
             noisy, var = acc.resolve(), acc.variance()
             guides = render_aov(width, height, aov_spp, ds, cam, planes=("albedo", "normal", "depth", "id"))
-            color, variance, history = hist.push(noisy, cam, variance=var, **guides, **params)
+            clamped = None
+            if fkw is not None:
+                clamped, var, firefly_counts = _firefly(noisy, var, variance_out=var, counts=True, **fkw)
+            color, variance, history = hist.push(noisy if clamped is None else clamped, cam, variance=var, **guides, **params)
             frame = dict(noisy=noisy, temporal=color, variance=variance, history=history)
+            if clamped is not None:
+                frame["clamped"], frame["firefly_counts"] = clamped, firefly_counts
             if denoise:
                 frame["filtered"] = denoise_variance(color, variance, albedo=guides["albedo"], normal=guides["normal"], depth=guides["depth"],
                                                      **(denoise_kw or {}))
