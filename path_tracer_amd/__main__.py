@@ -38,6 +38,12 @@ With --firefly-clamp [K] the firefly stage (render.firefly; include/pt_post.h) r
 brightest — is scaled down to that, and a pixel that is not finite becomes the mean of its finite neighbours.  The clamp is biased (it
 removes energy), so it is never on unless asked; the numbers of clamped and repaired pixels are printed.  out.png is byte-identical to the
 one written without the options.
+With --spatial-variance [RADIUS] the spatial variance estimate (render.spatial_variance; include/pt_spatial_variance.h) gives
+--denoise-variance the variance of the pixels that have none, from the squared differences of adjacent pixels in a (2 RADIUS + 1)^2 window
+(default: the header's radius) on the pixel's own surface: --denoise-variance then works WITHOUT --noise-threshold — the whole plane is
+estimated from the plain frame —, with --noise-threshold the stage fills the pixels the half buffers give no estimate for, and with
+--temporal those of a young history.  The numbers of estimated pixels and of holes (no estimate either) are printed.  out.png is
+byte-identical to the one written without the option.
 """
 import argparse
 import os
@@ -88,6 +94,11 @@ def print_firefly_counts(a, what, n) -> None:
     print(f"{what}: firefly clamp (rank {a.firefly_kw['rank']}, k {a.firefly_kw['k']:g}): {clamped} pixels clamped, {repaired} repaired")
 
 
+def print_variance_counts(a, what, n) -> None:
+    estimated, holes = (int(v) for v in n.cpu().numpy())
+    print(f"{what}: spatial variance (radius {a.spatial_kw['radius']}): {estimated} pixels estimated, {holes} holes")
+
+
 def write_frames(a, packed, cam_args, move, denoise_kw) -> None:
     """The camera path of --frames: DIR/frame_<f>.png, frame f looking from look_from + f x move.  Plain: render() per frame.  --temporal:
     render_temporal's accumulated frame, or with --denoise-variance that frame through the variance-guided filter.  Each frame leaves
@@ -103,10 +114,14 @@ def write_frames(a, packed, cam_args, move, denoise_kw) -> None:
             write_png(os.path.join(a.frames_dir, f"frame_{f}.png"), show(fb).cpu().numpy())
         return
     extra = {} if a.firefly_kw is None else {"firefly": a.firefly_kw}  # (absent: render_temporal issues exactly the calls it always did)
+    if a.spatial_kw is not None:
+        extra["spatial_variance"] = a.spatial_kw
     for f, frame in enumerate(R.render_temporal(a.width, a.height, a.spp, packed, cams, a.depth, aov_spp=a.aov_spp, denoise=a.denoise_variance,
                                                 denoise_kw=denoise_kw, **extra)):
         if a.firefly_kw is not None:
             print_firefly_counts(a, f"frame {f}", frame["firefly_counts"])
+        if a.spatial_kw is not None:
+            print_variance_counts(a, f"frame {f}", frame["variance_counts"])
         write_png(os.path.join(a.frames_dir, f"frame_{f}.png"), show(frame["filtered" if a.denoise_variance else "temporal"]).cpu().numpy())
 
 
@@ -160,7 +175,15 @@ def main() -> None:
                     help="firefly stage: scale a pixel brighter than K x (default 1) its brightest neighbour down to that, repair NaN / inf; "
                          "acts on what --denoise-out, --display-out and --frames-dir consume (biased: off unless given)")
     ap.add_argument("--firefly-rank", type=int, default=None, metavar="R", help="firefly stage: 1 = the brightest neighbour (default), 2 = the second brightest")
+    ap.add_argument("--spatial-variance", type=int, nargs="?", const=R.abi.PT_SVAR_DEFAULT_RADIUS, default=None, metavar="RADIUS",
+                    help=f"spatial variance estimate: give --denoise-variance a variance where there is none, from a (2 RADIUS + 1)^2 window "
+                         f"(1 .. {R.abi.PT_SVAR_MAX_RADIUS}, default {R.abi.PT_SVAR_DEFAULT_RADIUS}); --denoise-variance then needs no --noise-threshold")
     a = ap.parse_args()
+    if a.spatial_variance is not None and not a.denoise_variance:
+        ap.error("--spatial-variance needs --denoise-variance (the filter that takes the variance)")
+    if a.spatial_variance is not None and not 1 <= a.spatial_variance <= R.abi.PT_SVAR_MAX_RADIUS:
+        ap.error(f"--spatial-variance must be in 1 .. {R.abi.PT_SVAR_MAX_RADIUS}")
+    a.spatial_kw = None if a.spatial_variance is None else dict(radius=a.spatial_variance)
     if a.firefly_rank is not None and a.firefly_clamp is None:
         ap.error("--firefly-rank needs --firefly-clamp")
     if a.firefly_clamp is not None and a.denoise_out is None and a.display_out is None and a.frames_dir is None:
@@ -199,9 +222,9 @@ def main() -> None:
         if a.spp < 1:
             ap.error("--frames needs --spp >= 1")
     temporal_filter = a.temporal and a.denoise_variance
-    if temporal_filter and a.denoise_out is not None and a.noise_threshold is None:
+    if temporal_filter and a.denoise_out is not None and a.noise_threshold is None and a.spatial_kw is None:
         ap.error("--denoise-out with --denoise-variance needs --noise-threshold (without --denoise-out, --temporal --denoise-variance filters the frames only)")
-    if a.denoise_variance and a.noise_threshold is None and not a.temporal:
+    if a.denoise_variance and a.noise_threshold is None and not a.temporal and a.spatial_kw is None:
         ap.error("--denoise-variance needs --noise-threshold (the variance comes from the adaptive accumulator's half buffers)")
     if a.denoise_variance and a.denoise_out is None and not a.temporal:
         ap.error("--denoise-variance needs --denoise-out")
@@ -249,12 +272,14 @@ def main() -> None:
     cam = scenes.make_camera(cam_args, a.width, a.height)
     t0 = time.perf_counter()
     mean_spp = None
+    variance = [None]  # (the adaptive path's estimate; --spatial-variance makes or completes it)
     if adaptive:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        fb, counts, *variance = R.render_adaptive(a.width, a.height, packed, cam, a.depth, threshold=a.noise_threshold, min_spp=a.min_spp,
+        fb, counts, *estimate = R.render_adaptive(a.width, a.height, packed, cam, a.depth, threshold=a.noise_threshold, min_spp=a.min_spp,
                                                   max_spp=a.spp, step=a.adaptive_step, variance=a.denoise_variance)
         e1.record()
+        variance = estimate or variance
         rgb8 = R.tonemap_rgb8(fb)
         torch.cuda.synchronize()
         ms = e0.elapsed_time(e1)
@@ -287,10 +312,13 @@ def main() -> None:
     if a.aov_dir:
         write_aovs(a.aov_dir, planes)
     if a.denoise_out or a.display_out:
-        if a.denoise_out and a.denoise_variance:
+        if a.denoise_out and a.denoise_variance and variance[0] is not None:
             fb, variance[0] = clamp_fireflies(a, fb, "frame", variance[0])
         else:
             fb = clamp_fireflies(a, fb, "frame")
+    if a.denoise_out and a.spatial_kw is not None:
+        variance[0], n_var = R.spatial_variance(fb, variance[0], out=variance[0], counts=True, **planes, **a.spatial_kw)
+        print_variance_counts(a, "frame", n_var)
     if a.denoise_out:
         filtered = R.denoise_variance(fb, variance[0], **planes, **denoise_kw) if a.denoise_variance else R.denoise(fb, **planes, **denoise_kw)
         write_png(a.denoise_out, R.tonemap_rgb8(filtered).cpu().numpy())

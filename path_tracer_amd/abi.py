@@ -1,4 +1,5 @@
-"""ctypes mirror of include/pt_render.h — the C-ABI drop-in boundary of render() — and of include/pt_post.h (POST_SIGNATURES).
+"""ctypes mirror of include/pt_render.h — the C-ABI drop-in boundary of render() — and of include/pt_post.h (POST_SIGNATURES) and
+include/pt_spatial_variance.h (SPATIAL_VARIANCE_SIGNATURES).
 
 The structs are declared field-for-field as in the header; `load_library()` opens the
 in-tree `libpt_render.so` built by `__graft_entry__.build()` (hipcc, gfx950) and fails
@@ -164,6 +165,12 @@ class PtFireflyParams(C.Structure):
                 ("flags", C.c_uint32), ("reserved", C.c_int32 * 2)]
 
 
+class PtSpatialVarianceParams(C.Structure):
+    """include/pt_spatial_variance.h PtSpatialVarianceParams: the spatial variance estimate's parameters (pt_spatial_variance)."""
+    _fields_ = [("struct_size", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("radius", C.c_int32), ("min_pairs", C.c_int32),
+                ("tol_depth", C.c_float), ("tol_normal", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_int32 * 2)]
+
+
 assert C.sizeof(PtHittable) == 64 and C.sizeof(PtMaterial) == 32 and C.sizeof(PtTexture) == 48
 assert C.sizeof(PtCamera) == 96 and C.sizeof(PtRenderParams) == 32
 
@@ -288,6 +295,23 @@ PT_FIREFLY_TILE_W, PT_FIREFLY_TILE_H = 32, 8
 # the header's PT_FIREFLY_DEFAULT_* (pt_firefly_params_init)
 PT_FIREFLY_DEFAULT_RANK, PT_FIREFLY_DEFAULT_K, PT_FIREFLY_DEFAULT_FLAGS = 1, 1.0, PT_FIREFLY_REPAIR
 
+# name -> (restype, argtypes): every entry point include/pt_spatial_variance.h declares.  A table of its own, like POST_SIGNATURES and for
+# its reason: SIGNATURES and POST_SIGNATURES stay exactly what their headers declare.  load_library() applies a row where the library
+# exports the symbol; has_spatial_variance() tells whether the loaded one has the stage.
+SPATIAL_VARIANCE_SIGNATURES = {
+    "pt_spatial_variance_params_init": (None, [C.POINTER(PtSpatialVarianceParams), C.c_int32, C.c_int32]),
+    "pt_spatial_variance": (C.c_int, [C.POINTER(PtSpatialVarianceParams)] + [C.c_void_p] * 9),
+    "pt_debug_last_spatial_variance": (C.c_int, [C.POINTER(C.c_int32)]),
+}
+SPATIAL_VARIANCE_SYMBOLS = frozenset(SPATIAL_VARIANCE_SIGNATURES)
+PT_SVAR_DEMODULATE = 1
+PT_SVAR_NO_LDS = 2  # A/B switch, same bits: the window from global memory
+PT_SVAR_MAX_RADIUS = 3
+PT_SVAR_TILE_W, PT_SVAR_TILE_H = 32, 8
+# the header's PT_SVAR_DEFAULT_* (pt_spatial_variance_params_init)
+PT_SVAR_DEFAULT_RADIUS, PT_SVAR_DEFAULT_MIN_PAIRS, PT_SVAR_DEFAULT_TOL_DEPTH, PT_SVAR_DEFAULT_TOL_NORMAL = 2, 4, 0.1, 0.5
+PT_SVAR_DEFAULT_FLAGS = PT_SVAR_DEMODULATE
+
 # Entry points a library may lack and still load for everything else (include/pt_render.h: the feature is detected by their presence);
 # has_accumulator() tells whether the loaded one has them.
 ACCUM_SYMBOLS = frozenset(n for n in SIGNATURES if n.startswith("pt_accum_") or n == "pt_render_accumulate")
@@ -397,7 +421,7 @@ def load_library() -> C.CDLL:
         fn = getattr(lib, name)  # AttributeError if the library does not export what the header declares
         fn.restype = res
         fn.argtypes = args
-    for name, (res, args) in POST_SIGNATURES.items():  # include/pt_post.h: applied where the library has the symbol
+    for name, (res, args) in list(POST_SIGNATURES.items()) + list(SPATIAL_VARIANCE_SIGNATURES.items()):  # include/pt_post.h, pt_spatial_variance.h: applied where the library has the symbol
         if hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype = res
@@ -455,6 +479,12 @@ def has_firefly(lib=None) -> bool:
     """Does the loaded library offer the firefly stage (include/pt_post.h: pt_firefly)?"""
     lib = lib or load_library()
     return all(hasattr(lib, n) for n in FIREFLY_SYMBOLS)
+
+
+def has_spatial_variance(lib=None) -> bool:
+    """Does the loaded library offer the spatial variance estimate (include/pt_spatial_variance.h: pt_spatial_variance)?"""
+    lib = lib or load_library()
+    return all(hasattr(lib, n) for n in SPATIAL_VARIANCE_SYMBOLS)
 
 
 def check(code: int, where: str) -> None:

@@ -28,6 +28,7 @@
 
 #include "../../include/pt_render.h"
 #include "../../include/pt_post.h"
+#include "../../include/pt_spatial_variance.h"
 #include "pt_device.hpp"
 #include "pt_flatten.hpp"
 
@@ -2008,6 +2009,7 @@ __global__ __launch_bounds__(256) void display_apply_kernel(const float* color, 
 }
 
 #include "pt_firefly.hpp"
+#include "pt_spatial_variance.hpp"
 
 thread_local std::string g_last_error;
 
@@ -4032,6 +4034,77 @@ int pt_debug_last_firefly(int32_t out[4]) {
   if (!out) return fail(PT_ERR_INVALID_ARG, "pt_debug_last_firefly: NULL argument");
   std::lock_guard<std::mutex> lock(g_firefly_mutex);
   std::memcpy(out, g_last_firefly, sizeof g_last_firefly);
+  return PT_OK;
+}
+
+// ---- spatial variance estimate (include/pt_spatial_variance.h): pt_spatial_variance (svar_kernel) ----------------------------------------
+static std::mutex g_svar_mutex;
+static int32_t g_last_svar[4] = {0, 0, 0, 0}; // pt_debug_last_spatial_variance
+
+void pt_spatial_variance_params_init(PtSpatialVarianceParams* params, int32_t width, int32_t height) {
+  if (!params) return;
+  std::memset(params, 0, sizeof *params);
+  params->struct_size = (int32_t)sizeof(PtSpatialVarianceParams);
+  params->width = width; params->height = height;
+  params->radius = PT_SVAR_DEFAULT_RADIUS;
+  params->min_pairs = PT_SVAR_DEFAULT_MIN_PAIRS;
+  params->tol_depth = PT_SVAR_DEFAULT_TOL_DEPTH;
+  params->tol_normal = PT_SVAR_DEFAULT_TOL_NORMAL;
+  params->flags = PT_SVAR_DEFAULT_FLAGS;
+}
+
+int pt_spatial_variance(const PtSpatialVarianceParams* params, const float* color, const float* albedo, const float* normal,
+                        const float* depth, const int32_t* id, const float* variance_in, float* variance_out, uint32_t* counts,
+                        void* stream) {
+  auto bad = [&](const char* what) { return fail(PT_ERR_INVALID_ARG, std::string("pt_spatial_variance: ") + what); };
+  if (!params || !color || !variance_out) return bad("NULL params, color or variance_out");
+  if (params->struct_size != (int32_t)sizeof(PtSpatialVarianceParams)) return bad("PtSpatialVarianceParams.struct_size is not this library's");
+  if (params->width <= 0 || params->height <= 0) return bad("width and height must be > 0");
+  if (params->radius < 1 || params->radius > PT_SVAR_MAX_RADIUS) return bad("radius must be 1 ... PT_SVAR_MAX_RADIUS");
+  if (params->min_pairs < 1) return bad("min_pairs must be >= 1");
+  if (!(std::isfinite(params->tol_depth) && params->tol_depth > 0.0f)) return bad("tol_depth must be finite and > 0");
+  if (!(std::isfinite(params->tol_normal) && params->tol_normal > 0.0f)) return bad("tol_normal must be finite and > 0");
+  if (params->flags & ~(PT_SVAR_DEMODULATE | PT_SVAR_NO_LDS)) return bad("unknown flags");
+  if ((params->flags & PT_SVAR_DEMODULATE) && !albedo) return bad("PT_SVAR_DEMODULATE needs albedo");
+  const int64_t pixels = (int64_t)params->width * params->height;
+  if (pixels > ((int64_t)1 << 30)) return fail(PT_ERR_TOO_LARGE, "pt_spatial_variance: more than 2^30 pixels");
+  if ((uintptr_t)counts % 8) return bad("counts must be 8-byte aligned");
+  const uintptr_t frame = (uintptr_t)pixels * 12, plane = (uintptr_t)pixels * 4;
+  const void* const var_written = variance_out == variance_in ? nullptr : variance_out; // variance_out may BE variance_in
+  const struct { const void* ptr; uintptr_t bytes; } read[] = {{color, frame}, {albedo, frame}, {normal, frame}, {depth, plane}, {id, plane},
+                                                                {variance_in, frame}};
+  for (const auto& in : read)
+    if (overlaps(var_written, frame, in.ptr, in.bytes) || overlaps(counts, 8, in.ptr, in.bytes))
+      return bad("variance_out and counts must not overlap color, a guide or variance_in (variance_out may be variance_in itself)");
+  if (overlaps(counts, 8, variance_out, frame)) return bad("variance_out and counts must not overlap one another");
+
+  hipStream_t st = (hipStream_t)stream;
+  const bool lds = !(params->flags & PT_SVAR_NO_LDS);
+  SvarArgs a;
+  a.color = color; a.albedo = albedo; a.normal = normal; a.depth = depth; a.id = id; a.variance_in = variance_in; a.variance_out = variance_out;
+  a.counts = reinterpret_cast<unsigned long long*>(counts);
+  a.width = params->width; a.height = params->height;
+  a.tiles_x = (params->width + PT_SVAR_TILE_W - 1) / PT_SVAR_TILE_W;
+  a.radius = params->radius; a.min_pairs = params->min_pairs;
+  a.demodulate = params->flags & PT_SVAR_DEMODULATE;
+  a.tol_depth = params->tol_depth; a.tol_normal = params->tol_normal;
+  const int64_t tiles_y = (params->height + PT_SVAR_TILE_H - 1) / PT_SVAR_TILE_H;
+  a.tiles = (int)(a.tiles_x * tiles_y); // (at most 2^30: a frame one pixel wide and 2^30 rows high has 2^27)
+  const dim3 grid((unsigned)std::min(a.tiles, (int)PT_SVAR_MAX_BLOCKS)); // one dimension; each workgroup walks the tiles grid.x apart
+  std::lock_guard<std::mutex> lock(g_svar_mutex);
+  std::memset(g_last_svar, 0, sizeof g_last_svar);
+  if (counts) PT_HIP(hipMemsetAsync(counts, 0, 8, st));
+  if (lds) hipLaunchKernelGGL(svar_kernel<true>, grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(svar_kernel<false>, grid, dim3(256), 0, st, a);
+  PT_HIP(hipGetLastError());
+  g_last_svar[0] = lds ? 2 : 1; g_last_svar[1] = a.tiles_x; g_last_svar[2] = (int32_t)tiles_y; g_last_svar[3] = params->radius;
+  return PT_OK;
+}
+
+int pt_debug_last_spatial_variance(int32_t out[4]) {
+  if (!out) return fail(PT_ERR_INVALID_ARG, "pt_debug_last_spatial_variance: NULL argument");
+  std::lock_guard<std::mutex> lock(g_svar_mutex);
+  std::memcpy(out, g_last_svar, sizeof g_last_svar);
   return PT_OK;
 }
 

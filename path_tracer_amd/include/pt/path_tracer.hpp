@@ -35,6 +35,7 @@
 
 #include "../../../include/pt_render.h"
 #include "../../../include/pt_post.h"
+#include "../../../include/pt_spatial_variance.h"
 #include "image_io.hpp"
 
 namespace pt {
@@ -536,6 +537,34 @@ inline void firefly(int width, int height, const float* color, const float* vari
                     uint32_t* counts = nullptr, const firefly_params& fp = {}, void* stream = nullptr) {
   const PtFireflyParams p{(int32_t)sizeof(PtFireflyParams), width, height, fp.rank, fp.k, fp.repair ? PT_FIREFLY_REPAIR : 0u, {0, 0}};
   check(pt_firefly(&p, color, variance, out, variance_out, counts, stream), "pt_firefly");
+}
+
+// The spatial variance estimate (include/pt_spatial_variance.h: pt_spatial_variance): the variance of each pixel's mean from the squared
+// differences of adjacent pixels in a (2 radius + 1)^2 window, over the pixels that lie on the centre's surface by the guides.  With
+// `variance_in` it fills only the pixels that have no estimate (a channel that is not >= 0 and finite) and keeps the others bit for bit;
+// without, it makes the whole plane.  color, variance_out and the optional albedo, normal, variance_in ([height][width][3]), depth, id
+// ([height][width]) and counts (uint32[2]: estimated, holes) are DEVICE buffers the caller owns; variance_out may be variance_in.  The
+// defaults are the header's (pt_spatial_variance_params_init); demodulate < 0: where albedo is given.
+struct spatial_variance_params {
+  int radius = PT_SVAR_DEFAULT_RADIUS;
+  int min_pairs = PT_SVAR_DEFAULT_MIN_PAIRS;
+  float tol_depth = PT_SVAR_DEFAULT_TOL_DEPTH;
+  float tol_normal = PT_SVAR_DEFAULT_TOL_NORMAL;
+  int demodulate = -1; // 0: off, 1: on (needs albedo), -1: on where albedo is given
+};
+struct spatial_variance_guides {
+  const float* albedo = nullptr;
+  const float* normal = nullptr;
+  const float* depth = nullptr;
+  const int32_t* id = nullptr;
+};
+// asynchronous on `stream`
+inline void spatial_variance(int width, int height, const float* color, const spatial_variance_guides& g, const float* variance_in,
+                             float* variance_out, uint32_t* counts = nullptr, const spatial_variance_params& sp = {}, void* stream = nullptr) {
+  const bool demodulate = sp.demodulate < 0 ? g.albedo != nullptr : sp.demodulate != 0;
+  const PtSpatialVarianceParams p{(int32_t)sizeof(PtSpatialVarianceParams), width, height, sp.radius, sp.min_pairs, sp.tol_depth, sp.tol_normal,
+                                  demodulate ? PT_SVAR_DEMODULATE : 0u, {0, 0}};
+  check(pt_spatial_variance(&p, color, g.albedo, g.normal, g.depth, g.id, variance_in, variance_out, counts, stream), "pt_spatial_variance");
 }
 
 // Progressive rendering: one frame in sample windows; RAII over pt_accum_create / pt_accum_destroy (include/pt_render.h, PtAccum).

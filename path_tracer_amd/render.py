@@ -296,6 +296,75 @@ def _firefly_kw(firefly_arg, who):
     raise TypeError(f"{who}: firefly must be True or a dict of rank, k, repair, no_lds")
 
 
+def spatial_variance(fb, variance=None, *, albedo=None, normal=None, depth=None, id=None, radius: int = abi.PT_SVAR_DEFAULT_RADIUS,
+                     min_pairs: int = abi.PT_SVAR_DEFAULT_MIN_PAIRS, tol_depth: float = abi.PT_SVAR_DEFAULT_TOL_DEPTH,
+                     tol_normal: float = abi.PT_SVAR_DEFAULT_TOL_NORMAL, demodulate=None, no_lds: bool = False, out=None, counts=False,
+                     **other_planes):
+    """The spatial variance estimate (include/pt_spatial_variance.h: pt_spatial_variance): the variance of each pixel's mean, estimated
+    from the squared differences of adjacent pixels in a (2 `radius` + 1)^2 window over the pixels that lie on the centre's surface by the
+    guides.  `fb`: [H][W][3] float32 on the GPU, a whole frame; `albedo`, `normal` [H][W][3], `depth` [H][W], `id` [H][W] int32
+    (optional): its feature buffers — spatial_variance(fb, **render_aov(...)) works: the planes the stage does not take are ignored.
+    `variance` (optional): a plane shaped like fb — FILL MODE: a pixel whose three values are >= 0 and finite keeps them bit for bit, the
+    others (+inf "no estimate", NaN, negative) are estimated.  A pixel with fewer than `min_pairs` pairs gets +inf.  `demodulate`: estimate
+    on fb / (albedo + 1e-3); None (the default) = where `albedo` is given.  `out` may be `variance`.  `no_lds`: the A/B switch
+    PT_SVAR_NO_LDS (the same bits).  Asynchronous on torch's current stream.
+    Returns the variance plane; with `counts` (True, or a 2-element uint32 / int32 device tensor to write), (plane, counts): the uint32
+    device tensor {estimated, holes} — nothing is read back: .cpu() it when the numbers are wanted."""
+    import torch
+
+    if not torch.cuda.is_available():
+        raise RuntimeError("path_tracer_amd.spatial_variance needs a HIP device: there is no CPU path in the product")
+    lib = abi.load_library()
+    if not abi.has_spatial_variance(lib):
+        raise ImportError(f"{abi.library_path()} predates the spatial variance estimate (no pt_spatial_variance entry point)")
+    unknown = set(other_planes) - set(abi.AOV_PLANES)
+    if unknown:
+        raise TypeError(f"spatial_variance() got unexpected keyword arguments {sorted(unknown)}")
+    if fb is None or fb.dim() != 3 or fb.shape[2] != 3:
+        raise ValueError("fb must be a whole frame [H][W][3] (gather and unshard a multi-GPU frame first)")
+    h, w, _ = (int(n) for n in fb.shape)
+    if out is None:
+        out = torch.empty((h, w, 3), dtype=torch.float32, device=fb.device)
+    for what, t in (("fb", fb), ("variance", variance), ("albedo", albedo), ("normal", normal), ("out", out)):
+        if t is not None:
+            if tuple(t.shape) != (h, w, 3):
+                raise ValueError(f"{what} must have the frame's shape")
+            _frame_ptr(t, what)
+    for what, t, dtype in (("depth", depth, torch.float32), ("id", id, torch.int32)):
+        if t is not None and (tuple(t.shape) != (h, w) or t.dtype != dtype or not t.is_cuda or not t.is_contiguous()):
+            raise ValueError(f"{what} must be a contiguous {dtype} CUDA tensor of shape [H][W]")
+    n = None
+    if counts is True:
+        n = torch.empty(2, dtype=torch.uint32, device=fb.device)
+    elif counts is not None and counts is not False:
+        n = counts
+        if n.numel() != 2 or n.dtype not in (torch.uint32, torch.int32) or not n.is_cuda or not n.is_contiguous():
+            raise ValueError("counts must be a contiguous uint32 (or int32) CUDA tensor of 2 elements")
+    if demodulate is None:
+        demodulate = albedo is not None
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    p = abi.PtSpatialVarianceParams(C.sizeof(abi.PtSpatialVarianceParams), w, h, int(radius), int(min_pairs), float(tol_depth), float(tol_normal),
+                                    (abi.PT_SVAR_DEMODULATE if demodulate else 0) | (abi.PT_SVAR_NO_LDS if no_lds else 0))
+    abi.check(lib.pt_spatial_variance(C.byref(p), ptr(fb), ptr(albedo), ptr(normal), ptr(depth), ptr(id), ptr(variance), ptr(out), ptr(n),
+                                      _stream_ptr(torch)), "pt_spatial_variance")
+    return (out, n.view(torch.uint32)) if n is not None else out
+
+
+_spatial_variance = spatial_variance  # (render_temporal takes a keyword named `spatial_variance`)
+
+
+def _spatial_kw(arg, who, name="spatial"):
+    """The `spatial=` / `spatial_variance=` keyword of the hosts that take it: None / False -> None (the stage is not run), True -> {} (the
+    defaults), a dict -> spatial_variance()'s parameters."""
+    if arg is None or arg is False:
+        return None
+    if arg is True:
+        return {}
+    if isinstance(arg, dict) and not set(arg) - {"radius", "min_pairs", "tol_depth", "tol_normal", "demodulate", "no_lds"}:
+        return dict(arg)
+    raise TypeError(f"{who}: {name} must be True or a dict of radius, min_pairs, tol_depth, tol_normal, demodulate, no_lds")
+
+
 def render_host(width: int, height: int, samples: int, scene, cam: camera, depth: int = 50, *, flags: int = 0,
                 shard_index: int = 0, shard_count: int = 1) -> np.ndarray:
     """Torch-free path: pt_render_host renders into a numpy array (allocates, copies back, syncs)."""
@@ -636,13 +705,28 @@ class Accumulator:
         abi.check(self.lib.pt_variance_estimate(self.handle, C.c_void_p(out.data_ptr()), _stream_ptr(torch)), "pt_variance_estimate")
         return out
 
-    def denoise_variance(self, aov_spp: int = 16, *, firefly=None, **kw):
+    def denoise_variance(self, aov_spp: int = 16, *, firefly=None, spatial=None, **kw):
         """resolve(), variance(), the feature buffers of the accumulator's own scene and bound camera (render_aov at `aov_spp` camera
         rays per pixel) and denoise_variance() over them.  Adaptive accumulators, whole frames only.  `firefly` (True, or a dict of
-        firefly()'s rank, k, repair): the firefly stage runs on the resolved frame and its variance before the filter."""
+        firefly()'s rank, k, repair): the firefly stage runs on the resolved frame and its variance before the filter.
+        `spatial` (True, or a dict of spatial_variance()'s radius, min_pairs, tol_depth, tol_normal, demodulate): the spatial variance
+        estimate (guides: albedo, normal, depth and id) fills the pixels of variance() that have no estimate — after the firefly stage,
+        whose repaired pixels are such — and on a PLAIN accumulator, which has no variance(), it makes the whole plane: the only way
+        this method works on one."""
         if self.shard_count != 1:
             raise ValueError("Accumulator.denoise_variance: whole frames only (the filter reads neighbours: gather and unshard first)")
         fkw = _firefly_kw(firefly, "Accumulator.denoise_variance")
+        skw = _spatial_kw(spatial, "Accumulator.denoise_variance")
+        if skw is not None:
+            guides = render_aov(self.width, self.height, aov_spp, self._ds, self.cam, planes=("albedo", "normal", "depth", "id"))
+            color, var = self.resolve(), self.variance() if self.adaptive else None
+            if fkw is not None:
+                if var is None:
+                    color = _firefly(color, **fkw)
+                else:
+                    color, var = _firefly(color, var, variance_out=var, **fkw)
+            var = _spatial_variance(color, var, out=var, **guides, **skw)
+            return denoise_variance(color, var, albedo=guides["albedo"], normal=guides["normal"], depth=guides["depth"], **kw)
         guides = render_aov(self.width, self.height, aov_spp, self._ds, self.cam, planes=("albedo", "normal", "depth"))
         if fkw is None:
             return denoise_variance(self.resolve(), self.variance(), **guides, **kw)
@@ -831,7 +915,7 @@ class TemporalAccumulator:
 
 
 def render_temporal(width: int, height: int, spp: int, scene, cams, depth: int = 50, *, aov_spp: int = 4, denoise: bool = True,
-                    denoise_kw: "dict | None" = None, display: "Display | None" = None, firefly=None, **params):
+                    denoise_kw: "dict | None" = None, display: "Display | None" = None, firefly=None, spatial_variance=None, **params):
     """A camera path rendered at `spp` samples per frame with its history carried along: for each camera of `cams` yields a dict with
     `noisy` (the frame alone), `temporal`, `variance`, `history` (TemporalAccumulator.push's results) and, with `denoise`, `filtered` —
     denoise_variance() over the temporal colour and variance with that frame's guides (render_aov at `aov_spp` camera rays per pixel).
@@ -843,12 +927,17 @@ def render_temporal(width: int, height: int, spp: int, scene, cams, depth: int =
     With `firefly` (True, or a dict of firefly()'s rank, k, repair) the firefly stage runs on `noisy` and its variance before the push, and
     each frame also has `clamped`: the frame the history took in (`noisy` stays the frame alone), and `firefly_counts`: the stage's
     {clamped, repaired} as a uint32 device tensor.
+    With `spatial_variance` (True, or a dict of spatial_variance()'s radius, min_pairs, tol_depth, tol_normal, demodulate) the spatial
+    variance estimate runs after the push, on the accumulated colour with the frame's guides, and fills `variance` in place where the push
+    left no estimate (a young history without one of the frame's own, a repaired pixel); each frame also has `variance_counts`: the
+    stage's {estimated, holes} as a uint32 device tensor.
     `params`: push()'s alpha, tol_depth, tol_normal; `denoise_kw`: denoise_variance()'s parameters."""
     import torch
 
     if spp <= 0:
         raise ValueError("spp must be > 0")
     fkw = _firefly_kw(firefly, "render_temporal")
+    skw = _spatial_kw(spatial_variance, "render_temporal", "spatial_variance")
     ds = _as_device_scene(scene, cache_key=("cuda", torch.cuda.current_device(), torch.cuda.current_stream().cuda_stream))
     acc, hist = None, TemporalAccumulator(width, height)
     try:
@@ -869,6 +958,8 @@ def render_temporal(width: int, height: int, spp: int, scene, cams, depth: int =
             frame = dict(noisy=noisy, temporal=color, variance=variance, history=history)
             if clamped is not None:
                 frame["clamped"], frame["firefly_counts"] = clamped, firefly_counts
+            if skw is not None:
+                _, frame["variance_counts"] = _spatial_variance(color, variance, out=variance, counts=True, **guides, **skw)
             if denoise:
                 frame["filtered"] = denoise_variance(color, variance, albedo=guides["albedo"], normal=guides["normal"], depth=guides["depth"],
                                                      **(denoise_kw or {}))
