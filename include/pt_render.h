@@ -1048,6 +1048,12 @@ int pt_debug_last_kernels(const PtScene* scene, int32_t out[24]);
  * first record.  out[1..3] say what the scene's blob holds whether or not out[0] claims it.  For tests (tests/test_gpu_pool_plan.py).   */
 int pt_debug_last_pool_plan(const PtScene* scene, int32_t out[4]);
 
+/* The plan's first word as that pass's kernel read it (csrc/pt_device.hpp: PoolPlan.one), which says what the kernel DID with a claimed
+ * pool: 0 = no plan, the run list was walked; 2 = the pool is one chunk of the slab pass (<= 16 entries) and the kernel took it from its
+ * arguments; 1 = claimed, but larger than one chunk: the LDS-resident rect / box-only kernels hold no chunk loop on that path and walked
+ * the run list record by record.  (pt_debug_last_pool_plan's out[0] is 1 for both claimed kinds.)  For tests (tests/test_gpu_headline_flags.py). */
+int pt_debug_last_pool_word(const PtScene* scene, int32_t* out);
+
 /* The same derivation host-only — no device call — for the frame pass of a render of `desc` with `params` (tuning NULL = defaults +
  * environment): out[0..3] as above; out[4] = offset of the pool's slab entries, out[5] = the bits of its largest |coordinate|,
  * out[6..8] = the first run's header (device kind, first record, count); out[9] = 1 if the SCENE allows the plan (whatever kernel and

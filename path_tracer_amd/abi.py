@@ -277,6 +277,7 @@ SIGNATURES = {
     "pt_debug_plan_pass": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     # the one-pool plan of rect / box-only scenes, as the last frame pass got it and as derived without a device: likewise optional (POOL_PLAN_SYMBOLS)
     "pt_debug_last_pool_plan": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "pt_debug_last_pool_word": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "pt_debug_pool_plan": (C.c_int, [C.POINTER(PtSceneDesc), C.POINTER(PtTuning), C.POINTER(PtRenderParams), C.POINTER(C.c_int32)]),
 }
 

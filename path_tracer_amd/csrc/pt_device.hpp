@@ -174,12 +174,14 @@ __device__ __forceinline__ float div_exact(float n, float d, float y, float q0);
 // origin + offset == origin, (...) - origin - offset == (...) - origin bit for bit (x + (+-0) == x unless x is -0, and a
 // difference of floats is never -0 unless its first operand is): the lens arithmetic, and the square root that only scales
 // the second draw, are skipped — the three draws are not (the generator's state must advance as in camera.hpp:93-100).
-__device__ __forceinline__ Ray camera_ray(const Cam& c, int x, int y, int width, int height, float inv_w, float inv_h, uint32_t& rng,
+// xf, yf, wf, hf: (float)x, (float)y, (float)width, (float)height.  The persistent loop has them ready — the frame's two as launch constants
+// (KArgs.width_f / height_f), the pixel's two in its cold state — so a regeneration converts nothing; the overload below converts on the spot.
+__device__ __forceinline__ Ray camera_ray(const Cam& c, float xf, float yf, float wf, float hf, float inv_w, float inv_h, uint32_t& rng,
                                           bool pinhole = false) {
-  const float nu = (float)x + rng_float(rng);
-  const float su = div_exact(nu, (float)width, inv_w, nu * inv_w);
-  const float nv = (float)y + rng_float(rng);
-  const float sv = div_exact(nv, (float)height, inv_h, nv * inv_h);
+  const float nu = xf + rng_float(rng);
+  const float su = div_exact(nu, wf, inv_w, nu * inv_w);
+  const float nv = yf + rng_float(rng);
+  const float sv = div_exact(nv, hf, inv_h, nv * inv_h);
   V3 origin = mk(c.origin[0], c.origin[1], c.origin[2]);
   Ray r;
   if (pinhole) {
@@ -201,6 +203,10 @@ __device__ __forceinline__ Ray camera_ray(const Cam& c, int x, int y, int width,
   }
   r.tm = rng_float(rng, c.time0, c.time1);
   return r;
+}
+__device__ __forceinline__ Ray camera_ray(const Cam& c, int x, int y, int width, int height, float inv_w, float inv_h, uint32_t& rng,
+                                          bool pinhole = false) {
+  return camera_ray(c, (float)x, (float)y, (float)width, (float)height, inv_w, inv_h, rng, pinhole);
 }
 __host__ __device__ inline bool cam_is_pinhole(const Cam& c) {
   return c.lens_radius == 0.0f && c.origin[0] != 0.0f && c.origin[1] != 0.0f && c.origin[2] != 0.0f;
@@ -238,7 +244,11 @@ __device__ __forceinline__ float rcp_rn_guarded(float d) {
   return __builtin_fmaf(__builtin_fmaf(-d, y0, 1.0f), y0, y0);
 }
 
-__device__ __forceinline__ RayCtx make_ctx(const Ray& r, bool scene_fast_ok) {
+// VOTE (the headline family's loop): the four comparisons also leave the wave's mask of irregular lanes in *irregular — each comparison's own
+// SGPR pair, joined by scalar ORs — so the loop's vote on "every live ray regular" is scalar arithmetic on that mask and the live lanes' mask.
+// (A ballot of the per-lane flag itself is a v_cndmask 0 / 1 and a v_cmp on it: the compiler materialises every boolean that is not a comparison.)
+template <bool VOTE = false>
+__device__ __forceinline__ RayCtx make_ctx(const Ray& r, bool scene_fast_ok, unsigned long long* irregular = nullptr) {
   RayCtx c;
   c.r = r;
   c.live = true;
@@ -253,6 +263,13 @@ __device__ __forceinline__ RayCtx make_ctx(const Ray& r, bool scene_fast_ok) {
   const float dmin = __builtin_fminf(__builtin_fminf(ax, ay), az), dmax = __builtin_fmaxf(__builtin_fmaxf(ax, ay), az);
   const float omax = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(r.o.x), __builtin_fabsf(r.o.y)), __builtin_fabsf(r.o.z));
   const float osum = (r.o.x + r.o.y) + r.o.z;
+  if constexpr (VOTE) {
+    unsigned long long m = __builtin_amdgcn_ballot_w64(!(dmin >= lo)) | __builtin_amdgcn_ballot_w64(!(dmax <= hi)) |
+                           __builtin_amdgcn_ballot_w64(!(omax <= ohi)) | __builtin_amdgcn_ballot_w64(__builtin_isunordered(c.a, osum));
+    m |= scene_fast_ok ? 0ull : ~0ull;
+    *irregular = m;
+    c.reg = !__builtin_amdgcn_inverse_ballot_w64(m);
+  } else
   c.reg = scene_fast_ok && dmin >= lo && dmax <= hi && omax <= ohi && !__builtin_isunordered(c.a, osum);
   c.yx = rcp_rn_guarded(r.d.x); // only used when the ray is regular
   c.yy = rcp_rn_guarded(r.d.y);
@@ -560,14 +577,48 @@ __device__ __forceinline__ bool box_fast(f4 R0, f4 R1, const RayCtx& c, float mx
 // is ONE asm statement, so nothing the compiler schedules can run under the narrowed mask; it declares what it touches
 // (closest, hit in/out; vcc clobbered: v_cmpx_e32 also writes it; EXEC is restored before the block ends).
 // `hit_base` = hit id of this box with side 0, in a VGPR; side S adds S << PT_HIT_SIDE_SHIFT (hit_pack).
-template <int AX, int S>
+// POP (the last side of a slab pool's trip: slab_chunk_pass): the statement goes on, behind the s_mov that restores EXEC, with the trip's close —
+// `closest` (the scan's own; `cl` above is the trip's bound) takes the trip's t where the hit changed hands, and the lane's nearest key is popped: each
+// register written in place, the pops between the comparison and the select that waits for its VCC.  As a statement of its own directly behind
+// this one it cost a wait state per trip: the hazard pass puts one between two asm statements that share a register (here the hit), whatever
+// their text holds, and counts no asm statement as one — neither reordering that statement nor splitting it removed it.
+struct TripPop {
+  float &kdone, &k1, &k2, &k3, &closest;
+  float none;
+  int holder;
+};
+template <int AX, int S, bool POP = false>
 __device__ __forceinline__ void rect_side_cmpx(float a0, float a1, float b0, float b1, float k, const RayCtx& c,
-                                               unsigned long long exec_all, int hit_base, float& closest, int& hit) {
+                                               unsigned long long exec_all, int hit_base, float& closest, int& hit, const TripPop* pop = nullptr) {
   typedef AxisSel<AX> Sel;
   const float n = k - Sel::ok(c);
   const float t = div_exact(n, Sel::dk(c), Sel::yk(c), n * Sel::yk(c));
   const float a = Sel::oa(c) + t * Sel::da(c);
   const float b = Sel::ob(c) + t * Sel::db(c);
+  if constexpr (POP) {
+    asm volatile(
+        "v_cmpx_le_f32_e32 vcc, %[tmin], %[t]\n\t"
+        "v_cmpx_ngt_f32_e32 vcc, %[t], %[cl]\n\t"
+        "v_cmpx_nlt_f32_e32 vcc, %[a], %[a0]\n\t"
+        "v_cmpx_ngt_f32_e32 vcc, %[a], %[a1]\n\t"
+        "v_cmpx_nlt_f32_e32 vcc, %[b], %[b0]\n\t"
+        "v_cmpx_ngt_f32_e32 vcc, %[b], %[b1]\n\t"
+        "v_mov_b32_e32 %[cl], %[t]\n\t"
+        "v_or_b32_e32 %[hit], %[sbits], %[base]\n\t"
+        "s_mov_b64 exec, %[all]\n\t"
+        "v_cmp_ne_u32_e32 vcc, %[hit], %[holder]\n\t"
+        "v_mov_b32_e32 %[kd], %[k1]\n\t"
+        "v_mov_b32_e32 %[k1], %[k2]\n\t"
+        "v_cndmask_b32_e32 %[closest], %[closest], %[cl], vcc\n\t"
+        "v_mov_b32_e32 %[k2], %[k3]\n\t"
+        "v_mov_b32_e32 %[k3], %[none]"
+        : [cl] "+v"(closest), [hit] "+v"(hit), [kd] "+v"(pop->kdone), [k1] "+v"(pop->k1), [k2] "+v"(pop->k2), [k3] "+v"(pop->k3),
+          [closest] "+v"(pop->closest)
+        : [t] "v"(t), [a] "v"(a), [b] "v"(b), [a0] "v"(a0), [a1] "v"(a1), [b0] "v"(b0), [b1] "v"(b1), [tmin] "s"(PT_TMIN),
+          [sbits] "n"(S << PT_HIT_SIDE_SHIFT), [base] "v"(hit_base), [all] "s"(exec_all), [holder] "v"(pop->holder), [none] "v"(pop->none)
+        : "vcc");
+    return;
+  }
   asm volatile(
       "v_cmpx_le_f32_e32 vcc, %[tmin], %[t]\n\t"   // min <= t  ==  !(t < min): t is never NaN here (a slab pool's rect entry relies on NaN failing)
       "v_cmpx_ngt_f32_e32 vcc, %[t], %[cl]\n\t"    // !(t > max)
@@ -585,8 +636,10 @@ __device__ __forceinline__ void rect_side_cmpx(float a0, float a1, float b0, flo
 }
 
 // box.hpp:29-50 for a regular ray on a fast_ok scene; closest / hit are the traversal's own running state
-__device__ __forceinline__ void box_cmpx(f4 R0, f4 R1, const RayCtx& c, unsigned long long exec_all, int hit_base, float& closest, int& hit) {
-#define PT_BOX_SIDE(S, AX, A0, A1, B0, B1, K) rect_side_cmpx<AX, S>(A0, A1, B0, B1, K, c, exec_all, hit_base, closest, hit);
+template <bool POP = false>
+__device__ __forceinline__ void box_cmpx(f4 R0, f4 R1, const RayCtx& c, unsigned long long exec_all, int hit_base, float& closest, int& hit,
+                                         const TripPop* pop = nullptr) {
+#define PT_BOX_SIDE(S, AX, A0, A1, B0, B1, K) rect_side_cmpx<AX, S, POP && S == 5>(A0, A1, B0, B1, K, c, exec_all, hit_base, closest, hit, pop);
   PT_BOX_SIDES(R0, R1)
 #undef PT_BOX_SIDE
 }
@@ -1193,7 +1246,7 @@ __device__ __forceinline__ void sphere_scan(P recs, cst_f4p cblob, int n, int go
 // Idle lanes and lanes of an irregular wave never get here with a vote (c.live, `fast`); their octant is three sign bits of whatever y holds: an
 // address inside the table whatever the value.
 template <bool FILTER, int FORM, typename P>
-__device__ __forceinline__ unsigned long long slab_chunk_pass(P xrecs, P slrecs, cst_f4p srecs, P otab, int cn, float bmax, const RayCtx& c, V3 om, V3 op, float& kdone,
+__device__ __forceinline__ unsigned long long slab_chunk_pass(P xrecs, P slrecs, cst_f4p srecs, P otab, int cn, V3 sp, const RayCtx& c, V3 om, V3 op, float& kdone,
                                                 HitState& h) {
   constexpr bool OCT = FORM > 0; // 0: the scalar form; 1 / 2: the sign-resolved form, one / two entries per trip
   const float none = as_f(PT_KEY_NONE);
@@ -1303,22 +1356,22 @@ __device__ __forceinline__ unsigned long long slab_chunk_pass(P xrecs, P slrecs,
           S0 = slrecs[offs]; S1 = slrecs[offs + 1];
         }
         const float e = 0x1p-20f, tlo = PT_TMIN * (1.0f - 0x1p-20f);
-        auto ends = [&](float o, float y, float lo, float hi, float& lw, float& us, float& ws) { // returns (1) for this axis
+        auto ends = [&](float o, float y, float lo, float hi, float S, float& lw, float& us, float& ws) { // returns (1) for this axis
           const float a = (lo - o) * y, b = (hi - o) * y;
           lw = OCT ? a : __builtin_fminf(a, b);
           const float up = OCT ? b : __builtin_fmaxf(a, b);
           // slab_pool's shift S = 9u |o| + 7u B as it can come out of RN(o +- S) and of rounding (o +- S) y: up to
-          // ulp(o +- S)/2 <= u (|o| + S) and u |o +- S| more; the fma's own rounding is in the 2^-20 below
-          const float S = __builtin_fmaf(__builtin_fabsf(o), 0x1.7p-21f, 0x1.dp-22f * bmax); // 11.5u |o| + 7.25u B
+          // ulp(o +- S)/2 <= u (|o| + S) and u |o +- S| more; the fma's own rounding is in the 2^-20 below: S = 11.5u |o| + 7.25u B, a
+          // constant of the ray — slab_pool computes it (`sp`) with its other set-up, ahead of the pass
           const float w = __builtin_fmaf(__builtin_fabsf(y), S, up);
           us = __builtin_fmaf(__builtin_fabsf(up), -e, up); // up lowered
           ws = __builtin_fmaf(__builtin_fabsf(w), e, w);    // W raised
           return __builtin_fmaf(__builtin_fabsf(up), e, up) < PT_TMIN;
         };
         float lwx, lwy, lwz, usx, usy, usz, wsx, wsy, wsz;
-        const bool ownx = ends(c.r.o.x, c.yx, S0.x, S1.x, lwx, usx, wsx);
-        const bool owny = ends(c.r.o.y, c.yy, S0.y, S1.y, lwy, usy, wsy);
-        const bool ownz = ends(c.r.o.z, c.yz, S0.z, S1.z, lwz, usz, wsz);
+        const bool ownx = ends(c.r.o.x, c.yx, S0.x, S1.x, sp.x, lwx, usx, wsx);
+        const bool owny = ends(c.r.o.y, c.yy, S0.y, S1.y, sp.y, lwy, usy, wsy);
+        const bool ownz = ends(c.r.o.z, c.yz, S0.z, S1.z, sp.z, lwz, usz, wsz);
         const float lwm = __builtin_fmaxf(__builtin_fmaxf(lwx, lwy), lwz);
         const bool near_behind = __builtin_fmaf(__builtin_fabsf(lwm), e, lwm) < PT_TMIN;
         const bool kx = ownx & (usy > wsx) & (usz > wsx);
@@ -1355,9 +1408,13 @@ __device__ __forceinline__ unsigned long long slab_chunk_pass(P xrecs, P slrecs,
       // the trip writes the hit in place; the holder's id is the copy (the compiler copies the other way round, and back after the trip)
       int holder;
       asm("v_mov_b32_e32 %0, %1" : "=v"(holder) : "v"(h.hit));
+      // closest takes the trip's t where the hit changed hands, and the key is popped inside the block that consumed it — in the last side's own
+      // statement (rect_side_cmpx: POP), each register written in place (EXEC is the block's own throughout)
+#ifndef PT_NO_TRIP_POP
+      const TripPop pop{kdone, k1, k2, k3, h.closest, none, holder};
+      box_cmpx<true>(X0, X1, c, exec_now, hit_base, cl, h.hit, &pop);
+#else /* A/B build: the close as a statement of its own behind the last side's — the same instructions and an s_nop in front of them */
       box_cmpx(X0, X1, c, exec_now, hit_base, cl, h.hit);
-      // closest takes the trip's t where the hit changed hands, and the key is popped inside the block that consumed it: one statement, each
-      // register written in place, the pops between the comparison and the select that waits for its VCC (EXEC is the block's own throughout)
       asm("v_cmp_ne_u32_e32 vcc, %[hit], %[holder]\n\t"
           "v_mov_b32_e32 %[kd], %[k1]\n\t"
           "v_mov_b32_e32 %[k1], %[k2]\n\t"
@@ -1367,6 +1424,7 @@ __device__ __forceinline__ unsigned long long slab_chunk_pass(P xrecs, P slrecs,
           : [kd] "+v"(kdone), [k1] "+v"(k1), [k2] "+v"(k2), [k3] "+v"(k3), [closest] "+v"(h.closest)
           : [hit] "v"(h.hit), [holder] "v"(holder), [cl] "v"(cl), [none] "v"(none)
           : "vcc");
+#endif
     }
   } while (vote != 0);
   return had3 & __builtin_amdgcn_ballot_w64(ku(k1) == PT_KEY_NONE);
@@ -1388,7 +1446,8 @@ __host__ __device__ __forceinline__ void pool_tables(int pool_off, int n, int& x
 // pool's aux record would say, as launch constants (pt_render.hip: KArgs.plan, scene_pool_plan, pass_pool_plan).  `one` = 0: every bounce walks the list.
 struct PoolPlan {
   // the four words the kernel reads, in ONE s_load_dwordx4:
-  int one = 0;       // the first run heads a pool with an octant table that spans every run, and the launch's kernel may use that
+  int one = 0;       // != 0: the first run heads a pool with an octant table that spans every run, and the launch's kernel may use that;
+                     // 2: the pool is ONE chunk (n <= 16) — the only kind the planned path takes (slab_pool: ONE_CHUNK); 1: a larger pool, walked
   int n = 0;         // the pool's entries
   float bmax = 0.0f; // the largest |coordinate| of the pool (aux.x)
   int x_off = 0;     // f4 offset into the blob of the exact entries; the octant table's first record follows them: x_off + 2 n
@@ -1399,7 +1458,7 @@ struct PoolPlan {
 };
 static_assert(offsetof(PoolPlan, x_off) == 12, "the kernel's four words lead");
 
-template <int LDS_FORM, typename P>
+template <int LDS_FORM, bool ONE_CHUNK = false, typename P>
 __device__ __forceinline__ void slab_pool(P blob, cst_f4p cblob, int pool_off, int x_off, int oct_off, int n, float bmax, const RayCtx& c, HitState& h) {
   constexpr int FORM = __is_same(P, lds_f4p) ? LDS_FORM : 0;
   constexpr bool OCT = FORM > 0;
@@ -1408,6 +1467,13 @@ __device__ __forceinline__ void slab_pool(P blob, cst_f4p cblob, int pool_off, i
   const V3 pp = mk(__builtin_fmaf(__builtin_fabsf(c.r.o.x), kP, bP), __builtin_fmaf(__builtin_fabsf(c.r.o.y), kP, bP),
                    __builtin_fmaf(__builtin_fabsf(c.r.o.z), kP, bP));
   const V3 yv = mk(c.yx, c.yy, c.yz);
+  // the shift of the leaving-ray proof (slab_chunk_pass: `ends`), 11.5u |o| + 7.25u B: the ray's constant, computed here with the rest of the set-up
+  float bS = 0x1.dp-22f * bmax;
+#ifdef __HIP_DEVICE_COMPILE__
+  asm volatile("" : "+v"(bS)); // (taken here: left to itself the product's constant is materialised behind the pass's loop, in front of the scan)
+#endif
+  const V3 sp = mk(__builtin_fmaf(__builtin_fabsf(c.r.o.x), 0x1.7p-21f, bS), __builtin_fmaf(__builtin_fabsf(c.r.o.y), 0x1.7p-21f, bS),
+                   __builtin_fmaf(__builtin_fabsf(c.r.o.z), 0x1.7p-21f, bS));
   V3 om, op; // the fma addends of the slab test
   P otab = blob;
   if constexpr (OCT) {
@@ -1426,17 +1492,21 @@ __device__ __forceinline__ void slab_pool(P blob, cst_f4p cblob, int pool_off, i
 #ifdef PT_STAMPS_POOL
   if ((threadIdx.x & 63) == 0) atomicAdd(&g_stamps[4], 1ull);
 #endif
-  for (int base = 0; base < n; base += 16) {
-    const int cn = n - base < 16 ? n - base : 16;
+  // ONE_CHUNK (the planned path of hit_world_range: the plan claims a pool for it only when n <= 16): the loop below runs once, with base = 0 and
+  // cn = n — the chunk's count, its table addresses and the loop's control are launch constants, not work of every bounce
+  // (the plan claims no empty pool: said here, the slab pass keeps the form the chunk loop's own test gave it — no guard for a pass of no entries)
+  if constexpr (ONE_CHUNK) __builtin_assume(n > 0);
+  for (int base = 0; base < (ONE_CHUNK ? 1 : n); base += 16) {
+    const int cn = ONE_CHUNK ? n : (n - base < 16 ? n - base : 16);
     const P xrecs = blob + x_off + 2 * base;
     const cst_f4p srecs = cblob + pool_off + 2 * base; // the slab entries through the scalar cache (wave-uniform reads) ...
     const P slrecs = blob + pool_off + 2 * base;       // ... and where the lanes read them individually
     const P ochunk = otab + 16 * base;                 // sign-resolved form: the lane's octant record of the chunk's first entry
     float kdone = 0.0f;
-    unsigned long long more = slab_chunk_pass<false, FORM>(xrecs, slrecs, srecs, ochunk, cn, bmax, c, om, op, kdone, h);
+    unsigned long long more = slab_chunk_pass<false, FORM>(xrecs, slrecs, srecs, ochunk, cn, sp, c, om, op, kdone, h);
     while (more) {
       if (!__builtin_amdgcn_inverse_ballot_w64(more)) kdone = as_f(PT_KEY_NONE); // lanes that are done: no key passes the filter
-      more = slab_chunk_pass<true, FORM>(xrecs, slrecs, srecs, ochunk, cn, bmax, c, om, op, kdone, h);
+      more = slab_chunk_pass<true, FORM>(xrecs, slrecs, srecs, ochunk, cn, sp, c, om, op, kdone, h);
     }
   }
 }
@@ -2356,8 +2426,9 @@ __device__ __forceinline__ void hit_world_range(P blob, cst_f4p cblob, int ri0, 
     // path behind the branch, the pool's two early exits included)
     asm volatile("" : "+v"(h.closest), "+v"(h.hit));
 #endif
-    ri1 = planned != 0 ? ri0 : ri1; // the pool covers every run: the walk below has none left (decided ahead of the pool, not behind it)
-    if (planned != 0) slab_pool<2>(blob, cblob, 0 /* the slab entries: the sign-resolved form reads the octant table instead */, x_off, x_off + 2 * n, n, bmax, c, h);
+    // (`one` is 2 for a pool of ONE chunk, <= 16 entries, and 1 for a larger one, which these kernels leave to the walk: PoolPlan)
+    ri1 = planned == 2 ? ri0 : ri1; // the pool covers every run: the walk below has none left (decided ahead of the pool, not behind it)
+    if (planned == 2) slab_pool<2, true>(blob, cblob, 0 /* the slab entries: the sign-resolved form reads the octant table instead */, x_off, x_off + 2 * n, n, bmax, c, h);
   }
   for (int ri = ri0; ri < ri1; ++ri) {
 #ifdef PT_STAMPS_RUNS /* diagnostic build: cycles per run of the list (wave leader's clock), g_runs[min(ri, 15)] */

@@ -99,7 +99,7 @@ constexpr unsigned kQueueRing = 256;        // launches in flight on one scene m
 struct KArgs {
   Cam cam = {};
   // Behind the camera, and read like it — from the kernarg segment, once per bounce, where the bounce has latency to hide (render_kernel):
-  // the one slab pool of a rect / box-only scene as launch constants (pt_device.hpp: PoolPlan; scene_pool_plan, pass_pool_plan).  one = 0: no such scene.
+  // the one slab pool of a rect / box-only scene as launch constants (pt_device.hpp: PoolPlan; scene_pool_plan, pass_pool_plan).  one = 0: no such scene; 2: a pool of one chunk.
   PoolPlan plan = {};
   const f4* blob = nullptr;
   const f4* mats = nullptr;
@@ -152,6 +152,7 @@ struct KArgs {
   // the camera rays' candidate cache of the triangle-pool kernels (pt_device.hpp: TriPrimCtx): one line per resident lane; NULL: none
   unsigned int* tri_cache = nullptr;
   float foot[11] = {};      // (llc - origin) xyz, hor / W xyz, ver / H xyz, the bound dd on |d - d_centre| over a pixel's camera rays, dd's rounding term
+  float width_f = 0.0f, height_f = 0.0f; // (float)width, (float)height: the divisors of render.hpp:96-97, converted once (lane_regenerate)
 };
 static_assert(std::is_trivially_copyable<KArgs>::value, "KArgs is copied into the kernarg segment as it is");
 
@@ -448,7 +449,9 @@ __device__ __forceinline__ void lane_regenerate(Lane& L, const KArgs& a) {
     const Cam cam = a.cam; // (host pass of the single-source compile: never run)
     const KArgs& k = a;
 #endif
-    L.ray = camera_ray(cam, L.cold.get_x(), L.cold.get_y(), k.width, k.height, k.inv_w, k.inv_h, L.rng, k.pinhole != 0);
+    // (the frame's size as floats, converted once on the host: set_frame.  The pixel's x and y stay integers in the cold state: its eight
+    // slots are taken, and lane_store needs the integers for frames wider than 2^24, where the float does not give them back)
+    L.ray = camera_ray(cam, (float)L.cold.get_x(), (float)L.cold.get_y(), k.width_f, k.height_f, k.inv_w, k.inv_h, L.rng, k.pinhole != 0);
     L.att = mk(1.0f, 1.0f, 1.0f);
     L.b = 0;
     L.need_new = false;
@@ -663,9 +666,12 @@ void render_kernel(KArgs a) {
           plan = a.plan;
 #endif
         }
-        RayCtx c = make_ctx(L.ray, a.fast_ok != 0);
+        // (the headline family votes on masks: the irregular lanes' from the context's own comparisons, the live lanes' the one the pull loop
+        // above has just tested — two scalar instructions where the vote on the per-lane flags materialised them first)
+        unsigned long long irregular = 0;
+        RayCtx c = kSkyFirst ? make_ctx<true>(L.ray, a.fast_ok != 0, &irregular) : make_ctx(L.ray, a.fast_ok != 0);
         c.live = L.live;
-        const bool fast = wave_all_regular(c, L.live);
+        const bool fast = kSkyFirst ? (irregular & __builtin_amdgcn_ballot_w64(L.live)) == 0 : wave_all_regular(c, L.live);
         regular = fast;
         hit_world<IMG, BADOUEL, GRID, false, (MATS & MATS_RECTBOX_ONLY) != 0>((lds_f4p)smem, (cst_f4p)a.blob, a.n_runs, c, fast, L.rng, h, nullptr, nullptr, &plan);
       }
@@ -2433,6 +2439,8 @@ Variant choose_variant(const PtScene* s, const PtRenderParams* p, int local_tile
 // first record, and from (pool offset, n) the tables' places as slab_pool's callers compute them.  `one` is set where run 0 heads a pool
 // that spans EVERY run of the list and carries an octant table; a list with a run outside the pool, with more than one pool, or whose
 // pools have no tables (the blob beyond the LDS image) leaves it clear.  Which kernel runs, and under which flags, is pass_pool_plan's.
+// The kernel's word says one thing more: whether the pool is ONE chunk of the slab pass (<= 16 entries: `one` = 2), which is the only pool its
+// planned path holds code for; a larger one (`one` = 1) is claimed here, reported by the read-backs like any claimed pool, and walked.
 PoolPlan scene_pool_plan(const ptf::Flat& flat) {
   PoolPlan pl;
   if (flat.n_runs < 1 || flat.blob.size() <= (size_t)flat.n_runs) return pl;
@@ -2444,7 +2452,8 @@ PoolPlan scene_pool_plan(const ptf::Flat& flat) {
   const int span = word(aux.y);
   pl.bmax = aux.x; pl.pool_off = word(aux.z); pl.n = word(aux.w);
   pool_tables(pl.pool_off, pl.n, pl.x_off, pl.oct_off);
-  pl.one = (span == flat.n_runs && pl.n > 0 && flat.pool_octants && flat.fast_ok) ? 1 : 0;
+  // (2: the pool is one chunk of the slab pass, which is all the planned path of the kernels holds — a larger pool is claimed, reported, and walked)
+  pl.one = (span == flat.n_runs && pl.n > 0 && flat.pool_octants && flat.fast_ok) ? (pl.n <= 16 ? 2 : 1) : 0;
   return pl;
 }
 
@@ -3068,6 +3077,7 @@ void set_frame(Args& a, const PtScene* s, const PtCamera* cam, const PtRenderPar
   a.n_runs = s->n_runs;
   a.width = p->width; a.height = p->height; a.samples = p->samples;
   a.inv_w = 1.0f / (float)p->width; a.inv_h = 1.0f / (float)p->height; // host IEEE division: correctly rounded
+  if constexpr (requires { a.width_f; }) { a.width_f = (float)p->width; a.height_f = (float)p->height; } // (KArgs: what v_cvt_f32_i32 gives, RNE)
   a.pinhole = cam_is_pinhole(a.cam) ? 1 : 0;
   a.shard_index = p->shard_index; a.shard_count = p->shard_count;
   a.n_tiles = n_tiles_of(p, &a.tiles_x);
@@ -4699,12 +4709,19 @@ int pt_debug_last_kernels(const PtScene* scene, int32_t out[24]) {
   return PT_OK;
 }
 
-static void pool_plan_words(const PoolPlan& pl, int32_t out[4]) { out[0] = pl.one; out[1] = pl.n; out[2] = pl.x_off; out[3] = pl.oct_off; }
+static void pool_plan_words(const PoolPlan& pl, int32_t out[4]) { out[0] = pl.one != 0; out[1] = pl.n; out[2] = pl.x_off; out[3] = pl.oct_off; }
 
 int pt_debug_last_pool_plan(const PtScene* scene, int32_t out[4]) {
   if (!scene || !out) return fail(PT_ERR_INVALID_ARG, "pt_debug_last_pool_plan: NULL argument");
   std::lock_guard<std::mutex> lock(scene->sched);
   pool_plan_words(scene->last_pool_plan, out);
+  return PT_OK;
+}
+
+int pt_debug_last_pool_word(const PtScene* scene, int32_t* out) {
+  if (!scene || !out) return fail(PT_ERR_INVALID_ARG, "pt_debug_last_pool_word: NULL argument");
+  std::lock_guard<std::mutex> lock(scene->sched);
+  *out = scene->last_pool_plan.one;
   return PT_OK;
 }
 
@@ -4733,7 +4750,7 @@ int pt_debug_pool_plan(const PtSceneDesc* desc, const PtTuning* tuning, const Pt
   pool_plan_words(pl, out);
   out[4] = pl.pool_off; std::memcpy(&out[5], &pl.bmax, 4);
   out[6] = pl.kind; out[7] = pl.off; out[8] = pl.count;
-  out[9] = s.pool_plan.one; out[10] = lds; out[11] = mats;
+  out[9] = s.pool_plan.one != 0; out[10] = lds; out[11] = mats;
   return PT_OK;
 }
 
