@@ -44,6 +44,11 @@ With --spatial-variance [RADIUS] the spatial variance estimate (render.spatial_v
 estimated from the plain frame —, with --noise-threshold the stage fills the pixels the half buffers give no estimate for, and with
 --temporal those of a young history.  The numbers of estimated pixels and of holes (no estimate either) are printed.  out.png is
 byte-identical to the one written without the option.
+With --compare REF.npy the image error (render.image_error; include/pt_metrics.h) measures the frame behind out.png — and the filtered
+frame of --denoise-out, if given — against a reference frame, a float32 [height][width][3] array with y = 0 the bottom row as --save-frame
+FILE.npy writes it: MSE, relMSE (eps 1e-4), PSNR against a peak of 1, the pixels that took part and the skipped ones (a NaN or inf on
+either side).  The sums behind them are exact and rounded once on the device, so the printed MSE does not depend on the order in which
+the hardware adds.  out.png is byte-identical to the one written without the options.
 """
 import argparse
 import os
@@ -97,6 +102,12 @@ def print_firefly_counts(a, what, n) -> None:
 def print_variance_counts(a, what, n) -> None:
     estimated, holes = (int(v) for v in n.cpu().numpy())
     print(f"{what}: spatial variance (radius {a.spatial_kw['radius']}): {estimated} pixels estimated, {holes} holes")
+
+
+def print_compare(a, what, fb, ref) -> None:
+    """--compare: one line of figures for the frame `fb` against the reference (all of them from one ImageError)."""
+    e = R.image_error(fb, ref)
+    print(f"{what} vs {a.compare}: MSE {e.mse!r} relMSE {e.rel_mse!r} PSNR {e.psnr(1.0):.4f} dB (peak 1), {e.pixels} pixels, {e.skipped} skipped")
 
 
 def write_frames(a, packed, cam_args, move, denoise_kw) -> None:
@@ -178,7 +189,23 @@ def main() -> None:
     ap.add_argument("--spatial-variance", type=int, nargs="?", const=R.abi.PT_SVAR_DEFAULT_RADIUS, default=None, metavar="RADIUS",
                     help=f"spatial variance estimate: give --denoise-variance a variance where there is none, from a (2 RADIUS + 1)^2 window "
                          f"(1 .. {R.abi.PT_SVAR_MAX_RADIUS}, default {R.abi.PT_SVAR_DEFAULT_RADIUS}); --denoise-variance then needs no --noise-threshold")
+    ap.add_argument("--compare", default=None, metavar="REF.npy",
+                    help="image error: print MSE, relMSE, PSNR and the skipped pixels of the frame behind --out (and of --denoise-out) against "
+                         "this float32 [height][width][3] frame")
+    ap.add_argument("--save-frame", default=None, metavar="FILE.npy", help="write the frame behind --out as float32 [height][width][3] (a reference for --compare)")
     a = ap.parse_args()
+    if a.save_frame is not None and not a.save_frame.endswith(".npy"):
+        ap.error("--save-frame needs a file name that ends in .npy")
+    if a.compare is not None:
+        if a.save_frame is not None and os.path.abspath(a.compare) == os.path.abspath(a.save_frame):
+            ap.error("--compare and --save-frame name the same file")
+        import numpy as np
+        try:
+            ref_frame = np.load(a.compare, mmap_mode="r", allow_pickle=False)
+        except (OSError, ValueError) as e:
+            ap.error(f"--compare: cannot read {a.compare}: {e}")
+        if ref_frame.dtype != np.float32 or ref_frame.shape != (a.height, a.width, 3):
+            ap.error(f"--compare: {a.compare} holds {ref_frame.dtype} {list(ref_frame.shape)}, not float32 [{a.height}, {a.width}, 3] (--height, --width)")
     if a.spatial_variance is not None and not a.denoise_variance:
         ap.error("--spatial-variance needs --denoise-variance (the filter that takes the variance)")
     if a.spatial_variance is not None and not 1 <= a.spatial_variance <= R.abi.PT_SVAR_MAX_RADIUS:
@@ -301,13 +328,18 @@ def main() -> None:
             torch.cuda.synchronize()
             ms += e0.elapsed_time(e1)
             write_png(os.path.join(a.preview_dir, f"preview_{acc.samples}.png"), rgb8.cpu().numpy())
-        fb = acc.resolve() if a.denoise_out or a.display_out else None
+        fb = acc.resolve() if a.denoise_out or a.display_out or a.compare or a.save_frame else None
         acc.close()
     else:
         fb, ms = R.render(a.width, a.height, a.spp, packed, cam, a.depth, timed=True)
         rgb8 = R.tonemap_rgb8(fb)
     torch.cuda.synchronize()
     write_png(a.out, rgb8.cpu().numpy())
+    if a.save_frame:
+        np.save(a.save_frame, fb.cpu().numpy())
+    ref = torch.from_numpy(np.ascontiguousarray(ref_frame)).cuda() if a.compare else None
+    if a.compare:
+        print_compare(a, a.out, fb, ref)
     planes = R.render_aov(a.width, a.height, a.aov_spp, packed, cam) if a.aov_dir or a.denoise_out else None
     if a.aov_dir:
         write_aovs(a.aov_dir, planes)
@@ -322,6 +354,8 @@ def main() -> None:
     if a.denoise_out:
         filtered = R.denoise_variance(fb, variance[0], **planes, **denoise_kw) if a.denoise_variance else R.denoise(fb, **planes, **denoise_kw)
         write_png(a.denoise_out, R.tonemap_rgb8(filtered).cpu().numpy())
+        if a.compare:
+            print_compare(a, a.denoise_out, filtered, ref)
     if a.display_out:
         write_png(a.display_out, make_shower(a)(fb).cpu().numpy())
     if a.frames is not None:

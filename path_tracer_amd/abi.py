@@ -1,5 +1,5 @@
 """ctypes mirror of include/pt_render.h — the C-ABI drop-in boundary of render() — and of include/pt_post.h (POST_SIGNATURES) and
-include/pt_spatial_variance.h (SPATIAL_VARIANCE_SIGNATURES).
+include/pt_spatial_variance.h (SPATIAL_VARIANCE_SIGNATURES) and include/pt_metrics.h (METRICS_SIGNATURES).
 
 The structs are declared field-for-field as in the header; `load_library()` opens the
 in-tree `libpt_render.so` built by `__graft_entry__.build()` (hipcc, gfx950) and fails
@@ -171,6 +171,19 @@ class PtSpatialVarianceParams(C.Structure):
                 ("tol_depth", C.c_float), ("tol_normal", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_int32 * 2)]
 
 
+class PtImageErrorParams(C.Structure):
+    """include/pt_metrics.h PtImageErrorParams: the image error's parameters (pt_image_error)."""
+    _fields_ = [("struct_size", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("rect_x0", C.c_int32), ("rect_y0", C.c_int32),
+                ("rect_x1", C.c_int32), ("rect_y1", C.c_int32), ("flags", C.c_uint32), ("eps", C.c_double), ("scratch_bytes", C.c_int64),
+                ("reserved", C.c_int32 * 2)]
+
+
+class PtImageErrorResult(C.Structure):
+    """include/pt_metrics.h PtImageErrorResult: what pt_image_error leaves on the device."""
+    _fields_ = [("sum_sq", C.c_double * 3), ("sum_abs", C.c_double * 3), ("sum_rel", C.c_double * 3), ("pixels", C.c_uint64),
+                ("skipped", C.c_uint64), ("max_abs", C.c_float * 3), ("reserved", C.c_uint32)]
+
+
 assert C.sizeof(PtHittable) == 64 and C.sizeof(PtMaterial) == 32 and C.sizeof(PtTexture) == 48
 assert C.sizeof(PtCamera) == 96 and C.sizeof(PtRenderParams) == 32
 
@@ -313,6 +326,20 @@ PT_SVAR_TILE_W, PT_SVAR_TILE_H = 32, 8
 PT_SVAR_DEFAULT_RADIUS, PT_SVAR_DEFAULT_MIN_PAIRS, PT_SVAR_DEFAULT_TOL_DEPTH, PT_SVAR_DEFAULT_TOL_NORMAL = 2, 4, 0.1, 0.5
 PT_SVAR_DEFAULT_FLAGS = PT_SVAR_DEMODULATE
 
+# name -> (restype, argtypes): every entry point include/pt_metrics.h declares.  A table of its own, like SPATIAL_VARIANCE_SIGNATURES and
+# for its reason.  load_library() applies a row where the library exports the symbol; has_metrics() tells whether the loaded one has the
+# stage.
+METRICS_SIGNATURES = {
+    "pt_image_error_params_init": (None, [C.POINTER(PtImageErrorParams), C.c_int32, C.c_int32]),
+    "pt_image_error_scratch_bytes": (C.c_int64, []),
+    "pt_image_error": (C.c_int, [C.POINTER(PtImageErrorParams)] + [C.c_void_p] * 6),
+    "pt_debug_last_image_error": (C.c_int, [C.POINTER(C.c_int32)]),
+}
+METRICS_SYMBOLS = frozenset(METRICS_SIGNATURES)
+PT_IMAGE_ERROR_NO_LDS = 1  # A/B switch, same bits: global atomics only
+PT_IMAGE_ERROR_WORDS, PT_IMAGE_ERROR_SUMS = 68, 9
+PT_IMAGE_ERROR_DEFAULT_EPS = 1e-4  # the header's (pt_image_error_params_init)
+
 # Entry points a library may lack and still load for everything else (include/pt_render.h: the feature is detected by their presence);
 # has_accumulator() tells whether the loaded one has them.
 ACCUM_SYMBOLS = frozenset(n for n in SIGNATURES if n.startswith("pt_accum_") or n == "pt_render_accumulate")
@@ -422,7 +449,7 @@ def load_library() -> C.CDLL:
         fn = getattr(lib, name)  # AttributeError if the library does not export what the header declares
         fn.restype = res
         fn.argtypes = args
-    for name, (res, args) in list(POST_SIGNATURES.items()) + list(SPATIAL_VARIANCE_SIGNATURES.items()):  # include/pt_post.h, pt_spatial_variance.h: applied where the library has the symbol
+    for name, (res, args) in list(POST_SIGNATURES.items()) + list(SPATIAL_VARIANCE_SIGNATURES.items()) + list(METRICS_SIGNATURES.items()):  # include/pt_post.h, pt_spatial_variance.h, pt_metrics.h: applied where the library has the symbol
         if hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype = res
@@ -486,6 +513,12 @@ def has_spatial_variance(lib=None) -> bool:
     """Does the loaded library offer the spatial variance estimate (include/pt_spatial_variance.h: pt_spatial_variance)?"""
     lib = lib or load_library()
     return all(hasattr(lib, n) for n in SPATIAL_VARIANCE_SYMBOLS)
+
+
+def has_metrics(lib=None) -> bool:
+    """Does the loaded library offer the image error (include/pt_metrics.h: pt_image_error)?"""
+    lib = lib or load_library()
+    return all(hasattr(lib, n) for n in METRICS_SYMBOLS)
 
 
 def check(code: int, where: str) -> None:

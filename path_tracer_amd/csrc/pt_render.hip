@@ -29,6 +29,7 @@
 #include "../../include/pt_render.h"
 #include "../../include/pt_post.h"
 #include "../../include/pt_spatial_variance.h"
+#include "../../include/pt_metrics.h"
 #include "pt_device.hpp"
 #include "pt_flatten.hpp"
 
@@ -2016,6 +2017,7 @@ __global__ __launch_bounds__(256) void display_apply_kernel(const float* color, 
 
 #include "pt_firefly.hpp"
 #include "pt_spatial_variance.hpp"
+#include "pt_metrics.hpp"
 
 thread_local std::string g_last_error;
 
@@ -4115,6 +4117,77 @@ int pt_debug_last_spatial_variance(int32_t out[4]) {
   if (!out) return fail(PT_ERR_INVALID_ARG, "pt_debug_last_spatial_variance: NULL argument");
   std::lock_guard<std::mutex> lock(g_svar_mutex);
   std::memcpy(out, g_last_svar, sizeof g_last_svar);
+  return PT_OK;
+}
+
+// ---- image error (include/pt_metrics.h): pt_image_error (imgerr_accumulate_kernel, imgerr_finish_kernel) ---------------------------------
+static std::mutex g_imgerr_mutex;
+static int32_t g_last_imgerr[4] = {0, 0, 0, 0}; // pt_debug_last_image_error
+
+void pt_image_error_params_init(PtImageErrorParams* params, int32_t width, int32_t height) {
+  if (!params) return;
+  std::memset(params, 0, sizeof *params);
+  params->struct_size = (int32_t)sizeof(PtImageErrorParams);
+  params->width = width; params->height = height;
+  params->eps = PT_IMAGE_ERROR_DEFAULT_EPS;
+}
+
+int64_t pt_image_error_scratch_bytes(void) { return (int64_t)IMGERR_SCRATCH_WORDS * 8; }
+
+int pt_image_error(const PtImageErrorParams* params, const float* a, const float* ref, PtImageErrorResult* result, float* error_plane,
+                   void* scratch, void* stream) {
+  auto bad = [&](const char* what) { return fail(PT_ERR_INVALID_ARG, std::string("pt_image_error: ") + what); };
+  if (!params || !a || !ref || !result || !scratch) return bad("NULL params, a, ref, result or scratch");
+  if (params->struct_size != (int32_t)sizeof(PtImageErrorParams)) return bad("PtImageErrorParams.struct_size is not this library's");
+  const int width = params->width, height = params->height;
+  if (width <= 0 || height <= 0) return bad("width and height must be > 0");
+  int x0 = params->rect_x0, y0 = params->rect_y0, x1 = params->rect_x1, y1 = params->rect_y1;
+  if (!(x0 || y0 || x1 || y1)) { x1 = width; y1 = height; } // four zeros: the whole frame
+  if (x0 < 0 || y0 < 0 || x1 > width || y1 > height || x0 > x1 || y0 > y1) return bad("the rectangle leaves the frame");
+  if (!(std::isfinite(params->eps) && params->eps >= 0x1p-126)) return bad("eps must be finite and >= 2^-126");
+  if (params->flags & ~PT_IMAGE_ERROR_NO_LDS) return bad("unknown flags");
+  const int64_t pixels = (int64_t)width * height;
+  if (pixels > ((int64_t)1 << 30)) return fail(PT_ERR_TOO_LARGE, "pt_image_error: more than 2^30 pixels");
+  if ((uintptr_t)result % 8 || (uintptr_t)scratch % 8) return bad("result and scratch must be 8-byte aligned");
+  const uintptr_t scratch_bytes = (uintptr_t)IMGERR_SCRATCH_WORDS * 8;
+  if (params->scratch_bytes < (int64_t)scratch_bytes) return bad("scratch_bytes is less than pt_image_error_scratch_bytes()");
+  const uintptr_t frame = (uintptr_t)pixels * 12, plane = (uintptr_t)pixels * 4;
+  for (const float* in : {a, ref})
+    if (overlaps(error_plane, plane, in, frame) || overlaps(result, sizeof(PtImageErrorResult), in, frame) || overlaps(scratch, scratch_bytes, in, frame))
+      return bad("error_plane, result and scratch must not overlap an input");
+  if (overlaps(error_plane, plane, result, sizeof(PtImageErrorResult)) || overlaps(error_plane, plane, scratch, scratch_bytes) ||
+      overlaps(result, sizeof(PtImageErrorResult), scratch, scratch_bytes))
+    return bad("error_plane, result and scratch must not overlap one another");
+
+  hipStream_t st = (hipStream_t)stream;
+  const bool lds = !(params->flags & PT_IMAGE_ERROR_NO_LDS);
+  ImgErrArgs k;
+  k.a = a; k.ref = ref; k.plane = error_plane; k.scratch = static_cast<unsigned long long*>(scratch);
+  k.width = width;
+  k.x0 = x0; k.y0 = y0; k.x1 = x1; k.y1 = y1;
+  const bool whole = error_plane != nullptr; // the plane has a value for every pixel of the frame
+  k.wx0 = whole ? 0 : x0; k.wy0 = whole ? 0 : y0; k.ww = whole ? width : x1 - x0;
+  k.n = (unsigned)(whole ? pixels : (int64_t)(x1 - x0) * (y1 - y0));
+  k.eps = params->eps;
+  const unsigned blocks = (unsigned)std::min<int64_t>(((int64_t)k.n + 255) / 256, PT_IMGERR_MAX_BLOCKS);
+  std::lock_guard<std::mutex> lock(g_imgerr_mutex);
+  std::memset(g_last_imgerr, 0, sizeof g_last_imgerr);
+  PT_HIP(hipMemsetAsync(scratch, 0, scratch_bytes, st));
+  if (blocks) { // (an empty rectangle without a plane: nothing to walk)
+    if (lds) hipLaunchKernelGGL(imgerr_accumulate_kernel<true>, dim3(blocks), dim3(256), 0, st, k);
+    else hipLaunchKernelGGL(imgerr_accumulate_kernel<false>, dim3(blocks), dim3(256), 0, st, k);
+    PT_HIP(hipGetLastError());
+  }
+  hipLaunchKernelGGL(imgerr_finish_kernel, dim3(1), dim3(64), 0, st, k.scratch, result);
+  PT_HIP(hipGetLastError());
+  g_last_imgerr[0] = lds ? 2 : 1; g_last_imgerr[1] = (int32_t)blocks; g_last_imgerr[2] = x1 - x0; g_last_imgerr[3] = y1 - y0;
+  return PT_OK;
+}
+
+int pt_debug_last_image_error(int32_t out[4]) {
+  if (!out) return fail(PT_ERR_INVALID_ARG, "pt_debug_last_image_error: NULL argument");
+  std::lock_guard<std::mutex> lock(g_imgerr_mutex);
+  std::memcpy(out, g_last_imgerr, sizeof g_last_imgerr);
   return PT_OK;
 }
 

@@ -22,6 +22,7 @@
 #pragma once
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -36,6 +37,7 @@
 #include "../../../include/pt_render.h"
 #include "../../../include/pt_post.h"
 #include "../../../include/pt_spatial_variance.h"
+#include "../../../include/pt_metrics.h"
 #include "image_io.hpp"
 
 namespace pt {
@@ -565,6 +567,39 @@ inline void spatial_variance(int width, int height, const float* color, const sp
   const PtSpatialVarianceParams p{(int32_t)sizeof(PtSpatialVarianceParams), width, height, sp.radius, sp.min_pairs, sp.tol_depth, sp.tol_normal,
                                   demodulate ? PT_SVAR_DEMODULATE : 0u, {0, 0}};
   check(pt_spatial_variance(&p, color, g.albedo, g.normal, g.depth, g.id, variance_in, variance_out, counts, stream), "pt_spatial_variance");
+}
+
+// The image error (include/pt_metrics.h: pt_image_error): frame `a` against frame `ref` inside `rect`; each sum is the exact sum of its
+// terms rounded once to binary64, whatever the order in which the device adds.  a, ref ([height][width][3]), the optional error_plane
+// ([height][width]), `result` (a DEVICE PtImageErrorResult, 8-byte aligned) and `scratch` (image_error_scratch_bytes() bytes, 8-byte
+// aligned) are DEVICE buffers the caller owns.  Nothing is read back: copy `result` into an image_error_result when the numbers are wanted.
+struct image_error_params {
+  int rect[4] = {0, 0, 0, 0}; // x0, y0, x1, y1; four zeros: the whole frame
+  double eps = PT_IMAGE_ERROR_DEFAULT_EPS;
+  bool no_lds = false;        // the A/B switch PT_IMAGE_ERROR_NO_LDS (the same bits)
+};
+// The result on the host, with the derived figures: ordinary binary64 host arithmetic on the sums, in the order the header writes.
+struct image_error_result : PtImageErrorResult {
+  static double mean(const double v[3], uint64_t n) { return n ? ((v[0] + v[1]) + v[2]) / (3.0 * (double)n) : std::nan(""); }
+  double mse() const { return mean(sum_sq, pixels); }
+  double mae() const { return mean(sum_abs, pixels); }
+  double rel_mse() const { return mean(sum_rel, pixels); }
+  double psnr(double peak = 1.0) const {
+    const double m = mse();
+    return m != m ? m : m == 0.0 ? HUGE_VAL : 10.0 * std::log10(peak * peak / m);
+  }
+};
+inline size_t image_error_scratch_bytes() { return (size_t)pt_image_error_scratch_bytes(); }
+// asynchronous on `stream`
+inline void image_error(int width, int height, const float* a, const float* ref, PtImageErrorResult* result, void* scratch,
+                        float* error_plane = nullptr, const image_error_params& ip = {}, void* stream = nullptr) {
+  PtImageErrorParams p;
+  pt_image_error_params_init(&p, width, height);
+  p.rect_x0 = ip.rect[0]; p.rect_y0 = ip.rect[1]; p.rect_x1 = ip.rect[2]; p.rect_y1 = ip.rect[3];
+  p.eps = ip.eps;
+  p.flags = ip.no_lds ? PT_IMAGE_ERROR_NO_LDS : 0u;
+  p.scratch_bytes = pt_image_error_scratch_bytes();
+  check(pt_image_error(&p, a, ref, result, error_plane, scratch, stream), "pt_image_error");
 }
 
 // Progressive rendering: one frame in sample windows; RAII over pt_accum_create / pt_accum_destroy (include/pt_render.h, PtAccum).

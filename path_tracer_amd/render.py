@@ -10,6 +10,7 @@ the RCCL process group.  All arithmetic happens in the hand-written gfx950 kerne
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Optional
 
 import numpy as np
@@ -365,6 +366,117 @@ def _spatial_kw(arg, who, name="spatial"):
     raise TypeError(f"{who}: {name} must be True or a dict of radius, min_pairs, tol_depth, tol_normal, demodulate, no_lds")
 
 
+class ImageError:
+    """What image_error() returns: the DEVICE result of one pt_image_error call (include/pt_metrics.h: PtImageErrorResult), read back on
+    demand — the first property that wants a number copies the 104 bytes once (synchronising on them), and every figure comes from that
+    copy.  The sums are the stage's exact sums rounded once; the derived figures are ORDINARY binary64 host arithmetic on them, in the
+    order the header writes: mse = ((sum_sq.r + sum_sq.g) + sum_sq.b) / (3.0 * pixels), mae and rel_mse likewise from sum_abs and sum_rel,
+    psnr(peak) = 10 log10(peak^2 / mse).  pixels = 0 gives NaN.  `plane` is the per-pixel error plane ([H][W] float32 on the device) where
+    one was asked for, else None; `result` the device tensor itself (13 int64 words)."""
+
+    def __init__(self, result, plane, scratch):
+        self.result, self.plane, self._scratch, self._host = result, plane, scratch, None
+
+    def read(self) -> "abi.PtImageErrorResult":
+        """The result struct on the host (copied once)."""
+        if self._host is None:
+            raw = self.result.cpu().numpy().tobytes()
+            self._host = abi.PtImageErrorResult.from_buffer_copy(raw)
+        return self._host
+
+    def sums(self) -> dict:
+        """The raw doubles: {"sq": (r, g, b), "abs": (r, g, b), "rel": (r, g, b)}."""
+        r = self.read()
+        return {"sq": tuple(r.sum_sq), "abs": tuple(r.sum_abs), "rel": tuple(r.sum_rel)}
+
+    @staticmethod
+    def _mean(v, pixels):
+        return ((v[0] + v[1]) + v[2]) / (3.0 * pixels) if pixels else math.nan
+
+    @property
+    def pixels(self) -> int:
+        return int(self.read().pixels)
+
+    @property
+    def skipped(self) -> int:
+        return int(self.read().skipped)
+
+    @property
+    def max_abs(self) -> tuple:
+        return tuple(float(v) for v in self.read().max_abs)
+
+    @property
+    def mse(self) -> float:
+        return self._mean(self.read().sum_sq, self.pixels)
+
+    @property
+    def mae(self) -> float:
+        return self._mean(self.read().sum_abs, self.pixels)
+
+    @property
+    def rel_mse(self) -> float:
+        return self._mean(self.read().sum_rel, self.pixels)
+
+    def psnr(self, peak: float = 1.0) -> float:
+        """10 log10(peak^2 / mse); +inf for identical frames, NaN where no pixel took part."""
+        m = self.mse
+        if math.isnan(m):
+            return math.nan
+        return math.inf if m == 0.0 else 10.0 * math.log10(float(peak) * float(peak) / m)
+
+
+def image_error(a, ref, *, rect=None, eps: float = abi.PT_IMAGE_ERROR_DEFAULT_EPS, error_plane=False, no_lds: bool = False) -> ImageError:
+    """The image error (include/pt_metrics.h: pt_image_error): frame `a` against frame `ref`, both [H][W][3] float32 on the GPU, whole
+    frames; `a` may be `ref`.  `rect` = (x0, y0, x1, y1), None for the whole frame.  A pixel takes part iff its six values and three
+    differences are finite; the others are counted in `.skipped`.  Each sum — of d^2, |d| and d^2 / (ref^2 + eps) per channel — is the
+    EXACT sum of its terms rounded once to binary64: it does not depend on the order in which the device adds.  `error_plane`: True
+    allocates, a [H][W] float32 device tensor is written — the per-pixel mean squared difference, +inf where a pixel is skipped or outside
+    `rect`.  `no_lds`: the A/B switch PT_IMAGE_ERROR_NO_LDS (the same bits).  Asynchronous on torch's current stream; nothing is read back
+    until a property of the returned ImageError asks for a number."""
+    import torch
+
+    if not torch.cuda.is_available():
+        raise RuntimeError("path_tracer_amd.image_error needs a HIP device: there is no CPU path in the product")
+    lib = abi.load_library()
+    if not abi.has_metrics(lib):
+        raise ImportError(f"{abi.library_path()} predates the image error (no pt_image_error entry point)")
+    _frame_ptr(a, "a")
+    _frame_ptr(ref, "ref")
+    if a.shape != ref.shape:
+        raise ValueError("a and ref must have the same shape")
+    h, w, _ = (int(n) for n in a.shape)
+    plane = None
+    if error_plane is True:
+        plane = torch.empty((h, w), dtype=torch.float32, device=a.device)
+    elif error_plane is not None and error_plane is not False:
+        plane = error_plane
+        if tuple(plane.shape) != (h, w) or plane.dtype != torch.float32 or not plane.is_cuda or not plane.is_contiguous():
+            raise ValueError("error_plane must be a contiguous float32 CUDA tensor of shape [H][W]")
+    p = abi.PtImageErrorParams()
+    lib.pt_image_error_params_init(C.byref(p), w, h)
+    if rect is not None:
+        x0, y0, x1, y1 = (int(v) for v in rect)
+        if (x0, y0, x1, y1) == (0, 0, 0, 0):
+            raise ValueError("rect (0, 0, 0, 0) means the whole frame at the C boundary: pass None for that, or another empty rectangle")
+        p.rect_x0, p.rect_y0, p.rect_x1, p.rect_y1 = x0, y0, x1, y1
+    p.eps = float(eps)
+    p.flags = abi.PT_IMAGE_ERROR_NO_LDS if no_lds else 0
+    p.scratch_bytes = int(lib.pt_image_error_scratch_bytes())
+    scratch = torch.empty((p.scratch_bytes + 7) // 8, dtype=torch.int64, device=a.device)
+    result = torch.empty(C.sizeof(abi.PtImageErrorResult) // 8, dtype=torch.int64, device=a.device)
+    abi.check(lib.pt_image_error(C.byref(p), C.c_void_p(a.data_ptr()), C.c_void_p(ref.data_ptr()), C.c_void_p(result.data_ptr()),
+                                 C.c_void_p(plane.data_ptr()) if plane is not None else None, C.c_void_p(scratch.data_ptr()),
+                                 _stream_ptr(torch)), "pt_image_error")
+    return ImageError(result, plane, scratch)
+
+
+def mse_ratio(filtered, noisy, ref) -> float:
+    """MSE(filtered, ref) / MSE(noisy, ref): the figure every quality record of DESIGN.md quotes (below 1: the filter helped).  Two
+    image_error() calls; the division is the host's."""
+    f, n = image_error(filtered, ref), image_error(noisy, ref)
+    return f.mse / n.mse
+
+
 def render_host(width: int, height: int, samples: int, scene, cam: camera, depth: int = 50, *, flags: int = 0,
                 shard_index: int = 0, shard_count: int = 1) -> np.ndarray:
     """Torch-free path: pt_render_host renders into a numpy array (allocates, copies back, syncs)."""
@@ -648,10 +760,16 @@ class Accumulator:
         abi.check(self.lib.pt_adaptive_counts(self.handle, C.c_void_p(out.data_ptr()), _stream_ptr(torch)), "pt_adaptive_counts")
         return out
 
-    def error(self):
-        """Each pixel's two-half-buffer error estimate (adaptive; include/pt_render.h): float32, shaped like counts()."""
+    def error(self, ref=None, **kw):
+        """Without `ref`: each pixel's two-half-buffer error estimate (adaptive; include/pt_render.h): float32, shaped like counts().
+        With `ref` (a [H][W][3] float32 device frame): image_error(resolve(), ref, **kw) — the accumulated frame's error against a
+        reference (whole frames only), an ImageError."""
         import torch
 
+        if ref is not None:
+            if self.shard_count != 1:
+                raise ValueError("Accumulator.error(ref): whole frames only (gather and unshard first)")
+            return image_error(self.resolve(), ref, **kw)
         out = torch.empty(self._pixel_shape(), dtype=torch.float32, device="cuda")
         abi.check(self.lib.pt_adaptive_error(self.handle, C.c_void_p(out.data_ptr()), _stream_ptr(torch)), "pt_adaptive_error")
         return out
