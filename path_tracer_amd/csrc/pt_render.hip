@@ -3414,37 +3414,137 @@ int pt_tonemap_rgb8(const float* fb_device, int32_t width, int32_t height, uint8
   return PT_OK;
 }
 
-// ---- the denoisers' host side, once: what pt_denoise and pt_variance_denoise check, decide and launch alike ---------------------------------
+// ---- the image stages' host prelude: what every stage below checks, tables and records alike.  A stage calls these pieces at its OWN
+// positions — the order in which an entry point reports its refusals is its own (tests/test_stage_refusal_order_cpu.py) -------------------
 } // extern "C"
 
 namespace {
-// do the bytes [a, a + a_bytes) and [b, b + b_bytes) meet?  A NULL plane meets nothing.
-bool overlaps(const void* a, uintptr_t a_bytes, const void* b, uintptr_t b_bytes) {
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a && b && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+// an entry point's refusals, in its name
+struct Refuse {
+  const char* who;
+  int operator()(const std::string& what) const { return fail(PT_ERR_INVALID_ARG, std::string(who) + ": " + what); }
+  int too_large() const { return fail(PT_ERR_TOO_LARGE, std::string(who) + ": more than 2^30 pixels"); }
+};
+
+// a pt_*_params_init's first step: zeros and the struct's size; false for a NULL struct, which is ignored
+template <class P>
+bool init_params(P* p) {
+  if (!p) return false;
+  std::memset(p, 0, sizeof *p);
+  p->struct_size = (int32_t)sizeof(P);
+  return true;
+}
+template <class P>
+bool is_ours(const P* p) { return p->struct_size == (int32_t)sizeof(P); }
+
+constexpr int64_t kMaxPixels = (int64_t)1 << 30;
+// the pixels of a frame, or -1 for a frame without pixels or with more than 2^30
+int64_t frame_pixels(int32_t width, int32_t height) {
+  return width <= 0 || height <= 0 || (int64_t)width * height > kMaxPixels ? -1 : (int64_t)width * height;
 }
 
+// the bytes [p, p + bytes) of a plane; a NULL plane meets nothing
+struct Span {
+  const void* p;
+  uintptr_t bytes;
+  Span unless_it_is(const void* input) const { return p == input ? Span{nullptr, 0} : *this; } // a written plane that may BE that input: left out
+};
+using Spans = std::initializer_list<Span>;
+bool overlaps(Span a, Span b) {
+  const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
+  return a.p && b.p && a0 < b0 + b.bytes && b0 < a0 + a.bytes;
+}
+// does any of the written spans meet any of the read ones?
+bool overlaps(Spans written, Spans read) {
+  for (const Span& w : written)
+    for (const Span& r : read)
+      if (overlaps(w, r)) return true;
+  return false;
+}
+// do the written spans meet one another?
+bool overlap_one_another(Spans written) {
+  for (const Span* i = written.begin(); i != written.end(); i++)
+    for (const Span* j = i + 1; j != written.end(); j++)
+      if (overlaps(*i, *j)) return true;
+  return false;
+}
+
+// A parameter struct's rectangle inside a width x height frame: four zeros mean the whole frame.  False where it leaves the frame or is
+// inverted — or, without `allow_empty`, holds no pixel.
+struct Rect { int x0, y0, x1, y1; };
+template <class P>
+bool frame_rect(const P& p, int width, int height, bool allow_empty, Rect& r) {
+  r = {p.rect_x0, p.rect_y0, p.rect_x1, p.rect_y1};
+  if (!(r.x0 || r.y0 || r.x1 || r.y1)) { r.x1 = width; r.y1 = height; }
+  const bool ordered = allow_empty ? r.x0 <= r.x1 && r.y0 <= r.y1 : r.x0 < r.x1 && r.y0 < r.y1;
+  return r.x0 >= 0 && r.y0 >= 0 && r.x1 <= width && r.y1 <= height && ordered;
+}
+
+// The 32 x 8 tile walk of pt_firefly and pt_spatial_variance: one dimension of at most max_blocks workgroups, each of which walks the
+// tiles grid.x apart.  (tiles is at most 2^30: a frame one pixel wide and 2^30 rows high has 2^27.)
+static_assert(PT_FIREFLY_TILE_W == PT_SVAR_TILE_W && PT_FIREFLY_TILE_H == PT_SVAR_TILE_H, "TileGrid is either stage's tile");
+struct TileGrid {
+  int tiles_x, tiles_y, tiles;
+  dim3 grid;
+  TileGrid(int width, int height, int max_blocks)
+      : tiles_x((width + PT_FIREFLY_TILE_W - 1) / PT_FIREFLY_TILE_W), tiles_y((height + PT_FIREFLY_TILE_H - 1) / PT_FIREFLY_TILE_H),
+        tiles((int)((int64_t)tiles_x * tiles_y)), grid((unsigned)std::min(tiles, max_blocks)) {}
+};
+
+// a kernel's <true> / <false> pair (its LDS path, its vector path), 256 threads per workgroup
+template <class... Params, class... Args>
+int launch_pair(bool first, void (*k_true)(Params...), void (*k_false)(Params...), dim3 grid, hipStream_t st, Args... args) {
+  hipLaunchKernelGGL(first ? k_true : k_false, grid, dim3(256), 0, st, args...);
+  PT_HIP(hipGetLastError());
+  return PT_OK;
+}
+
+// What a pt_debug_last_* getter reports: N words about an entry point's last call.  begin(): a call starts — the words are zeroed and the
+// lock is held while it launches and writes `words`; set(): words written under a lock of their own, the others kept.
+template <int N>
+struct LastRecord {
+  std::mutex mutex;
+  int32_t words[N] = {};
+  std::unique_lock<std::mutex> begin() {
+    std::unique_lock<std::mutex> lock(mutex);
+    std::memset(words, 0, sizeof words);
+    return lock;
+  }
+  template <class... W>
+  void set(int first, W... w) {
+    const int32_t v[] = {(int32_t)w...};
+    std::lock_guard<std::mutex> lock(mutex);
+    std::memcpy(words + first, v, sizeof v);
+  }
+  int copy_out(const char* who, int32_t* out) {
+    if (!out) return fail(PT_ERR_INVALID_ARG, std::string(who) + ": NULL argument");
+    std::lock_guard<std::mutex> lock(mutex);
+    std::memcpy(out, words, sizeof words);
+    return PT_OK;
+  }
+};
+// the filters: the read path per iteration (0: not run, 1: global memory, 2: an LDS tile); the other stages: the header's words
+LastRecord<8> g_last_denoise, g_last_vdn, g_last_display;
+LastRecord<4> g_last_firefly, g_last_svar, g_last_imgerr;
+
+// pt_firefly's and pt_spatial_variance's launch: the record begun, the counts zeroed on the stream, the kernel's LDS pair over the tile walk,
+// and the record's words {the read path (1: global memory, 2: LDS), tiles_x, tiles_y, the stage's own fourth word}
+template <class Args>
+int launch_counted_tiles(LastRecord<4>& last, bool lds, void (*k_true)(Args), void (*k_false)(Args), const TileGrid& tg, uint32_t* counts,
+                         hipStream_t st, const Args& a, int32_t fourth) {
+  const auto lock = last.begin();
+  if (counts) PT_HIP(hipMemsetAsync(counts, 0, 8, st));
+  if (const int rc = launch_pair(lds, k_true, k_false, tg.grid, st, a)) return rc;
+  const int32_t words[4] = {lds ? 2 : 1, tg.tiles_x, tg.tiles_y, fourth};
+  std::memcpy(last.words, words, sizeof words);
+  return PT_OK;
+}
+
+// ---- the denoisers' host side, once: what pt_denoise and pt_variance_denoise check, decide and launch alike ---------------------------------
 // the largest step whose reads come from an LDS-staged tile (profiles/denoise_bench.txt, profiles/variance_denoise_bench.txt: the A/Bs)
 constexpr int kFilterLdsMaxStep = 2;
 static_assert(PT_DENOISE_DEMODULATE == PT_VDENOISE_DEMODULATE && PT_DENOISE_NO_LDS == PT_VDENOISE_NO_LDS &&
               PT_DENOISE_MAX_ITERATIONS == 8 && PT_VDENOISE_MAX_ITERATIONS == 8, "filter_plan reads either filter's flags and iterations");
-
-// an entry point's read path per iteration of its last call (0: not run, 1: global memory, 2: an LDS tile), for its pt_debug_last_* getter
-struct LastPath {
-  std::mutex mutex;
-  int32_t path[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  std::unique_lock<std::mutex> begin() { // a call starts: held while it launches
-    std::unique_lock<std::mutex> lock(mutex);
-    std::memset(path, 0, sizeof path);
-    return lock;
-  }
-  int copy_out(const char* who, int32_t out[8]) {
-    if (!out) return fail(PT_ERR_INVALID_ARG, std::string(who) + ": NULL argument");
-    std::lock_guard<std::mutex> lock(mutex);
-    std::memcpy(out, path, sizeof path);
-    return PT_OK;
-  }
-} g_last_denoise, g_last_vdn;
 
 // k = 1.0f / (sigma * sigma) in binary32, as the header defines it (host arithmetic: IEEE, no excess precision on this target)
 float denoise_k(float sigma) {
@@ -3480,7 +3580,7 @@ struct FilterPlan {
 // colour sigma (> 0) where that conversion's error is due and returns what is wrong with it, or NULL.
 template <class ColorK>
 int filter_plan(const FilterCall& c, ColorK&& color_k, FilterPlan& p) {
-  auto bad = [&](const std::string& what) { return fail(PT_ERR_INVALID_ARG, std::string(c.who) + ": " + what); };
+  const Refuse bad{c.who};
   if (c.width <= 0 || c.height <= 0) return bad("width and height must be > 0");
   if (c.iterations < 1 || c.iterations > PT_DENOISE_MAX_ITERATIONS) return bad("need 1 <= iterations <= 8");
   for (float s : {c.sigma_color, c.sigma_normal, c.sigma_depth, c.sigma_albedo})
@@ -3511,14 +3611,12 @@ int filter_plan(const FilterCall& c, ColorK&& color_k, FilterPlan& p) {
     if (!denoise_k_ok(p.k_a)) return bad("1 / sigma_albedo^2 leaves binary32");
   }
   p.pixels = (int64_t)c.width * c.height;
-  if (p.pixels > ((int64_t)1 << 30)) return fail(PT_ERR_TOO_LARGE, std::string(c.who) + ": more than 2^30 pixels");
+  if (p.pixels > kMaxPixels) return bad.too_large();
   if ((uintptr_t)c.scratch % 16) return bad("scratch must be 16-byte aligned");
   const uintptr_t frame = (uintptr_t)p.pixels * 12;
-  const struct { const float* p; uintptr_t bytes; } guides[3] = {{c.albedo, frame}, {c.normal, frame}, {c.depth, frame / 3}};
-  for (const auto& g : guides)
-    if (overlaps(c.written[0], frame, g.p, g.bytes) || overlaps(c.written[1], frame, g.p, g.bytes) ||
-        overlaps(c.scratch, (uintptr_t)c.scratch_floats * 4, g.p, g.bytes))
-      return bad(std::string(c.written_names) + " and scratch must not overlap a guide plane");
+  if (overlaps({{c.written[0], frame}, {c.written[1], frame}, {c.scratch, (uintptr_t)c.scratch_floats * 4}},
+               {{c.albedo, frame}, {c.normal, frame}, {c.depth, frame / 3}}))
+    return bad(std::string(c.written_names) + " and scratch must not overlap a guide plane");
   p.nd = p.terms & (DN_NORMAL | DN_DEPTH); p.al = p.demod || (p.terms & DN_ALBEDO);
   p.grid = dim3((unsigned)((c.width + 31) / 32), (unsigned)((c.height + 7) / 8));
   // the kernel of an iteration: reads from an LDS-staged tile at the steps 1 and 2 (unless PT_*_NO_LDS), from global memory beyond
@@ -3534,7 +3632,7 @@ int filter_plan(const FilterCall& c, ColorK&& color_k, FilterPlan& p) {
 
 // The iterations: fill(a, i) completes iteration i's arguments — its planes, a.f.g_nd / g_al, a.f.k_color and its own bits of a.f.terms.
 template <class Args, class Fill>
-int filter_launch(const FilterPlan& p, void (*const (&kernels)[3][2][2])(Args), LastPath& last, hipStream_t st, Fill&& fill) {
+int filter_launch(const FilterPlan& p, void (*const (&kernels)[3][2][2])(Args), LastRecord<8>& last, hipStream_t st, Fill&& fill) {
   for (int i = 0; i < p.iterations; i++) {
     Args a;
     a.f.width = p.width; a.f.height = p.height; a.f.step = 1 << i;
@@ -3542,7 +3640,7 @@ int filter_launch(const FilterPlan& p, void (*const (&kernels)[3][2][2])(Args), 
     fill(a, i);
     hipLaunchKernelGGL(kernels[p.staged[i]][p.nd ? 1 : 0][p.al ? 1 : 0], p.grid, dim3(256), 0, st, a);
     PT_HIP(hipGetLastError());
-    last.path[i] = p.staged[i] ? 2 : 1;
+    last.words[i] = p.staged[i] ? 2 : 1;
   }
   return PT_OK;
 }
@@ -3553,9 +3651,7 @@ extern "C" {
 // ---- denoiser: pt_denoise (atrous_pack_kernel, atrous_kernel): its colour ladder k_c(i), its scratch of one colour plane ---------------------
 
 void pt_denoise_params_init(PtDenoiseParams* params, int32_t width, int32_t height) {
-  if (!params) return;
-  std::memset(params, 0, sizeof *params);
-  params->struct_size = (int32_t)sizeof(PtDenoiseParams);
+  if (!init_params(params)) return;
   params->width = width; params->height = height;
   params->iterations = PT_DENOISE_DEFAULT_ITERATIONS;
   params->sigma_color = PT_DENOISE_DEFAULT_SIGMA_COLOR; params->sigma_normal = PT_DENOISE_DEFAULT_SIGMA_NORMAL;
@@ -3567,15 +3663,15 @@ void pt_denoise_params_init(PtDenoiseParams* params, int32_t width, int32_t heig
 static int64_t denoise_color_floats(int64_t pixels) { return (pixels * 3 + 3) / 4 * 4; }
 
 int64_t pt_denoise_scratch_floats(int32_t width, int32_t height) {
-  if (width <= 0 || height <= 0 || (int64_t)width * height > ((int64_t)1 << 30)) return -1;
-  const int64_t pixels = (int64_t)width * height;
-  return denoise_color_floats(pixels) + 8 * pixels;
+  const int64_t pixels = frame_pixels(width, height);
+  return pixels < 0 ? -1 : denoise_color_floats(pixels) + 8 * pixels;
 }
 
 int pt_denoise(const PtDenoiseParams* params, const float* color, const float* albedo, const float* normal, const float* depth,
                float* out, float* scratch, void* stream) {
-  if (!params || !color || !out || !scratch) return fail(PT_ERR_INVALID_ARG, "pt_denoise: NULL params, color, out or scratch");
-  if (params->struct_size != (int32_t)sizeof(PtDenoiseParams)) return fail(PT_ERR_INVALID_ARG, "pt_denoise: PtDenoiseParams.struct_size is not this library's");
+  const Refuse bad{"pt_denoise"};
+  if (!params || !color || !out || !scratch) return bad("NULL params, color, out or scratch");
+  if (!is_ours(params)) return bad("PtDenoiseParams.struct_size is not this library's");
   const int n_it = params->iterations;
   const int64_t scratch_floats = pt_denoise_scratch_floats(params->width, params->height);
   float k_c[PT_DENOISE_MAX_ITERATIONS] = {};
@@ -3593,8 +3689,7 @@ int pt_denoise(const PtDenoiseParams* params, const float* color, const float* a
   if (rc) return rc;
   const int64_t pixels = plan.pixels;
   const uintptr_t frame = (uintptr_t)pixels * 12;
-  if (overlaps(scratch, (uintptr_t)scratch_floats * 4, color, frame) || overlaps(scratch, (uintptr_t)scratch_floats * 4, out, frame))
-    return fail(PT_ERR_INVALID_ARG, "pt_denoise: scratch must not overlap color or out");
+  if (overlaps({{scratch, (uintptr_t)scratch_floats * 4}}, {{color, frame}, {out, frame}})) return bad("scratch must not overlap color or out");
 
   hipStream_t st = (hipStream_t)stream;
   float* const plane = scratch; // the colour plane the iterations ping-pong with `out`
@@ -3609,7 +3704,7 @@ int pt_denoise(const PtDenoiseParams* params, const float* color, const float* a
   // Iteration i writes `out` when an even number of iterations follows it and the scratch plane otherwise, so the last one writes `out`.
   // With an odd count the first would read `color` while writing `out`: where the two overlap it reads a copy in the scratch plane.
   const float* src = color;
-  if (n_it % 2 == 1 && overlaps(out, frame, color, frame)) {
+  if (n_it % 2 == 1 && overlaps(Span{out, frame}, Span{color, frame})) {
     PT_HIP(hipMemcpyAsync(plane, color, (size_t)pixels * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
     src = plane;
   }
@@ -3629,9 +3724,7 @@ int pt_debug_last_denoise(int32_t out[8]) { return g_last_denoise.copy_out("pt_d
 // ---- variance-guided denoiser: pt_variance_denoise (vdn_pack_kernel, vdn_kernel): its sv2, its variance planes, its scratch of records ------
 
 void pt_variance_denoise_params_init(PtVarianceDenoiseParams* params, int32_t width, int32_t height) {
-  if (!params) return;
-  std::memset(params, 0, sizeof *params);
-  params->struct_size = (int32_t)sizeof(PtVarianceDenoiseParams);
+  if (!init_params(params)) return;
   params->width = width; params->height = height;
   params->iterations = PT_VDENOISE_DEFAULT_ITERATIONS;
   params->sigma_variance = PT_VDENOISE_DEFAULT_SIGMA_VARIANCE; params->sigma_normal = PT_VDENOISE_DEFAULT_SIGMA_NORMAL;
@@ -3641,15 +3734,15 @@ void pt_variance_denoise_params_init(PtVarianceDenoiseParams* params, int32_t wi
 
 // per pixel: two working planes of a 16-byte and an 8-byte record (6 floats each) and two 16-byte guide records
 int64_t pt_variance_denoise_scratch_floats(int32_t width, int32_t height) {
-  if (width <= 0 || height <= 0 || (int64_t)width * height > ((int64_t)1 << 30)) return -1;
-  return 20 * ((int64_t)width * height);
+  const int64_t pixels = frame_pixels(width, height);
+  return pixels < 0 ? -1 : 20 * pixels;
 }
 
 int pt_variance_denoise(const PtVarianceDenoiseParams* params, const float* color, const float* variance, const float* albedo,
                         const float* normal, const float* depth, float* out, float* variance_out, float* scratch, void* stream) {
-  auto bad = [&](const char* what) { return fail(PT_ERR_INVALID_ARG, std::string("pt_variance_denoise: ") + what); };
+  const Refuse bad{"pt_variance_denoise"};
   if (!params || !color || !variance || !out || !scratch) return bad("NULL params, color, variance, out or scratch");
-  if (params->struct_size != (int32_t)sizeof(PtVarianceDenoiseParams)) return bad("PtVarianceDenoiseParams.struct_size is not this library's");
+  if (!is_ours(params)) return bad("PtVarianceDenoiseParams.struct_size is not this library's");
   const int64_t scratch_floats = pt_variance_denoise_scratch_floats(params->width, params->height);
   float sv2 = 0.0f;
   FilterPlan plan;
@@ -3665,9 +3758,9 @@ int pt_variance_denoise(const PtVarianceDenoiseParams* params, const float* colo
   if (rc) return rc;
   const int64_t pixels = plan.pixels;
   const uintptr_t frame = (uintptr_t)pixels * 12;
-  for (const float* f : {color, variance, (const float*)out, (const float*)variance_out})
-    if (overlaps(scratch, (uintptr_t)scratch_floats * 4, f, frame)) return bad("scratch must not overlap color, variance, out or variance_out");
-  if (overlaps(variance_out, frame, color, frame) || overlaps(variance_out, frame, out, frame)) return bad("variance_out must not overlap color or out");
+  if (overlaps({{scratch, (uintptr_t)scratch_floats * 4}}, {{color, frame}, {variance, frame}, {out, frame}, {variance_out, frame}}))
+    return bad("scratch must not overlap color, variance, out or variance_out");
+  if (overlaps({{variance_out, frame}}, {{color, frame}, {out, frame}})) return bad("variance_out must not overlap color or out");
 
   hipStream_t st = (hipStream_t)stream;
   // scratch: [A0 | A1 | g_nd | g_al] 16-byte records, then [B0 | B1] 8-byte records
@@ -3732,9 +3825,7 @@ TemporalConsts temporal_consts(const PtCamera& c) {
 extern "C" {
 
 void pt_temporal_params_init(PtTemporalParams* params) {
-  if (!params) return;
-  std::memset(params, 0, sizeof *params);
-  params->struct_size = (int32_t)sizeof(PtTemporalParams);
+  if (!init_params(params)) return;
   params->alpha = PT_TEMPORAL_DEFAULT_ALPHA;
   params->tol_depth = PT_TEMPORAL_DEFAULT_TOL_DEPTH;
   params->tol_normal = PT_TEMPORAL_DEFAULT_TOL_NORMAL;
@@ -3742,15 +3833,16 @@ void pt_temporal_params_init(PtTemporalParams* params) {
 
 // two histories of three 16-byte records per pixel
 int64_t pt_temporal_state_bytes(int32_t width, int32_t height) {
-  if (width <= 0 || height <= 0 || (int64_t)width * height > ((int64_t)1 << 30)) return -1;
-  return 96 * ((int64_t)width * height);
+  const int64_t pixels = frame_pixels(width, height);
+  return pixels < 0 ? -1 : 96 * pixels;
 }
 
 int pt_temporal_create(int32_t width, int32_t height, PtTemporal** out) {
   if (!out) return fail(PT_ERR_INVALID_ARG, "pt_temporal_create: out is NULL");
   *out = nullptr;
-  if (width <= 0 || height <= 0) return fail(PT_ERR_INVALID_ARG, "pt_temporal_create: width and height must be > 0");
-  if ((int64_t)width * height > ((int64_t)1 << 30)) return fail(PT_ERR_TOO_LARGE, "pt_temporal_create: more than 2^30 pixels");
+  const Refuse bad{"pt_temporal_create"};
+  if (width <= 0 || height <= 0) return bad("width and height must be > 0");
+  if (frame_pixels(width, height) < 0) return bad.too_large();
   std::unique_ptr<PtTemporal> t(new PtTemporal());
   t->width = width; t->height = height; t->pixels = (long long)width * height;
   const hipError_t e = t->rec.alloc((size_t)t->pixels * 6);
@@ -3773,10 +3865,10 @@ int32_t pt_temporal_frames(const PtTemporal* t) { return t ? t->frames : -1; }
 int pt_temporal_push(PtTemporal* t, const PtTemporalParams* params, const PtCamera* cam, const float* color, const float* depth,
                      const float* normal, const int32_t* id, const float* variance_in, float* out_color, float* out_variance,
                      float* out_history, void* stream) {
-  auto bad = [&](const char* what) { return fail(PT_ERR_INVALID_ARG, std::string("pt_temporal_push: ") + what); };
+  const Refuse bad{"pt_temporal_push"};
   // (the arguments that can be judged without the state first: the state is read only once they are sound)
   if (!t || !params || !cam || !color || !depth || !out_color) return bad("NULL state, params, cam, color, depth or out_color");
-  if (params->struct_size != (int32_t)sizeof(PtTemporalParams)) return bad("PtTemporalParams.struct_size is not this library's");
+  if (!is_ours(params)) return bad("PtTemporalParams.struct_size is not this library's");
   if (!(params->alpha > 0.0f && params->alpha <= 1.0f)) return bad("need 0 < alpha <= 1");
   if (!(std::isfinite(params->tol_depth) && params->tol_depth > 0.0f) || !(std::isfinite(params->tol_normal) && params->tol_normal > 0.0f))
     return bad("a tolerance is not a finite number > 0");
@@ -3784,14 +3876,9 @@ int pt_temporal_push(PtTemporal* t, const PtTemporalParams* params, const PtCame
   if (!temporal_consts(*cam).ok) return bad("a degenerate camera (fo, hh or vv is not a finite number > 0)");
   const long long pixels = t->pixels;
   const uintptr_t plane = (uintptr_t)pixels * 4;
-  const struct { const void* p; uintptr_t bytes; } outs[3] = {{out_color, plane * 3}, {out_variance, plane * 3}, {out_history, plane}},
-                                                   guides[3] = {{depth, plane}, {normal, plane * 3}, {id, plane}};
-  for (const auto& o : outs)
-    for (const auto& g : guides)
-      if (overlaps(o.p, o.bytes, g.p, g.bytes)) return bad("an out plane overlaps a guide plane");
-  for (int i = 0; i < 3; i++)
-    for (int j = i + 1; j < 3; j++)
-      if (overlaps(outs[i].p, outs[i].bytes, outs[j].p, outs[j].bytes)) return bad("the out planes overlap one another");
+  const Spans outs = {{out_color, plane * 3}, {out_variance, plane * 3}, {out_history, plane}};
+  if (overlaps(outs, {{depth, plane}, {normal, plane * 3}, {id, plane}})) return bad("an out plane overlaps a guide plane");
+  if (overlap_one_another(outs)) return bad("the out planes overlap one another");
 
   TemporalArgs a;
   a.color = color; a.depth = depth; a.normal = normal; a.id = id; a.var_in = variance_in;
@@ -3828,14 +3915,11 @@ struct PtDisplay {
 };
 
 namespace {
-std::mutex g_display_mutex;
-int32_t g_last_display[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // pt_debug_last_display
-
 // What can be judged of a call without a live object: the params, the frame, the rectangle.  iw2 = 1.0f / (white * white), rounded twice.
 int display_check(const char* call, const PtDisplayParams* p, const float* color, int32_t width, int32_t height, float* iw2_out) {
-  auto bad = [&](const char* what) { return fail(PT_ERR_INVALID_ARG, std::string(call) + ": " + what); };
+  const Refuse bad{call};
   if (!p || !color) return bad("NULL params or color");
-  if (p->struct_size != (int32_t)sizeof(PtDisplayParams)) return bad("PtDisplayParams.struct_size is not this library's");
+  if (!is_ours(p)) return bad("PtDisplayParams.struct_size is not this library's");
   if (width <= 0 || height <= 0) return bad("width and height must be > 0");
   if ((int64_t)width * height > ((int64_t)1 << 31)) return bad("more than 2^31 pixels");
   if (p->tone != PT_TONE_REFERENCE && p->tone != PT_TONE_REINHARD && p->tone != PT_TONE_ACES) return bad("unknown tone");
@@ -3847,10 +3931,7 @@ int display_check(const char* call, const PtDisplayParams* p, const float* color
   volatile float w2 = p->white * p->white;
   volatile float iw2 = 1.0f / w2;
   if (!(std::isfinite(iw2) && iw2 > 0.0f)) return bad("white: 1 / (white * white) is not a finite binary32 number > 0");
-  if (p->rect_x0 || p->rect_y0 || p->rect_x1 || p->rect_y1) {
-    if (p->rect_x0 < 0 || p->rect_y0 < 0 || p->rect_x1 > width || p->rect_y1 > height || p->rect_x0 >= p->rect_x1 || p->rect_y0 >= p->rect_y1)
-      return bad("the metering rectangle is empty or leaves the frame");
-  }
+  if (Rect r; !frame_rect(*p, width, height, false, r)) return bad("the metering rectangle is empty or leaves the frame");
   if (iw2_out) *iw2_out = iw2;
   return PT_OK;
 }
@@ -3859,9 +3940,7 @@ int display_check(const char* call, const PtDisplayParams* p, const float* color
 extern "C" {
 
 void pt_display_params_init(PtDisplayParams* params) {
-  if (!params) return;
-  std::memset(params, 0, sizeof *params);
-  params->struct_size = (int32_t)sizeof(PtDisplayParams);
+  if (!init_params(params)) return;
   params->tone = PT_DISPLAY_DEFAULT_TONE;
   params->ev_bias = PT_DISPLAY_DEFAULT_EV_BIAS; params->ev_min = PT_DISPLAY_DEFAULT_EV_MIN; params->ev_max = PT_DISPLAY_DEFAULT_EV_MAX;
   params->lo_permille = PT_DISPLAY_DEFAULT_LO_PERMILLE; params->hi_permille = PT_DISPLAY_DEFAULT_HI_PERMILLE;
@@ -3906,20 +3985,19 @@ int pt_display_set_exposure(PtDisplay* d, float ev, void* stream) {
 int pt_display_meter(PtDisplay* d, const PtDisplayParams* p, const float* color, int32_t width, int32_t height, void* stream) {
   if (const int rc = display_check("pt_display_meter", p, color, width, height, nullptr)) return rc;
   if (!d) return fail(PT_ERR_INVALID_ARG, "pt_display_meter: NULL state");
-  const bool whole = !(p->rect_x0 || p->rect_y0 || p->rect_x1 || p->rect_y1);
-  const int x0 = whole ? 0 : p->rect_x0, y0 = whole ? 0 : p->rect_y0, x1 = whole ? width : p->rect_x1, y1 = whole ? height : p->rect_y1;
+  Rect r;
+  frame_rect(*p, width, height, false, r);
+  const int x0 = r.x0, y0 = r.y0, x1 = r.x1, y1 = r.y1;
   const int64_t n = (int64_t)(x1 - x0) * (y1 - y0); // 1 ... 2^31
   // four pixels per thread where the rectangle is one contiguous, 16-byte aligned range of the frame
   const bool vec = x1 - x0 == width && ((uintptr_t)(color + ((int64_t)y0 * width + x0) * 3) & 15) == 0;
   const int64_t items = vec ? (n + 3) / 4 : n;
   const unsigned blocks = (unsigned)std::min<int64_t>((items + DISP_METER_THREADS - 1) / DISP_METER_THREADS, DISP_METER_MAX_BLOCKS);
   unsigned* const work = d->words.p + DISP_WORK;
-  const dim3 grid(blocks), block(DISP_METER_THREADS);
-  if (vec)
-    hipLaunchKernelGGL(display_meter_kernel<true>, grid, block, 0, (hipStream_t)stream, color, work, (int)width, x0, y0, x1 - x0, (unsigned)n);
-  else
-    hipLaunchKernelGGL(display_meter_kernel<false>, grid, block, 0, (hipStream_t)stream, color, work, (int)width, x0, y0, x1 - x0, (unsigned)n);
-  PT_HIP(hipGetLastError());
+  static_assert(DISP_METER_THREADS == 256, "launch_pair's workgroup");
+  if (const int rc = launch_pair(vec, display_meter_kernel<true>, display_meter_kernel<false>, dim3(blocks), (hipStream_t)stream, color, work,
+                                 (int)width, x0, y0, x1 - x0, (unsigned)n))
+    return rc;
   DisplaySolveArgs a;
   a.state = d->words.p;
   a.lo_permille = p->lo_permille; a.hi_permille = p->hi_permille;
@@ -3927,12 +4005,8 @@ int pt_display_meter(PtDisplay* d, const PtDisplayParams* p, const float* color,
   hipLaunchKernelGGL(display_solve_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a);
   PT_HIP(hipGetLastError());
   if (d->frames < INT32_MAX) d->frames++;
-  {
-    std::lock_guard<std::mutex> lock(g_display_mutex);
-    g_last_display[0] = (int32_t)blocks; g_last_display[1] = DISP_METER_THREADS;
-    g_last_display[2] = (int32_t)((items + (int64_t)blocks * DISP_METER_THREADS - 1) / ((int64_t)blocks * DISP_METER_THREADS));
-    g_last_display[3] = vec ? 4 : 1;
-  }
+  g_last_display.set(0, blocks, DISP_METER_THREADS, (items + (int64_t)blocks * DISP_METER_THREADS - 1) / ((int64_t)blocks * DISP_METER_THREADS),
+                     vec ? 4 : 1);
   return PT_OK;
 }
 
@@ -3940,11 +4014,11 @@ int pt_display_apply(const PtDisplay* d, const PtDisplayParams* p, const float* 
                      float* linear_out, void* stream) {
   float iw2 = 0.0f;
   if (const int rc = display_check("pt_display_apply", p, color, width, height, &iw2)) return rc;
-  auto bad = [&](const char* what) { return fail(PT_ERR_INVALID_ARG, std::string("pt_display_apply: ") + what); };
+  const Refuse bad{"pt_display_apply"};
   if (!rgb8_out && !linear_out) return bad("rgb8_out and linear_out are both NULL");
   const uintptr_t values = (uintptr_t)width * (uintptr_t)height * 3;
-  if (overlaps(rgb8_out, values, color, values * 4) || overlaps(rgb8_out, values, linear_out, values * 4)) return bad("rgb8_out overlaps color or linear_out");
-  if (linear_out != color && overlaps(linear_out, values * 4, color, values * 4)) return bad("linear_out overlaps color without being color");
+  if (overlaps({{rgb8_out, values}}, {{color, values * 4}, {linear_out, values * 4}})) return bad("rgb8_out overlaps color or linear_out");
+  if (linear_out != color && overlaps(Span{linear_out, values * 4}, Span{color, values * 4})) return bad("linear_out overlaps color without being color");
   const float ev = std::fmin(std::fmax(p->ev_bias, -32.0f), 32.0f);
   const unsigned* state = d ? d->words.p : nullptr;
   // four values per thread where the rows and the planes allow 16-byte loads and stores
@@ -3958,10 +4032,7 @@ int pt_display_apply(const PtDisplay* d, const PtDisplayParams* p, const float* 
   else { if (vec) PT_DISPLAY_APPLY(PT_TONE_REFERENCE, true); else PT_DISPLAY_APPLY(PT_TONE_REFERENCE, false); }
 #undef PT_DISPLAY_APPLY
   PT_HIP(hipGetLastError());
-  {
-    std::lock_guard<std::mutex> lock(g_display_mutex);
-    g_last_display[4] = (int32_t)grid.x; g_last_display[5] = (int32_t)grid.y; g_last_display[6] = vec ? 4 : 1; g_last_display[7] = p->tone + 1;
-  }
+  g_last_display.set(4, grid.x, grid.y, vec ? 4 : 1, p->tone + 1);
   return PT_OK;
 }
 
@@ -3979,21 +4050,11 @@ int pt_display_histogram(const PtDisplay* d, uint32_t host[257], void* stream) {
   return PT_OK;
 }
 
-int pt_debug_last_display(int32_t out[8]) {
-  if (!out) return fail(PT_ERR_INVALID_ARG, "pt_debug_last_display: NULL argument");
-  std::lock_guard<std::mutex> lock(g_display_mutex);
-  std::memcpy(out, g_last_display, sizeof g_last_display);
-  return PT_OK;
-}
+int pt_debug_last_display(int32_t out[8]) { return g_last_display.copy_out("pt_debug_last_display", out); }
 
 // ---- firefly stage (include/pt_post.h): pt_firefly (firefly_kernel) ------------------------------------------------------------------------
-static std::mutex g_firefly_mutex;
-static int32_t g_last_firefly[4] = {0, 0, 0, 0}; // pt_debug_last_firefly
-
 void pt_firefly_params_init(PtFireflyParams* params, int32_t width, int32_t height) {
-  if (!params) return;
-  std::memset(params, 0, sizeof *params);
-  params->struct_size = (int32_t)sizeof(PtFireflyParams);
+  if (!init_params(params)) return;
   params->width = width; params->height = height;
   params->rank = PT_FIREFLY_DEFAULT_RANK;
   params->k = PT_FIREFLY_DEFAULT_K;
@@ -4002,24 +4063,22 @@ void pt_firefly_params_init(PtFireflyParams* params, int32_t width, int32_t heig
 
 int pt_firefly(const PtFireflyParams* params, const float* color, const float* variance, float* out, float* variance_out, uint32_t* counts,
                void* stream) {
-  auto bad = [&](const char* what) { return fail(PT_ERR_INVALID_ARG, std::string("pt_firefly: ") + what); };
+  const Refuse bad{"pt_firefly"};
   if (!params || !color || !out) return bad("NULL params, color or out");
-  if (params->struct_size != (int32_t)sizeof(PtFireflyParams)) return bad("PtFireflyParams.struct_size is not this library's");
+  if (!is_ours(params)) return bad("PtFireflyParams.struct_size is not this library's");
   if (params->width <= 0 || params->height <= 0) return bad("width and height must be > 0");
   if (params->rank != 1 && params->rank != 2) return bad("rank must be 1 or 2");
   if (!(std::isfinite(params->k) && params->k > 0.0f)) return bad("k must be finite and > 0");
   if (params->flags & ~(PT_FIREFLY_REPAIR | PT_FIREFLY_NO_LDS)) return bad("unknown flags");
   if (variance_out && !variance) return bad("variance_out needs variance");
   const int64_t pixels = (int64_t)params->width * params->height;
-  if (pixels > ((int64_t)1 << 30)) return fail(PT_ERR_TOO_LARGE, "pt_firefly: more than 2^30 pixels");
+  if (pixels > kMaxPixels) return bad.too_large();
   if ((uintptr_t)counts % 8) return bad("counts must be 8-byte aligned");
   const uintptr_t frame = (uintptr_t)pixels * 12;
-  const void* const var_written = variance_out == variance ? nullptr : variance_out; // variance_out may BE variance
-  if (overlaps(out, frame, color, frame) || overlaps(out, frame, variance, frame) || overlaps(var_written, frame, color, frame) ||
-      overlaps(var_written, frame, variance, frame) || overlaps(counts, 8, color, frame) || overlaps(counts, 8, variance, frame))
+  const Span var_out{variance_out, frame};
+  if (overlaps({{out, frame}, var_out.unless_it_is(variance), {counts, 8}}, {{color, frame}, {variance, frame}}))
     return bad("out, variance_out and counts must not overlap color or variance (variance_out may be variance itself)");
-  if (overlaps(out, frame, variance_out, frame) || overlaps(counts, 8, out, frame) || overlaps(counts, 8, variance_out, frame))
-    return bad("out, variance_out and counts must not overlap one another");
+  if (overlap_one_another({{out, frame}, var_out, {counts, 8}})) return bad("out, variance_out and counts must not overlap one another");
 
   hipStream_t st = (hipStream_t)stream;
   const bool lds = !(params->flags & PT_FIREFLY_NO_LDS);
@@ -4027,36 +4086,17 @@ int pt_firefly(const PtFireflyParams* params, const float* color, const float* v
   a.color = color; a.variance = variance; a.out = out; a.variance_out = variance_out;
   a.counts = reinterpret_cast<unsigned long long*>(counts);
   a.width = params->width; a.height = params->height;
-  a.tiles_x = (params->width + PT_FIREFLY_TILE_W - 1) / PT_FIREFLY_TILE_W;
+  const TileGrid tg(params->width, params->height, PT_FIREFLY_MAX_BLOCKS);
+  a.tiles_x = tg.tiles_x; a.tiles = tg.tiles;
   a.rank = params->rank; a.repair = params->flags & PT_FIREFLY_REPAIR; a.k = params->k;
-  const int64_t tiles_y = (params->height + PT_FIREFLY_TILE_H - 1) / PT_FIREFLY_TILE_H;
-  a.tiles = (int)(a.tiles_x * tiles_y); // (at most 2^30: a frame one pixel wide and 2^30 rows high has 2^27)
-  const dim3 grid((unsigned)std::min(a.tiles, (int)PT_FIREFLY_MAX_BLOCKS)); // one dimension; each workgroup walks the tiles grid.x apart
-  std::lock_guard<std::mutex> lock(g_firefly_mutex);
-  std::memset(g_last_firefly, 0, sizeof g_last_firefly);
-  if (counts) PT_HIP(hipMemsetAsync(counts, 0, 8, st));
-  if (lds) hipLaunchKernelGGL(firefly_kernel<true>, grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(firefly_kernel<false>, grid, dim3(256), 0, st, a);
-  PT_HIP(hipGetLastError());
-  g_last_firefly[0] = lds ? 2 : 1; g_last_firefly[1] = a.tiles_x; g_last_firefly[2] = (int32_t)tiles_y; g_last_firefly[3] = variance_out ? 2 : 1;
-  return PT_OK;
+  return launch_counted_tiles(g_last_firefly, lds, firefly_kernel<true>, firefly_kernel<false>, tg, counts, st, a, variance_out ? 2 : 1);
 }
 
-int pt_debug_last_firefly(int32_t out[4]) {
-  if (!out) return fail(PT_ERR_INVALID_ARG, "pt_debug_last_firefly: NULL argument");
-  std::lock_guard<std::mutex> lock(g_firefly_mutex);
-  std::memcpy(out, g_last_firefly, sizeof g_last_firefly);
-  return PT_OK;
-}
+int pt_debug_last_firefly(int32_t out[4]) { return g_last_firefly.copy_out("pt_debug_last_firefly", out); }
 
 // ---- spatial variance estimate (include/pt_spatial_variance.h): pt_spatial_variance (svar_kernel) ----------------------------------------
-static std::mutex g_svar_mutex;
-static int32_t g_last_svar[4] = {0, 0, 0, 0}; // pt_debug_last_spatial_variance
-
 void pt_spatial_variance_params_init(PtSpatialVarianceParams* params, int32_t width, int32_t height) {
-  if (!params) return;
-  std::memset(params, 0, sizeof *params);
-  params->struct_size = (int32_t)sizeof(PtSpatialVarianceParams);
+  if (!init_params(params)) return;
   params->width = width; params->height = height;
   params->radius = PT_SVAR_DEFAULT_RADIUS;
   params->min_pairs = PT_SVAR_DEFAULT_MIN_PAIRS;
@@ -4068,9 +4108,9 @@ void pt_spatial_variance_params_init(PtSpatialVarianceParams* params, int32_t wi
 int pt_spatial_variance(const PtSpatialVarianceParams* params, const float* color, const float* albedo, const float* normal,
                         const float* depth, const int32_t* id, const float* variance_in, float* variance_out, uint32_t* counts,
                         void* stream) {
-  auto bad = [&](const char* what) { return fail(PT_ERR_INVALID_ARG, std::string("pt_spatial_variance: ") + what); };
+  const Refuse bad{"pt_spatial_variance"};
   if (!params || !color || !variance_out) return bad("NULL params, color or variance_out");
-  if (params->struct_size != (int32_t)sizeof(PtSpatialVarianceParams)) return bad("PtSpatialVarianceParams.struct_size is not this library's");
+  if (!is_ours(params)) return bad("PtSpatialVarianceParams.struct_size is not this library's");
   if (params->width <= 0 || params->height <= 0) return bad("width and height must be > 0");
   if (params->radius < 1 || params->radius > PT_SVAR_MAX_RADIUS) return bad("radius must be 1 ... PT_SVAR_MAX_RADIUS");
   if (params->min_pairs < 1) return bad("min_pairs must be >= 1");
@@ -4079,16 +4119,14 @@ int pt_spatial_variance(const PtSpatialVarianceParams* params, const float* colo
   if (params->flags & ~(PT_SVAR_DEMODULATE | PT_SVAR_NO_LDS)) return bad("unknown flags");
   if ((params->flags & PT_SVAR_DEMODULATE) && !albedo) return bad("PT_SVAR_DEMODULATE needs albedo");
   const int64_t pixels = (int64_t)params->width * params->height;
-  if (pixels > ((int64_t)1 << 30)) return fail(PT_ERR_TOO_LARGE, "pt_spatial_variance: more than 2^30 pixels");
+  if (pixels > kMaxPixels) return bad.too_large();
   if ((uintptr_t)counts % 8) return bad("counts must be 8-byte aligned");
   const uintptr_t frame = (uintptr_t)pixels * 12, plane = (uintptr_t)pixels * 4;
-  const void* const var_written = variance_out == variance_in ? nullptr : variance_out; // variance_out may BE variance_in
-  const struct { const void* ptr; uintptr_t bytes; } read[] = {{color, frame}, {albedo, frame}, {normal, frame}, {depth, plane}, {id, plane},
-                                                                {variance_in, frame}};
-  for (const auto& in : read)
-    if (overlaps(var_written, frame, in.ptr, in.bytes) || overlaps(counts, 8, in.ptr, in.bytes))
-      return bad("variance_out and counts must not overlap color, a guide or variance_in (variance_out may be variance_in itself)");
-  if (overlaps(counts, 8, variance_out, frame)) return bad("variance_out and counts must not overlap one another");
+  const Span var_out{variance_out, frame};
+  if (overlaps({var_out.unless_it_is(variance_in), {counts, 8}},
+               {{color, frame}, {albedo, frame}, {normal, frame}, {depth, plane}, {id, plane}, {variance_in, frame}}))
+    return bad("variance_out and counts must not overlap color, a guide or variance_in (variance_out may be variance_in itself)");
+  if (overlap_one_another({var_out, {counts, 8}})) return bad("variance_out and counts must not overlap one another");
 
   hipStream_t st = (hipStream_t)stream;
   const bool lds = !(params->flags & PT_SVAR_NO_LDS);
@@ -4096,38 +4134,19 @@ int pt_spatial_variance(const PtSpatialVarianceParams* params, const float* colo
   a.color = color; a.albedo = albedo; a.normal = normal; a.depth = depth; a.id = id; a.variance_in = variance_in; a.variance_out = variance_out;
   a.counts = reinterpret_cast<unsigned long long*>(counts);
   a.width = params->width; a.height = params->height;
-  a.tiles_x = (params->width + PT_SVAR_TILE_W - 1) / PT_SVAR_TILE_W;
+  const TileGrid tg(params->width, params->height, PT_SVAR_MAX_BLOCKS);
+  a.tiles_x = tg.tiles_x; a.tiles = tg.tiles;
   a.radius = params->radius; a.min_pairs = params->min_pairs;
   a.demodulate = params->flags & PT_SVAR_DEMODULATE;
   a.tol_depth = params->tol_depth; a.tol_normal = params->tol_normal;
-  const int64_t tiles_y = (params->height + PT_SVAR_TILE_H - 1) / PT_SVAR_TILE_H;
-  a.tiles = (int)(a.tiles_x * tiles_y); // (at most 2^30: a frame one pixel wide and 2^30 rows high has 2^27)
-  const dim3 grid((unsigned)std::min(a.tiles, (int)PT_SVAR_MAX_BLOCKS)); // one dimension; each workgroup walks the tiles grid.x apart
-  std::lock_guard<std::mutex> lock(g_svar_mutex);
-  std::memset(g_last_svar, 0, sizeof g_last_svar);
-  if (counts) PT_HIP(hipMemsetAsync(counts, 0, 8, st));
-  if (lds) hipLaunchKernelGGL(svar_kernel<true>, grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(svar_kernel<false>, grid, dim3(256), 0, st, a);
-  PT_HIP(hipGetLastError());
-  g_last_svar[0] = lds ? 2 : 1; g_last_svar[1] = a.tiles_x; g_last_svar[2] = (int32_t)tiles_y; g_last_svar[3] = params->radius;
-  return PT_OK;
+  return launch_counted_tiles(g_last_svar, lds, svar_kernel<true>, svar_kernel<false>, tg, counts, st, a, params->radius);
 }
 
-int pt_debug_last_spatial_variance(int32_t out[4]) {
-  if (!out) return fail(PT_ERR_INVALID_ARG, "pt_debug_last_spatial_variance: NULL argument");
-  std::lock_guard<std::mutex> lock(g_svar_mutex);
-  std::memcpy(out, g_last_svar, sizeof g_last_svar);
-  return PT_OK;
-}
+int pt_debug_last_spatial_variance(int32_t out[4]) { return g_last_svar.copy_out("pt_debug_last_spatial_variance", out); }
 
 // ---- image error (include/pt_metrics.h): pt_image_error (imgerr_accumulate_kernel, imgerr_finish_kernel) ---------------------------------
-static std::mutex g_imgerr_mutex;
-static int32_t g_last_imgerr[4] = {0, 0, 0, 0}; // pt_debug_last_image_error
-
 void pt_image_error_params_init(PtImageErrorParams* params, int32_t width, int32_t height) {
-  if (!params) return;
-  std::memset(params, 0, sizeof *params);
-  params->struct_size = (int32_t)sizeof(PtImageErrorParams);
+  if (!init_params(params)) return;
   params->width = width; params->height = height;
   params->eps = PT_IMAGE_ERROR_DEFAULT_EPS;
 }
@@ -4136,28 +4155,25 @@ int64_t pt_image_error_scratch_bytes(void) { return (int64_t)IMGERR_SCRATCH_WORD
 
 int pt_image_error(const PtImageErrorParams* params, const float* a, const float* ref, PtImageErrorResult* result, float* error_plane,
                    void* scratch, void* stream) {
-  auto bad = [&](const char* what) { return fail(PT_ERR_INVALID_ARG, std::string("pt_image_error: ") + what); };
+  const Refuse bad{"pt_image_error"};
   if (!params || !a || !ref || !result || !scratch) return bad("NULL params, a, ref, result or scratch");
-  if (params->struct_size != (int32_t)sizeof(PtImageErrorParams)) return bad("PtImageErrorParams.struct_size is not this library's");
+  if (!is_ours(params)) return bad("PtImageErrorParams.struct_size is not this library's");
   const int width = params->width, height = params->height;
   if (width <= 0 || height <= 0) return bad("width and height must be > 0");
-  int x0 = params->rect_x0, y0 = params->rect_y0, x1 = params->rect_x1, y1 = params->rect_y1;
-  if (!(x0 || y0 || x1 || y1)) { x1 = width; y1 = height; } // four zeros: the whole frame
-  if (x0 < 0 || y0 < 0 || x1 > width || y1 > height || x0 > x1 || y0 > y1) return bad("the rectangle leaves the frame");
+  Rect r;
+  if (!frame_rect(*params, width, height, true, r)) return bad("the rectangle leaves the frame");
+  const int x0 = r.x0, y0 = r.y0, x1 = r.x1, y1 = r.y1;
   if (!(std::isfinite(params->eps) && params->eps >= 0x1p-126)) return bad("eps must be finite and >= 2^-126");
   if (params->flags & ~PT_IMAGE_ERROR_NO_LDS) return bad("unknown flags");
   const int64_t pixels = (int64_t)width * height;
-  if (pixels > ((int64_t)1 << 30)) return fail(PT_ERR_TOO_LARGE, "pt_image_error: more than 2^30 pixels");
+  if (pixels > kMaxPixels) return bad.too_large();
   if ((uintptr_t)result % 8 || (uintptr_t)scratch % 8) return bad("result and scratch must be 8-byte aligned");
   const uintptr_t scratch_bytes = (uintptr_t)IMGERR_SCRATCH_WORDS * 8;
   if (params->scratch_bytes < (int64_t)scratch_bytes) return bad("scratch_bytes is less than pt_image_error_scratch_bytes()");
   const uintptr_t frame = (uintptr_t)pixels * 12, plane = (uintptr_t)pixels * 4;
-  for (const float* in : {a, ref})
-    if (overlaps(error_plane, plane, in, frame) || overlaps(result, sizeof(PtImageErrorResult), in, frame) || overlaps(scratch, scratch_bytes, in, frame))
-      return bad("error_plane, result and scratch must not overlap an input");
-  if (overlaps(error_plane, plane, result, sizeof(PtImageErrorResult)) || overlaps(error_plane, plane, scratch, scratch_bytes) ||
-      overlaps(result, sizeof(PtImageErrorResult), scratch, scratch_bytes))
-    return bad("error_plane, result and scratch must not overlap one another");
+  const Spans written = {{error_plane, plane}, {result, sizeof(PtImageErrorResult)}, {scratch, scratch_bytes}};
+  if (overlaps(written, {{a, frame}, {ref, frame}})) return bad("error_plane, result and scratch must not overlap an input");
+  if (overlap_one_another(written)) return bad("error_plane, result and scratch must not overlap one another");
 
   hipStream_t st = (hipStream_t)stream;
   const bool lds = !(params->flags & PT_IMAGE_ERROR_NO_LDS);
@@ -4170,26 +4186,18 @@ int pt_image_error(const PtImageErrorParams* params, const float* a, const float
   k.n = (unsigned)(whole ? pixels : (int64_t)(x1 - x0) * (y1 - y0));
   k.eps = params->eps;
   const unsigned blocks = (unsigned)std::min<int64_t>(((int64_t)k.n + 255) / 256, PT_IMGERR_MAX_BLOCKS);
-  std::lock_guard<std::mutex> lock(g_imgerr_mutex);
-  std::memset(g_last_imgerr, 0, sizeof g_last_imgerr);
+  const auto lock = g_last_imgerr.begin();
   PT_HIP(hipMemsetAsync(scratch, 0, scratch_bytes, st));
-  if (blocks) { // (an empty rectangle without a plane: nothing to walk)
-    if (lds) hipLaunchKernelGGL(imgerr_accumulate_kernel<true>, dim3(blocks), dim3(256), 0, st, k);
-    else hipLaunchKernelGGL(imgerr_accumulate_kernel<false>, dim3(blocks), dim3(256), 0, st, k);
-    PT_HIP(hipGetLastError());
-  }
+  if (blocks) // (an empty rectangle without a plane: nothing to walk)
+    if (const int rc = launch_pair(lds, imgerr_accumulate_kernel<true>, imgerr_accumulate_kernel<false>, dim3(blocks), st, k)) return rc;
   hipLaunchKernelGGL(imgerr_finish_kernel, dim3(1), dim3(64), 0, st, k.scratch, result);
   PT_HIP(hipGetLastError());
-  g_last_imgerr[0] = lds ? 2 : 1; g_last_imgerr[1] = (int32_t)blocks; g_last_imgerr[2] = x1 - x0; g_last_imgerr[3] = y1 - y0;
+  const int32_t words[4] = {lds ? 2 : 1, (int32_t)blocks, x1 - x0, y1 - y0};
+  std::memcpy(g_last_imgerr.words, words, sizeof words);
   return PT_OK;
 }
 
-int pt_debug_last_image_error(int32_t out[4]) {
-  if (!out) return fail(PT_ERR_INVALID_ARG, "pt_debug_last_image_error: NULL argument");
-  std::lock_guard<std::mutex> lock(g_imgerr_mutex);
-  std::memcpy(out, g_last_imgerr, sizeof g_last_imgerr);
-  return PT_OK;
-}
+int pt_debug_last_image_error(int32_t out[4]) { return g_last_imgerr.copy_out("pt_debug_last_image_error", out); }
 
 // ---- progressive rendering: sample windows into a PtAccum (include/pt_render.h) ------------------------------------------------
 } // extern "C"

@@ -89,6 +89,93 @@ def _stream_ptr(torch) -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+# ---- the image stages' host prelude: what every stage below checks before it calls the library; a new stage is written against it --------
+
+def _stage(me, has, what, entry):
+    """A stage's first two checks — a HIP device, and a library that has the stage (`has`: abi.has_*) — and the library."""
+    import torch
+
+    if not torch.cuda.is_available():
+        raise RuntimeError(f"path_tracer_amd.{me} needs a HIP device: there is no CPU path in the product")
+    lib = abi.load_library()
+    if not has(lib):
+        raise ImportError(f"{abi.library_path()} predates {what} (no {entry})")
+    return lib
+
+
+def _aov_kwargs_ok(me, other_planes) -> None:
+    """`**other_planes` takes render_aov()'s planes that the stage does not use, and nothing else."""
+    unknown = set(other_planes) - set(abi.AOV_PLANES)
+    if unknown:
+        raise TypeError(f"{me}() got unexpected keyword arguments {sorted(unknown)}")
+
+
+def _whole_frame(fb):
+    """(H, W) of a frame [H][W][3]."""
+    if fb is None or fb.dim() != 3 or fb.shape[2] != 3:
+        raise ValueError("fb must be a whole frame [H][W][3] (gather and unshard a multi-GPU frame first)")
+    return int(fb.shape[0]), int(fb.shape[1])
+
+
+def _plane(t, shape, what, dtype=None):
+    """None -> None; a contiguous CUDA tensor of `shape` (an int: of that many elements) and `dtype` (float32 unless given; a tuple: any of
+    them) -> its pointer."""
+    import torch
+
+    if t is None:
+        return None
+    dtypes = dtype if isinstance(dtype, tuple) else (dtype or torch.float32,)
+    fits = t.numel() == shape if isinstance(shape, int) else tuple(t.shape) == shape
+    if not fits or t.dtype not in dtypes or not t.is_cuda or not t.is_contiguous():
+        names = " (or ".join(str(d).replace("torch.", "") for d in dtypes) + ")" * (len(dtypes) - 1)
+        raise ValueError(f"{what} must be a contiguous {names} CUDA tensor of " + (f"{shape} elements" if isinstance(shape, int) else f"shape {shape}"))
+    return C.c_void_p(t.data_ptr())
+
+
+def _frame_ptr(fb, what="fb"):
+    """_plane() for a frame whose size is not known yet."""
+    import torch
+
+    if fb is None or fb.dim() != 3 or fb.shape[2] != 3 or fb.dtype != torch.float32 or not fb.is_cuda or not fb.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous float32 CUDA tensor of shape [H][W][3]")
+    return C.c_void_p(fb.data_ptr())
+
+
+def _optional_out(arg, shape, dtype, what, device):
+    """An optional output: True allocates it (`dtype`, or the first of a tuple), a tensor is checked and written, False / None give None."""
+    import torch
+
+    if arg is None or arg is False:
+        return None
+    if arg is True:
+        return torch.empty(shape, dtype=dtype[0] if isinstance(dtype, tuple) else dtype, device=device)
+    _plane(arg, shape, what, dtype)
+    return arg
+
+
+def _counts(arg, device):
+    """The `counts=` of firefly() and spatial_variance(): two uint32 words (an int32 tensor is taken too)."""
+    import torch
+
+    return _optional_out(arg, 2, (torch.uint32, torch.int32), "counts", device)
+
+
+def _stage_kw(arg, who, name, allowed):
+    """The `firefly=` / `spatial=` / `spatial_variance=` keyword of the hosts that take one: None / False -> None (the stage is not run),
+    True -> {} (the defaults), a dict -> the stage's keyword arguments, of `allowed`."""
+    if arg is None or arg is False:
+        return None
+    if arg is True:
+        return {}
+    if isinstance(arg, dict) and not set(arg) - set(allowed):
+        return dict(arg)
+    raise TypeError(f"{who}: {name} must be True or a dict of {', '.join(allowed)}")
+
+
+_FIREFLY_KW = ("rank", "k", "repair", "no_lds")
+_SPATIAL_KW = ("radius", "min_pairs", "tol_depth", "tol_normal", "demodulate", "no_lds")
+
+
 def render(width: int, height: int, samples: int, scene, cam: camera, depth: int = 50, *, flags: int = 0,
            out=None, shard_index: int = 0, shard_count: int = 1, timed: bool = False):
     """Launch the render kernel on torch's current device/stream; asynchronous like queue.submit
@@ -162,36 +249,22 @@ def render_aov(width: int, height: int, samples: int, scene, cam: camera, *, pla
 
 def _filter_call(me, entry, has, stage, fb, out, other_planes, **needed):
     """What denoise() and denoise_variance() (`me`) do before they call `entry`: the device and entry-point checks, the unknown keywords,
-    the frame's shape, the planes in `needed` that must not be None, `out` and the scratch.  Returns the library, the plane checker
-    (tensor or None -> pointer or None), H, W, out, the scratch tensor (the caller keeps it alive across the call) and the stream."""
+    the frame's shape, the planes in `needed` that must not be None, `out` and the scratch.  Returns the library, H, W, out, the scratch
+    tensor (the caller keeps it alive across the call) and the stream."""
     import torch
 
-    if not torch.cuda.is_available():
-        raise RuntimeError(f"path_tracer_amd.{me} needs a HIP device: there is no CPU path in the product")
-    lib = abi.load_library()
-    if not has(lib):
-        raise ImportError(f"{abi.library_path()} predates the {stage} (no {entry} entry point)")
-    unknown = set(other_planes) - set(abi.AOV_PLANES)
-    if unknown:
-        raise TypeError(f"{me}() got unexpected keyword arguments {sorted(unknown)}")
-
-    def plane(t, shape, what):
-        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()):
-            raise ValueError(f"{what} must be a contiguous float32 CUDA tensor of shape {shape}")
-        return C.c_void_p(t.data_ptr()) if t is not None else None
-
-    if fb.dim() != 3 or fb.shape[2] != 3:
-        raise ValueError("fb must be a whole frame [H][W][3] (gather and unshard a multi-GPU frame first)")
+    lib = _stage(me, has, f"the {stage}", f"{entry} entry point")
+    _aov_kwargs_ok(me, other_planes)
+    h, w = _whole_frame(fb)
     for what, t in needed.items():
         if t is None:
             raise ValueError(f"{what} must be a contiguous float32 CUDA tensor shaped like fb")
-    h, w, _ = (int(n) for n in fb.shape)
     if out is None:
         out = torch.empty((h, w, 3), dtype=torch.float32, device=fb.device)
     n = getattr(lib, entry + "_scratch_floats")(w, h)
     if n < 0:
         abi.check(abi.PT_ERR_INVALID_ARG, entry + "_scratch_floats")
-    return lib, plane, h, w, out, torch.empty(n, dtype=torch.float32, device=fb.device), _stream_ptr(torch)
+    return lib, h, w, out, torch.empty(n, dtype=torch.float32, device=fb.device), _stream_ptr(torch)
 
 
 def denoise(fb, *, albedo=None, normal=None, depth=None, iterations: int = abi.PT_DENOISE_DEFAULT_ITERATIONS,
@@ -205,11 +278,11 @@ def denoise(fb, *, albedo=None, normal=None, depth=None, iterations: int = abi.P
     `no_lds`: the A/B switch PT_DENOISE_NO_LDS (every tap from global memory; the same bits).
     Asynchronous on torch's current stream; torch allocates the scratch.  Returns the filtered frame — `out` if given, which may be
     `fb` itself."""
-    lib, plane, h, w, out, scratch, stream = _filter_call("denoise", "pt_denoise", abi.has_denoise, "denoiser", fb, out, other_planes)
+    lib, h, w, out, scratch, stream = _filter_call("denoise", "pt_denoise", abi.has_denoise, "denoiser", fb, out, other_planes)
     p = abi.PtDenoiseParams(C.sizeof(abi.PtDenoiseParams), w, h, int(iterations), float(sigma_color), float(sigma_normal), float(sigma_depth),
                             float(sigma_albedo), (abi.PT_DENOISE_DEMODULATE if demodulate else 0) | (abi.PT_DENOISE_NO_LDS if no_lds else 0), 0)
-    abi.check(lib.pt_denoise(C.byref(p), plane(fb, (h, w, 3), "fb"), plane(albedo, (h, w, 3), "albedo"), plane(normal, (h, w, 3), "normal"),
-                             plane(depth, (h, w), "depth"), plane(out, (h, w, 3), "out"), C.c_void_p(scratch.data_ptr()), stream), "pt_denoise")
+    abi.check(lib.pt_denoise(C.byref(p), _plane(fb, (h, w, 3), "fb"), _plane(albedo, (h, w, 3), "albedo"), _plane(normal, (h, w, 3), "normal"),
+                             _plane(depth, (h, w), "depth"), _plane(out, (h, w, 3), "out"), C.c_void_p(scratch.data_ptr()), stream), "pt_denoise")
     return out
 
 
@@ -224,14 +297,14 @@ def denoise_variance(fb, variance, *, albedo=None, normal=None, depth=None, iter
     in standard deviations (<= 0: guide-only).  `variance_out` (optional, may be `variance`) receives the filtered frame's residual
     variance.  Asynchronous on torch's current stream; torch allocates the scratch.  Returns the filtered frame — `out` if given, which
     may be `fb` itself."""
-    lib, plane, h, w, out, scratch, stream = _filter_call("denoise_variance", "pt_variance_denoise", abi.has_variance_denoise,
-                                                          "variance-guided denoiser", fb, out, other_planes, variance=variance)
+    lib, h, w, out, scratch, stream = _filter_call("denoise_variance", "pt_variance_denoise", abi.has_variance_denoise,
+                                                   "variance-guided denoiser", fb, out, other_planes, variance=variance)
     p = abi.PtVarianceDenoiseParams(C.sizeof(abi.PtVarianceDenoiseParams), w, h, int(iterations), float(sigma_variance), float(sigma_normal),
                                     float(sigma_depth), float(sigma_albedo),
                                     (abi.PT_VDENOISE_DEMODULATE if demodulate else 0) | (abi.PT_VDENOISE_NO_LDS if no_lds else 0), 0)
-    abi.check(lib.pt_variance_denoise(C.byref(p), plane(fb, (h, w, 3), "fb"), plane(variance, (h, w, 3), "variance"),
-                                      plane(albedo, (h, w, 3), "albedo"), plane(normal, (h, w, 3), "normal"), plane(depth, (h, w), "depth"),
-                                      plane(out, (h, w, 3), "out"), plane(variance_out, (h, w, 3), "variance_out"),
+    abi.check(lib.pt_variance_denoise(C.byref(p), _plane(fb, (h, w, 3), "fb"), _plane(variance, (h, w, 3), "variance"),
+                                      _plane(albedo, (h, w, 3), "albedo"), _plane(normal, (h, w, 3), "normal"), _plane(depth, (h, w), "depth"),
+                                      _plane(out, (h, w, 3), "out"), _plane(variance_out, (h, w, 3), "variance_out"),
                                       C.c_void_p(scratch.data_ptr()), stream), "pt_variance_denoise")
     return out
 
@@ -248,53 +321,24 @@ def firefly(fb, variance=None, *, rank: int = abi.PT_FIREFLY_DEFAULT_RANK, k: fl
     the uint32 device tensor {clamped, repaired} appended — nothing is read back: .cpu() it when the numbers are wanted."""
     import torch
 
-    if not torch.cuda.is_available():
-        raise RuntimeError("path_tracer_amd.firefly needs a HIP device: there is no CPU path in the product")
-    lib = abi.load_library()
-    if not abi.has_firefly(lib):
-        raise ImportError(f"{abi.library_path()} predates the firefly stage (no pt_firefly entry point)")
-    if fb is None or fb.dim() != 3 or fb.shape[2] != 3:
-        raise ValueError("fb must be a whole frame [H][W][3] (gather and unshard a multi-GPU frame first)")
-    h, w, _ = (int(n) for n in fb.shape)
+    lib = _stage("firefly", abi.has_firefly, "the firefly stage", "pt_firefly entry point")
+    h, w = _whole_frame(fb)
     if variance is None and variance_out is not None:
         raise ValueError("variance_out needs variance")
     if out is None:
         out = torch.empty((h, w, 3), dtype=torch.float32, device=fb.device)
     if variance is not None and variance_out is None:
         variance_out = torch.empty((h, w, 3), dtype=torch.float32, device=fb.device)
-    for what, t in (("fb", fb), ("variance", variance), ("out", out), ("variance_out", variance_out)):
-        if t is not None:
-            if tuple(t.shape) != (h, w, 3):
-                raise ValueError(f"{what} must have the frame's shape")
-            _frame_ptr(t, what)
-    n = None
-    if counts is True:
-        n = torch.empty(2, dtype=torch.uint32, device=fb.device)
-    elif counts is not None and counts is not False:
-        n = counts
-        if n.numel() != 2 or n.dtype not in (torch.uint32, torch.int32) or not n.is_cuda or not n.is_contiguous():
-            raise ValueError("counts must be a contiguous uint32 (or int32) CUDA tensor of 2 elements")
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    planes = [_plane(t, (h, w, 3), what) for what, t in (("fb", fb), ("variance", variance), ("out", out), ("variance_out", variance_out))]
+    n = _counts(counts, fb.device)
     p = abi.PtFireflyParams(C.sizeof(abi.PtFireflyParams), w, h, int(rank), float(k),
                             (abi.PT_FIREFLY_REPAIR if repair else 0) | (abi.PT_FIREFLY_NO_LDS if no_lds else 0))
-    abi.check(lib.pt_firefly(C.byref(p), ptr(fb), ptr(variance), ptr(out), ptr(variance_out), ptr(n), _stream_ptr(torch)), "pt_firefly")
+    abi.check(lib.pt_firefly(C.byref(p), *planes, C.c_void_p(n.data_ptr()) if n is not None else None, _stream_ptr(torch)), "pt_firefly")
     res = (out,) + ((variance_out,) if variance is not None else ()) + ((n.view(torch.uint32),) if n is not None else ())
     return res[0] if len(res) == 1 else res
 
 
 _firefly = firefly  # (the hosts below take a keyword named `firefly`)
-
-
-def _firefly_kw(firefly_arg, who):
-    """The `firefly=` keyword of the hosts that take it: None / False -> None (the stage is not run), True -> {} (the defaults), a dict ->
-    firefly()'s keyword arguments."""
-    if firefly_arg is None or firefly_arg is False:
-        return None
-    if firefly_arg is True:
-        return {}
-    if isinstance(firefly_arg, dict) and not set(firefly_arg) - {"rank", "k", "repair", "no_lds"}:
-        return dict(firefly_arg)
-    raise TypeError(f"{who}: firefly must be True or a dict of rank, k, repair, no_lds")
 
 
 def spatial_variance(fb, variance=None, *, albedo=None, normal=None, depth=None, id=None, radius: int = abi.PT_SVAR_DEFAULT_RADIUS,
@@ -313,57 +357,24 @@ def spatial_variance(fb, variance=None, *, albedo=None, normal=None, depth=None,
     device tensor {estimated, holes} — nothing is read back: .cpu() it when the numbers are wanted."""
     import torch
 
-    if not torch.cuda.is_available():
-        raise RuntimeError("path_tracer_amd.spatial_variance needs a HIP device: there is no CPU path in the product")
-    lib = abi.load_library()
-    if not abi.has_spatial_variance(lib):
-        raise ImportError(f"{abi.library_path()} predates the spatial variance estimate (no pt_spatial_variance entry point)")
-    unknown = set(other_planes) - set(abi.AOV_PLANES)
-    if unknown:
-        raise TypeError(f"spatial_variance() got unexpected keyword arguments {sorted(unknown)}")
-    if fb is None or fb.dim() != 3 or fb.shape[2] != 3:
-        raise ValueError("fb must be a whole frame [H][W][3] (gather and unshard a multi-GPU frame first)")
-    h, w, _ = (int(n) for n in fb.shape)
+    lib = _stage("spatial_variance", abi.has_spatial_variance, "the spatial variance estimate", "pt_spatial_variance entry point")
+    _aov_kwargs_ok("spatial_variance", other_planes)
+    h, w = _whole_frame(fb)
     if out is None:
         out = torch.empty((h, w, 3), dtype=torch.float32, device=fb.device)
-    for what, t in (("fb", fb), ("variance", variance), ("albedo", albedo), ("normal", normal), ("out", out)):
-        if t is not None:
-            if tuple(t.shape) != (h, w, 3):
-                raise ValueError(f"{what} must have the frame's shape")
-            _frame_ptr(t, what)
-    for what, t, dtype in (("depth", depth, torch.float32), ("id", id, torch.int32)):
-        if t is not None and (tuple(t.shape) != (h, w) or t.dtype != dtype or not t.is_cuda or not t.is_contiguous()):
-            raise ValueError(f"{what} must be a contiguous {dtype} CUDA tensor of shape [H][W]")
-    n = None
-    if counts is True:
-        n = torch.empty(2, dtype=torch.uint32, device=fb.device)
-    elif counts is not None and counts is not False:
-        n = counts
-        if n.numel() != 2 or n.dtype not in (torch.uint32, torch.int32) or not n.is_cuda or not n.is_contiguous():
-            raise ValueError("counts must be a contiguous uint32 (or int32) CUDA tensor of 2 elements")
+    ptr = {what: _plane(t, (h, w, 3), what) for what, t in (("fb", fb), ("variance", variance), ("albedo", albedo), ("normal", normal), ("out", out))}
+    ptr.update(depth=_plane(depth, (h, w), "depth"), id=_plane(id, (h, w), "id", torch.int32))
+    n = _counts(counts, fb.device)
     if demodulate is None:
         demodulate = albedo is not None
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
     p = abi.PtSpatialVarianceParams(C.sizeof(abi.PtSpatialVarianceParams), w, h, int(radius), int(min_pairs), float(tol_depth), float(tol_normal),
                                     (abi.PT_SVAR_DEMODULATE if demodulate else 0) | (abi.PT_SVAR_NO_LDS if no_lds else 0))
-    abi.check(lib.pt_spatial_variance(C.byref(p), ptr(fb), ptr(albedo), ptr(normal), ptr(depth), ptr(id), ptr(variance), ptr(out), ptr(n),
-                                      _stream_ptr(torch)), "pt_spatial_variance")
+    abi.check(lib.pt_spatial_variance(C.byref(p), *(ptr[k] for k in ("fb", "albedo", "normal", "depth", "id", "variance", "out")),
+                                      C.c_void_p(n.data_ptr()) if n is not None else None, _stream_ptr(torch)), "pt_spatial_variance")
     return (out, n.view(torch.uint32)) if n is not None else out
 
 
 _spatial_variance = spatial_variance  # (render_temporal takes a keyword named `spatial_variance`)
-
-
-def _spatial_kw(arg, who, name="spatial"):
-    """The `spatial=` / `spatial_variance=` keyword of the hosts that take it: None / False -> None (the stage is not run), True -> {} (the
-    defaults), a dict -> spatial_variance()'s parameters."""
-    if arg is None or arg is False:
-        return None
-    if arg is True:
-        return {}
-    if isinstance(arg, dict) and not set(arg) - {"radius", "min_pairs", "tol_depth", "tol_normal", "demodulate", "no_lds"}:
-        return dict(arg)
-    raise TypeError(f"{who}: {name} must be True or a dict of radius, min_pairs, tol_depth, tol_normal, demodulate, no_lds")
 
 
 class ImageError:
@@ -435,23 +446,13 @@ def image_error(a, ref, *, rect=None, eps: float = abi.PT_IMAGE_ERROR_DEFAULT_EP
     until a property of the returned ImageError asks for a number."""
     import torch
 
-    if not torch.cuda.is_available():
-        raise RuntimeError("path_tracer_amd.image_error needs a HIP device: there is no CPU path in the product")
-    lib = abi.load_library()
-    if not abi.has_metrics(lib):
-        raise ImportError(f"{abi.library_path()} predates the image error (no pt_image_error entry point)")
+    lib = _stage("image_error", abi.has_metrics, "the image error", "pt_image_error entry point")
     _frame_ptr(a, "a")
     _frame_ptr(ref, "ref")
     if a.shape != ref.shape:
         raise ValueError("a and ref must have the same shape")
     h, w, _ = (int(n) for n in a.shape)
-    plane = None
-    if error_plane is True:
-        plane = torch.empty((h, w), dtype=torch.float32, device=a.device)
-    elif error_plane is not None and error_plane is not False:
-        plane = error_plane
-        if tuple(plane.shape) != (h, w) or plane.dtype != torch.float32 or not plane.is_cuda or not plane.is_contiguous():
-            raise ValueError("error_plane must be a contiguous float32 CUDA tensor of shape [H][W]")
+    plane = _optional_out(error_plane, (h, w), torch.float32, "error_plane", a.device)
     p = abi.PtImageErrorParams()
     lib.pt_image_error_params_init(C.byref(p), w, h)
     if rect is not None:
@@ -549,9 +550,10 @@ def tonemap_rgb8(fb):
     import torch
 
     lib = abi.load_library()
+    src = _frame_ptr(fb)
     h, w, _ = fb.shape
     out = torch.empty((h, w, 3), dtype=torch.uint8, device=fb.device)
-    abi.check(lib.pt_tonemap_rgb8(C.c_void_p(fb.data_ptr()), w, h, C.c_void_p(out.data_ptr()), _stream_ptr(torch)),
+    abi.check(lib.pt_tonemap_rgb8(src, w, h, C.c_void_p(out.data_ptr()), _stream_ptr(torch)),
               "pt_tonemap_rgb8")
     return out
 
@@ -566,33 +568,15 @@ def _display_params(tone, ev_bias, ev_min, ev_max, lo_permille, hi_permille, ada
                                int(hi_permille), float(adapt_up), float(adapt_down), float(white), int(x0), int(y0), int(x1), int(y1), 0)
 
 
-def _frame_ptr(fb, what="fb"):
-    import torch
-
-    if fb is None or fb.dim() != 3 or fb.shape[2] != 3 or fb.dtype != torch.float32 or not fb.is_cuda or not fb.is_contiguous():
-        raise ValueError(f"{what} must be a contiguous float32 CUDA tensor of shape [H][W][3]")
-    return C.c_void_p(fb.data_ptr())
-
-
 def _display_apply(lib, handle, p, fb, out, linear):
     """pt_display_apply -> the uint8 image [H][W][3] (row 0 = top), or (image, linear plane) with `linear`: True allocates the plane, a tensor
     is written (it may be `fb`)."""
     import torch
 
-    h, w, _ = fb.shape
     src = _frame_ptr(fb)
-    if out is None:
-        out = torch.empty((h, w, 3), dtype=torch.uint8, device=fb.device)
-    elif tuple(out.shape) != (h, w, 3) or out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous():
-        raise ValueError("out must be a contiguous uint8 CUDA tensor of shape [H][W][3]")
-    lin = None
-    if linear is True:
-        lin = torch.empty((h, w, 3), dtype=torch.float32, device=fb.device)
-    elif linear is not None and linear is not False:
-        lin = linear
-        if tuple(lin.shape) != (h, w, 3):
-            raise ValueError("linear must have the frame's shape")
-        _frame_ptr(lin, "linear")
+    h, w, _ = fb.shape
+    out = _optional_out(True if out is None else out, (h, w, 3), torch.uint8, "out", fb.device)
+    lin = _optional_out(linear, (h, w, 3), torch.float32, "linear", fb.device)
     abi.check(lib.pt_display_apply(handle, C.byref(p), src, w, h, C.c_void_p(out.data_ptr()), C.c_void_p(lin.data_ptr()) if lin is not None else None,
                                    _stream_ptr(torch)), "pt_display_apply")
     return out if lin is None else (out, lin)
@@ -610,13 +594,7 @@ class Display:
                  ev_max: float = abi.PT_DISPLAY_DEFAULT_EV_MAX, lo_permille: int = abi.PT_DISPLAY_DEFAULT_LO_PERMILLE,
                  hi_permille: int = abi.PT_DISPLAY_DEFAULT_HI_PERMILLE, adapt_up: float = abi.PT_DISPLAY_DEFAULT_ADAPT_UP,
                  adapt_down: float = abi.PT_DISPLAY_DEFAULT_ADAPT_DOWN, white: float = abi.PT_DISPLAY_DEFAULT_WHITE, rect=None):
-        import torch
-
-        if not torch.cuda.is_available():
-            raise RuntimeError("path_tracer_amd.render.Display needs a HIP device: there is no CPU path in the product")
-        self.lib = abi.load_library()
-        if not abi.has_display(self.lib):
-            raise ImportError(f"{abi.library_path()} predates the display stage (no pt_display_* entry points)")
+        self.lib = _stage("render.Display", abi.has_display, "the display stage", "pt_display_* entry points")
         self.params = _display_params(tone, ev_bias, ev_min, ev_max, lo_permille, hi_permille, adapt_up, adapt_down, white, rect)
         self.handle = C.c_void_p()
         abi.check(self.lib.pt_display_create(C.byref(self.handle)), "pt_display_create")
@@ -630,8 +608,9 @@ class Display:
         """Histogram, solve and adaptation over the frame `fb`."""
         import torch
 
+        src = _frame_ptr(fb)
         h, w, _ = fb.shape
-        abi.check(self.lib.pt_display_meter(self.handle, C.byref(self.params), _frame_ptr(fb), w, h, _stream_ptr(torch)), "pt_display_meter")
+        abi.check(self.lib.pt_display_meter(self.handle, C.byref(self.params), src, w, h, _stream_ptr(torch)), "pt_display_meter")
         return self
 
     def apply(self, fb, out=None, linear=False):
@@ -802,7 +781,7 @@ class Accumulator:
         firefly()'s rank, k, repair): the firefly stage runs on the resolved frame before the filter."""
         if self.shard_count != 1:
             raise ValueError("Accumulator.denoise: whole frames only (the filter reads neighbours: gather and unshard first)")
-        fkw = _firefly_kw(firefly, "Accumulator.denoise")
+        fkw = _stage_kw(firefly, "Accumulator.denoise", "firefly", _FIREFLY_KW)
         guides = render_aov(self.width, self.height, aov_spp, self._ds, self.cam, planes=("albedo", "normal", "depth"))
         if fkw is None:
             return denoise(self.resolve(), **guides, **kw)
@@ -833,8 +812,8 @@ class Accumulator:
         this method works on one."""
         if self.shard_count != 1:
             raise ValueError("Accumulator.denoise_variance: whole frames only (the filter reads neighbours: gather and unshard first)")
-        fkw = _firefly_kw(firefly, "Accumulator.denoise_variance")
-        skw = _spatial_kw(spatial, "Accumulator.denoise_variance")
+        fkw = _stage_kw(firefly, "Accumulator.denoise_variance", "firefly", _FIREFLY_KW)
+        skw = _stage_kw(spatial, "Accumulator.denoise_variance", "spatial", _SPATIAL_KW)
         if skw is not None:
             guides = render_aov(self.width, self.height, aov_spp, self._ds, self.cam, planes=("albedo", "normal", "depth", "id"))
             color, var = self.resolve(), self.variance() if self.adaptive else None
@@ -966,13 +945,7 @@ class TemporalAccumulator:
     torch's current stream; pushes of one TemporalAccumulator must be stream-ordered."""
 
     def __init__(self, width: int, height: int):
-        import torch
-
-        if not torch.cuda.is_available():
-            raise RuntimeError("path_tracer_amd.render.TemporalAccumulator needs a HIP device: there is no CPU path in the product")
-        self.lib = abi.load_library()
-        if not abi.has_temporal(self.lib):
-            raise ImportError(f"{abi.library_path()} predates temporal reprojection (no pt_temporal_* entry points)")
+        self.lib = _stage("render.TemporalAccumulator", abi.has_temporal, "temporal reprojection", "pt_temporal_* entry points")
         self.width, self.height = int(width), int(height)
         self.handle = C.c_void_p()
         abi.check(self.lib.pt_temporal_create(self.width, self.height, C.byref(self.handle)), "pt_temporal_create")
@@ -991,16 +964,8 @@ class TemporalAccumulator:
         `fb`), the variance of the accumulated mean (+inf where there is no estimate) and the history length [H][W]."""
         import torch
 
-        unknown = set(other_planes) - set(abi.AOV_PLANES)
-        if unknown:
-            raise TypeError(f"push() got unexpected keyword arguments {sorted(unknown)}")
+        _aov_kwargs_ok("push", other_planes)
         h, w = self.height, self.width
-
-        def plane(t, shape, what, dtype=torch.float32):
-            if t is not None and (tuple(t.shape) != shape or t.dtype != dtype or not t.is_cuda or not t.is_contiguous()):
-                raise ValueError(f"{what} must be a contiguous {dtype} CUDA tensor of shape {shape}")
-            return C.c_void_p(t.data_ptr()) if t is not None else None
-
         if fb is None or depth is None:
             raise ValueError("push() needs the frame and its depth plane")
         if out is None:
@@ -1008,9 +973,9 @@ class TemporalAccumulator:
         var_out = torch.empty((h, w, 3), dtype=torch.float32, device=fb.device)
         hist = torch.empty((h, w), dtype=torch.float32, device=fb.device)
         p = abi.PtTemporalParams(C.sizeof(abi.PtTemporalParams), float(alpha), float(tol_depth), float(tol_normal), 0)
-        abi.check(self.lib.pt_temporal_push(self.handle, C.byref(p), C.byref(cam.c), plane(fb, (h, w, 3), "fb"), plane(depth, (h, w), "depth"),
-                                            plane(normal, (h, w, 3), "normal"), plane(id, (h, w), "id", torch.int32),
-                                            plane(variance, (h, w, 3), "variance"), plane(out, (h, w, 3), "out"),
+        abi.check(self.lib.pt_temporal_push(self.handle, C.byref(p), C.byref(cam.c), _plane(fb, (h, w, 3), "fb"), _plane(depth, (h, w), "depth"),
+                                            _plane(normal, (h, w, 3), "normal"), _plane(id, (h, w), "id", torch.int32),
+                                            _plane(variance, (h, w, 3), "variance"), _plane(out, (h, w, 3), "out"),
                                             C.c_void_p(var_out.data_ptr()), C.c_void_p(hist.data_ptr()), _stream_ptr(torch)), "pt_temporal_push")
         return out, var_out, hist
 
@@ -1054,8 +1019,8 @@ def render_temporal(width: int, height: int, spp: int, scene, cams, depth: int =
 
     if spp <= 0:
         raise ValueError("spp must be > 0")
-    fkw = _firefly_kw(firefly, "render_temporal")
-    skw = _spatial_kw(spatial_variance, "render_temporal", "spatial_variance")
+    fkw = _stage_kw(firefly, "render_temporal", "firefly", _FIREFLY_KW)
+    skw = _stage_kw(spatial_variance, "render_temporal", "spatial_variance", _SPATIAL_KW)
     ds = _as_device_scene(scene, cache_key=("cuda", torch.cuda.current_device(), torch.cuda.current_stream().cuda_stream))
     acc, hist = None, TemporalAccumulator(width, height)
     try:
