@@ -1061,6 +1061,13 @@ int pt_debug_last_pool_word(const PtScene* scene, int32_t* out);
  * runs).  Scenes that are not rects and boxes under lambertian / light materials never read a plan: out[0] = 0 without asking further. */
 int pt_debug_pool_plan(const PtSceneDesc* desc, const PtTuning* tuning, const PtRenderParams* params, int32_t out[12]);
 
+/* The SHADE TABLE of the flattened scene (csrc/pt_flatten.hpp: Flat::shade), host-only: one 16-byte record per hittable of a small scene
+ * of rects and boxes under lambertian / light materials over solid textures — (the material's colour, one word: bits 0-1 a rect's axis,
+ * bit 2 box, bits 4-6 the material kind, bits 8-30 the hittable's index) — from which the kernels of such scenes shade a hit.  The
+ * record of the hittable whose records start at blob offset `off` (16-byte records) is record (off >> 1) - *base; records no hittable
+ * maps to are zero.  *n_f4 = the table's records (0: the scene has none); table_out may be NULL to query.  For tests.                 */
+int pt_debug_shade_table(const PtSceneDesc* desc, const PtTuning* tuning, float* table_out, int64_t table_cap_f4, int32_t* n_f4, int32_t* base);
+
 /* Which aov_kernel the LAST pt_render_aov of this scene launched: out[0] = its sphere-grid walk (1 wave-synchronous, 2 through the LDS pair
  * queue; scenes without a sphere grid: 1), out[1] = 1 if u,v are tracked through the scan; both 0 before the first pass.  For tests.  */
 int pt_debug_last_aov(const PtScene* scene, int32_t out[2]);

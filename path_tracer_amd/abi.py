@@ -292,6 +292,8 @@ SIGNATURES = {
     "pt_debug_last_pool_plan": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "pt_debug_last_pool_word": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "pt_debug_pool_plan": (C.c_int, [C.POINTER(PtSceneDesc), C.POINTER(PtTuning), C.POINTER(PtRenderParams), C.POINTER(C.c_int32)]),
+    # the shade table of a small rect / box-only scene, host-only (csrc/pt_flatten.hpp: Flat::shade)
+    "pt_debug_shade_table": (C.c_int, [C.POINTER(PtSceneDesc), C.POINTER(PtTuning), _FP, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }
 
 # name -> (restype, argtypes): every entry point include/pt_post.h declares — the image-space stages added since pt_render.h's table was

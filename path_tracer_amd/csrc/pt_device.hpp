@@ -1403,7 +1403,8 @@ __device__ __forceinline__ unsigned long long slab_chunk_pass(P xrecs, P slrecs,
       int hit_base = as_i(X0.w);
       // (a later holder that is a SPHERE — an absorbed run's, tested through an earlier run's lists — is strict itself: in list order this
       // hittable takes an equal t first and the sphere then fails t < max, so the candidate keeps the non-strict comparison)
-      const bool holder_later = ((h.hit >= 0) & (hit_off(h.hit) > hit_off(hit_base))) && hit_kind(h.hit) != DK_SPHERE;
+      // (FORM 2 is the form of rect / box-only kernels — slab_pool: LDS_FORM —, whose holder is never a sphere: the test is not compiled in)
+      const bool holder_later = ((h.hit >= 0) & (hit_off(h.hit) > hit_off(hit_base))) && (FORM == 2 || hit_kind(h.hit) != DK_SPHERE);
       float cl = holder_later ? as_f(as_i(h.closest) - 1) : h.closest;
       // the trip writes the hit in place; the holder's id is the copy (the compiler copies the other way round, and back after the trip)
       int holder;
@@ -2736,6 +2737,34 @@ __device__ __forceinline__ Rec resolve_hit(P blob, int hit, const Ray& r, float 
   return rec;
 }
 
+// The hit record of a rect / box hit and its material's two words from the scene's SHADE TABLE (pt_flatten.hpp: Flat::shade): ONE ds_read_b128
+// where resolve_hit<RECTBOX> reads R0, R1 of the hittable and shade() then M0, M1 of the material it names — two dependent round trips for
+// the material index, the rect's axis, the material kind and the colour.  `image`: the LDS image [blob][materials][shade table]; the
+// record of the hittable at record offset `off` is image[shade_k + (off >> 1)] — the offset field is the hit word's low bits: one AND,
+// one shift-and-add on the table's byte address.  The record's word: bits 0-1 a rect's axis (0 for a box), bits 4-6 the material kind.
+// The axis is the rect's own — its hit word carries side 0 — or the one of the side a box was hit on — its record carries axis 0: an OR.
+// M0, M1: (kind, -, -, -) and (colour, -) as shade_with reads them for a lambertian or a light over a solid texture.
+__device__ __forceinline__ Rec shade_record(lds_f4p image, int shade_k, int hit, const Ray& r, float t, f4& M0, f4& M1) {
+  Rec rec;
+  rec.p = r.o + t * r.d; // ray::at ray.hpp:21
+  unsigned int at = (unsigned int)(uintptr_t)(image + shade_k) + (((unsigned int)hit & (unsigned int)(PT_HIT_OFF_MASK & ~1)) << 3);
+#ifdef __HIP_DEVICE_COMPILE__
+  // (said as the two instructions it is: left to itself the compiler shifts first, masks the shifted word and adds the base — three)
+  asm("v_lshl_add_u32 %0, %1, 3, %2" : "=v"(at) : "v"((unsigned int)hit & (unsigned int)(PT_HIT_OFF_MASK & ~1)), "s"((unsigned int)(uintptr_t)(image + shade_k)));
+#endif
+  const f4 S = *(lds_f4p)(uintptr_t)at;
+  const int w = as_i(S.w);
+  const int axis = (w & 3) | (hit_side(hit) >> 1);
+  rec.mat = 0; // (the record stands for the material)
+  rec.hittable = (int)((unsigned int)w >> 8);
+  M0 = f4{as_f((w >> 4) & 7), 0.0f, 0.0f, 0.0f};
+  M1 = S;
+  // (the products with the normal's zeros stay, as in resolve_hit: dot(d, n) is the reference's, NaN for an infinite d included)
+  const V3 n = mk(axis == 0 || axis == 1 ? 0.0f : 1.0f, axis == 1 ? 1.0f : 0.0f, axis == 0 ? 1.0f : 0.0f);
+  set_face_normal(rec, r, n);
+  return rec;
+}
+
 // u,v of the final hit, from the hit itself (sphere.hpp:88-89 mercator of the face normal; rectangle.hpp:41-42 and its
 // xz/yz twins; box = its hit side).  The reference fills them on EVERY accepted candidate; for sphere, rect and box hits
 // they are a pure function of (ray, primitive, t), so the value of the final hit is the same computed once here.
@@ -2900,11 +2929,11 @@ __device__ __forceinline__ V3 sky_color(const Ray& r, V3 att, bool regular = fal
 // One iteration of the bounce loop render.hpp:58-89 after hit_world: emitted + scatter.
 // Returns true if the path continues (ray/att updated); false if it ended with `out`.
 // `uv(u, v)` yields the hit's texture coordinates; it is called before the ray is overwritten.
+// shade_with: the material's first two words come with the call (shade: read from the table; lane_shade's SHADE_REC form: from the hit's shade
+// record); M: the material's record, for the words a texture other than a solid one reads.
 template <int MATS = MATS_ALL, typename PM, typename UV>
-__device__ __forceinline__ bool shade(PM mats, const uint8_t* __restrict__ atlas, const Rec& rec,
-                                      UV uv, Ray& ray, V3& att, uint32_t& rng, V3& out, bool regular = false) {
-  PM M = mats + rec.mat * SZ_MATERIAL;
-  f4 M0 = M[0], M1 = M[1];
+__device__ __forceinline__ bool shade_with(f4 M0, f4 M1, PM M, const uint8_t* __restrict__ atlas, const Rec& rec,
+                                           UV uv, Ray& ray, V3& att, uint32_t& rng, V3& out, bool regular = false) {
   const int mk_ = as_i(M0.x);
   constexpr bool LAMB = MATS & 1, METAL = (MATS >> 1) & 1, GLASS = (MATS >> 2) & 1, LIGHT = (MATS >> 3) & 1, ISO = (MATS >> 4) & 1;
   // A wave holds lanes of every material, and each `if` below runs once for the lanes that take it.  What several materials
@@ -2918,6 +2947,10 @@ __device__ __forceinline__ bool shade(PM mats, const uint8_t* __restrict__ atlas
   if constexpr (METAL || ISO) { if (mk_ == 1 || mk_ >= 4) ball = rng_in_unit_ball(rng); }
   if constexpr (!(MATS & 0x100)) tv = xyz(M1); // solid textures only: every material's colour slot IS its texture value
   else if (mk_ == 0 || mk_ >= 3) tv = texture_value<MATS>(M0, M1, M[2], M[3], rec.p, uv, atlas);
+  // (lambertian + light over solid textures: the light's `out` is written for EVERY lane, ahead of the switch.  A path that continues leaves
+  // `out` to no reader — the callers read it only where the path ended —, and written under the light's lanes alone the compiler restores the
+  // incoming value for the lambertian's: three copies on the hot path of the bounce)
+  if constexpr (LAMB && LIGHT && !(METAL || GLASS || ISO) && !(MATS & 0x100)) out = tv;
   if (LAMB && (mk_ == 0 || !(METAL || GLASS || LIGHT || ISO))) { // lambertian material.hpp:18-28
     V3 dir = rec.normal + rng_unit_vec(rng);
     ray.o = rec.p; ray.d = dir;
@@ -2958,6 +2991,14 @@ __device__ __forceinline__ bool shade(PM mats, const uint8_t* __restrict__ atlas
   ray.o = rec.p; ray.d = ball;
   att = att * tv;
   return true;
+}
+
+template <int MATS = MATS_ALL, typename PM, typename UV>
+__device__ __forceinline__ bool shade(PM mats, const uint8_t* __restrict__ atlas, const Rec& rec,
+                                      UV uv, Ray& ray, V3& att, uint32_t& rng, V3& out, bool regular = false) {
+  PM M = mats + rec.mat * SZ_MATERIAL;
+  const f4 M0 = M[0], M1 = M[1];
+  return shade_with<MATS>(M0, M1, M, atlas, rec, uv, ray, att, rng, out, regular);
 }
 
 } // namespace ptd

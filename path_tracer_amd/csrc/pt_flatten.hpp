@@ -51,6 +51,10 @@ struct Flat {
   std::vector<F4> blob; // [n_runs run headers][records; a sphere run is preceded by its offset lists + aux F4]
   std::vector<F4> mats; // 4 F4 per material, texture inlined
   PoolLayout pool;      // tables of the triangle pools (pt_tripool.hpp): a buffer of their own, addressed by 32-bit F4 offsets from the pools' headers
+  // SHADE TABLE of a small rect / box-only scene (flatten_layout): one F4 per hittable with everything the shading of a hit reads; it rides
+  // behind the materials.  The record of the hittable whose record offset is `off` is shade[(off >> 1) - shade_base].  Empty: none.
+  std::vector<F4> shade;
+  int32_t shade_base = 0;
   int32_t n_runs = 0;
   bool has_image = false;
   bool has_medium = false;
@@ -86,6 +90,8 @@ inline int device_kind(const PtHittable& h) { // a Badouel-strategy triangle is 
   if (h.kind == PT_HIT_TRIANGLE && h.strategy == PT_TRI_BADOUEL) return DK_TRI_B;
   return device_kind(h.kind);
 }
+
+constexpr int kShadeMaxHittables = 512; // 512 rect / box records are 16 KB: pt_render.hip's kMaxLdsWithMaterials, beyond which no kernel reads a shade table
 
 inline int record_size(int dk) {
   switch (dk) { case DK_SPHERE: return 3; case DK_RECT: return 2; case DK_TRI: case DK_TRI_B: return 3; case DK_BOX: return 2; default: return 4; }
@@ -396,6 +402,12 @@ inline int flatten_layout(const PtSceneDesc* sc, Flat& out, std::string& err, bo
     }
     out.mats.push_back(M0); out.mats.push_back(M1); out.mats.push_back(M2); out.mats.push_back(M3);
   }
+  // (every material a lambertian or a light over a solid texture: the scenes of the MATS_LAMB_LIGHT_SOLID kernels — the shade table below)
+  bool mats_simple = sc->n_materials > 0;
+  for (int i = 0; i < sc->n_materials && mats_simple; i++) {
+    const PtMaterial& m = sc->materials[i];
+    if ((m.kind != PT_MAT_LAMBERTIAN && m.kind != PT_MAT_LIGHTSOURCE) || sc->textures[m.texture].kind != PT_TEX_SOLID) mats_simple = false;
+  }
   // runs: maximal stretches of one device kind, in list order (traversal order is semantics:
   // constant_medium draws RNG against the current closest hit, ties resolve by position)
   struct Run { int kind, first, count; };
@@ -430,6 +442,21 @@ inline int flatten_layout(const PtSceneDesc* sc, Flat& out, std::string& err, bo
     }
   }
   out.n_runs = (int32_t)runs.size();
+  // SHADE TABLE: one F4 per hittable — (the material's colour slot M1.xyz, kind word) — so that a kernel shades a hit from ONE record
+  // instead of two of the hittable's and two of the material's (pt_device.hpp: shade_record).  Written for the scenes of the kernels that
+  // read it: every hittable a rect or a box, every material a lambertian or a light over a solid texture (the colour slot is then both
+  // the lambertian's attenuation and the light's emission), and few enough of them that materials can ride in the LDS image at all
+  // (kShadeMaxHittables records alone fill it).  Indexed by the hit word's own offset field: every rect / box record is 2 F4 and each
+  // run puts one aux F4 in front of its records — a pool's tables lie in front of run 0 —, so hittable g, in run k, lies at
+  // off0 + 2 g + k and off >> 1 = ((off0 + k) >> 1) + g is strictly increasing along the list: record (off >> 1) - (off0 >> 1) of the
+  // table, n + (runs >> 1) records in all (the gaps a run's odd shift leaves stay zero).  Whichever way a hit was found — the pool's
+  // trip, a run's scan — its word names its record.  The kind word: bits 0-1 a rect's axis (0 for a box: its axis is the hit side's),
+  // bit 2 box, bits 4-6 the material kind, bits 8-30 the hittable's index.  Not in the blob, which is what it was.
+  {
+    bool rectbox = sc->n_hittables > 0 && sc->n_hittables <= kShadeMaxHittables;
+    for (const Run& r : runs) rectbox = rectbox && (r.kind == DK_RECT || r.kind == DK_BOX);
+    if (rectbox && mats_simple) out.shade.assign((size_t)sc->n_hittables + (runs.size() >> 1), F4{0, 0, 0, 0});
+  }
   std::vector<F4>& b = out.blob;
   b.resize(runs.size());
   size_t pool_at = 0, pool_x = 0;  // the current slab pool: where its table / its exact entries start, its first hittable, its entries
@@ -579,6 +606,16 @@ inline int flatten_layout(const PtSceneDesc* sc, Flat& out, std::string& err, bo
       const float* f = h.f;
       if (pool_n > 0 && i >= pool_first && i < pool_first + pool_n && (run.kind == DK_BOX || run.kind == DK_RECT))
         b[pool_x + 2 * (size_t)(i - pool_first)].w = as_f((int32_t)((run.kind << kHitKindShift) | (int32_t)b.size())); // hit_pack(kind, 0, offset)
+      if (!out.shade.empty()) {
+        if (i == 0) out.shade_base = (int32_t)(b.size() >> 1); // (the list's first record: off0)
+        const PtMaterial& m = sc->materials[h.material];
+        const float* col = sc->textures[m.texture].color0;
+        const int axis = h.kind == PT_HIT_XZ_RECT ? 1 : h.kind == PT_HIT_YZ_RECT ? 2 : 0;
+        const int32_t word = axis | (h.kind == PT_HIT_BOX ? 4 : 0) | (m.kind << 4) | (i << 8);
+        const size_t at = (b.size() >> 1) - (size_t)out.shade_base;
+        if (at >= out.shade.size()) { err = "shade table: a record lies outside it"; return PT_ERR_BAD_SCENE; } // (cannot happen: the bound above)
+        out.shade[at] = {col[0], col[1], col[2], as_f(word)};
+      }
       switch (h.kind) {
         case PT_HIT_SPHERE: put_sphere(b, f, h.material, i); break;
         case PT_HIT_XY_RECT: case PT_HIT_XZ_RECT: case PT_HIT_YZ_RECT: {

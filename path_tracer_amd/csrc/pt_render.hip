@@ -107,7 +107,10 @@ struct KArgs {
   const f4* pool = nullptr;    // tables of the triangle pools (pt_flatten.hpp: put_tri_pool); NULL when the scene has none
   const uint8_t* atlas = nullptr;
   float* fb = nullptr;
-  int n_runs = 0, blob_f4 = 0, mats_f4 = 0;
+  int n_runs = 0, blob_f4 = 0, mats_f4 = 0; // (mats_f4: the materials AND the shade table behind them — what an LDS image stages behind the blob)
+  // the shade table of a small rect / box-only scene (pt_flatten.hpp: Flat::shade; pt_device.hpp: shade_record): the hittable at record offset `off` has
+  // record shade_k + (off >> 1) of the image [blob][materials][shade table].  0: the scene has none (no kernel that reads it is chosen then)
+  int shade_k = 0;
   int width = 0, height = 0, samples = 0, depth = 0;
   float inv_w = 0.0f, inv_h = 0.0f; // RN(1 / (float)width), RN(1 / (float)height): camera_ray
   int pinhole = 0;    // cam_is_pinhole(cam): camera_ray skips the lens arithmetic
@@ -162,8 +165,8 @@ static_assert(std::is_trivially_copyable<KArgs>::value, "KArgs is copied into th
 // tied to a tile: a lane that has finished its pixel pulls the next one from a per-launch queue, so every lane
 // of the chip stays busy until the frame's pixels run out.
 // The part of a lane's state that is touched only when a sample or a pixel ends — the radiance sum, the sample count,
-// which pixel it is — lives either in registers or, for small scenes, in per-thread LDS slots (~10 LDS instructions per
-// finished sample): 8 registers less pressure inside the traversal.  It would even fit 8 waves per SIMD (64 VGPRs, no
+// which pixel it is — lives either in registers or, for small scenes, in per-thread LDS slots (three LDS instructions per
+// finished sample: Cold<true>): 8 registers less pressure inside the traversal.  It would even fit 8 waves per SIMD (64 VGPRs, no
 // spill), but that is slower than 7 (-5 % vs +2 % on the headline scene; PT_MIN_WAVES_CL).
 typedef __attribute__((address_space(3))) float* lds_fp;
 constexpr int kColdSlots = 8; // dwords per thread
@@ -182,30 +185,50 @@ template <> struct Cold<false> {
   __device__ __forceinline__ int get_pix() const { return pix; }
   __device__ __forceinline__ int get_x() const { return x; }
   __device__ __forceinline__ int get_y() const { return y; }
+  __device__ __forceinline__ void get_xy(int& x_, int& y_) const { x_ = x; y_ = y; }
   __device__ __forceinline__ unsigned int get_iters() const { return iters; }
 };
+// Two 16-byte records per thread: A = (acc.x, acc.y, acc.z, s) at p[0], B = (x, y, pix, iters) at p[kBlock].  A finished sample is ONE
+// ds_read_b128, three adds and an increment, ONE ds_write_b128 (field by field, strided kBlock dwords apart, it was four dword reads and four
+// dword writes); a new sample reads (x, y) with one ds_read_b64 — they lead B so that the pair is 8-byte aligned.  Thread t's records lie at
+// 16 t: each 16-lane group of a b128 access covers 256 contiguous bytes, every bank once.
+typedef __attribute__((address_space(3))) f4* lds_rec_p;
+typedef int i2v __attribute__((ext_vector_type(2)));
 template <> struct Cold<true> {
-  lds_fp p; // this thread's slots: field k at p[k * kBlock]
-  __device__ __forceinline__ void init(lds_fp base) { p = base + threadIdx.x; }
-  __device__ __forceinline__ void begin(int pix_, int x_, int y_, int s0 = 0) {
-    p[0] = 0.0f; p[kBlock] = 0.0f; p[2 * kBlock] = 0.0f;
-    p[3 * kBlock] = __int_as_float(s0); p[4 * kBlock] = __int_as_float(pix_); p[5 * kBlock] = __int_as_float(x_);
-    p[6 * kBlock] = __int_as_float(y_); p[7 * kBlock] = __int_as_float(0);
+  lds_rec_p p; // this thread's records: A at p[0], B at p[kBlock]
+  __device__ __forceinline__ lds_fp a_word(int k) const { return (lds_fp)p + k; }
+  __device__ __forceinline__ lds_fp b_word(int k) const { return (lds_fp)(p + kBlock) + k; }
+  __device__ __forceinline__ void init(lds_fp base) { p = (lds_rec_p)base + threadIdx.x; }
+  // (the zeros as one opaque 64-bit pair: a constant quad is hoisted out of the loop and held across the traversal — four of its 72 registers —,
+  // and a pair is one v_mov_b64 to make and one to copy where four dwords are four moves)
+  __device__ __forceinline__ void begin(int pix_, int x_, int y_) {
+    unsigned long long z = 0;
+#ifdef __HIP_DEVICE_COMPILE__
+    asm volatile("" : "+v"(z));
+#endif
+    const float zl = __int_as_float((int)(unsigned int)z), zh = __int_as_float((int)(unsigned int)(z >> 32));
+    p[0] = f4{zl, zh, zl, zh};
+    p[kBlock] = f4{__int_as_float(x_), __int_as_float(y_), __int_as_float(pix_), zh};
   }
-  __device__ __forceinline__ void resume(V3 acc_, int s0) { p[0] = acc_.x; p[kBlock] = acc_.y; p[2 * kBlock] = acc_.z; p[3 * kBlock] = __int_as_float(s0); }
+  __device__ __forceinline__ void begin(int pix_, int x_, int y_, int s0) {
+    p[0] = f4{0.0f, 0.0f, 0.0f, __int_as_float(s0)};
+    p[kBlock] = f4{__int_as_float(x_), __int_as_float(y_), __int_as_float(pix_), __int_as_float(0)};
+  }
+  __device__ __forceinline__ void resume(V3 acc_, int s0) { p[0] = f4{acc_.x, acc_.y, acc_.z, __int_as_float(s0)}; }
   __device__ __forceinline__ int add_sample(V3 o) {
-    p[0] = p[0] + o.x; p[kBlock] = p[kBlock] + o.y; p[2 * kBlock] = p[2 * kBlock] + o.z;
-    const int s = __float_as_int(p[3 * kBlock]) + 1;
-    p[3 * kBlock] = __int_as_float(s);
+    f4 r = p[0];
+    const int s = __float_as_int(r.w) + 1;
+    p[0] = f4{r.x + o.x, r.y + o.y, r.z + o.z, __int_as_float(s)};
     return s;
   }
-  __device__ __forceinline__ void count_ray() { p[7 * kBlock] = __int_as_float(__float_as_int(p[7 * kBlock]) + 1); }
-  __device__ __forceinline__ V3 get_acc() const { return mk(p[0], p[kBlock], p[2 * kBlock]); }
-  __device__ __forceinline__ int get_s() const { return __float_as_int(p[3 * kBlock]); }
-  __device__ __forceinline__ int get_pix() const { return __float_as_int(p[4 * kBlock]); }
-  __device__ __forceinline__ int get_x() const { return __float_as_int(p[5 * kBlock]); }
-  __device__ __forceinline__ int get_y() const { return __float_as_int(p[6 * kBlock]); }
-  __device__ __forceinline__ unsigned int get_iters() const { return (unsigned int)__float_as_int(p[7 * kBlock]); }
+  __device__ __forceinline__ void count_ray() { *b_word(3) = __int_as_float(__float_as_int(*b_word(3)) + 1); }
+  __device__ __forceinline__ V3 get_acc() const { const f4 r = p[0]; return mk(r.x, r.y, r.z); }
+  __device__ __forceinline__ int get_s() const { return __float_as_int(*a_word(3)); }
+  __device__ __forceinline__ int get_pix() const { return __float_as_int(*b_word(2)); }
+  __device__ __forceinline__ int get_x() const { return __float_as_int(*b_word(0)); }
+  __device__ __forceinline__ int get_y() const { return __float_as_int(*b_word(1)); }
+  __device__ __forceinline__ void get_xy(int& x, int& y) const { const i2v v = *(const __attribute__((address_space(3))) i2v*)(p + kBlock); x = v.x; y = v.y; }
+  __device__ __forceinline__ unsigned int get_iters() const { return (unsigned int)__float_as_int(*b_word(3)); }
 };
 
 template <bool CL>
@@ -452,7 +475,9 @@ __device__ __forceinline__ void lane_regenerate(Lane& L, const KArgs& a) {
 #endif
     // (the frame's size as floats, converted once on the host: set_frame.  The pixel's x and y stay integers in the cold state: its eight
     // slots are taken, and lane_store needs the integers for frames wider than 2^24, where the float does not give them back)
-    L.ray = camera_ray(cam, (float)L.cold.get_x(), (float)L.cold.get_y(), k.width_f, k.height_f, k.inv_w, k.inv_h, L.rng, k.pinhole != 0);
+    int px, py;
+    L.cold.get_xy(px, py);
+    L.ray = camera_ray(cam, (float)px, (float)py, k.width_f, k.height_f, k.inv_w, k.inv_h, L.rng, k.pinhole != 0);
     L.att = mk(1.0f, 1.0f, 1.0f);
     L.b = 0;
     L.need_new = false;
@@ -491,18 +516,29 @@ struct HitUv {
 // misses — a closed scene — the sky's code ran for nothing: ~17 issue slots of an iteration's ~900 when every live ray is regular, ~30 on
 // the general path.  The other kernel families keep the sky inside the miss branch: their iterations are several
 // times as long, and the cooperative kernels and irregular waves would pay the general path.
+// SHADE_REC (kernels of rect / box-only scenes with lambertian + light materials whose records AND materials are in LDS — the headline kernel):
+// the hit is shaded from its ONE shade record (pt_device.hpp: shade_record) — every scene these kernels are chosen for has the table (choose_variant)
+// — instead of two records of the hittable and two of the material in two dependent round trips.
 template <int UV, bool FAST = false, int MATS = MATS_ALL, bool SKY_FIRST = false, typename Lane, typename PB, typename PM>
 __device__ __forceinline__ void lane_shade(Lane& L, const KArgs& a, const HitState& h, PB recs, PM mats, bool regular = false) {
+  constexpr bool SHADE_REC = !FAST && MATS == (MATS_LAMB_LIGHT_SOLID | MATS_RECTBOX_ONLY) && __is_same(PB, lds_f4p) && __is_same(PM, lds_f4p);
   if (!L.live) return;
   if (a.cost) L.cold.count_ray(); // cost-probe pass (wave-uniform)
   V3 out = mk(0.0f, 0.0f, 0.0f);
   bool cont = false;
   auto hit_branch = [&]() {
+    if constexpr (SHADE_REC) {
+      f4 M0, M1;
+      const Rec rec = shade_record(recs, a.shade_k, h.hit, L.ray, h.closest, M0, M1); // per-lane gather of the one shade record of what was hit
+      const HitUv<UV, PB> uv{recs, h, L.ray, rec};
+      cont = shade_with<(MATS & 0x1ff)>(M0, M1, mats, a.atlas, rec, uv, L.ray, L.att, L.rng, out, regular);
+    } else {
     Rec rec = resolve_hit<(MATS & MATS_RECTBOX_ONLY) != 0>(recs, h.hit, L.ray, h.closest); // per-lane gather of the one record that was hit
     // UV_TRACKED kernels carried u,v through the scan (stale values included); UV_WINNER derives them from the final hit
     // when an image texture asks; UV_NONE: the scene has no image texture, nothing reads them
     const HitUv<UV, PB> uv{recs, h, L.ray, rec};
     cont = shade<(MATS & 0x1ff)>(mats, a.atlas, rec, uv, L.ray, L.att, L.rng, out, regular);
+    }
     if (cont && ++L.b >= a.depth) { // bounce loop exhausted: black (render.hpp:91)
       out = mk(0.0f, 0.0f, 0.0f);
       cont = false;
@@ -564,7 +600,7 @@ void render_kernel(KArgs a) {
   static_assert(!CL || BLOCK == kBlock, "the LDS-resident cold lane state is laid out for kBlock threads");
   static_assert(BLOCK % 64 == 0 && BLOCK / 64 <= PT_MAX_WAVES_PER_BLOCK, "per-wave LDS arrays are sized for PT_MAX_WAVES_PER_BLOCK waves");
   static_assert(!TRIPOOL || BLOCK == kBlock, "the triangle pool's per-wave LDS arrays are sized for kBlock threads");
-  __shared__ float cold_slots[CL ? kColdSlots * kBlock : 1];
+  __shared__ __attribute__((aligned(16))) float cold_slots[CL ? kColdSlots * kBlock : 1];
   extern __shared__ f4 smem[];
   if (LDS) {
     const int n = a.blob_f4 + (MLDS ? a.mats_f4 : 0); // a.mats == a.blob + a.blob_f4 (one device buffer)
@@ -2207,6 +2243,7 @@ struct PtScene {
   size_t pool_bytes = 0;
   DevBuf<uint8_t> atlas;
   int n_runs = 0, blob_f4 = 0, mats_f4 = 0;
+  int shade_f4 = 0, shade_base = 0; // the one pool's shade table (pt_flatten.hpp: Flat::shade): its records ride behind the materials, on the device and in the LDS image
   bool has_image = false;
   bool track_uv = false; // an image texture sits on a triangle or a medium: the stale u,v such hits inherit must be tracked
   bool fast_ok = false;
@@ -2347,8 +2384,13 @@ Variant choose_variant_uv(const PtScene* s, const PtRenderParams* p, int local_t
   // The LDS kernels hold only the sign-resolved slab pass, which reads a pool's octant table (pt_device.hpp: slab_chunk_pass): a scene whose pools
   // have none — the tables would have pushed its blob past the LDS image — takes the scalar-cache kernels it would take under PT_FLAG_NO_LDS.
   const bool lds = v.resident && !(p->flags & PT_FLAG_NO_LDS) && !v.tri_pool && !s->pools_need_scalar;
-  const bool mlds = lds && blob_bytes + (size_t)s->mats_f4 * 16 <= kMaxLdsWithMaterials;
-  v.shmem = lds ? blob_bytes + (mlds ? (size_t)s->mats_f4 * 16 : 0) : 0;
+  // (the shade table rides behind the materials and weighs on both thresholds with them: 16 bytes per hittable of a small rect / box-only
+  // scene — the 16-entry pool's 6.1 KB image holds 304 of them — so a cold-state workgroup stays within 18 KB, seven to a CU's 160 KB.
+  // A rect / box-only scene of simple materials WITHOUT a table — more than ptf::kShadeMaxHittables records, which no 16 KB image holds —
+  // never gets its materials staged: the kernels that would stage them read the table)
+  const size_t mats_bytes = ((size_t)s->mats_f4 + (size_t)s->shade_f4) * 16;
+  const bool mlds = lds && blob_bytes + mats_bytes <= kMaxLdsWithMaterials && !(s->rectbox_only && s->mats_simple && s->shade_f4 == 0);
+  v.shmem = lds ? blob_bytes + (mlds ? mats_bytes : 0) : 0;
   const bool cold = mlds && v.shmem <= kMaxLdsColdScene && !s->knobs.no_cold_lds; // small scene: cold lane state in LDS (7 workgroups x (scene + 8 KB) per CU)
   // Cooperative kernels (a ray's list split over idle lanes; the heaviest tiles rendered G lanes per pixel) cost ~15 % of
   // the ordinary-mode throughput, and the part of an iteration that cannot be split (camera, shading, ray context:
@@ -2509,6 +2551,8 @@ void set_scene_facts(PtScene* s, const PtSceneDesc* desc, const PtTuning& tun, c
   s->tri_pooled = flat.has_badouel ? 0 : flat.tri_pooled; // (scenes with Badouel-strategy triangles keep the round-2 kernels)
   s->blob_bytes = flat.blob.size() * 16;
   s->mats_f4 = (int)flat.mats.size();
+  s->shade_f4 = (int)flat.shade.size();
+  s->shade_base = flat.shade_base;
   s->pool_plan = scene_pool_plan(flat);
 }
 
@@ -2596,6 +2640,23 @@ int pt_debug_flatten_tuned(const PtSceneDesc* desc, const PtTuning* tuning, floa
   return PT_OK;
 }
 
+int pt_debug_shade_table(const PtSceneDesc* desc, const PtTuning* tuning, float* table_out, int64_t table_cap_f4, int32_t* n_f4, int32_t* base) {
+  ptf::Flat flat;
+  std::string err;
+  PtTuning t;
+  int rc = resolve_tuning(tuning, t, err);
+  if (rc) return fail(rc, err);
+  rc = flatten_tuned(desc, t, flat, err);
+  if (rc) return fail(rc, err);
+  if (n_f4) *n_f4 = (int32_t)flat.shade.size();
+  if (base) *base = flat.shade_base;
+  if (table_out) {
+    if (table_cap_f4 < (int64_t)flat.shade.size()) return fail(PT_ERR_INVALID_ARG, "shade table buffer too small");
+    if (!flat.shade.empty()) std::memcpy(table_out, flat.shade.data(), flat.shade.size() * 16);
+  }
+  return PT_OK;
+}
+
 int pt_debug_flatten_pool(const PtSceneDesc* desc, const PtTuning* tuning, float* pool_out, int64_t pool_cap_f4, int64_t* n_pool_f4) {
   ptf::Flat flat;
   std::string err;
@@ -2670,12 +2731,13 @@ int pt_scene_create_tuned(const PtSceneDesc* desc, const PtTuning* tuning, PtSce
     s->bin_keys = (int)keys;
     s->bin_base1 = flat.tri_maps > 0 ? 3 * flat.tri_map_res[0] * flat.tri_map_res[0] : 0;
   }
-  // one buffer: [blob records][material table] so a kernel can stage both with one contiguous copy
+  // one buffer: [blob records][material table][shade table] so a kernel can stage all of it with one contiguous copy
   const size_t blob_bytes = flat.blob.size() * 16, mats_bytes = flat.mats.size() * 16;
-  PT_HIP(s->blob.alloc(flat.blob.size() + flat.mats.size()));
+  PT_HIP(s->blob.alloc(flat.blob.size() + flat.mats.size() + flat.shade.size()));
   s->mats = s->blob.p + flat.blob.size();
   if (blob_bytes) PT_HIP(hipMemcpy(s->blob.p, flat.blob.data(), blob_bytes, hipMemcpyHostToDevice));
   if (mats_bytes) PT_HIP(hipMemcpy(s->mats, flat.mats.data(), mats_bytes, hipMemcpyHostToDevice));
+  if (!flat.shade.empty()) PT_HIP(hipMemcpy(s->mats + flat.mats.size(), flat.shade.data(), flat.shade.size() * 16, hipMemcpyHostToDevice));
   if (flat.pool.size_f4) { // the triangle pools' tables: zeroed (spare records between the tables), then table by table from where the builder left them
     s->pool_bytes = (size_t)flat.pool.size_f4 * 16;
     PT_HIP(s->pool.alloc((size_t)flat.pool.size_f4));
@@ -2705,7 +2767,7 @@ int pt_scene_create_tuned(const PtSceneDesc* desc, const PtTuning* tuning, PtSce
 
 int64_t pt_scene_device_bytes(const PtScene* s) {
   if (!s) return -1;
-  return (int64_t)s->blob_bytes + (int64_t)s->mats_f4 * 16 + (int64_t)s->pool_bytes + (int64_t)s->atlas_bytes;
+  return (int64_t)s->blob_bytes + ((int64_t)s->mats_f4 + s->shade_f4) * 16 + (int64_t)s->pool_bytes + (int64_t)s->atlas_bytes;
 }
 
 #ifndef PT_BUILD_ID
@@ -3120,7 +3182,9 @@ int launch_render(const PtScene* s, const PtCamera* cam, const PtRenderParams* p
   KArgs base;
   set_frame(base, s, cam, p);
   base.fb = fb;
-  base.blob_f4 = s->blob_f4; base.mats_f4 = s->mats_f4; base.n_hittables = s->n_hittables;
+  base.blob_f4 = s->blob_f4; base.mats_f4 = s->mats_f4 + s->shade_f4 /* staged as one */;
+  base.shade_k = s->shade_f4 > 0 ? s->blob_f4 + s->mats_f4 - s->shade_base : 0;
+  base.n_hittables = s->n_hittables;
   base.depth = p->depth;
   const bool masked = w && w->mask;
   // tiles this shard owns (a masked window: the tiles it renders)

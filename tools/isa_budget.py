@@ -9,7 +9,9 @@ instruction of the kernel is attributed to the source function its `.loc` names 
 line, and the comment behind it the call sites it was inlined through — and functions are grouped into the phases of one loop iteration.
 A helper that several phases share (vector math, div_exact, the generator, wave builtins of the HIP headers) counts towards the phase
 it was inlined into; instructions without a location of their own (the register allocator's copies at a block's edge) towards the
-phase of the instruction stream they sit in.  Counts are STATIC: what the loop's text
+phase of the instruction stream they sit in — except the kernel's set-up ahead of the loop, behind render_kernel's own statements there (the
+staging, the depth check): the loop's hoisted constants and lane_reset's initial values, which count towards lane_reset's phase whether or
+not one of lane_reset's own instructions happens to stand in front of them.  Counts are STATIC: what the loop's text
 holds, not what a wave executes.  Beside each phase: what the reference's arithmetic needs there.
 """
 import argparse
@@ -27,7 +29,7 @@ HEADLINE = r"render_kernelILi0ELb1ELb1ELb0ELb1ELb0ELb0ELi0ELb0ELi65545E"  # cfg2
 PHASES = [
     ("loop head, back-edge, priority poll", ["render_kernel"], "-"),
     ("pixel queue, cold state, store", ["lane_acquire", "lane_store", "lane_reset", "store_rgb", "fast_seed", "begin", "resume", "add_sample", "count_ray",
-                                         "get_acc", "get_s", "get_pix", "get_x", "get_y", "get_iters", "init"], "12 B per pixel; mean: 3 div per pixel"),
+                                         "get_acc", "get_s", "get_pix", "get_x", "get_y", "get_xy", "get_iters", "init", "a_word", "b_word"], "12 B per pixel; mean: 3 div per pixel"),
     ("camera ray (lane_regenerate)", ["lane_regenerate", "lane_prepare", "camera_ray"], "91 per sample (5 draws x 8)"),
     ("ray context (make_ctx, wave_all_regular)", ["make_ctx", "wave_all_regular"], "0 (the reference divides per side; 3 reciprocals here)"),
     ("run loop + slab_pool set-up", ["hit_world_range", "hit_world", "hit_begin", "slab_pool"], "0 (list walk)"),
@@ -36,8 +38,8 @@ PHASES = [
     ("leaving-ray proof (inside gate)", ["slab_chunk_pass:proof"], "0 (culling)"),
     ("trip gate, record fetch, pool exit", ["slab_chunk_pass:trip"], "0"),
     ("exact sides (6 x rect_side_cmpx)", ["rect_side_cmpx", "box_cmpx"], "6 x (4 / 12 / 33) per candidate box"),
-    ("shade head + resolve_hit", ["lane_shade", "resolve_hit", "set_face_normal"], "hit point 6, face normal 6 + 3"),
-    ("scatter (lambertian, light)", ["shade", "texture_value", "rng_unit_vec"], "lambertian 46 (2 draws); light 0"),
+    ("shade head + resolve_hit", ["lane_shade", "resolve_hit", "shade_record", "set_face_normal"], "hit point 6, face normal 6 + 3"),
+    ("scatter (lambertian, light)", ["shade", "shade_with", "texture_value", "rng_unit_vec"], "lambertian 46 (2 draws); light 0"),
     ("sky", ["sky_color", "sky_unit_y"], "24"),
 ]
 COLS = ["total", "VALU", "SALU", "v_mov", "v_cndmask", "s_nop", "SMEM", "LDS", "VMEM", "branch", "wait"]
@@ -73,6 +75,14 @@ def function_ranges(src):
     return out
 
 
+def setup_lines(src):
+    """(first, last) line of render_kernel's statements ahead of its loop: the kernel's set-up"""
+    lines = (Path(src) / "pt_render.hip").read_text().splitlines()
+    first = next(i for i, line in enumerate(lines) if re.match(r"void render_kernel\(", line)) + 1
+    last = next(i for i in range(first, len(lines)) if re.match(r"\s*for \(;;\) \{", lines[i]))
+    return first, last
+
+
 def kind_of(op):
     if op == "s_nop":
         return "s_nop"
@@ -94,8 +104,10 @@ def kind_of(op):
 def budget(asm_path, kernel_re, src):
     ranges = function_ranges(src)
     scans = next(i for i, (_, fs, _) in enumerate(PHASES) if "hit_records" in fs)
+    reset = next(i for i, (_, fs, _) in enumerate(PHASES) if "lane_reset" in fs)
+    setup_first, setup_last = setup_lines(src)
     files, rows = {}, [collections.Counter() for _ in PHASES]
-    inside, phase, name = False, 0, None
+    inside, phase, name, in_setup = False, 0, None, False
     for line in open(asm_path):
         m = re.match(r"\s*\.file\s+(\d+)\s+(?:\"[^\"]*\"\s+)?\"([^\"]*)\"", line)
         if m:
@@ -113,6 +125,10 @@ def budget(asm_path, kernel_re, src):
             # the first of them that lies in a function PHASES names decides; none (a helper reached from a line 0, say): the phase stays
             chain = [(files.get(int(m.group(1)), ""), int(m.group(2)))]
             chain += [(Path(f).name, int(ln)) for f, ln in re.findall(r"@\[ (\S+?):(\d+):\d+", line)]
+            if chain[0][1] == 0 and in_setup:  # no location, behind the kernel's own set-up statements: lane_reset's (see above)
+                phase = reset
+                continue
+            in_setup = len(chain) == 1 and chain[0][0].endswith(".hip") and setup_first <= chain[0][1] <= setup_last
             hits = []
             for fname, ln in chain:
                 hits += [ph for first, last, ph in ranges.get("pt_render.hip" if fname.endswith(".hip") else fname, []) if first <= ln <= last][:1]
