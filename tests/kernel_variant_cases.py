@@ -108,7 +108,8 @@ def _extras(hs, extra, image, where, size, atlas):
 
 
 def cornell(extra=None):
-    """The headline scene: rects and boxes, lambertian + light over solid colours; 8 hittables — records + materials far below 10 KB."""
+    """The headline scene: rects and boxes, lambertian + light over solid colours; 8 hittables — records + materials far below 10 KB (the scenes ON
+    that limit, and on the 16 KB one: threshold_scenes.py, T1 / T2 families a to c — a new variant gets a row here AND a boundary pair there)."""
     hs, cam = scenes.cornell_box()
     hs = list(hs)
     _extras(hs, extra, None, (190, 240, 150), 60.0, None)
@@ -117,7 +118,8 @@ def cornell(extra=None):
 
 def boxes(extra=None, n=150):
     """n boxes in one slab pool: 96 bytes of records and 256 of octant table each — over the 16 KB that would hold the material table
-    in LDS too, within the 64 KB LDS image."""
+    in LDS too, within the 64 KB LDS image (the largest pool that keeps its tables, and one box more: threshold_scenes.py, T4 —
+    a new variant gets a row here AND a boundary pair there)."""
     mats = [lambertian_material(c) for c in _COLS] + [lightsource_material((4, 4, 4))]
     hs = []
     for i in range(n):
@@ -129,7 +131,8 @@ def boxes(extra=None, n=150):
 
 def field(n, image=None):
     """n small spheres (>= 48: they get a culling grid) of six shared materials on a checkered ground, a big glass ball inside the
-    field and a triangle behind it.  n = 56: records + grid + materials under 10 KB; n = 300: over 16 KB, within 64 KB."""
+    field and a triangle behind it.  n = 56: records + grid + materials under 10 KB; n = 300: over 16 KB, within 64 KB (the fields ON 10, 16 and
+    64 KB: threshold_scenes.py, T1 to T3 families d to f — a new variant gets a row here AND a boundary pair there)."""
     rng = scenes.HostRNG(77 + n)
     atlas = TextureAtlas() if image else None
     mats = [lambertian_material(_COLS[1]), lambertian_material(_COLS[3]), metal_material((0.8, 0.8, 0.9), 0.1), dielectric_material(1.5, (1, 1, 1)),
