@@ -49,6 +49,9 @@ frame of --denoise-out, if given — against a reference frame, a float32 [heigh
 FILE.npy writes it: MSE, relMSE (eps 1e-4), PSNR against a peak of 1, the pixels that took part and the skipped ones (a NaN or inf on
 either side).  The sums behind them are exact and rounded once on the device, so the printed MSE does not depend on the order in which
 the hardware adds.  out.png is byte-identical to the one written without the options.
+With --encode srgb the files of --display-out and --frames-dir hold exact sRGB codes (render.encode; include/pt_encode.h) instead of the
+reference's gamma-2 quantiser — fused with the display stage where that runs — and carry an sRGB chunk; --dither adds the 8 x 8 ordered
+dither in linear light.  out.png is byte-identical to the one written without the options.
 """
 import argparse
 import os
@@ -75,14 +78,16 @@ def write_aovs(aov_dir, planes) -> None:
 
 def make_shower(a):
     """The output stage of a frame -> uint8 image: the reference's (render.tonemap_rgb8) without display options; with them the display
-    stage — a manual exposure, or with --auto-exposure one Display whose exposure adapts over the frames it is shown in order."""
+    stage — a manual exposure, or with --auto-exposure one Display whose exposure adapts over the frames it is shown in order.  With
+    --encode the bytes are the encode stage's (fused with the display stage where that runs): sRGB codes, and the files say so."""
+    enc = {} if a.encode_kw is None else {"encode": a.encode_kw}  # (absent: exactly the calls there always were)
     if not a.display:
-        return R.tonemap_rgb8
+        return R.tonemap_rgb8 if a.encode_kw is None else lambda fb: R.encode(fb, **a.encode_kw)
     ev = 0.0 if a.exposure is None else a.exposure
     if not a.auto_exposure:
-        return lambda fb: R.display(fb, a.tone, ev)
+        return lambda fb: R.display(fb, a.tone, ev, **enc)
     disp = R.Display(a.tone, ev_bias=ev, adapt_up=1.0 if a.adapt_up is None else a.adapt_up, adapt_down=1.0 if a.adapt_down is None else a.adapt_down)
-    return lambda fb: disp.meter(fb).apply(fb)
+    return lambda fb: disp.meter(fb).apply(fb, **enc)
 
 
 def clamp_fireflies(a, fb, what, variance=None):
@@ -122,7 +127,7 @@ def write_frames(a, packed, cam_args, move, denoise_kw) -> None:
     if not a.temporal:
         for f, c in enumerate(cams):
             fb = clamp_fireflies(a, R.render(a.width, a.height, a.spp, packed, c, a.depth), f"frame {f}")
-            write_png(os.path.join(a.frames_dir, f"frame_{f}.png"), show(fb).cpu().numpy())
+            write_png(os.path.join(a.frames_dir, f"frame_{f}.png"), show(fb).cpu().numpy(), **a.png_kw)
         return
     extra = {} if a.firefly_kw is None else {"firefly": a.firefly_kw}  # (absent: render_temporal issues exactly the calls it always did)
     if a.spatial_kw is not None:
@@ -133,7 +138,7 @@ def write_frames(a, packed, cam_args, move, denoise_kw) -> None:
             print_firefly_counts(a, f"frame {f}", frame["firefly_counts"])
         if a.spatial_kw is not None:
             print_variance_counts(a, f"frame {f}", frame["variance_counts"])
-        write_png(os.path.join(a.frames_dir, f"frame_{f}.png"), show(frame["filtered" if a.denoise_variance else "temporal"]).cpu().numpy())
+        write_png(os.path.join(a.frames_dir, f"frame_{f}.png"), show(frame["filtered" if a.denoise_variance else "temporal"]).cpu().numpy(), **a.png_kw)
 
 
 def main() -> None:
@@ -182,6 +187,10 @@ def main() -> None:
     ap.add_argument("--adapt-up", type=float, default=None, metavar="A", help="auto-exposure over --frames: rate towards a higher exposure, in (0, 1]")
     ap.add_argument("--adapt-down", type=float, default=None, metavar="A", help="auto-exposure over --frames: rate towards a lower exposure, in (0, 1]")
     ap.add_argument("--display-out", default=None, metavar="FILE", help="also write the frame through the display stage (exposure + tone curve)")
+    ap.add_argument("--encode", default=None, choices=["srgb"],
+                    help="encode stage: write --display-out and the --frames-dir frames as exact sRGB codes (tagged sRGB) instead of the "
+                         "reference's gamma-2 quantiser; out.png stays as it is")
+    ap.add_argument("--dither", action="store_true", help="encode stage: 8 x 8 ordered dither in linear light (needs --encode srgb)")
     ap.add_argument("--firefly-clamp", type=float, nargs="?", const=1.0, default=None, metavar="K",
                     help="firefly stage: scale a pixel brighter than K x (default 1) its brightest neighbour down to that, repair NaN / inf; "
                          "acts on what --denoise-out, --display-out and --frames-dir consume (biased: off unless given)")
@@ -206,6 +215,12 @@ def main() -> None:
             ap.error(f"--compare: cannot read {a.compare}: {e}")
         if ref_frame.dtype != np.float32 or ref_frame.shape != (a.height, a.width, 3):
             ap.error(f"--compare: {a.compare} holds {ref_frame.dtype} {list(ref_frame.shape)}, not float32 [{a.height}, {a.width}, 3] (--height, --width)")
+    if a.dither and a.encode is None:
+        ap.error("--dither needs --encode srgb")
+    if a.encode is not None and a.display_out is None and a.frames_dir is None:
+        ap.error("--encode and --dither need --display-out or --frames-dir")
+    a.encode_kw = None if a.encode is None else dict(transfer=a.encode, dither=a.dither)
+    a.png_kw = {} if a.encode is None else {"srgb": True}
     if a.spatial_variance is not None and not a.denoise_variance:
         ap.error("--spatial-variance needs --denoise-variance (the filter that takes the variance)")
     if a.spatial_variance is not None and not 1 <= a.spatial_variance <= R.abi.PT_SVAR_MAX_RADIUS:
@@ -357,7 +372,7 @@ def main() -> None:
         if a.compare:
             print_compare(a, a.denoise_out, filtered, ref)
     if a.display_out:
-        write_png(a.display_out, make_shower(a)(fb).cpu().numpy())
+        write_png(a.display_out, make_shower(a)(fb).cpu().numpy(), **a.png_kw)
     if a.frames is not None:
         write_frames(a, packed, cam_args, move, denoise_kw)
     if mean_spp is not None:

@@ -1,5 +1,6 @@
 """ctypes mirror of include/pt_render.h — the C-ABI drop-in boundary of render() — and of include/pt_post.h (POST_SIGNATURES) and
-include/pt_spatial_variance.h (SPATIAL_VARIANCE_SIGNATURES) and include/pt_metrics.h (METRICS_SIGNATURES).
+include/pt_spatial_variance.h (SPATIAL_VARIANCE_SIGNATURES), include/pt_metrics.h (METRICS_SIGNATURES) and include/pt_encode.h
+(ENCODE_SIGNATURES).
 
 The structs are declared field-for-field as in the header; `load_library()` opens the
 in-tree `libpt_render.so` built by `__graft_entry__.build()` (hipcc, gfx950) and fails
@@ -184,6 +185,12 @@ class PtImageErrorResult(C.Structure):
                 ("skipped", C.c_uint64), ("max_abs", C.c_float * 3), ("reserved", C.c_uint32)]
 
 
+class PtEncodeParams(C.Structure):
+    """include/pt_encode.h PtEncodeParams: the encode stage's parameters (pt_encode, pt_display_encode)."""
+    _fields_ = [("struct_size", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("transfer", C.c_int32), ("flags", C.c_uint32),
+                ("phase_x", C.c_int32), ("phase_y", C.c_int32), ("reserved", C.c_int32)]
+
+
 assert C.sizeof(PtHittable) == 64 and C.sizeof(PtMaterial) == 32 and C.sizeof(PtTexture) == 48
 assert C.sizeof(PtCamera) == 96 and C.sizeof(PtRenderParams) == 32
 
@@ -342,6 +349,22 @@ PT_IMAGE_ERROR_NO_LDS = 1  # A/B switch, same bits: global atomics only
 PT_IMAGE_ERROR_WORDS, PT_IMAGE_ERROR_SUMS = 68, 9
 PT_IMAGE_ERROR_DEFAULT_EPS = 1e-4  # the header's (pt_image_error_params_init)
 
+# name -> (restype, argtypes): every entry point include/pt_encode.h declares.  A table of its own, like METRICS_SIGNATURES and for its
+# reason.  load_library() applies a row where the library exports the symbol; has_encode() tells whether the loaded one has the stage.
+ENCODE_SIGNATURES = {
+    "pt_encode_params_init": (None, [C.POINTER(PtEncodeParams), C.c_int32, C.c_int32]),
+    "pt_encode": (C.c_int, [C.POINTER(PtEncodeParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pt_display_encode": (C.c_int, [C.c_void_p, C.POINTER(PtDisplayParams), C.POINTER(PtEncodeParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pt_debug_last_encode": (C.c_int, [C.POINTER(C.c_int32)]),
+}
+ENCODE_SYMBOLS = frozenset(ENCODE_SIGNATURES)
+PT_TRANSFER_REFERENCE, PT_TRANSFER_SRGB = 0, 1
+TRANSFERS = {"reference": PT_TRANSFER_REFERENCE, "srgb": PT_TRANSFER_SRGB}
+PT_ENCODE_DITHER = 1
+PT_ENCODE_NO_VEC = 2  # A/B switch, same bits: one value per lane
+# the header's PT_ENCODE_DEFAULT_* (pt_encode_params_init)
+PT_ENCODE_DEFAULT_TRANSFER, PT_ENCODE_DEFAULT_FLAGS = PT_TRANSFER_SRGB, 0
+
 # Entry points a library may lack and still load for everything else (include/pt_render.h: the feature is detected by their presence);
 # has_accumulator() tells whether the loaded one has them.
 ACCUM_SYMBOLS = frozenset(n for n in SIGNATURES if n.startswith("pt_accum_") or n == "pt_render_accumulate")
@@ -451,7 +474,7 @@ def load_library() -> C.CDLL:
         fn = getattr(lib, name)  # AttributeError if the library does not export what the header declares
         fn.restype = res
         fn.argtypes = args
-    for name, (res, args) in list(POST_SIGNATURES.items()) + list(SPATIAL_VARIANCE_SIGNATURES.items()) + list(METRICS_SIGNATURES.items()):  # include/pt_post.h, pt_spatial_variance.h, pt_metrics.h: applied where the library has the symbol
+    for name, (res, args) in list(POST_SIGNATURES.items()) + list(SPATIAL_VARIANCE_SIGNATURES.items()) + list(METRICS_SIGNATURES.items()) + list(ENCODE_SIGNATURES.items()):  # include/pt_post.h, pt_spatial_variance.h, pt_metrics.h, pt_encode.h: applied where the library has the symbol
         if hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype = res
@@ -521,6 +544,12 @@ def has_metrics(lib=None) -> bool:
     """Does the loaded library offer the image error (include/pt_metrics.h: pt_image_error)?"""
     lib = lib or load_library()
     return all(hasattr(lib, n) for n in METRICS_SYMBOLS)
+
+
+def has_encode(lib=None) -> bool:
+    """Does the loaded library offer the encode stage (include/pt_encode.h: pt_encode, pt_display_encode)?"""
+    lib = lib or load_library()
+    return has_display(lib) and all(hasattr(lib, n) for n in ENCODE_SYMBOLS)
 
 
 def check(code: int, where: str) -> None:

@@ -30,6 +30,7 @@
 #include "../../include/pt_post.h"
 #include "../../include/pt_spatial_variance.h"
 #include "../../include/pt_metrics.h"
+#include "../../include/pt_encode.h"
 #include "pt_device.hpp"
 #include "pt_flatten.hpp"
 
@@ -2054,6 +2055,7 @@ __global__ __launch_bounds__(256) void display_apply_kernel(const float* color, 
 #include "pt_firefly.hpp"
 #include "pt_spatial_variance.hpp"
 #include "pt_metrics.hpp"
+#include "pt_encode.hpp"
 
 thread_local std::string g_last_error;
 
@@ -4262,6 +4264,97 @@ int pt_image_error(const PtImageErrorParams* params, const float* a, const float
 }
 
 int pt_debug_last_image_error(int32_t out[4]) { return g_last_imgerr.copy_out("pt_debug_last_image_error", out); }
+
+// ---- encode stage (include/pt_encode.h): pt_encode, pt_display_encode (encode_kernel) ------------------------------------------------------
+} // extern "C"
+
+namespace {
+LastRecord<8> g_last_encode;
+
+// What both entry points check once the frame has pixels, in the header's order; `in` is the plane the call reads.
+int encode_check(const Refuse& bad, const PtEncodeParams* p, const float* in, const uint8_t* rgb8_out) {
+  const int64_t pixels = (int64_t)p->width * p->height;
+  if (pixels > kMaxPixels) return bad.too_large();
+  if (p->transfer != PT_TRANSFER_REFERENCE && p->transfer != PT_TRANSFER_SRGB) return bad("unknown transfer");
+  if (p->flags & ~(PT_ENCODE_DITHER | PT_ENCODE_NO_VEC)) return bad("unknown flags");
+  if ((p->flags & PT_ENCODE_DITHER) && p->transfer != PT_TRANSFER_SRGB) return bad("PT_ENCODE_DITHER needs PT_TRANSFER_SRGB");
+  const uintptr_t values = (uintptr_t)pixels * 3;
+  if (overlaps(Span{rgb8_out, values}, Span{in, values * 4})) return bad("rgb8_out overlaps the input");
+  return PT_OK;
+}
+
+template <int TONE, int MODE>
+void encode_launch(bool vec, dim3 grid, hipStream_t st, const EncodeArgs& a) {
+  if (vec) hipLaunchKernelGGL((encode_kernel<TONE, MODE, true>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((encode_kernel<TONE, MODE, false>), grid, dim3(256), 0, st, a);
+}
+template <int TONE>
+void encode_launch(int mode, bool vec, dim3 grid, hipStream_t st, const EncodeArgs& a) {
+  if (mode == ENC_DITHER) encode_launch<TONE, ENC_DITHER>(vec, grid, st, a);
+  else if (mode == ENC_SRGB) encode_launch<TONE, ENC_SRGB>(vec, grid, st, a);
+  else encode_launch<TONE, ENC_REFERENCE>(vec, grid, st, a);
+}
+
+// The launch of a checked call; tone: ENCODE_PLAIN (pt_encode) or display_params' tone (pt_display_encode).
+int encode_run(const PtEncodeParams* p, int tone, EncodeArgs a, hipStream_t st) {
+  const int mode = p->transfer == PT_TRANSFER_REFERENCE ? ENC_REFERENCE : (p->flags & PT_ENCODE_DITHER) ? ENC_DITHER : ENC_SRGB;
+  a.width = p->width; a.height = p->height;
+  a.phase_x = (unsigned)p->phase_x & 7u; a.phase_y = (unsigned)p->phase_y & 7u;
+  // four values per lane where the rows and the planes allow 16-byte loads and 4-byte stores
+  const bool vec = !(p->flags & PT_ENCODE_NO_VEC) && p->width % 4 == 0 && ((uintptr_t)a.src & 15) == 0 && ((uintptr_t)a.rgb8 & 3) == 0;
+  const long long row_items = vec ? 3ll * p->width / 4 : 3ll * p->width;
+  const unsigned gx = (unsigned)((row_items + 255) / 256);
+  const dim3 grid(gx, (unsigned)std::min<int64_t>(p->height, std::max<int64_t>(1, PT_ENCODE_MAX_BLOCKS / gx)));
+  const auto lock = g_last_encode.begin();
+  if (tone == PT_TONE_REINHARD) encode_launch<PT_TONE_REINHARD>(mode, vec, grid, st, a);
+  else if (tone == PT_TONE_ACES) encode_launch<PT_TONE_ACES>(mode, vec, grid, st, a);
+  else if (tone == PT_TONE_REFERENCE) encode_launch<PT_TONE_REFERENCE>(mode, vec, grid, st, a);
+  else encode_launch<ENCODE_PLAIN>(mode, vec, grid, st, a);
+  PT_HIP(hipGetLastError());
+  const int32_t words[8] = {vec ? 2 : 1, (int32_t)grid.x, (int32_t)grid.y, vec ? 4 : 1, p->transfer + 1, tone != ENCODE_PLAIN,
+                            (p->flags & PT_ENCODE_DITHER) != 0, 0};
+  std::memcpy(g_last_encode.words, words, sizeof words);
+  return PT_OK;
+}
+} // namespace
+
+extern "C" {
+
+void pt_encode_params_init(PtEncodeParams* params, int32_t width, int32_t height) {
+  if (!init_params(params)) return;
+  params->width = width; params->height = height;
+  params->transfer = PT_ENCODE_DEFAULT_TRANSFER;
+  params->flags = PT_ENCODE_DEFAULT_FLAGS;
+}
+
+int pt_encode(const PtEncodeParams* params, const float* linear, uint8_t* rgb8_out, void* stream) {
+  const Refuse bad{"pt_encode"};
+  if (!params || !linear || !rgb8_out) return bad("NULL params, linear or rgb8_out");
+  if (!is_ours(params)) return bad("PtEncodeParams.struct_size is not this library's");
+  if (params->width <= 0 || params->height <= 0) return bad("width and height must be > 0");
+  if (const int rc = encode_check(bad, params, linear, rgb8_out)) return rc;
+  EncodeArgs a{};
+  a.src = linear; a.rgb8 = rgb8_out;
+  return encode_run(params, ENCODE_PLAIN, a, (hipStream_t)stream);
+}
+
+int pt_display_encode(const PtDisplay* state, const PtDisplayParams* display_params, const PtEncodeParams* encode_params, const float* color,
+                      uint8_t* rgb8_out, void* stream) {
+  const Refuse bad{"pt_display_encode"};
+  if (!encode_params || !rgb8_out) return bad("NULL encode_params or rgb8_out");
+  if (!is_ours(encode_params)) return bad("PtEncodeParams.struct_size is not this library's");
+  float iw2 = 0.0f;
+  if (const int rc = display_check("pt_display_encode", display_params, color, encode_params->width, encode_params->height, &iw2)) return rc;
+  if (const int rc = encode_check(bad, encode_params, color, rgb8_out)) return rc;
+  EncodeArgs a{};
+  a.src = color; a.rgb8 = rgb8_out;
+  a.state = state ? state->words.p : nullptr;
+  a.ev = std::fmin(std::fmax(display_params->ev_bias, -32.0f), 32.0f); // pt_display_apply's
+  a.iw2 = iw2;
+  return encode_run(encode_params, display_params->tone, a, (hipStream_t)stream);
+}
+
+int pt_debug_last_encode(int32_t out[8]) { return g_last_encode.copy_out("pt_debug_last_encode", out); }
 
 // ---- progressive rendering: sample windows into a PtAccum (include/pt_render.h) ------------------------------------------------
 } // extern "C"

@@ -590,7 +590,9 @@ inline const char* load_rgb8(const char* path, Image& im) {
 
 // RGB8 -> PNG file (colour type 2, 8 bits, filter 0, stored deflate blocks: no compressor needed; any PNG reader decodes the exact
 // bytes).  The output stage of main.cpp:33-59 ends in stbi_write_png.  Returns false if the file cannot be written.
-inline bool write_png(const char* path, const uint8_t* rgb, std::size_t width, std::size_t height) {
+// srgb: the bytes are sRGB codes (pt::encode) — the file says so with an sRGB chunk (rendering intent 0) and gAMA 45455 before IDAT;
+// without it the file is byte for byte what it always was.
+inline bool write_png(const char* path, const uint8_t* rgb, std::size_t width, std::size_t height, bool srgb = false) {
   if (!path || !rgb || !width || !height) return false;
   std::vector<uint8_t> raw;
   raw.reserve(height * (width * 3 + 1));
@@ -622,6 +624,10 @@ inline bool write_png(const char* path, const uint8_t* rgb, std::size_t width, s
   for (int k = 0; k < 4; k++) { ihdr[(std::size_t)k] = (uint8_t)(width >> (8 * (3 - k))); ihdr[(std::size_t)(4 + k)] = (uint8_t)(height >> (8 * (3 - k))); }
   ihdr[8] = 8; ihdr[9] = 2;
   chunk("IHDR", ihdr);
+  if (srgb) {
+    chunk("sRGB", {0});
+    chunk("gAMA", {0x00, 0x00, 0xb1, 0x8f}); // 45455 = 1 / 2.2 in 1 / 100000
+  }
   chunk("IDAT", z);
   chunk("IEND", {});
   return std::fclose(f) == 0;

@@ -38,6 +38,7 @@
 #include "../../../include/pt_post.h"
 #include "../../../include/pt_spatial_variance.h"
 #include "../../../include/pt_metrics.h"
+#include "../../../include/pt_encode.h"
 #include "image_io.hpp"
 
 namespace pt {
@@ -600,6 +601,35 @@ inline void image_error(int width, int height, const float* a, const float* ref,
   p.flags = ip.no_lds ? PT_IMAGE_ERROR_NO_LDS : 0u;
   p.scratch_bytes = pt_image_error_scratch_bytes();
   check(pt_image_error(&p, a, ref, result, error_plane, scratch, stream), "pt_image_error");
+}
+
+// The encode stage (include/pt_encode.h: pt_encode, pt_display_encode): linear light -> 8-bit codes by the exact sRGB transfer (the code
+// of the real sRGB function, correctly rounded, for every binary32 value), optionally with the 8 x 8 ordered dither in linear light; or
+// the reference's quantiser (PT_TRANSFER_REFERENCE: pt_tonemap_rgb8's bytes).  linear / color ([height][width][3] float, row 0 = bottom)
+// and rgb8_out ([height][width][3] bytes, row 0 = top) are DEVICE buffers the caller owns and must not overlap.  The defaults are the
+// header's (pt_encode_params_init).  display_encode() is display_apply()'s exposure and curve and encode() in one pass: `d` null is the
+// stateless form (the exposure is dp.ev_bias).
+struct encode_params {
+  int transfer = PT_ENCODE_DEFAULT_TRANSFER; // PT_TRANSFER_REFERENCE, PT_TRANSFER_SRGB
+  bool dither = false;
+  int phase_x = 0, phase_y = 0;              // the dither pattern's offset in pixels
+  bool no_vec = false;                       // the A/B switch PT_ENCODE_NO_VEC (the same bits)
+  PtEncodeParams c(int width, int height) const {
+    return PtEncodeParams{(int32_t)sizeof(PtEncodeParams), width, height, transfer,
+                          (dither ? PT_ENCODE_DITHER : 0u) | (no_vec ? PT_ENCODE_NO_VEC : 0u), phase_x, phase_y, 0};
+  }
+};
+// asynchronous on `stream`
+inline void encode(int width, int height, const float* linear, uint8_t* rgb8_out, const encode_params& ep = {}, void* stream = nullptr) {
+  const PtEncodeParams p = ep.c(width, height);
+  check(pt_encode(&p, linear, rgb8_out, stream), "pt_encode");
+}
+// asynchronous on `stream`
+inline void display_encode(int width, int height, const float* color, uint8_t* rgb8_out, const display_params& dp = {},
+                           const encode_params& ep = {}, const display* d = nullptr, void* stream = nullptr) {
+  const PtDisplayParams p = dp.c();
+  const PtEncodeParams e = ep.c(width, height);
+  check(pt_display_encode(d ? d->handle() : nullptr, &p, &e, color, rgb8_out, stream), "pt_display_encode");
 }
 
 // Progressive rendering: one frame in sample windows; RAII over pt_accum_create / pt_accum_destroy (include/pt_render.h, PtAccum).

@@ -558,6 +558,65 @@ def tonemap_rgb8(fb):
     return out
 
 
+_ENCODE_KW = ("transfer", "dither", "phase", "no_vec")
+
+
+def _encode_kw(arg, who):
+    """The `encode=` keyword of the display hosts: None / False -> None (today's call, the reference's quantiser), "srgb" / True -> the sRGB
+    transfer, a dict -> encode()'s transfer, dither, phase, no_vec."""
+    if arg is None or arg is False:
+        return None
+    if arg is True or arg == "srgb":
+        return {}
+    if isinstance(arg, dict) and not set(arg) - set(_ENCODE_KW):
+        return dict(arg)
+    raise TypeError(f"{who}: encode must be None, \"srgb\" or a dict of {', '.join(_ENCODE_KW)}")
+
+
+def _encode_params(lib, w, h, transfer="srgb", dither=False, phase=(0, 0), no_vec=False) -> "abi.PtEncodeParams":
+    if isinstance(transfer, str):
+        if transfer not in abi.TRANSFERS:
+            raise ValueError(f"transfer must be one of {sorted(abi.TRANSFERS)}")
+        transfer = abi.TRANSFERS[transfer]
+    p = abi.PtEncodeParams()
+    lib.pt_encode_params_init(C.byref(p), w, h)
+    p.transfer = int(transfer)
+    p.flags = (abi.PT_ENCODE_DITHER if dither else 0) | (abi.PT_ENCODE_NO_VEC if no_vec else 0)
+    p.phase_x, p.phase_y = int(phase[0]), int(phase[1])
+    return p
+
+
+def encode(linear, transfer="srgb", dither: bool = False, phase=(0, 0), out=None, *, no_vec: bool = False):
+    """The encode stage (include/pt_encode.h: pt_encode): a linear-light frame [H][W][3] float32 on the GPU -> the uint8 image [H][W][3],
+    row 0 = top (`out` if given), by the exact sRGB transfer ("srgb": the code of the real sRGB function, correctly rounded, for every
+    binary32 value) or the reference's quantiser ("reference": tonemap_rgb8's bytes).  `dither`: the 8 x 8 ordered dither in linear
+    light, its pattern offset by `phase` = (x, y) pixels (sRGB only).  no_vec: the A/B switch PT_ENCODE_NO_VEC (same bits).
+    Asynchronous on torch's current stream; allocates nothing on the device but `out`."""
+    import torch
+
+    lib = _stage("encode", abi.has_encode, "the encode stage", "pt_encode")
+    h, w = _whole_frame(linear)
+    src = _frame_ptr(linear, "linear")
+    p = _encode_params(lib, w, h, transfer, dither, phase, no_vec)
+    out = _optional_out(True if out is None else out, (h, w, 3), torch.uint8, "out", linear.device)
+    abi.check(lib.pt_encode(C.byref(p), src, C.c_void_p(out.data_ptr()), _stream_ptr(torch)), "pt_encode")
+    return out
+
+
+def _display_encode(lib, handle, p, fb, out, ekw):
+    """pt_display_encode: pt_display_apply's exposure and curve and the encode stage in one pass -> the uint8 image [H][W][3], row 0 = top."""
+    import torch
+
+    if not abi.has_encode(lib):
+        raise ImportError(f"{abi.library_path()} predates the encode stage (no pt_display_encode)")
+    src = _frame_ptr(fb)
+    h, w, _ = fb.shape
+    ep = _encode_params(lib, w, h, **ekw)
+    out = _optional_out(True if out is None else out, (h, w, 3), torch.uint8, "out", fb.device)
+    abi.check(lib.pt_display_encode(handle, C.byref(p), C.byref(ep), src, C.c_void_p(out.data_ptr()), _stream_ptr(torch)), "pt_display_encode")
+    return out
+
+
 def _display_params(tone, ev_bias, ev_min, ev_max, lo_permille, hi_permille, adapt_up, adapt_down, white, rect) -> abi.PtDisplayParams:
     if isinstance(tone, str):
         if tone not in abi.TONES:
@@ -568,10 +627,16 @@ def _display_params(tone, ev_bias, ev_min, ev_max, lo_permille, hi_permille, ada
                                int(hi_permille), float(adapt_up), float(adapt_down), float(white), int(x0), int(y0), int(x1), int(y1), 0)
 
 
-def _display_apply(lib, handle, p, fb, out, linear):
+def _display_apply(lib, handle, p, fb, out, linear, encode=None, who="display"):
     """pt_display_apply -> the uint8 image [H][W][3] (row 0 = top), or (image, linear plane) with `linear`: True allocates the plane, a tensor
-    is written (it may be `fb`)."""
+    is written (it may be `fb`).  With `encode` (see _encode_kw) the fused pt_display_encode instead: the image alone, no plane."""
     import torch
+
+    ekw = _encode_kw(encode, who)
+    if ekw is not None:
+        if linear is not None and linear is not False:
+            raise ValueError(f"{who}: encode= takes the fused call, which writes no linear plane (call encode() on the plane instead)")
+        return _display_encode(lib, handle, p, fb, out, ekw)
 
     src = _frame_ptr(fb)
     h, w, _ = fb.shape
@@ -613,10 +678,12 @@ class Display:
         abi.check(self.lib.pt_display_meter(self.handle, C.byref(self.params), src, w, h, _stream_ptr(torch)), "pt_display_meter")
         return self
 
-    def apply(self, fb, out=None, linear=False):
+    def apply(self, fb, out=None, linear=False, encode=None):
         """The frame at the state's exposure through the tone curve: the uint8 image [H][W][3], row 0 = top (`out` if given); with `linear`
-        (True, or a float32 tensor to write, which may be `fb`) also the curve's output before the quantiser: (image, plane)."""
-        return _display_apply(self.lib, self.handle, self.params, fb, out, linear)
+        (True, or a float32 tensor to write, which may be `fb`) also the curve's output before the quantiser: (image, plane).
+        encode: None — the reference's quantiser, as ever —, "srgb" or a dict of encode()'s transfer, dither, phase: the curve's output
+        through the encode stage instead, in one pass (pt_display_encode); not with `linear`."""
+        return _display_apply(self.lib, self.handle, self.params, fb, out, linear, encode, "Display.apply")
 
     def exposure(self) -> float:
         """The exposure in stops (synchronises the stream: for inspection)."""
@@ -659,15 +726,16 @@ class Display:
             pass
 
 
-def display(fb, tone="aces", ev: float = 0.0, *, white: float = abi.PT_DISPLAY_DEFAULT_WHITE, out=None, linear=False):
+def display(fb, tone="aces", ev: float = 0.0, *, white: float = abi.PT_DISPLAY_DEFAULT_WHITE, out=None, linear=False, encode=None):
     """The stateless display stage: `fb` at a manual exposure of `ev` stops through the tone curve -> uint8 [H][W][3], row 0 = top (with
-    `linear`: (image, plane), as Display.apply).  display(fb, "reference", 0.0) is tonemap_rgb8(fb)."""
+    `linear`: (image, plane), as Display.apply; with `encode`: through the encode stage, as there).  display(fb, "reference", 0.0) is
+    tonemap_rgb8(fb)."""
     lib = abi.load_library()
     if not abi.has_display(lib):
         raise ImportError(f"{abi.library_path()} predates the display stage (no pt_display_* entry points)")
     p = _display_params(tone, ev, abi.PT_DISPLAY_DEFAULT_EV_MIN, abi.PT_DISPLAY_DEFAULT_EV_MAX, abi.PT_DISPLAY_DEFAULT_LO_PERMILLE,
                         abi.PT_DISPLAY_DEFAULT_HI_PERMILLE, 1.0, 1.0, white, None)
-    return _display_apply(lib, None, p, fb, out, linear)
+    return _display_apply(lib, None, p, fb, out, linear, encode, "display")
 
 
 class Accumulator:
@@ -839,13 +907,13 @@ class Accumulator:
         abi.check(self.lib.pt_accum_tonemap_rgb8(self.handle, C.c_void_p(out.data_ptr()), _stream_ptr(torch)), "pt_accum_tonemap_rgb8")
         return out
 
-    def display(self, disp: "Display", out=None):
+    def display(self, disp: "Display", out=None, encode=None):
         """resolve(), then disp.meter() and disp.apply() over it: the uint8 image [H][W][3], row 0 = top, at the exposure the Display
-        adapted to (whole frames)."""
+        adapted to (whole frames).  encode: Display.apply's."""
         if self.shard_count != 1:
             raise ValueError("Accumulator.display: whole frames only (gather and unshard first)")
         fb = self.resolve()
-        return disp.meter(fb).apply(fb, out=out)
+        return disp.meter(fb).apply(fb, out=out, encode=encode)
 
     def reset(self) -> None:
         """Back to 0 samples (the next window binds its camera: set .cam first to render another view)."""
@@ -998,7 +1066,7 @@ class TemporalAccumulator:
 
 
 def render_temporal(width: int, height: int, spp: int, scene, cams, depth: int = 50, *, aov_spp: int = 4, denoise: bool = True,
-                    denoise_kw: "dict | None" = None, display: "Display | None" = None, firefly=None, spatial_variance=None, **params):
+                    denoise_kw: "dict | None" = None, display: "Display | None" = None, firefly=None, spatial_variance=None, encode=None, **params):
     """A camera path rendered at `spp` samples per frame with its history carried along: for each camera of `cams` yields a dict with
     `noisy` (the frame alone), `temporal`, `variance`, `history` (TemporalAccumulator.push's results) and, with `denoise`, `filtered` —
     denoise_variance() over the temporal colour and variance with that frame's guides (render_aov at `aov_spp` camera rays per pixel).
@@ -1006,7 +1074,8 @@ def render_temporal(width: int, height: int, spp: int, scene, cams, depth: int =
     of 2 samples or more is rendered in two windows, so that its own variance estimate (Accumulator.variance(), from the two halves)
     exists and is what `variance` holds where the history is younger than 4 frames.
     With `display` (a Display) each frame also has `rgb8`: the end of the chain — `filtered` (or `temporal` without `denoise`) metered and
-    shown by it, its exposure adapting from frame to frame.
+    shown by it, its exposure adapting from frame to frame.  With `encode` ("srgb", or a dict of encode()'s transfer, dither, phase) `rgb8`
+    is the encode stage's, fused with the display's curve (Display.apply's `encode`); it needs `display`.
     With `firefly` (True, or a dict of firefly()'s rank, k, repair) the firefly stage runs on `noisy` and its variance before the push, and
     each frame also has `clamped`: the frame the history took in (`noisy` stays the frame alone), and `firefly_counts`: the stage's
     {clamped, repaired} as a uint32 device tensor.
@@ -1019,6 +1088,8 @@ def render_temporal(width: int, height: int, spp: int, scene, cams, depth: int =
 
     if spp <= 0:
         raise ValueError("spp must be > 0")
+    if _encode_kw(encode, "render_temporal") is not None and display is None:
+        raise ValueError("render_temporal: encode needs display")
     fkw = _stage_kw(firefly, "render_temporal", "firefly", _FIREFLY_KW)
     skw = _stage_kw(spatial_variance, "render_temporal", "spatial_variance", _SPATIAL_KW)
     ds = _as_device_scene(scene, cache_key=("cuda", torch.cuda.current_device(), torch.cuda.current_stream().cuda_stream))
@@ -1048,7 +1119,7 @@ def render_temporal(width: int, height: int, spp: int, scene, cams, depth: int =
                                                      **(denoise_kw or {}))
             if display is not None:
                 shown = frame["filtered" if denoise else "temporal"]
-                frame["rgb8"] = display.meter(shown).apply(shown)
+                frame["rgb8"] = display.meter(shown).apply(shown, encode=encode)
             yield frame
     finally:
         if acc is not None:
